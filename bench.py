@@ -1,7 +1,12 @@
 """Benchmark of the shifted-scale calibration hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`,
+`ms_per_step`); `--dump-outputs DIR` also writes what the last step computed.  `--full` adds
+everything else described below and in DESIGN.md: the kernel rooflines and stream ceilings,
+the reconstruction loops, the validation pass and the CPU baselines.
 
 `--gpus N` alone starts its own N rank processes (shiftedscalequantization_amd/launch.py, as
 the reference's mp.spawn, Brecq/main_imagenet_dist.py:268-271); under an external launcher
@@ -18,7 +23,7 @@ value = elements processed by all ranks / max-over-ranks wall time (Gelem/s, wea
 scaling: every rank owns its own calibration shard; no data-path collective).
 The reconstruction iteration rate (block_recon_fused_shiftedScale, batch 32, bias_cal, every
 ResNet-18 block, reference-faithful deterministic conv solvers as the headline) is reported
-beside it as `recon`, with its SURVEY §8(d) roofline as `roofline_recon` (priced on the
+beside it under --full as `recon`, with its SURVEY §8(d) roofline as `roofline_recon` (priced on the
 loop's own kernel launches from a rocprofv3 trace of these loops: tools/recon_roofline.py).
 """
 import argparse
@@ -64,6 +69,13 @@ def parse():
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--n-cali", type=int, default=1024)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed as "
+                        "DIR/<name>.npy (float32; the activation as a fixed, seeded sample)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: kernel rooflines and ceilings, the recon loops, "
+                        "validation and the CPU baselines (the --no-* / --recon-iters / "
+                        "--cpu-seconds options below shape this part only)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=15.0)
     p.add_argument("--no-recon", action="store_true")
@@ -124,6 +136,33 @@ def make_workload(dev, rank, n_cali):
         zws.append(z)
         bits.append(b)
     return act, d_a, z_a, weights, dws, zws, bits
+
+
+RAMP_STEPS = 1000            # untimed steps of a plain run before its warm-up (main)
+DUMP_ACT_EDGE = 1 << 16     # head and tail elements of the activation kept whole
+DUMP_ACT_RANDOM = 1 << 21    # seeded random picks in between
+DUMP_SEED = 1005
+
+
+def dump_outputs(path, y_act, y_w):
+    """--dump-outputs: the arrays the last timed step left with its caller, as float32 .npy
+    files under `path`: every weight's q/dq whole (w00_qdq .. w20_qdq, 46.7 MB) and, of the
+    822 MB activation q/dq, a fixed sample (act_qdq_sample: the first and last 2^16 elements
+    and 2^21 seeded picks of the flat tensor, 8.9 MB; the whole tensor when it is no larger).
+    The workload is seeded, so two builds' dumps compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = y_act.reshape(-1)
+    n = flat.numel()
+    if n > 2 * DUMP_ACT_EDGE + DUMP_ACT_RANDOM:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        pick = torch.randint(DUMP_ACT_EDGE, n - DUMP_ACT_EDGE, (DUMP_ACT_RANDOM,), generator=g)
+        idx = torch.cat([torch.arange(DUMP_ACT_EDGE), pick.sort().values,
+                         torch.arange(n - DUMP_ACT_EDGE, n)])
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(path, "act_qdq_sample.npy"), flat.cpu().numpy())
+    for i, y in enumerate(y_w):
+        np.save(os.path.join(path, f"w{i:02d}_qdq.npy"), y.cpu().numpy())
 
 
 PMC_FILE = "profiles/pmc_traffic.json"
@@ -335,10 +374,75 @@ def main():
             w_plan()
             K.fake_quant_fwd(act, d_a, z_a, 4, out=y_act)
 
-    # the timed region comes after the kernel probes below, so that the W warm-up steps
-    # start on a GPU whose clocks have already left idle (the driver runs --steps 20
-    # --warmup 5: a 6 ms region)
+    # the W warm-up steps must start on a GPU whose clocks have already left idle (the
+    # driver runs --steps 20 --warmup 5: a 6 ms region).  --full: the kernel probes
+    # (rooflines, ceilings) run before the timed region and see to that; a plain run
+    # launches the step itself RAMP_STEPS times (0.3 s) in their place
+    probes = None
+    if args.full:
+        probes = kernel_probes(step, act, y_act, d_a, z_a, weights, dws, zws, bits, dev,
+                               args.n_cali)
+    else:
+        for _ in range(RAMP_STEPS):
+            step()
+        torch.cuda.synchronize(dev)
 
+    for _ in range(args.warmup):
+        step()
+    torch.cuda.synchronize(dev)
+    barrier(world)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    torch.cuda.synchronize(dev)
+    barrier(world)
+    elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
+    value = world * elems_per_step * args.steps / elapsed / 1e9
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y_act, y_w)
+
+    out = {
+        "metric": "Gelem/s shifted-scale q/dq + recon iters/s, ResNet-18 W2A4; top-1 vs ref",
+        "value": round(value, 3),
+        "unit": "Gelem/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (ReLU(N(0,1)) activation cache, N(0,0.02^2) ResNet-18-shaped weights)",
+        "config": {"workload": "resnet18 W2A4 bias_cal+bias_ch_quant, 1024 calib samples: A4 "
+                               "per-tensor q/dq of act [1024,64,56,56] + W2 per-channel q/dq of "
+                               "all 21 conv/fc weights (8-bit stem/head)",
+                   "elems_per_step_per_rank": elems_per_step, "parallelism": f"dp{world}"},
+        # how the ranks came to be and what the process group saw (n_gpus is the latter)
+        "launch": {"launcher": os.environ.get("SSQ_LAUNCHER",
+                                              "external" if "WORLD_SIZE" in os.environ else "none"),
+                   "world_size_backend": dist.get_world_size() if world > 1 else 1,
+                   "allreduce_backend": dist.get_backend() if world > 1 else None,
+                   "devices_visible": torch.cuda.device_count()},
+    }
+    if args.full:
+        out.update(probes)
+        full_report(out, args, dev, world, rank, act, d_a, z_a)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def kernel_probes(step, act, y_act, d_a, z_a, weights, dws, zws, bits, dev, n_cali):
+    """--full: the step's kernel against its rooflines and the box's measured ceilings (the
+    `roofline`, `weights_multi_*` and `roofline_per_channel` entries of the result line).
+    Runs before the timed region, so that the warm-up steps start on a GPU whose clocks
+    have already left idle."""
+    n_act = act.numel()
+    n_w = sum(w.numel() for w in weights)
     # dominant kernel: the step's one launch (fq_fwd_pt_ride: the A4 activation q/dq with
     # the weights' tiles riding on it), timed with HIP events on the stream it is launched
     # on: 20 launches replayed from a HIP graph (the step's host-side argument packing for
@@ -348,8 +452,8 @@ def main():
     ms_step_k = graph_time_ms(step, reps=20, rounds=9)
     ms_fq = time_events(lambda: K.fake_quant_fwd(act, d_a, z_a, 4, out=y_act), 20, dev, rounds=9)
     # the committed PMC passes were collected on the default workload (1024 samples)
-    traffic, traffic_prov = pmc_traffic("fq_fwd_pt_ride") if args.n_cali == 1024 else (None, None)
-    traffic_k1, _ = pmc_traffic("fq_fwd_pt") if args.n_cali == 1024 else (None, None)
+    traffic, traffic_prov = pmc_traffic("fq_fwd_pt_ride") if n_cali == 1024 else (None, None)
+    traffic_k1, _ = pmc_traffic("fq_fwd_pt") if n_cali == 1024 else (None, None)
     alg_bytes = 8.0 * (n_act + n_w)
     achieved = alg_bytes / (ms_step_k * 1e-3) / 1e9
     achieved_k1 = 8.0 * n_act / (ms_fq * 1e-3) / 1e9
@@ -379,64 +483,7 @@ def main():
     ms_pc = time_events(lambda: K.fake_quant_fwd(big, d_big, z_big, 2, out=y_big), 10, dev)
     pc_gbs = 8.0 * big.numel() / (ms_pc * 1e-3) / 1e9
     del big, y_big
-
-    for _ in range(args.warmup):
-        step()
-    torch.cuda.synchronize(dev)
-    barrier(world)
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize(dev)
-    barrier(world)
-    elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
-    value = world * elems_per_step * args.steps / elapsed / 1e9
-
-    recon = None
-    recon_state = None
-    recon_configs = None
-    if not args.no_recon:
-        from shiftedscalequantization_amd.recon_bench import run_recon_bench
-        want_cpu = world == 1 and rank == 0 and not args.no_cpu_baseline
-        recon = run_recon_bench(dev, world, rank, iters=args.recon_iters,
-                                cpu_sample=64 if want_cpu else 0)
-        recon_state = recon.pop("_cpu_state", None)
-        if not args.no_recon_configs:
-            from shiftedscalequantization_amd.recon_bench import run_recon_configs
-            recon_configs = run_recon_configs(dev, world, rank, iters=args.recon_iters)
-
-    validation = None
-    if not args.no_validate:
-        from shiftedscalequantization_amd.validate_bench import run_validate_bench
-        validation = run_validate_bench(dev, world, rank)
-        el = max_over_ranks(validation.pop("_elapsed_s"), world, dev)
-        validation["images_per_s"] = round(world * validation["_images"] / el, 1)
-        validation.pop("_images")
-
-    out = {
-        "metric": "Gelem/s shifted-scale q/dq + recon iters/s, ResNet-18 W2A4; top-1 vs ref",
-        "value": round(value, 3),
-        "unit": "Gelem/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (ReLU(N(0,1)) activation cache, N(0,0.02^2) ResNet-18-shaped weights)",
-        "config": {"workload": "resnet18 W2A4 bias_cal+bias_ch_quant, 1024 calib samples: A4 "
-                               "per-tensor q/dq of act [1024,64,56,56] + W2 per-channel q/dq of "
-                               "all 21 conv/fc weights (8-bit stem/head)",
-                   "elems_per_step_per_rank": elems_per_step, "parallelism": f"dp{world}"},
-        # how the ranks came to be and what the process group saw (n_gpus is the latter)
-        "launch": {"launcher": os.environ.get("SSQ_LAUNCHER",
-                                              "external" if "WORLD_SIZE" in os.environ else "none"),
-                   "world_size_backend": dist.get_world_size() if world > 1 else 1,
-                   "allreduce_backend": dist.get_backend() if world > 1 else None,
-                   "devices_visible": torch.cuda.device_count()},
+    return {
         "roofline": {"bound": "hbm",
                      "kernel": "fq_fwd_pt_ride (ssq_fq_fwd per-tensor A4 with the 21 weights' "
                                "ssq_fq_fwd_multi tiles riding on the launch: the whole step)",
@@ -466,6 +513,33 @@ def main():
                                  "achieved": round(pc_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                  "frac": round(pc_gbs / HBM_PEAK_GBS, 4), "kernel_ms": round(ms_pc, 4)},
     }
+
+
+def full_report(out, args, dev, world, rank, act, d_a, z_a):
+    """--full, after the timed region: the reconstruction loops (`recon`, `recon_configs`)
+    with their committed rooflines, the validation pass and the CPU baselines, added to the
+    result line `out`."""
+    recon = None
+    recon_state = None
+    recon_configs = None
+    if not args.no_recon:
+        from shiftedscalequantization_amd.recon_bench import run_recon_bench
+        want_cpu = world == 1 and rank == 0 and not args.no_cpu_baseline
+        recon = run_recon_bench(dev, world, rank, iters=args.recon_iters,
+                                cpu_sample=64 if want_cpu else 0)
+        recon_state = recon.pop("_cpu_state", None)
+        if not args.no_recon_configs:
+            from shiftedscalequantization_amd.recon_bench import run_recon_configs
+            recon_configs = run_recon_configs(dev, world, rank, iters=args.recon_iters)
+
+    validation = None
+    if not args.no_validate:
+        from shiftedscalequantization_amd.validate_bench import run_validate_bench
+        validation = run_validate_bench(dev, world, rank)
+        el = max_over_ranks(validation.pop("_elapsed_s"), world, dev)
+        validation["images_per_s"] = round(world * validation["_images"] / el, 1)
+        validation.pop("_images")
+
     if recon is not None:
         rr = recon_roofline()
         if rr is not None:
@@ -489,10 +563,6 @@ def main():
         out["validation"] = validation
     if world == 1 and rank == 0 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(act, d_a, z_a, args.cpu_seconds, recon_state)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

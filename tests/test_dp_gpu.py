@@ -156,7 +156,7 @@ def test_bench_self_launches_two_ranks():
     root = os.path.dirname(HERE)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
                         "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-validate", "--recon-iters", "8"],
+                        "--full", "--no-cpu-baseline", "--no-validate", "--recon-iters", "8"],
                        env=env, cwd=root, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]

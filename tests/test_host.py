@@ -358,6 +358,46 @@ def test_eight_rccl_ranks_map_to_distinct_devices(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
+def test_bench_dump_outputs_is_a_fixed_sample(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: every weight output whole, the activation output as the
+    same head + seeded picks + tail of the flat tensor on every call (float32 .npy), and a
+    tensor no larger than the sample whole."""
+    import importlib
+    import sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_ACT_EDGE", 8)
+    monkeypatch.setattr(bench, "DUMP_ACT_RANDOM", 32)
+    act = torch.arange(5 * 7 * 11, dtype=torch.float32).reshape(5, 7, 11)
+    ws = [torch.full((3, 2), 1.5), torch.arange(4, dtype=torch.float32)]
+    bench.dump_outputs(str(tmp_path / "a"), act, ws)
+    bench.dump_outputs(str(tmp_path / "b"), act, ws)
+    assert sorted(os.listdir(tmp_path / "a")) == ["act_qdq_sample.npy", "w00_qdq.npy", "w01_qdq.npy"]
+    a, b = (np.load(tmp_path / d / "act_qdq_sample.npy") for d in "ab")
+    assert a.dtype == np.float32 and a.shape == (48,) and np.array_equal(a, b)
+    assert np.array_equal(a[:8], np.arange(8)) and np.array_equal(a[-8:], np.arange(377, 385))
+    mid = a[8:-8]                      # the values are their own flat indices
+    assert np.all(np.diff(mid) >= 0) and mid.min() >= 8 and mid.max() < 377 and len(set(mid)) > 16
+    for i, w in enumerate(ws):
+        assert np.array_equal(np.load(tmp_path / "a" / f"w{i:02d}_qdq.npy"), w.numpy())
+    bench.dump_outputs(str(tmp_path / "c"), act.reshape(-1)[:40], [])
+    assert np.array_equal(np.load(tmp_path / "c" / "act_qdq_sample.npy"), np.arange(40))
+
+
+def test_bench_plain_run_skips_the_full_report(monkeypatch):
+    """The options of a plain run: `--full` and `--dump-outputs` are off by default."""
+    import importlib
+    import sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
 def test_collective_stays_outside_graph_capture(monkeypatch):
     """At world > 1 the reconstruction iteration is captured as two HIP graphs around the
     gradient bucket's all-reduce (_engine.IterationGraph): the body's kernels are captured,

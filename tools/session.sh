@@ -6,7 +6,7 @@
 # Steps, run in the order given; the first failure, abort, segfault or time limit ends the
 # session (no later GPU step runs after it):
 #   tests     pytest -m gpu (parity log parity_TAG.jsonl) + smoke()   [TESTS_K: a -k filter]
-#   bench     python bench.py (the driver's default line)              -> bench_TAG.log
+#   bench     python bench.py --full (every figure of the line)        -> bench_TAG.log
 #   trace     rocprofv3 kernel trace of bench.py: K1 launch stats, the ResNet-18 recon
 #             roofline JSON, the iteration anatomy                      -> k1_trace / recon_roofline / iter_anatomy
 #   cfgtrace  rocprofv3 kernel trace of BASELINE configs 3-5's loops (tools/recon_configs_trace.py)
@@ -43,14 +43,14 @@ step_tests() {
 
 step_bench() {
   cd $R
-  timeout -k 10 600 python bench.py > $OUT/bench_$TAG.log 2>&1 || fail "bench failed" $OUT/bench_$TAG.log
+  timeout -k 10 600 python bench.py --full > $OUT/bench_$TAG.log 2>&1 || fail "bench failed" $OUT/bench_$TAG.log
   tail -1 $OUT/bench_$TAG.log | cut -c1-300
 }
 
 step_trace() {
   cd /tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o bench \
-    -- python3 $R/bench.py --no-cpu-baseline --no-validate --no-recon-configs --recon-iters 100 \
+    -- python3 $R/bench.py --full --no-cpu-baseline --no-validate --no-recon-configs --recon-iters 100 \
     > $OUT/prof_bench_$TAG.log 2>&1 || fail "rocprof bench failed" $OUT/prof_bench_$TAG.log
   local KT=$(find $OUT/prof_$TAG -name "*kernel_trace.csv" | head -1)
   python3 $R/tools/k1_trace_stats.py "$KT" > $OUT/k1_trace_$TAG.json 2>&1
@@ -76,7 +76,7 @@ step_cfgtrace() {
 
 step_pmc() {
   cd /tmp
-  local B="$R/bench.py --no-recon --no-validate --no-cpu-baseline --steps 3 --warmup 1"
+  local B="$R/bench.py --full --no-recon --no-validate --no-cpu-baseline --steps 3 --warmup 1"
   timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$TAG -o f \
     -- python3 $B > $OUT/pmc_fetch_$TAG.log 2>&1 || fail "fetch pass failed" $OUT/pmc_fetch_$TAG.log
   timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_$TAG -o w \
@@ -113,7 +113,7 @@ step_fc() {
 
 step_dist2() {
   cd $R
-  timeout -k 10 400 python bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --no-cpu-baseline \
+  timeout -k 10 400 python bench.py --gpus 2 --dist-backend gloo --steps 20 --warmup 5 --full --no-cpu-baseline \
     --no-recon-configs --recon-iters 30 > $OUT/dist2_$TAG.log 2>&1 || fail "dist2 failed" $OUT/dist2_$TAG.log
   tail -1 $OUT/dist2_$TAG.log | cut -c1-200
 }
