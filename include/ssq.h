@@ -364,6 +364,28 @@ int ssq_fc_recon_iter(const float* x_cache, const float* tgt_cache, const int64_
                       int64_t Ci, float one_minus_beta1, float beta2, float one_minus_beta2,
                       float eps, float* exp_avg, float* exp_avg_sq, float* g, float* gv_out,
                       float* loss_out, void* ws, size_t ws_bytes, ssq_stream_t stream);
+/* The same iteration split where V's gradient exists, for data parallel: the reference
+ * all-reduces the gradients between err.backward() and optimizer.step()
+ * (block_recon.py:100-102).  ssq_fc_recon_grad runs the forward launch and then the
+ * backward up to V's gradient, written to gv_out (required; 4-B aligned is enough, so it
+ * may be a slice of a flat all-reduce bucket); V, What and Adam's moments are only read or
+ * not touched.  Shapes, alignment, slot and workspace as ssq_fc_recon_iter.
+ * ssq_fc_recon_apply is the rest, one elementwise launch: V's Adam step from `grad` (any
+ * gradient of V's shape, e.g. the reduced one; 4-B aligned, read as float4 when 16-B
+ * aligned) and What = AdaRound(W, V) of the updated V for the next ssq_fc_recon_grad; only
+ * Adam's words of `slot` (after its bs indices and (lambda, b)) are read.  W, V, What and
+ * the moments 16-B aligned.  The per-element operations of the pair are
+ * ssq_fc_recon_iter's: fed its own gv_out, the pair gives that call's bits.           */
+int ssq_fc_recon_grad(const float* x_cache, const float* tgt_cache, const int64_t* slot,
+                      int64_t bs, const float* W, const float* V, const float* What,
+                      const float* delta, const float* zp, int qmin, int qmax,
+                      const float* bias, int64_t Co, int64_t Ci, float* g, float* gv_out,
+                      float* loss_out, void* ws, size_t ws_bytes, ssq_stream_t stream);
+int ssq_fc_recon_apply(const float* W, float* V, float* What, const float* delta,
+                       const float* zp, int qmin, int qmax, int64_t Co, int64_t Ci,
+                       const int64_t* slot, int64_t bs, const float* grad,
+                       float one_minus_beta1, float beta2, float one_minus_beta2, float eps,
+                       float* exp_avg, float* exp_avg_sq, ssq_stream_t stream);
 
 /* ---------------------------------------------------------------- K13 fused epilogue
  * QuantModule conv bias add (quant_layer.py:250), the block's residual add and ReLU

@@ -1623,6 +1623,59 @@ def fc_recon_iter(x_cache, tgt_cache, slot, bs, w, v, what, delta, zp, n_bits, b
     return loss, g
 
 
+def _fc_state(name, w, tensors):
+    """[Co, Ci] of the fc weight after checking the contiguous fp32 [Co, Ci] arrays."""
+    Co, Ci = int(w.shape[0]), int(w.shape[1])
+    for t, nm in tensors:
+        A.check(t, nm)
+        if not t.is_contiguous() or t.numel() != Co * Ci:
+            raise A.SSQError(f"{name}: {nm} must be contiguous [Co, Ci]")
+    return Co, Ci
+
+
+def fc_recon_grad(x_cache, tgt_cache, slot, bs, w, v, what, delta, zp, n_bits, bias, gv_out,
+                  g=None, loss_out=None):
+    """fc_recon_iter up to V's gradient (ssq_fc_recon_grad): the forward on what, the p = 2
+    loss and its gradient, dW and V's gradient with the rounding regulariser into gv_out --
+    a contiguous tensor of V's size, which may be a slice of a flat all-reduce bucket (4-B
+    aligned).  v, what and Adam's state are not written; fc_recon_apply does the rest once
+    the gradient is reduced.  Returns (loss, g)."""
+    xc, xp = fptr(x_cache, "x cache")
+    tc, tp = fptr(tgt_cache, "target cache")
+    Co, Ci = _fc_state("fc_recon_grad", w, ((w, "weight"), (v, "V"), (what, "W^"),
+                                            (gv_out, "V gradient")))
+    if xc.shape[1:].numel() != Ci or tc.shape[1:].numel() != Co or slot.dtype != torch.int64 \
+            or not slot.is_contiguous() or slot.numel() < bs + 2:
+        raise A.SSQError("fc_recon_grad: shapes / slot")
+    d, dp = fptr(delta.detach().reshape(-1), "delta")
+    z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
+    bt, bp = fptr(bias.detach().reshape(-1), "bias") if bias is not None else (None, None)
+    dev_ = w.device
+    g = torch.empty(bs, Co, device=dev_) if g is None else g
+    loss = torch.empty(1, device=dev_) if loss_out is None else loss_out
+    ws, wsn = workspace(query("ssq_fc_recon_workspace_size", Co, Ci, bs), dev_, "fc")
+    call("ssq_fc_recon_grad", xp, tp, _vp(slot), bs, _vp(w), _vp(v), _vp(what), dp, zpp, 0,
+         2 ** n_bits - 1, bp, Co, Ci, _vp(g), _vp(gv_out), _vp(loss), ws, wsn, stream_of(w))
+    return loss, g
+
+
+def fc_recon_apply(w, v, what, delta, zp, n_bits, slot, bs, grad, exp_avg, exp_avg_sq, beta1,
+                   beta2, eps):
+    """The rest of fc_recon_iter after fc_recon_grad (ssq_fc_recon_apply): V's Adam step from
+    `grad` (the reduced gradient; contiguous, V's size, 4-B aligned) with the step constants
+    of `slot`, and what = AdaRound(w, v) of the updated V for the next fc_recon_grad."""
+    Co, Ci = _fc_state("fc_recon_apply", w, ((w, "weight"), (v, "V"), (what, "W^"),
+                                             (grad, "V gradient"), (exp_avg, "exp_avg"),
+                                             (exp_avg_sq, "exp_avg_sq")))
+    if slot.dtype != torch.int64 or not slot.is_contiguous() or slot.numel() < bs + 2:
+        raise A.SSQError("fc_recon_apply: slot")
+    d, dp = fptr(delta.detach().reshape(-1), "delta")
+    z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
+    call("ssq_fc_recon_apply", _vp(w), _vp(v), _vp(what), dp, zpp, 0, 2 ** n_bits - 1, Co, Ci,
+         _vp(slot), bs, _vp(grad), float(1 - beta1), float(beta2), float(1 - beta2), float(eps),
+         _vp(exp_avg), _vp(exp_avg_sq), stream_of(w))
+
+
 def adam_arm(params, exp_avgs, exp_avg_sqs, beta1, beta2, eps, hyper):
     """Arm one Adam step of `params` (include/ssq.h ssq_adam_arm): the next prepared alpha
     backward on the current stream applies it where the gradients are finalised, when it

@@ -191,19 +191,44 @@ def _eager_loop(opt_params, loss_func, feeder, bucket, cached_grads, block, iter
 
 
 # BRECQ's layer loop on a Linear layer (the network's last layer, 20000 iterations in the
-# end-to-end flow), AdaRound weight phase at world 1: the whole iteration as the fused K19
+# end-to-end flow), AdaRound weight phase: at world 1 the whole iteration as the fused K19
 # pair (kernels.fc_recon_iter) instead of gather / AdaRound / GEMM / loss / GEMM / AdaRound
 # backward / Adam launches.  A/B knob: SSQ_FUSE_FC=0.
 FUSE_FC = _FAST and os.environ.get("SSQ_FUSE_FC", "1") != "0"
 
 
+def _fc_split_mode(value):
+    """SSQ_FC_SPLIT -> 'auto' | 'on' | 'off'."""
+    modes = {"auto": "auto", "": "auto", "1": "on", "on": "on", "0": "off", "off": "off"}
+    try:
+        return modes[str(value).strip().lower()]
+    except KeyError:
+        raise ValueError(f"SSQ_FC_SPLIT: expected auto, 1 or 0, got {value!r}") from None
+
+
+# The same iteration under data parallel: K19's second launch split where V's gradient
+# exists (kernels.fc_recon_grad / fc_recon_apply, three launches), so that the bucket's
+# all-reduce sits between the backward and Adam as in the reference (block_recon.py:100-102).
+# 'auto': exactly when a bucket exists (world 1 stays on fc_recon_iter); 'on': at world 1
+# too (A/B runs, tests); 'off': never -- world > 1 then runs the unfused iteration.
+FC_SPLIT = _fc_split_mode(os.environ.get("SSQ_FC_SPLIT", "auto"))
+
+
+def _noop():
+    pass
+
+
 def _fc_fused_body(layer, qmodules, act_quant, p, bucket, feeder, optimizer, last):
-    """The fused fc iteration's body, or None when the loop is not one it covers: a
-    Linear QuantModule alone, soft AdaRound with per-row delta, no activation, no act
-    quantizer, no gamma^z / phi^z affine, p = 2, world 1, batch <= 64, C_in a multiple of 64
-    up to 4096."""
+    """The fused fc iteration as a (pre, post) pair of the loop's body, or None when the
+    loop is not one it covers: a Linear QuantModule alone, soft AdaRound with per-row delta,
+    no activation, no act quantizer, no gamma^z / phi^z affine, p = 2, batch <= 64, C_in a
+    multiple of 64 up to 4096.  Without a bucket pre is the whole K19 iteration and post
+    nothing; in the split form (FC_SPLIT) pre ends at V's gradient -- written into V's slice
+    of the bucket once that is built -- and post is Adam and the next W^ from v.grad, the
+    collective between them being the loop's (IterationGraph's two graphs)."""
     import torch.nn.functional as F
-    if not (FUSE_FC and not act_quant and bucket is None and float(p) == 2.0
+    split = FC_SPLIT == "on" or (FC_SPLIT == "auto" and bucket is not None)
+    if not (FUSE_FC and not act_quant and (bucket is None or split) and float(p) == 2.0
             and ITER_PROBE[0] is None      # a probe may rewrite V: W^ is carried over
             and len(qmodules) == 1 and qmodules[0] is layer and isinstance(layer, QuantModule)):
         return None
@@ -238,15 +263,32 @@ def _fc_fused_body(layer, qmodules, act_quant, p, bucket, feeder, optimizer, las
     with torch.no_grad():
         what = K.adaround(v, w, q.delta, q.zero_point, q.n_bits, False, False).detach().clone()
 
+    def words():
+        return feeder.chunk_dev[feeder.slot] if feeder.slot is not None else feeder._dev
+
     def body():
-        src = feeder.chunk_dev[feeder.slot] if feeder.slot is not None else feeder._dev
-        loss, _ = K.fc_recon_iter(feeder.inp, feeder.out, src, feeder.bs, w.detach(), v.data,
+        loss, _ = K.fc_recon_iter(feeder.inp, feeder.out, words(), feeder.bs, w.detach(), v.data,
                                   what, q.delta, q.zero_point, q.n_bits, bias, st["exp_avg"],
                                   st["exp_avg_sq"], b1, b2, eps, g=gbuf, gv_out=gv)
         v.grad = gv
         last['rec'] = loss
         last['step'] = True
-    return body
+
+    def pre():
+        # V's slice of the bucket once it is built (the first eager iteration hands gv over
+        # through .grad: bucket.allreduce_ builds the bucket and copies it in)
+        dst = gv if bucket is None else bucket.into_map().get(v.data_ptr(), gv)
+        loss, _ = K.fc_recon_grad(feeder.inp, feeder.out, words(), feeder.bs, w.detach(), v.data,
+                                  what, q.delta, q.zero_point, q.n_bits, bias, dst, g=gbuf)
+        v.grad = dst
+        last['rec'] = loss
+        last['step'] = True
+
+    def post():
+        K.fc_recon_apply(w.detach(), v.data, what, q.delta, q.zero_point, q.n_bits, words(),
+                         feeder.bs, v.grad, st["exp_avg"], st["exp_avg_sq"], b1, b2, eps)
+
+    return (pre, post) if split else (body, _noop)
 
 
 def _fast_loop(block, qmodules, opt_params, loss_func, feeder, bucket, iters, act_quant, lr, p,
@@ -351,7 +393,9 @@ def _fast_loop(block, qmodules, opt_params, loss_func, feeder, bucket, iters, ac
 
     fc_body = _fc_fused_body(block, qmodules, act_quant, p, bucket, feeder, optimizer, last)
     if fc_body is not None:
-        body_pre = fc_body          # gather, forward, loss, backward and Adam: two launches
+        # gather, forward, loss, backward and Adam: two launches, or three around the
+        # bucket's all-reduce
+        body_pre, body_post = fc_body
 
     ws_cache = {}
     with contextlib.ExitStack() as stack:

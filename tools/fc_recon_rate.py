@@ -2,7 +2,13 @@
 layer_reconstruction on ResNet-18's last QuantModule, batch 32, synthetic data): the
 end-to-end flow's 20000-iteration loop on a tiny layer, where the host's per-iteration work
 can outlast the GPU's.  Rate = 2000 / (T(2200) - T(200)); then a cProfile of one
-2200-iteration run (top host functions by own time).  Usage: python tools/fc_recon_rate.py"""
+2200-iteration run (top host functions by own time).  Usage: python tools/fc_recon_rate.py
+
+--split-ab [--rounds R] [--out FILE]: the iteration's three forms at world 1, us per iteration
+of back-to-back chunk-graph replays (block_recon.CHUNK_PROBE; GPU work and launch boundaries,
+no host work or collective), alternated R times in one process: the unfused launches
+(FUSE_FC off: the world > 1 body without the split), the split pair (FC_SPLIT on:
+ssq_fc_recon_grad + ssq_fc_recon_apply) and K19 (ssq_fc_recon_iter)."""
 import cProfile
 import io
 import json
@@ -41,7 +47,50 @@ def run(dev, cali, iters):
     return time.perf_counter() - t0
 
 
+FORMS = (("unfused", False, "off"), ("split", True, "on"), ("k19", True, "off"))
+
+
+def split_ab(rounds, out_path):
+    from shiftedscalequantization_amd.build import provenance
+    from shiftedscalequantization_amd.quant import block_recon as BR
+    dev = torch.device("cuda")
+    cali = torch.randn(256, 3, 224, 224, device=dev)
+    probe = BR.ChunkGraph.probe
+    BR.ChunkGraph.probe = lambda self: probe(self, reps=200)      # 5000 iterations a window
+    prev = (BR.FUSE_FC, BR.FC_SPLIT)
+    lines = []
+    try:
+        for r in range(rounds + 1):                               # round 0 warms every form up
+            for name, fuse, split in FORMS:
+                BR.FUSE_FC, BR.FC_SPLIT = fuse, split
+                BR.CHUNK_PROBE[0] = False
+                run(dev, cali, 300)
+                us, BR.CHUNK_PROBE[0] = BR.CHUNK_PROBE[0], None
+                if r:
+                    lines.append(json.dumps({"round": r, "form": name,
+                                             "chunk_replay_us_per_iter": round(us, 2)}))
+                    print(lines[-1], flush=True)
+    finally:
+        BR.ChunkGraph.probe = probe
+        BR.FUSE_FC, BR.FC_SPLIT = prev
+    med = {}
+    for name, _, _ in FORMS:
+        v = sorted(json.loads(ln)["chunk_replay_us_per_iter"] for ln in lines
+                   if json.loads(ln)["form"] == name)
+        med[name] = {"median": v[len(v) // 2], "min": v[0], "max": v[-1]}
+    lines.append(json.dumps({"summary_us_per_iter": med, "iters_per_chunk": BR.CHUNK_ITERS,
+                             "shape": "512 -> 1000, batch 32, 8-bit", **provenance()}))
+    print(lines[-1])
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
+    if "--split-ab" in sys.argv:
+        arg = lambda k, d: sys.argv[sys.argv.index(k) + 1] if k in sys.argv else d  # noqa: E731
+        return split_ab(int(arg("--rounds", 3)), arg("--out", None))
     dev = torch.device("cuda")
     cali = torch.randn(256, 3, 224, 224, device=dev)
     run(dev, cali, 20)
