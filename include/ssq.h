@@ -326,6 +326,40 @@ int ssq_lp_loss_rows(const float* pred, const float* tgt_cache, const int64_t* i
                      const float* gscale, int relu_mask, void* ws, size_t ws_bytes,
                      ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- K20 Fisher-weighted losses
+ * BRECQ's opt_mode 'fisher_diag' / 'fisher_full' (block_recon.py:156-162, layer_recon.py:
+ * 144-148): value and gradient wrt pred, with fis = the cached |dKL/d(output)| + 1 rows
+ * (data_utils.py:40-71).  loss_out / grad / gscale / relu_mask / ws, the deterministic loss
+ * reduction and the deferral rules are ssq_lp_loss's (the finalize is the same kind of task);
+ * the _rows forms read BOTH the target and the Fisher rows in place from [N_cache, row]
+ * caches through the same idx, as ssq_lp_loss_rows reads its target (n % row == 0, n < 2^31).
+ *   fisher_diag: loss = sum (pred-tgt)^2 * fis^2 / M, M = n / C (2-D predictions included);
+ *     grad = gscale * ((1/M * fis*fis) * (2*d)), d = pred - tgt: torch autograd's operations
+ *     in its order, each rounded to fp32 -- bit-identical to the reference's backward.
+ *     One pass, 16 B/elem.
+ *   fisher_full: a = |pred-tgt|, s_k = sum over sample k of a*|fis| (N samples of n / N
+ *     elements), loss = sum_k s_k * sum(a*|fis|) / (100*n),
+ *     grad = gscale * (2*s_k/(100*n) * |fis| * sgn(d)), sgn(0) = 0.  Two launches: the
+ *     per-(sample, chunk) partials of s_k in ws (doubles, fixed order), then the gradient and
+ *     the loss partials.  ndim is the prediction's rank: anything but 4 is SSQ_E_ARG, as the
+ *     reference's torch.sum(..., (1, 2, 3)) raises.  idx holds N entries.
+ * ssq_fisher_loss_workspace_size(n, N): bytes either loss needs for n elements in N samples. */
+size_t ssq_fisher_loss_workspace_size(int64_t n, int64_t N);
+int ssq_fisher_diag_loss(const float* pred, const float* tgt, const float* fis, int64_t n,
+                         int64_t M, float* loss_out, float* grad, const float* gscale,
+                         int relu_mask, void* ws, size_t ws_bytes, ssq_stream_t stream);
+int ssq_fisher_diag_loss_rows(const float* pred, const float* tgt_cache, const float* fis_cache,
+                              const int64_t* idx, int64_t row, int64_t n, int64_t M,
+                              float* loss_out, float* grad, const float* gscale, int relu_mask,
+                              void* ws, size_t ws_bytes, ssq_stream_t stream);
+int ssq_fisher_full_loss(const float* pred, const float* tgt, const float* fis, int64_t n,
+                         int64_t N, int ndim, float* loss_out, float* grad, const float* gscale,
+                         int relu_mask, void* ws, size_t ws_bytes, ssq_stream_t stream);
+int ssq_fisher_full_loss_rows(const float* pred, const float* tgt_cache, const float* fis_cache,
+                              const int64_t* idx, int64_t n, int64_t N, int ndim,
+                              float* loss_out, float* grad, const float* gscale, int relu_mask,
+                              void* ws, size_t ws_bytes, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- K14 batch gather
  * dst_k[r] = src_k[idx[r]] for two sources at once (cached block input and output,
  * layer_recon_fused_shiftedScale.py:95-97). src1/dst1 may be NULL.                    */

@@ -9,6 +9,7 @@ Flow (the README flags mapped onto the snapshot's code):
   2. --bias_ch_quant: every residual block is reconstructed with the fused shifted-scale
      loop (ChannelQuant 'adaShift', learns the input-channel shift group R); --bias_cal
      additionally learns gamma^z / phi^z.  Otherwise BRECQ AdaRound reconstruction.
+     --opt_mode fisher_diag | fisher_full: BRECQ's loops use the Fisher-weighted loss.
   3. --act_quant: activation deltas initialised and reconstructed BRECQ-style (LSQ, p=2.4).
   4. Top-1 on --data_path/val.pt if present ("Weight quantization accuracy",
      "Full quantization (W{w}A{a}) accuracy"); otherwise the reconstruction losses.
@@ -34,7 +35,8 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from shiftedscalequantization_amd import drivers as D  # noqa: E402
-from shiftedscalequantization_amd.cli import parse_args, seed_all, validate_model  # noqa: E402
+from shiftedscalequantization_amd.cli import (parse_args, recon_kwargs, seed_all,  # noqa: E402
+                                              validate_model)
 from shiftedscalequantization_amd.parallel_dp import replicated, shard_rows  # noqa: E402
 from shiftedscalequantization_amd.quant import QuantModule  # noqa: E402
 
@@ -125,13 +127,9 @@ def main(argv=None):
         # the remaining single layers (fc) with BRECQ AdaRound
         last = [m for m in qnn.modules() if isinstance(m, QuantModule)][-1]
         from shiftedscalequantization_amd.quant import layer_reconstruction
-        layer_reconstruction(qnn, last, cali, batch_size=bs, iters=args.iters_w, weight=0.01,
-                             asym=True, b_range=(args.b_start, args.b_end), warmup=args.warmup,
-                             act_quant=False, opt_mode='mse')
+        layer_reconstruction(qnn, last, cali, **dict(recon_kwargs(args, False, bs), weight=0.01))
     else:
-        D.recon_model(qnn, qnn, cali_data=cali, iters=args.iters_w, weight=args.weight, asym=True,
-                      b_range=(args.b_start, args.b_end), warmup=args.warmup, act_quant=False,
-                      opt_mode='mse', batch_size=bs)
+        D.recon_model(qnn, qnn, cali_data=cali, **recon_kwargs(args, False, bs))
     torch.cuda.synchronize(device)
     phases['weight_recon'] = time.time() - t_phase
     t_phase = time.time()
@@ -147,8 +145,7 @@ def main(argv=None):
             # (Brecq/main_imagenet_dist.py:210-211) so the act phase starts replicated
             qnn.synchorize_activation_statistics()
         qnn.disable_network_output_quantization()
-        D.recon_model(qnn, qnn, cali_data=cali, iters=args.iters_a, act_quant=True, opt_mode='mse',
-                      lr=args.lr, p=args.p, batch_size=bs)
+        D.recon_model(qnn, qnn, cali_data=cali, **recon_kwargs(args, True, bs))
         qnn.set_quant_state(weight_quant=True, act_quant=True)
         torch.cuda.synchronize(device)
         phases['act_recon'] = time.time() - t_phase

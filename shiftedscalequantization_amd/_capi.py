@@ -71,6 +71,13 @@ SIGNATURES = {
     "ssq_lp_loss_workspace_size": (_sz, [_i64]),
     "ssq_lp_loss": (_i, [_p, _p, _i64, _i64, _f, _p, _p, _p, _i, _p, _sz, _p]),
     "ssq_lp_loss_rows": (_i, [_p, _p, _p, _i64, _i64, _i64, _f, _p, _p, _p, _i, _p, _sz, _p]),
+    "ssq_fisher_loss_workspace_size": (_sz, [_i64, _i64]),
+    "ssq_fisher_diag_loss": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _p, _i, _p, _sz, _p]),
+    "ssq_fisher_diag_loss_rows": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _i, _p, _sz,
+                                       _p]),
+    "ssq_fisher_full_loss": (_i, [_p, _p, _p, _i64, _i64, _i, _p, _p, _p, _i, _p, _sz, _p]),
+    "ssq_fisher_full_loss_rows": (_i, [_p, _p, _p, _p, _i64, _i64, _i, _p, _p, _p, _i, _p, _sz,
+                                       _p]),
     "ssq_gather_rows2": (_i, [_p, _p, _i64, _p, _p, _i64, _p, _i64, _p]),
     "ssq_gemm_col_epilogue": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _i] + [_i64] * 8 + [_p, _p]),
     "ssq_fc_recon_workspace_size": (_sz, [_i64, _i64, _i64]),

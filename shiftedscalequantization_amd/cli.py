@@ -48,6 +48,10 @@ def build_parser():
     p.add_argument('--b_end', default=2, type=int)
     p.add_argument('--warmup', default=0.2, type=float)
     p.add_argument('--step', default=20, type=int)
+    p.add_argument('--opt_mode', default='mse', type=str,
+                   choices=['mse', 'fisher_diag', 'fisher_full'],
+                   help="BRECQ's reconstruction loss: squared error, or weighted by the cached "
+                        "|dKL/d(output)| + 1 (Fisher diagonal / per-sample full approximation)")
     # activation calibration
     p.add_argument('--iters_a', default=5000, type=int)
     p.add_argument('--lr', default=4e-4, type=float)
@@ -84,6 +88,17 @@ def parse_args(argv=None):
     if a.run_device:
         a.device_gpu = a.run_device
     return a
+
+
+def recon_kwargs(args, act_quant, batch_size=32):
+    """The keyword arguments main_imagenet.py hands to BRECQ's block / layer reconstruction
+    (Brecq/main_imagenet.py:196-241): the AdaRound weight phase, or the act-delta phase."""
+    if act_quant:
+        return dict(iters=args.iters_a, act_quant=True, opt_mode=args.opt_mode, lr=args.lr,
+                    p=args.p, batch_size=batch_size)
+    return dict(iters=args.iters_w, weight=args.weight, asym=True,
+                b_range=(args.b_start, args.b_end), warmup=args.warmup, act_quant=False,
+                opt_mode=args.opt_mode, batch_size=batch_size)
 
 
 def seed_all(seed=1029, deterministic=True):

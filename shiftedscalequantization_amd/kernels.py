@@ -965,6 +965,84 @@ def lp_loss(pred, tgt, p=2.0, reduction="none"):
     return LpLossFn.apply(pred, tgt, float(p), reduction)
 
 
+# ------------------------------------------------------------------ K20 Fisher losses
+FISHER_MODES = ("fisher_diag", "fisher_full")
+
+
+def fisher_loss_and_grad(pred, tgt, fis, mode, relu_mask=False, want_grad=True, loss_out=None,
+                         gscale=None, want_loss=True):
+    """BRECQ's Fisher-weighted reconstruction loss (block_recon.py:156-162) and d/d pred in
+    one entry-point call: mode 'fisher_diag' (one pass; the gradient bit-identical to
+    autograd's) or 'fisher_full' (two launches; 4-D pred only).  tgt and fis are batches
+    shaped like pred, or both Rows views with the same idx (read in place).  relu_mask as
+    lp_loss_and_grad's.  Returns (loss [1] or None, grad or None)."""
+    if mode not in FISHER_MODES:
+        raise ValueError('Not supported reconstruction loss function: {}'.format(mode))
+    pred, pp = fptr(pred.detach(), "pred")
+    n, N = pred.numel(), int(pred.shape[0])
+    loss = None
+    if want_loss:
+        loss = torch.empty(1, dtype=torch.float32, device=pred.device) if loss_out is None \
+            else loss_out
+    grad = torch.empty_like(pred) if want_grad else None
+    ws, wsn = workspace(query("ssq_fisher_loss_workspace_size", n, N), pred.device, "fisher")
+    tail = (_vp(loss), _vp(grad), _vp(gscale), int(bool(relu_mask)), ws, wsn, stream_of(pred))
+    rows = isinstance(tgt, Rows)
+    if rows != isinstance(fis, Rows):
+        raise A.SSQError("fisher_loss: tgt and fis are both batches or both Rows")
+    if rows:
+        tc, tp = fptr(tgt.cache.detach(), "tgt cache")
+        fc, fp = fptr(fis.cache.detach(), "fis cache")
+        idx = tgt.idx
+        row = tc[0].numel()
+        if fis.idx is not idx and fis.idx.data_ptr() != idx.data_ptr():
+            raise A.SSQError("fisher_loss: the target and Fisher rows share one idx")
+        if idx.dtype != torch.int64 or idx.device != pred.device or not idx.is_contiguous() or \
+                idx.numel() != N or N * row != n or \
+                tuple(tc.shape[1:]) != tuple(pred.shape[1:]) or \
+                tuple(fc.shape[1:]) != tuple(pred.shape[1:]):
+            raise A.SSQError("fisher_loss: Rows target / Fisher rows do not match pred")
+        if mode == "fisher_diag":
+            call("ssq_fisher_diag_loss_rows", pp, tp, fp, _vp(idx), row, n, _lp_M(pred, "none"),
+                 *tail)
+        else:
+            call("ssq_fisher_full_loss_rows", pp, tp, fp, _vp(idx), n, N, pred.dim(), *tail)
+        return loss, grad
+    if tuple(tgt.shape) != tuple(pred.shape) or tuple(fis.shape) != tuple(pred.shape):
+        raise A.SSQError("fisher_loss: tgt and fis must be shaped like pred")
+    tgt, tp = fptr(tgt.detach(), "tgt")
+    fis, fp = fptr(fis.detach(), "fis")
+    if mode == "fisher_diag":
+        call("ssq_fisher_diag_loss", pp, tp, fp, n, _lp_M(pred, "none"), *tail)
+    else:
+        call("ssq_fisher_full_loss", pp, tp, fp, n, N, pred.dim(), *tail)
+    return loss, grad
+
+
+class FisherLossFn(torch.autograd.Function):
+    """The Fisher losses for callers outside the device loop (LossFunction.__call__):
+    forward = value only; backward = the gradient pass scaled by the upstream gradient
+    (device scalar).  tgt and fis get no gradient (cached data)."""
+
+    @staticmethod
+    def forward(ctx, pred, tgt, fis, mode):
+        loss, _ = fisher_loss_and_grad(pred, tgt, fis, mode, want_grad=False)
+        ctx.save_for_backward(pred, tgt, fis)
+        ctx.mode = mode
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, tgt, fis = ctx.saved_tensors
+        gs = g.detach().reshape(1).to(torch.float32).contiguous()
+        _, grad = fisher_loss_and_grad(pred, tgt, fis, ctx.mode, want_loss=False, gscale=gs)
+        return grad, None, None, None
+
+
+def fisher_loss(pred, tgt, fis, mode):
+    return FisherLossFn.apply(pred, tgt, fis, mode)
+
+
 def gather_rows2(src0, idx, src1=None, out0=None, out1=None):
     """src[idx] for one or two row-major sources (the cached block input / output)."""
     s0, p0 = fptr(src0, "src0")

@@ -78,6 +78,10 @@ CHUNK_ITERS = int(os.environ.get("SSQ_BRECQ_CHUNK", "25")) if _FAST else 1
 # are not gathered -- the epilogue kernels read them in place by the batch indices
 # (kernels.rows_view, ssq_epilogue_*_rows): no gather launch and no batch copy per iteration
 ROWS_IN_PLACE = CACHE_CONVS and os.environ.get("SSQ_BRECQ_ROWS", "1") != "0"
+# opt_mode 'fisher_diag' / 'fisher_full' on the device loop: the loss pass is K20
+# (kernels.fisher_loss_and_grad) with the target and the Fisher rows read in place; everything
+# else is the MSE loop's.  SSQ_FISHER_FAST=0: the reference's eager loop (_eager_loop) instead.
+FISHER_FAST = os.environ.get("SSQ_FISHER_FAST", "1") != "0"
 
 
 def _input_convs(block, qmodules, x):
@@ -144,17 +148,29 @@ def _reconstruct(model, block, qmodules, cali_data, batch_size, iters, weight, o
         cached_inps, cached_outs = save_inp_oup_data(model, block, cali_data, asym, act_quant,
                                                      batch_size)
         device = next(model.parameters()).device
-        cached_grads = save_grad_data(model, block, cali_data, act_quant, batch_size=batch_size) \
-            if opt_mode != 'mse' else None
         feeder = BatchFeeder(cached_inps, cached_outs, batch_size, device, extra_words=2)
+        fisher = None
+        if opt_mode != 'mse':
+            if opt_mode not in K.FISHER_MODES:
+                raise ValueError('Not supported reconstruction loss function: {}'.format(opt_mode))
+            # the Fisher cache: |dKL/d(output)| + 1 of every cached sample, kept on the device
+            # beside the cached outputs, row for row
+            fisher_cache = save_grad_data(model, block, cali_data, act_quant, batch_size=batch_size)
+            fisher_cache = fisher_cache.to(device=feeder.out.device,
+                                           dtype=torch.float32).contiguous()
+            if tuple(fisher_cache.shape) != tuple(feeder.out.shape):
+                raise ValueError("Fisher cache {} does not match the cached outputs {}".format(
+                    tuple(fisher_cache.shape), tuple(feeder.out.shape)))
+            fisher = (opt_mode, fisher_cache)
+            loss_func.fisher_cache = fisher_cache
         bucket = GradBucket(opt_params, average=dp_average) if (multi_gpu or world() > 1) else None
-        if opt_mode == 'mse' and opt_params[0].is_cuda:
+        if opt_params[0].is_cuda and (fisher is None or FISHER_FAST):
             with frozen_except(block, opt_params):
                 _fast_loop(block, qmodules, opt_params, loss_func, feeder, bucket, iters, act_quant,
                            lr, p, graph)
         else:
-            _eager_loop(opt_params, loss_func, feeder, bucket, cached_grads, block, iters, act_quant,
-                        lr)
+            _eager_loop(opt_params, loss_func, feeder, bucket, fisher[1] if fisher else None, block,
+                        iters, act_quant, lr)
     for m in qmodules:
         if isinstance(m.weight_quantizer, AdaRoundQuantizer):
             m.weight_quantizer.soft_targets = False
@@ -163,8 +179,9 @@ def _reconstruct(model, block, qmodules, cali_data, batch_size, iters, weight, o
 
 
 def _eager_loop(opt_params, loss_func, feeder, bucket, cached_grads, block, iters, act_quant, lr):
-    """The reference's loop (block_recon.py:90-105) as written, for the Fisher losses and
-    host tensors."""
+    """The reference's loop (block_recon.py:90-105) as written, for host tensors and the
+    Fisher losses' A/B (FISHER_FAST off); on the device its Fisher loss is K20 too
+    (LossFunction.__call__)."""
     if not act_quant:
         optimizer, scheduler = torch.optim.Adam(opt_params), None
     else:
@@ -218,16 +235,20 @@ def _noop():
     pass
 
 
-def _fc_fused_body(layer, qmodules, act_quant, p, bucket, feeder, optimizer, last):
+def _fc_fused_body(layer, qmodules, act_quant, p, bucket, feeder, optimizer, last,
+                   opt_mode='mse'):
     """The fused fc iteration as a (pre, post) pair of the loop's body, or None when the
     loop is not one it covers: a Linear QuantModule alone, soft AdaRound with per-row delta,
-    no activation, no act quantizer, no gamma^z / phi^z affine, p = 2, batch <= 64, C_in a
-    multiple of 64 up to 4096.  Without a bucket pre is the whole K19 iteration and post
+    no activation, no act quantizer, no gamma^z / phi^z affine, the MSE loss at p = 2 (K19
+    has no Fisher form: those loops run the unfused iteration), batch <= 64, C_in a multiple
+    of 64 up to 4096.  Without a bucket pre is the whole K19 iteration and post
     nothing; in the split form (FC_SPLIT) pre ends at V's gradient -- written into V's slice
     of the bucket once that is built -- and post is Adam and the next W^ from v.grad, the
     collective between them being the loop's (IterationGraph's two graphs)."""
     import torch.nn.functional as F
     split = FC_SPLIT == "on" or (FC_SPLIT == "auto" and bucket is not None)
+    if opt_mode != 'mse':
+        return None
     if not (FUSE_FC and not act_quant and (bucket is None or split) and float(p) == 2.0
             and ITER_PROBE[0] is None      # a probe may rewrite V: W^ is carried over
             and len(qmodules) == 1 and qmodules[0] is layer and isinstance(layer, QuantModule)):
@@ -302,12 +323,17 @@ def _fast_loop(block, qmodules, opt_params, loss_func, feeder, bucket, iters, ac
     CosineAnnealingLR recursion, value for value) is copied into Adam's device lr.
     Launch savings (module knobs above, bit-identical on or off): deferred finalizes with the
     Adam step riding on them, the block's fused tail, and in the act phase pinned weights and
-    the block-input convs precomputed for every cached sample."""
+    the block-input convs precomputed for every cached sample.
+    A Fisher loss (loss_func.rec_loss, with loss_func.fisher_cache the Fisher cache): the
+    loss pass is K20 instead of K11, reading the Fisher rows in place by the target rows' indices (the same staged words, so the single
+    and the chunk graphs replay as they do for MSE).  The fused tail and K19 have no Fisher
+    form: the block materialises its output and the loss takes the relu_mask or plain route."""
     if ITER_HOOK is not None:
         ITER_HOOK(-1, iters)
+    fisher = None if loss_func.rec_loss == 'mse' else (loss_func.rec_loss, loss_func.fisher_cache)
     use_graph = bool(graph and iters > GRAPH_WARMUP + 1)
     defer = DEFER_FINALIZE and bucket is None
-    fuse_tail = FUSE_TAIL and isinstance(block, BaseQuantBlock)
+    fuse_tail = FUSE_TAIL and isinstance(block, BaseQuantBlock) and fisher is None
     wq_params = {id(t) for m in qmodules for t in m.weight_quantizer.parameters()}
     pin = PIN_WEIGHTS and act_quant and not any(id(t) in wq_params for t in opt_params)
     stash_ada = STASH_ADAROUND and not act_quant and isinstance(block, BaseQuantBlock)
@@ -327,6 +353,11 @@ def _fast_loop(block, qmodules, opt_params, loss_func, feeder, bucket, iters, ac
     need_input = [True]     # False once cached_convs serves every reader of the block input
     conv_rows = []          # cached_convs' (all rows, batch buffer) pairs, gathered with the input
     rows_mode = [False, False]   # (cached rows read in place, the batch input as a row view)
+
+    def loss_and_grad(out, tgt, **kw):
+        if fisher is None:
+            return K.lp_loss_and_grad(out, tgt, p, **kw)
+        return K.fisher_loss_and_grad(out, tgt, K.Rows(fisher[1], tgt.idx), fisher[0], **kw)
 
     def body_pre():
         with K.deferred_finalize(defer):
@@ -371,14 +402,14 @@ def _fast_loop(block, qmodules, opt_params, loss_func, feeder, bucket, iters, ac
             # no optimised parameter reaches the output (e.g. the act delta of a layer whose
             # act quantizer is disabled): the reference's backward yields no gradient for it
             # and its Adam step skips it -- only the loss value remains
-            last['rec'], _ = K.lp_loss_and_grad(out, cur_out, p, want_grad=False)
+            last['rec'], _ = loss_and_grad(out, cur_out, want_grad=False)
             last['step'] = False
             return
         if relu_in:
-            rec, g = K.lp_loss_and_grad(out, cur_out, p, relu_mask=True)
+            rec, g = loss_and_grad(out, cur_out, relu_mask=True)
             run_backward(list(relu_in), [g] * len(relu_in))
         else:
-            rec, g = K.lp_loss_and_grad(out, cur_out, p)
+            rec, g = loss_and_grad(out, cur_out)
             run_backward([out], [g])
         last['rec'] = rec
         last['step'] = True
@@ -391,7 +422,8 @@ def _fast_loop(block, qmodules, opt_params, loss_func, feeder, bucket, iters, ac
         if bucket is not None:
             _step()
 
-    fc_body = _fc_fused_body(block, qmodules, act_quant, p, bucket, feeder, optimizer, last)
+    fc_body = _fc_fused_body(block, qmodules, act_quant, p, bucket, feeder, optimizer, last,
+                             'mse' if fisher is None else fisher[0])
     if fc_body is not None:
         # gather, forward, loss, backward and Adam: two launches, or three around the
         # bucket's all-reduce
@@ -621,6 +653,7 @@ class LossFunction:
         self._qmodules = quant_modules
         self.last_total = None
         self.track_values = False   # True: round_value() every iteration (tests)
+        self.fisher_cache = None    # the Fisher losses' [N, ...] cache (the device loop)
 
     def _modules(self):
         if self._qmodules is not None:
@@ -663,7 +696,9 @@ class LossFunction:
         b, _, active = self.schedule()
         if self.rec_loss == 'mse':
             rec_loss = K.lp_loss(pred, tgt, self.p)
-        elif self.rec_loss == 'fisher_diag':
+        elif self.rec_loss in K.FISHER_MODES and pred.is_cuda:
+            rec_loss = K.fisher_loss(pred, tgt, grad, self.rec_loss)
+        elif self.rec_loss == 'fisher_diag':      # host tensors: the reference's expressions
             rec_loss = ((pred - tgt).pow(2) * grad.pow(2)).sum(1).mean()
         elif self.rec_loss == 'fisher_full':
             a = (pred - tgt).abs()

@@ -1,0 +1,496 @@
+"""BRECQ's Fisher-weighted reconstruction losses on the device: the K20 kernels
+(ssq_fisher_diag_loss / ssq_fisher_full_loss and their _rows forms) against the reference's
+torch expressions and float64, and the device loop (block_recon._fast_loop with opt_mode
+'fisher_diag' / 'fisher_full') against the reference's trajectories
+(tests/golden/recon_brecq_fisher_*.npz, recon_layer_fisher_diag.npz)."""
+import importlib
+import os
+import socket
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import assert_hard_flips_bounded, assert_walk_bounded
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+MODES = ("fisher_diag", "fisher_full")
+# row of 400 (aligned float4 gather); row of 63 (scalar path); C = 1; 2-D; a sample spanning
+# many workgroups (49 chunks); many samples per launch
+SHAPES = [(8, 16, 5, 5), (4, 7, 3, 3), (3, 1, 2, 2), (8, 10), (2, 64, 56, 56), (64, 4, 2, 2)]
+N_CACHE = 16
+
+
+@pytest.fixture(scope="module")
+def K():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    from shiftedscalequantization_amd import kernels
+    return kernels
+
+
+@pytest.fixture(scope="module")
+def Q():
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    from shiftedscalequantization_amd import quant
+    return quant
+
+
+def bits(t):
+    return t.detach().contiguous().view(torch.int32)
+
+
+def expr(pred, tgt, fis, mode):
+    """The reference's expressions (block_recon.py:156-162)."""
+    if mode == "fisher_diag":
+        return ((pred - tgt).pow(2) * fis.pow(2)).sum(1).mean()
+    a = (pred - tgt).abs()
+    g = fis.abs()
+    return (torch.sum(a * g, (1, 2, 3)).view(-1, 1, 1, 1) * a * g).mean() / 100
+
+
+def eager(pred, tgt, fis, mode, dtype=torch.float32, relu=False):
+    """(loss, d loss / d pred -- with relu, d / d (the ReLU's input)) by torch autograd."""
+    t = pred.detach().to(dtype).clone().requires_grad_(True)
+    p = torch.relu(t) if relu else t
+    loss = expr(p, tgt.to(dtype), fis.to(dtype), mode)
+    g, = torch.autograd.grad(loss, t)
+    return loss.detach(), g
+
+
+_CASES = {}
+
+
+def case(shape):
+    """Seeded operands of one shape, built once: 16-row caches, a non-monotonic idx with a
+    repeat, pred = target rows + noise with some pred == tgt elements, and a ReLU-output
+    variant with exact zeros (negatives in its input)."""
+    if shape in _CASES:
+        return _CASES[shape]
+    gen = torch.Generator().manual_seed(sum(shape) * 31 + len(shape))
+    N, row = shape[0], shape[1:]
+    tcache = torch.randn((N_CACHE,) + row, generator=gen)
+    fcache = torch.randn((N_CACHE,) + row, generator=gen).abs() * 0.3 + 1.0
+    idx = torch.randperm(N_CACHE, generator=gen)[torch.arange(N) % N_CACHE]
+    idx[-1] = idx[0]                                   # a repeated row
+    assert N < 3 or not bool((idx[1:] > idx[:-1]).all())
+    pred = tcache[idx] + 0.1 * torch.randn(shape, generator=gen)
+    same = torch.rand(shape, generator=gen) < 0.05
+    pred = torch.where(same, tcache[idx], pred)
+    pre = pred.clone()
+    pre[torch.rand(shape, generator=gen) < 0.1] = 0.0   # exact zeros among the negatives
+    c = {k: v.cuda() for k, v in dict(tcache=tcache, fcache=fcache, idx=idx, pred=pred, pre=pre,
+                                      same=same).items()}
+    c["tgt"], c["fis"] = c["tcache"][c["idx"]].contiguous(), c["fcache"][c["idx"]].contiguous()
+    _CASES[shape] = c
+    return c
+
+
+def unaligned(t):
+    """t's values in a buffer that starts one float past a 16-byte boundary."""
+    buf = torch.empty(t.numel() + 1, device=t.device, dtype=t.dtype)
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+    return v
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=str)
+def test_fisher_diag_kernel(K, shape):
+    """Gradient bit-identical to torch autograd of the reference expression on the device, in
+    every form (batches, Rows, unaligned pred, relu_mask, loss only, gradient only); gscale
+    multiplies that gradient; loss within 1e-6 relative of float64 (double reduction)."""
+    c = case(shape)
+    mode = "fisher_diag"
+    l32, g32 = eager(c["pred"], c["tgt"], c["fis"], mode)
+    l64, _ = eager(c["pred"], c["tgt"], c["fis"], mode, torch.float64)
+    rows = (K.Rows(c["tcache"], c["idx"]), K.Rows(c["fcache"], c["idx"]))
+    outs = {"plain": K.fisher_loss_and_grad(c["pred"], c["tgt"], c["fis"], mode),
+            "rows": K.fisher_loss_and_grad(c["pred"], *rows, mode),
+            "unaligned": K.fisher_loss_and_grad(unaligned(c["pred"]), *rows, mode),
+            "unaligned_plain": K.fisher_loss_and_grad(unaligned(c["pred"]), c["tgt"], c["fis"], mode)}
+    for name, (loss, grad) in outs.items():
+        assert torch.equal(bits(grad), bits(g32)), name
+        rel = abs(float(loss) - float(l64)) / abs(float(l64))
+        print(f"fisher_diag {shape} {name}: loss rel err vs f64 {rel:.3e} "
+              f"(eager fp32: {abs(float(l32) - float(l64)) / abs(float(l64)):.3e})")
+        assert rel <= 1e-6, (name, rel)
+        if name == "rows":          # the same summation order as the batches' form
+            assert torch.equal(bits(loss), bits(outs["plain"][0])), name
+    assert bool((g32[c["same"]] == 0).all())            # pred == tgt: zero gradient
+    # relu_mask: pred is a ReLU output; the gradient is the one at the ReLU's input
+    out = torch.relu(c["pre"])
+    assert bool((out == 0).any()) and bool((c["pre"] < 0).any())
+    lr32, gr32 = eager(c["pre"], c["tgt"], c["fis"], mode, relu=True)
+    for tf in ((c["tgt"], c["fis"]), rows):
+        loss, grad = K.fisher_loss_and_grad(out, *tf, mode, relu_mask=True)
+        assert torch.equal(bits(grad), bits(gr32))
+        assert bool((grad[out <= 0] == 0).all())
+        np.testing.assert_allclose(float(loss), float(lr32), rtol=1e-5)
+    # loss only / gradient only / gscale
+    lo, none = K.fisher_loss_and_grad(c["pred"], *rows, mode, want_grad=False)
+    assert none is None and torch.equal(bits(lo), bits(outs["rows"][0]))
+    none, go = K.fisher_loss_and_grad(c["pred"], *rows, mode, want_loss=False)
+    assert none is None and torch.equal(bits(go), bits(g32))
+    gs = torch.tensor([0.37], device="cuda")
+    _, gg = K.fisher_loss_and_grad(c["pred"], *rows, mode, gscale=gs)
+    assert torch.equal(bits(gg), bits(g32 * gs))
+    # the autograd wrapper
+    p = c["pred"].clone().requires_grad_(True)
+    (K.fisher_loss(p, c["tgt"], c["fis"], mode) * 0.37).backward()
+    assert torch.equal(bits(p.grad), bits(g32 * gs))
+
+
+def full_err(got, ref64):
+    return float((got.double() - ref64).abs().max())
+
+
+@pytest.mark.parametrize("shape", [s for s in SHAPES if len(s) == 4], ids=str)
+def test_fisher_full_kernel(K, shape):
+    """Gradient and loss within 2x the eager fp32 expression's own distance from float64 on
+    the same operands (autograd reaches this gradient as two separately rounded products: no
+    bit pin), in every form; the Rows form equals the batches' form bit for bit."""
+    c = case(shape)
+    mode = "fisher_full"
+    l32, g32 = eager(c["pred"], c["tgt"], c["fis"], mode)
+    l64, g64 = eager(c["pred"], c["tgt"], c["fis"], mode, torch.float64)
+    e_g, e_l = full_err(g32, g64), abs(float(l32) - float(l64))
+    rows = (K.Rows(c["tcache"], c["idx"]), K.Rows(c["fcache"], c["idx"]))
+    outs = {"plain": K.fisher_loss_and_grad(c["pred"], c["tgt"], c["fis"], mode),
+            "rows": K.fisher_loss_and_grad(c["pred"], *rows, mode),
+            "unaligned": K.fisher_loss_and_grad(unaligned(c["pred"]), *rows, mode)}
+    for name, (loss, grad) in outs.items():
+        d_g, d_l = full_err(grad, g64), abs(float(loss) - float(l64))
+        print(f"fisher_full {shape} {name}: grad err vs f64 {d_g:.3e} (eager {e_g:.3e}), "
+              f"loss err {d_l:.3e} (eager {e_l:.3e})")
+        assert d_g <= 2 * e_g, (name, d_g, e_g)
+        assert d_l <= 2 * e_l, (name, d_l, e_l)
+        if name == "rows":          # the same summation order as the batches' form
+            assert torch.equal(bits(grad), bits(outs["plain"][1])), name
+            assert torch.equal(bits(loss), bits(outs["plain"][0])), name
+    sgn0 = outs["plain"][1][c["same"]]
+    assert bool((sgn0 == 0).all())                      # sgn(0) = 0, as abs's backward
+    out = torch.relu(c["pre"])
+    lr64, gr64 = eager(c["pre"], c["tgt"], c["fis"], mode, torch.float64, relu=True)
+    lr32, gr32 = eager(c["pre"], c["tgt"], c["fis"], mode, relu=True)
+    for tf in ((c["tgt"], c["fis"]), rows):
+        loss, grad = K.fisher_loss_and_grad(out, *tf, mode, relu_mask=True)
+        assert full_err(grad, gr64) <= 2 * full_err(gr32, gr64)
+        assert bool((grad[out <= 0] == 0).all())
+        np.testing.assert_allclose(float(loss), float(lr64), rtol=1e-6)
+    lo, none = K.fisher_loss_and_grad(c["pred"], *rows, mode, want_grad=False)
+    assert none is None and torch.equal(bits(lo), bits(outs["plain"][0]))
+    none, go = K.fisher_loss_and_grad(c["pred"], *rows, mode, want_loss=False)
+    assert none is None and torch.equal(bits(go), bits(outs["plain"][1]))
+    gs = torch.tensor([0.37], device="cuda")
+    _, gg = K.fisher_loss_and_grad(c["pred"], *rows, mode, gscale=gs)
+    assert torch.equal(bits(gg), bits(outs["plain"][1] * gs))
+    p = c["pred"].clone().requires_grad_(True)
+    (K.fisher_loss(p, c["tgt"], c["fis"], mode) * 0.37).backward()
+    assert torch.equal(bits(p.grad), bits(outs["plain"][1] * gs))
+
+
+def test_fisher_full_rejects_2d(K):
+    """The reference's torch.sum(..., (1, 2, 3)) raises on a Linear output: an argument error
+    here, in both forms; nothing is launched."""
+    from shiftedscalequantization_amd._capi import SSQError
+    c = case((8, 10))
+    with pytest.raises(SSQError, match="4-D"):
+        K.fisher_loss_and_grad(c["pred"], c["tgt"], c["fis"], "fisher_full")
+    with pytest.raises(SSQError, match="4-D"):
+        K.fisher_loss_and_grad(c["pred"], K.Rows(c["tcache"], c["idx"]),
+                               K.Rows(c["fcache"], c["idx"]), "fisher_full")
+    with pytest.raises(ValueError):
+        K.fisher_loss_and_grad(c["pred"], c["tgt"], c["fis"], "fisher")
+    with pytest.raises(SSQError):          # a Rows target with a batch of Fisher rows
+        K.fisher_loss_and_grad(c["pred"], K.Rows(c["tcache"], c["idx"]), c["fis"], "fisher_diag")
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("defer", [False, True])
+def test_fisher_run_to_run_bit_identical(K, mode, defer):
+    """Two calls, same bits (the loss reduction is in index order), standalone and with the
+    finalize deferred to a flush (fin_tasks.h)."""
+    c = case((2, 64, 56, 56))
+    rows = (K.Rows(c["tcache"], c["idx"]), K.Rows(c["fcache"], c["idx"]))
+    res = []
+    for _ in range(2):
+        with K.deferred_finalize(defer):
+            loss, grad = K.fisher_loss_and_grad(c["pred"], *rows, mode)
+        res.append((loss.clone(), grad.clone()))
+    plain = K.fisher_loss_and_grad(c["pred"], *rows, mode)
+    for loss, grad in res:
+        assert torch.equal(bits(loss), bits(plain[0])) and torch.equal(bits(grad), bits(plain[1]))
+
+
+@pytest.mark.parametrize("name", ["recon_brecq_fisher_diag", "recon_layer_fisher_diag",
+                                  "recon_brecq_fisher_full"])
+def test_fisher_kernel_matches_fixture(K, golden, name):
+    """Iteration 0 of the reference's loop (stored whole): fisher_diag's gradient equals the
+    reference's stored one bit for bit; fisher_full's is within 2x the stored fp32 gradient's
+    distance from the stored float64 one."""
+    g = golden(name)
+    mode = "fisher_full" if name.endswith("full") else "fisher_diag"
+    pred, tgt, fis = (torch.as_tensor(g["it0_" + k]).cuda() for k in ("pred", "tgt", "grad"))
+    loss, grad = K.fisher_loss_and_grad(pred, tgt, fis, mode)
+    np.testing.assert_allclose(float(loss), g["it_loss64"][0], rtol=1e-6)
+    got = grad.cpu().numpy()
+    if mode == "fisher_diag":
+        np.testing.assert_array_equal(got.view(np.int32), g["it0_g32"].view(np.int32))
+        return
+    at = g["it0_g64_at"]
+    ours = np.abs(got.reshape(-1)[at].astype(np.float64) - g["it0_g64"]).max()
+    ref = np.abs(g["it0_g32"].reshape(-1)[at].astype(np.float64) - g["it0_g64"]).max()
+    print(f"fisher_full fixture: grad err vs f64 {ours:.3e} (reference fp32 {ref:.3e})")
+    assert ours <= 2 * ref, (ours, ref)
+
+
+# ------------------------------------------------------------------ the device loop
+def run_loop(Q, g, mode, graph, fast=True, layer=False, iters=None):
+    """The repository's block / layer reconstruction on the fixture's network with the
+    reference's cached_grads, seeded as the reference; what the loop reported and used."""
+    import test_recon_gpu as T
+    from shiftedscalequantization_amd import _capi
+    from shiftedscalequantization_amd.quant._engine import GRAPH_REPLAYS
+    BR = importlib.import_module("shiftedscalequantization_amd.quant.block_recon")
+    qnn = T.build_qnn(Q, g)
+    target = qnn.model[6] if layer else qnn.model[3]
+    cali = T.dev(g["cali"])
+    iters = len(g["w_total_loss"]) if iters is None else iters
+    seen = {"rec": [], "total": [], "perms": [], "calls": set(), "adam": 0}
+    orig = (BR.LossFunction.record, BR.LossFunction.__init__, BR._fast_loop, BR.save_grad_data,
+            BR.BatchFeeder.draw, BR.FISHER_FAST, _capi.CALL_HOOK, torch.optim.Adam.__init__)
+
+    def record(self, rec, rnd, b, count=None):
+        r = orig[0](self, rec, rnd, b, count)
+        # read now: a graph replay overwrites it
+        seen["rec"].append(float(rec.detach() if torch.is_tensor(rec) else rec))
+        seen["total"].append(float(r.detach() if torch.is_tensor(r) else r))
+        return r
+
+    def init(self, *a, **k):
+        orig[1](self, *a, **k)
+        self.track_values = True
+
+    def draw(self):
+        p = orig[4](self)
+        seen["perms"].append(p.clone())
+        return p
+
+    def adam_init(self, *a, **k):
+        seen["adam"] += 1
+        return orig[7](self, *a, **k)
+
+    BR.LossFunction.record, BR.LossFunction.__init__ = record, init
+    BR._fast_loop = lambda *a: orig[2](*(a[:-1] + (a[-1] and graph,)))
+    BR.save_grad_data = lambda *a, **k: torch.as_tensor(g["cached_grads"])
+    BR.BatchFeeder.draw = draw
+    BR.FISHER_FAST = fast
+    _capi.CALL_HOOK = lambda name, args: seen["calls"].add(name)
+    torch.optim.Adam.__init__ = adam_init
+    replays0 = dict(GRAPH_REPLAYS)
+    try:
+        torch.manual_seed(1005)
+        fn = Q.layer_reconstruction if layer else Q.block_reconstruction
+        fn(qnn, target, cali, batch_size=8, iters=iters, weight=0.01, asym=True, b_range=(20, 2),
+           warmup=0.2, act_quant=False, opt_mode=mode)
+    finally:
+        (BR.LossFunction.record, BR.LossFunction.__init__, BR._fast_loop, BR.save_grad_data,
+         BR.BatchFeeder.draw, BR.FISHER_FAST, _capi.CALL_HOOK, torch.optim.Adam.__init__) = orig
+    seen["replays"] = sum(GRAPH_REPLAYS.values()) - sum(replays0.values())
+    seen["target"] = target
+    return seen
+
+
+def check_against_reference(g, seen, layers, tag):
+    """The bounds test_brecq_block_reconstruction_matches_reference states for its MSE weight
+    phase: identical batches, per-iteration losses to 1e-5, V to 1e-5 (a few walkers within
+    Adam's budget), hard W^ flips only where V's decision is within that budget."""
+    iters = len(seen["total"])
+    np.testing.assert_array_equal(np.stack([p.numpy() for p in seen["perms"]])[:, :8],
+                                  g["w_perms"][:iters, :8])
+    rec_rel = np.max(np.abs(np.array(seen["rec"]) - g["rec_loss"][:iters]) / np.abs(g["rec_loss"][:iters]))
+    tot_rel = np.max(np.abs(np.array(seen["total"]) - g["w_total_loss"][:iters]) /
+                     np.abs(g["w_total_loss"][:iters]))
+    ref_vs_f64 = np.max(np.abs(g["it_loss32"].astype(np.float64) - g["it_loss64"]) / g["it_loss64"])
+    print(f"FISHER_PARITY {tag}: rec rel err {rec_rel:.3e}, total rel err {tot_rel:.3e} "
+          f"(reference fp32 vs f64, first 3 iterations: {ref_vs_f64:.3e})")
+    np.testing.assert_allclose(seen["rec"], g["rec_loss"][:iters], rtol=1e-5)
+    np.testing.assert_allclose(seen["total"], g["w_total_loss"][:iters], rtol=1e-5)
+    for name, m in layers:
+        q = m.weight_quantizer
+        v = q.alpha.detach().cpu().numpy()
+        assert_walk_bounded(np.abs(v - g[name + "_alpha"]), 1e-5, iters * 2e-3, what=name)
+        with torch.no_grad():
+            what = q(m.weight).cpu().numpy()
+        assert_hard_flips_bounded(what, g[name + "_what_hard"], v, g[name + "_alpha"],
+                                  iters * 2e-3, name)
+
+
+@pytest.mark.parametrize("graph", [False, True])
+@pytest.mark.parametrize("mode", MODES)
+def test_fisher_block_loop_matches_reference(Q, golden, mode, graph):
+    g = golden("recon_brecq_" + mode)
+    seen = run_loop(Q, g, mode, graph)
+    # the device loop ran: K20, no torch optimizer, graph replays after the warm-up
+    assert any(c.startswith("ssq_fisher_" + mode.split("_")[1]) and c.endswith("_rows")
+               for c in seen["calls"]), sorted(seen["calls"])
+    assert "ssq_lp_loss" not in seen["calls"] and "ssq_lp_loss_rows" not in seen["calls"]
+    assert "ssq_epilogue_loss_bwd" not in seen["calls"]          # no fused tail
+    assert seen["adam"] == 0
+    assert (seen["replays"] > 0) == graph
+    block = seen["target"]
+    check_against_reference(g, seen, [(n, getattr(block, n)) for n in ("conv1", "conv2", "downsample")],
+                            f"block[{mode},graph={graph}]")
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_fisher_eager_knob(Q, golden, mode):
+    """SSQ_FISHER_FAST=0 (block_recon.FISHER_FAST): the reference's eager loop -- torch's Adam,
+    no graph -- with K20 as its loss; its losses equal the device loop's at the same bound."""
+    g = golden("recon_brecq_" + mode)
+    fast = run_loop(Q, g, mode, True)
+    slow = run_loop(Q, g, mode, True, fast=False)
+    assert slow["adam"] == 1 and slow["replays"] == 0 and fast["adam"] == 0
+    assert any(c.startswith("ssq_fisher_") for c in slow["calls"])
+    block = slow["target"]
+    check_against_reference(g, slow, [(n, getattr(block, n)) for n in ("conv1", "conv2", "downsample")],
+                            f"eager[{mode}]")
+    np.testing.assert_allclose(slow["rec"], fast["rec"], rtol=1e-5)
+    np.testing.assert_allclose(slow["total"], fast["total"], rtol=1e-5)
+
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_fisher_linear_layer_runs_unfused(Q, golden, graph):
+    """The 2-D case: layer_reconstruction on the Linear layer with fisher_diag takes the
+    unfused device iteration (K19 has no Fisher form)."""
+    g = golden("recon_layer_fisher_diag")
+    seen = run_loop(Q, g, "fisher_diag", graph, layer=True)
+    assert not any(c.startswith("ssq_fc_recon") for c in seen["calls"]), sorted(seen["calls"])
+    assert "ssq_fisher_diag_loss_rows" in seen["calls"]
+    assert seen["adam"] == 0 and (seen["replays"] > 0) == graph
+    check_against_reference(g, seen, [("fc", seen["target"])], f"fc[graph={graph}]")
+
+
+def test_fisher_chunked_loop_bit_identical(Q, golden):
+    """Past the warm-up a world-1 loop replays several iterations per graph (ChunkGraph); the
+    Fisher rows are read through the same staged indices, so the result is the same bits as
+    one iteration per replay."""
+    BR = importlib.import_module("shiftedscalequantization_amd.quant.block_recon")
+    from shiftedscalequantization_amd.quant._engine import GRAPH_REPLAYS
+    g = golden("recon_brecq_fisher_diag")
+    import test_recon_gpu as T
+    res = []
+    old = (BR.CHUNK_ITERS, BR.save_grad_data, torch.backends.cudnn.deterministic)
+    BR.save_grad_data = lambda *a, **k: torch.as_tensor(g["cached_grads"])
+    torch.backends.cudnn.deterministic = True
+    try:
+        for chunk in (1, 5):
+            BR.CHUNK_ITERS = chunk
+            n0 = GRAPH_REPLAYS.get("chunk", 0)
+            qnn = T.build_qnn(Q, g)
+            block = qnn.model[3]
+            torch.manual_seed(1005)
+            Q.block_reconstruction(qnn, block, T.dev(g["cali"]), batch_size=8, iters=24, weight=0.01,
+                                   asym=True, b_range=(20, 2), warmup=0.2, act_quant=False,
+                                   opt_mode="fisher_diag")
+            assert (GRAPH_REPLAYS.get("chunk", 0) > n0) == (chunk > 1)
+            res.append([getattr(block, n).weight_quantizer.alpha.detach().clone()
+                        for n in ("conv1", "conv2", "downsample")])
+    finally:
+        BR.CHUNK_ITERS, BR.save_grad_data, torch.backends.cudnn.deterministic = old
+    for a, b in zip(*res):
+        assert torch.equal(bits(a), bits(b))
+
+
+def test_save_grad_data_matches_reference(Q, golden):
+    """The repository's save_grad_data, as block_reconstruction calls it (the block's weight
+    quantizers already AdaRound's soft targets), against the reference's cached_grads.  The
+    two sides run different convolutions, so the yardstick is this repository's own spread
+    between its deterministic and default conv routes on the same input: the comparison is
+    bounded by 4x that spread.  |g| + 1: every value >= 1.
+    Measured on the MI355X: spread 0 and difference 0 -- |g| <= 4.2e-6 on this network, 35
+    ulps of the stored 1 + |g|, and every one of the 32768 values rounds the same way."""
+    import test_recon_gpu as T
+    BR = importlib.import_module("shiftedscalequantization_amd.quant.block_recon")
+    g = golden("recon_brecq_fisher_diag")
+    outs = {}
+    old, orig = torch.backends.cudnn.deterministic, BR.save_grad_data
+    try:
+        for det in (True, False):
+            torch.backends.cudnn.deterministic = det
+
+            def wrapped(*a, **k):
+                outs[det] = orig(*a, **k)
+                return outs[det]
+
+            BR.save_grad_data = wrapped
+            qnn = T.build_qnn(Q, g)
+            torch.manual_seed(1005)
+            Q.block_reconstruction(qnn, qnn.model[3], T.dev(g["cali"]), batch_size=8, iters=1,
+                                   weight=0.01, asym=True, b_range=(20, 2), warmup=0.2,
+                                   act_quant=False, opt_mode="fisher_diag")
+            assert outs[det].is_cuda            # the Fisher cache stays on the device
+            outs[det] = outs[det].cpu().numpy()
+    finally:
+        torch.backends.cudnn.deterministic, BR.save_grad_data = old, orig
+    ref = g["cached_grads"]
+    assert outs[True].shape == ref.shape and outs[True].dtype == np.float32
+    assert outs[True].min() >= 1.0 and outs[False].min() >= 1.0
+    spread = float(np.abs(outs[True].astype(np.float64) - outs[False]).max())
+    diff = max(float(np.abs(outs[d].astype(np.float64) - ref).max()) for d in (True, False))
+    print(f"FISHER_PARITY save_grad_data: spread deterministic vs default {spread:.3e}, "
+          f"max diff to the reference {diff:.3e}, max |g| {float(ref.max() - 1):.3e}")
+    assert diff <= 4 * spread, (diff, spread)
+
+
+# ------------------------------------------------------------------ world 2
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+def test_fisher_world2_replicated(tmp_path):
+    """fisher_diag, 6 iterations, two ranks over gloo on the one GPU (tests/test_dp_gpu.py's
+    pattern): every iteration's reduced bucket is the sum of the two local ones, and V is
+    bit-identical on both ranks; the iterations past the warm-up replay the split graphs."""
+    if not torch.cuda.is_available():
+        pytest.skip("no HIP device")
+    port = _free_port()
+    procs, outs = [], []
+    for r in range(2):
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK="0",
+                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+        outs.append(str(tmp_path / f"fisher_r{r}.npz"))
+        procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, "dp_fisher_worker.py"),
+                                       outs[-1]], env=env, stdout=subprocess.PIPE,
+                                      stderr=subprocess.STDOUT))
+    logs = []
+    try:
+        for p in procs:
+            logs.append(p.communicate(timeout=100)[0].decode(errors="replace"))
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+    for p, log in zip(procs, logs):
+        assert p.returncode == 0, log[-3000:]
+    r0, r1 = [dict(np.load(o)) for o in outs]
+    n = int(r0["n_rec"][0])
+    assert n == int(r1["n_rec"][0]) == 6
+    assert int(r0["split_replays"][0]) > 0 and int(r1["split_replays"][0]) > 0
+    assert int(r0["fisher_calls"][0]) > 0 and int(r0["adam"][0]) == 0
+    for k in range(n):
+        np.testing.assert_array_equal(r0[f"rec{k}_reduced"], r1[f"rec{k}_reduced"])
+        np.testing.assert_array_equal(r0[f"rec{k}_reduced"], r0[f"rec{k}_local"] + r1[f"rec{k}_local"])
+        assert not np.array_equal(r0[f"rec{k}_local"], r1[f"rec{k}_local"])
+    for name in ("conv1", "conv2", "downsample"):
+        np.testing.assert_array_equal(r0[name + "_V"], r1[name + "_V"], err_msg=name)
+        assert not np.array_equal(r0[name + "_V"], r0[name + "_V0"])

@@ -1,7 +1,13 @@
 """BRECQ block_reconstruction iteration rate (ResNet-50 block_recon):
 AdaRound weight phase and act-delta (LSQ) phase on one block, batch 32, synthetic data.
 Rate = (T(iters_long) - T(iters_short)) / (iters_long - iters_short), so caching and setup
-cancel out."""
+cancel out.
+
+    --opt_mode fisher_diag | fisher_full   the Fisher-weighted loss (its cache's setup cancels
+                                           out the same way); SSQ_FISHER_FAST=0 in the
+                                           environment times the eager loop instead
+    --phases weight[,act]  --blocks resnet18.layer1.0[,...]   a subset of the default runs"""
+import argparse
 import json
 import os
 import sys
@@ -38,12 +44,17 @@ def timed(fn):
     return time.perf_counter() - t0
 
 
-def main():
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--opt_mode", default="mse", choices=["mse", "fisher_diag", "fisher_full"])
+    ap.add_argument("--phases", default="weight,act")
+    ap.add_argument("--blocks", default="resnet18.layer1.0,resnet50.layer1.0")
+    args = ap.parse_args(argv)
     dev = torch.device("cuda")
     cali = torch.randn(128, 3, 224, 224, device=dev)
     res = {}
-    for arch, path in (("resnet18", "layer1.0"), ("resnet50", "layer1.0")):
-        for phase in ("weight", "act"):
+    for arch, path in (b.split(".", 1) for b in args.blocks.split(",")):
+        for phase in args.phases.split(","):
             times = {}
             for iters in (20, 20, 220):      # the first run pays one-time setup (MIOpen)
                 qnn = build(arch, dev)
@@ -52,15 +63,15 @@ def main():
                     qnn(cali[:64])
                 blk = block_of(qnn, path)
                 kw = dict(batch_size=32, iters=iters, weight=0.01, asym=True, b_range=(20, 2),
-                          warmup=0.2, act_quant=phase == "act", opt_mode="mse")
+                          warmup=0.2, act_quant=phase == "act", opt_mode=args.opt_mode)
                 if phase == "act":
                     kw.update(lr=4e-4, p=2.4)
                 times[iters] = timed(lambda: block_reconstruction(qnn, blk, cali, **kw))
             rate = 200 / (times[220] - times[20])
             res[f"{arch}.{path}.{phase}"] = round(rate, 1)
-            print(json.dumps({"block": f"{arch}.{path}", "phase": phase, "iters_per_s": round(rate, 1)}),
-                  flush=True)
-    print(json.dumps({"brecq_iters_per_s": res}))
+            print(json.dumps({"block": f"{arch}.{path}", "phase": phase, "opt_mode": args.opt_mode,
+                              "iters_per_s": round(rate, 1)}), flush=True)
+    print(json.dumps({"brecq_iters_per_s": res, "opt_mode": args.opt_mode}))
 
 
 if __name__ == "__main__":

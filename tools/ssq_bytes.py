@@ -78,6 +78,15 @@ def bytes_of(name, a):
     if name == "ssq_lp_loss_rows":
         # (pred, tgt_cache, idx, row, n, M, p, loss_out, grad, ...)
         return 4 * int(a[4]) * (2 + (not _null(a[8])))
+    if name in ("ssq_fisher_diag_loss", "ssq_fisher_diag_loss_rows"):
+        # (pred, tgt, fis, [idx, row,] n, M, loss_out, grad, ...): one pass
+        n, grad = (a[5], a[8]) if name.endswith("_rows") else (a[3], a[6])
+        return 4 * int(n) * (3 + (not _null(grad)))
+    if name in ("ssq_fisher_full_loss", "ssq_fisher_full_loss_rows"):
+        # (pred, tgt, fis, [idx,] n, N, ndim, loss_out, grad, ...): the per-sample sums, then
+        # the gradient pass over the same operands
+        n, grad = (a[4], a[8]) if name.endswith("_rows") else (a[3], a[7])
+        return 4 * int(n) * (6 + (not _null(grad)))
     if name in ("ssq_adam", "ssq_adam_arm"):
         # (n, p, [g,] m, v, nelem, ...): p, g, m, v in; p, m, v out
         cnt = a[5] if name == "ssq_adam" else a[4]
