@@ -660,6 +660,48 @@ int ssq_pack_decode(const void* packed, const float* zp, const float* d1, int d1
                     const float* d2, int64_t Co, int64_t Ci, int64_t K, int n_bits, int qmin,
                     float* What, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- K21-K23 integer inference
+ * A layer whose input is an act quantizer's output x_hat = (q_a - z_a) * delta_a (scalar
+ * delta_a, integer z_a) and whose weight is a packed export W_hat = (q_w - z_w[co]) * d1[co]
+ * (d1 per co, no column scale) computes, with groups == 1, dilation 1, R, S <= 7 and
+ * K = Ci*R*S <= 65536,
+ *     y[n,co,oh,ow] = fp32(I) * scale[co],  I = sum_{r,s,ci} (q_a - z_a)(q_w - z_w[co]),
+ * I exact (int8 MFMA, i32 accumulation, int64 epilogue), converted to fp32 once (round to
+ * nearest even) and multiplied once by the caller's scale[co] = fp32(delta_a * d1[co]): no
+ * bias, no FMA, reproducible bit for bit from a host integer reference.  A zero-padded tap
+ * contributes (q_a - z_a) = 0.  A Linear is the 1x1 conv on a 1x1 plane.
+ *
+ * K21 act_encode: fp32 NCHW (or (N, C) with H = W = 1) -> int8 codes in NHWC order with C
+ * padded to qinfer_cpad(C) = 16*ceil(C/16): q = clamp(rint(x/delta) + zp, qmin, qmax) stored as
+ * q - (qmin + 128), padded channels 0.  ADDS to *bad (device u32, caller-zeroed) the number
+ * of elements whose (q - zp) * delta is not bit-identical to x; NaN / +-inf are counted and
+ * stored as qmin.  qmax - qmin <= 255, zp an integer in [qmin, qmin + 255] (a padded tap
+ * stores zp - (qmin + 128) as an int8), N*H*W*Cpad < 2^31.
+ *
+ * K22 qweight_prepare (once per layer): packed codes (K15's layout: (co, ci, r, s) order,
+ * stored as q - qmin) + zp[co] -> the conv kernel's operand, qweight_prepared_bytes(Co, Ci,
+ * R, S) bytes: int8 q - (qmin + 128) as [64*ceil(Co/64)][64*ceil(R*S*Cpad/64)] with
+ * k = (r*S + s)*Cpad + ci (zero outside the real taps), the 0/1 row of real k, and the two
+ * per-channel int32 vectors of the epilogue (csrc/qinfer.hip).  qmin is 0 or -2^(n_bits-1).
+ * ADDS to *bad the number of channels whose zp is not an integer in [qmin-256, qmin+511].
+ *
+ * K23 qconv_i8_fwd: codes (K21) x prepared (K22) -> y, fp32 NCHW (or (N, Co)).  The
+ * activation quantizer's (zero point, qmin, qmax) are those given to K21.  Host-side checks
+ * before the launch (SSQ_E_ARG): null pointer, groups != 1, K > 65536, R or S > 7, a
+ * zero point that is not an integer in [qmin, qmin + 255].                                    */
+int64_t ssq_qinfer_cpad(int64_t C);
+size_t ssq_qweight_prepared_bytes(int64_t Co, int64_t Ci, int64_t R, int64_t S);
+int ssq_act_encode(const float* x, int64_t Nb, int64_t C, int64_t H, int64_t W, float delta,
+                   float zero_point, int qmin, int qmax, int8_t* codes, uint32_t* bad,
+                   ssq_stream_t stream);
+int ssq_qweight_prepare(const void* packed, const float* zp, int64_t Co, int64_t Ci, int64_t R,
+                        int64_t S, int n_bits, int qmin, void* prepared, uint32_t* bad,
+                        ssq_stream_t stream);
+int ssq_qconv_i8_fwd(const int8_t* codes, const void* prepared, const float* scale, int64_t Nb,
+                     int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S,
+                     int64_t stride, int64_t pad, int64_t groups, float act_zero_point,
+                     int act_qmin, int act_qmax, float* y, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- bandwidth probe
  * float4 device copy, used by bench.py to report the measured stream bandwidth.      */
 int ssq_stream_copy(const float* src, float* dst, int64_t n, ssq_stream_t stream);

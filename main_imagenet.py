@@ -152,6 +152,20 @@ def main(argv=None):
         if loader is not None:
             print('Full quantization (W{}A{}) accuracy: {}'.format(args.n_bits_w, args.n_bits_a,
                                                                    validate_model(loader, qnn)))
+    if args.int_infer and args.act_quant:
+        from shiftedscalequantization_amd.quant import enable_integer_inference, integer_report
+        plan = enable_integer_inference(qnn, cali[:8])
+        n_int = sum(v == 'int8' for v in plan.values())
+        print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
+        for name, why in plan.items():
+            print(f'  {name}: {why}')
+        if loader is not None:
+            print('Integer inference (W{}A{}) accuracy: {}'.format(args.n_bits_w, args.n_bits_a,
+                                                                   validate_model(loader, qnn)))
+        else:
+            with torch.no_grad():
+                qnn(cali[:bs])
+        print(f'integer inference: {integer_report(qnn)["off_grid"]} off-grid activations')
     print(f'calibration finished in {time.time() - t0:.1f}s '
           f'({", ".join(f"{k} {v:.1f}s" for k, v in phases.items())}); block rec losses: '
           f'{ {k: v for k, v in report.items()} }')

@@ -129,6 +129,11 @@ SIGNATURES = {
     "ssq_pack_bytes": (_sz, [_i64, _i]),
     "ssq_pack_encode": (_i, [_p, _p, _p, _i, _p, _i64, _i64, _i64, _i, _i, _i, _p, _p, _p]),
     "ssq_pack_decode": (_i, [_p, _p, _p, _i, _p, _i64, _i64, _i64, _i, _i, _p, _p]),
+    "ssq_qinfer_cpad": (_i64, [_i64]),
+    "ssq_qweight_prepared_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "ssq_act_encode": (_i, [_p, _i64, _i64, _i64, _i64, _f, _f, _i, _i, _p, _p, _p]),
+    "ssq_qweight_prepare": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i, _i, _p, _p, _p]),
+    "ssq_qconv_i8_fwd": (_i, [_p, _p, _p] + [_i64] * 10 + [_f, _i, _i, _p, _p]),
     "ssq_stream_copy": (_i, [_p, _p, _i64, _p]),
     "ssq_stream_probe": (_i, [_p, _p, _i64, _i, _p]),
 }

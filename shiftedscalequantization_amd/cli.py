@@ -70,6 +70,9 @@ def build_parser():
     p.add_argument('--test', default=False, type=bool, help='ChannelQuantMSE path (channelShift_wMSE)')
     p.add_argument('--skip_test', default=False, type=bool)
     p.add_argument('--keep_features_on_host', default=False, type=bool)
+    p.add_argument('--int_infer', action='store_true',
+                   help='after calibration, validate again with the interior layers on their '
+                        'integer codes (int8 MFMA conv / linear) and print the per-layer report')
     p.add_argument('--deterministic', default=1, type=int,
                    help='1 (reference): deterministic MIOpen conv solvers; 0: fastest solvers')
     # data parallel: one process per GPU, spawned by main_imagenet.py itself with --gpus N

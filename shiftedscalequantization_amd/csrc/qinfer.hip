@@ -1,0 +1,383 @@
+// K21-K23: integer inference from the packed export (int8 MFMA conv / linear).
+//
+// An interior layer of a calibrated model reads an input on an integer grid,
+// x_hat = (q_a - z_a) * delta_a (scalar delta_a, z_a), and a weight on one,
+// W_hat = (q_w - z_w[co]) * d1[co], so its raw output is
+//     y[co] = fp32(I) * s[co],   I = sum_k (q_a - z_a)(q_w - z_w[co]),   s[co] = fp32(delta_a * d1[co])
+// with I an exact integer.  q - z spans +-255 at 8 bits and does not fit int8, so both
+// operands are stored shifted by a per-tensor constant,
+//     a_s = q_a - ca,  ca = qmin_a + 128        w_s = q_w - cw,  cw = qmin_w + 128
+// (both in [-128, 127] for every bit width), and the cross terms come back in the epilogue:
+//     I = D + cwz[co] * SA + az * T[co]
+//     D  = sum_k a_s w_s   (the int8 MFMA)       SA = sum_k a_s  (window sum, one more MFMA
+//     cwz[co] = cw - z_w[co]                          against a 0/1 row: 1 on real k)
+//     az = ca - z_a                              T[co] = sum_k w_s + K * cwz[co]
+// The sums run over the K = Ci*R*S real taps.  A spatially padded tap holds a_s = z_a - ca,
+// i.e. (q_a - z_a) = 0; padded channels and the K tail hold zero weights and a zero in the
+// 0/1 row, so whatever the activation operand holds there contributes nothing.  The epilogue
+// is evaluated in int64 (|I| can pass 2^31 at K = 65536), converted once (round to nearest
+// even) and multiplied once: bit-reproducible from a host integer reference.
+//
+// Layouts.  Activation codes: NHWC int8 with C padded to Cp = 16*ceil(C/16) (padded channels
+// 0), so every 16-byte K chunk of the implicit GEMM lies inside one (r, s) tap and is one
+// aligned vector load.  Prepared weights: [Cop = 64*ceil(Co/64)][Kp = 64*ceil(R*S*Cp/64)]
+// int8, k = (r*S + s)*Cp + ci, then the 0/1 row [Kp], then cwz[Cop] and T[Cop] (int32).
+//
+// K23 tile: 64 output pixels x 64 output channels x 64 k per workgroup of 4 waves.  Both
+// operands are register-staged into one LDS buffer (rows of 64 B at an 80 B stride: the 16
+// lanes of a ds_read_b128 group land on 16 distinct 16-B slots), the next k step's global
+// loads fly during the MFMAs.  Wave w owns pixels 16w..16w+15 against all 64 channels:
+// 4 x v_mfma_i32_16x16x64_i8 (weights as the A operand, so C rows are channels and C columns
+// pixels: a store instruction writes 16 consecutive pixels per channel of the NCHW output)
+// plus one for SA.  Both operand fragments use the same lane map (row / column l & 15,
+// k chunk l >> 4), so the product does not depend on the k order inside a step.
+#include "ssq_common.h"
+
+namespace ssq {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kQT = 64;     // pixels, channels and k per tile step
+constexpr int kQRow = 80;   // LDS row stride in bytes (64 + 16)
+constexpr int64_t kQMaxK = 65536;
+
+static inline int64_t rup(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+
+struct QLayout {
+  int64_t Cp, Kp, Cop;
+  size_t off_mask, off_cwz, off_t, bytes;
+};
+
+static inline QLayout qlayout(int64_t Co, int64_t Ci, int64_t R, int64_t S) {
+  QLayout L;
+  L.Cp = rup(Ci, 16);
+  L.Kp = rup(R * S * L.Cp, kQT);
+  L.Cop = rup(Co, kQT);
+  L.off_mask = (size_t)L.Cop * (size_t)L.Kp;
+  L.off_cwz = L.off_mask + (size_t)L.Kp;
+  L.off_t = L.off_cwz + (size_t)L.Cop * 4;
+  L.bytes = L.off_t + (size_t)L.Cop * 4;
+  return L;
+}
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, kWave);
+  return v;
+}
+
+// ---------------------------------------------------------------- K21 activation encode
+__global__ __launch_bounds__(kBlock) void act_encode_kernel(const float* __restrict__ x,
+                                                            uint32_t npix, uint32_t HW, uint32_t C,
+                                                            uint32_t Cp, FastDiv div_npix,
+                                                            FastDiv div_hw, float d, float z,
+                                                            float lo, float hi,
+                                                            int8_t* __restrict__ out,
+                                                            uint32_t* __restrict__ bad) {
+  const uint32_t total = npix * (Cp / 16);
+  const uint32_t stride = gridDim.x * blockDim.x;
+  uint32_t nbad = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const uint32_t ch = fdiv(i, div_npix);
+    const uint32_t pix = i - ch * npix;
+    const uint32_t n = fdiv(pix, div_hw);
+    const uint32_t p = pix - n * HW;
+    const float* src = x + ((size_t)n * C + (size_t)ch * 16) * HW + p;
+    union {
+      i32x4 v;
+      int8_t b[16];
+    } o;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      int8_t code = 0;
+      if (ch * 16 + j < C) {
+        const float xv = src[(size_t)j * HW];
+        float q = lo;   // NaN / +-inf: counted below, stored as qmin
+        if (isfinite(xv)) {
+          const float v = __fadd_rn(rintf(xv / d), z);
+          q = v >= lo ? (v <= hi ? v : hi) : lo;
+        }
+        const bool ok = __float_as_uint(__fmul_rn(__fsub_rn(q, z), d)) == __float_as_uint(xv);
+        nbad += ok ? 0u : 1u;
+        code = (int8_t)((int)__fsub_rn(q, lo) - 128);
+      }
+      o.b[j] = code;
+    }
+    *(i32x4*)(out + (size_t)pix * Cp + (size_t)ch * 16) = o.v;
+  }
+  nbad = wave_sum_u32(nbad);
+  if ((threadIdx.x & (kWave - 1)) == 0 && nbad) atomicAdd(bad, nbad);
+}
+
+// ---------------------------------------------------------------- K22 weight prepare
+// One workgroup per padded output channel, one more (blockIdx.x == Cop) for the 0/1 row.
+__global__ __launch_bounds__(kBlock) void qweight_prepare_kernel(
+    const uint8_t* __restrict__ packed, const float* __restrict__ zp, int bs, int qmin,
+    uint32_t Co, uint32_t Ci, uint32_t RS, uint32_t Cp, uint32_t Kp, uint32_t Cop, FastDiv div_cp,
+    int8_t* __restrict__ wp, int8_t* __restrict__ mask, int32_t* __restrict__ cwz,
+    int32_t* __restrict__ tt, uint32_t* __restrict__ bad) {
+  __shared__ int red[kBlock / kWave];
+  const uint32_t co = blockIdx.x;
+  if (co == Cop) {
+    for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
+      const uint32_t tap = fdiv(k, div_cp);
+      mask[k] = (tap < RS && k - tap * Cp < Ci) ? 1 : 0;
+    }
+    return;
+  }
+  int sum = 0;
+  for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
+    const uint32_t tap = fdiv(k, div_cp);
+    const uint32_t ci = k - tap * Cp;
+    int v = 0;
+    if (co < Co && tap < RS && ci < Ci) {
+      const size_t bit = (((size_t)co * Ci + ci) * RS + tap) * (size_t)bs;
+      const uint32_t u = ((uint32_t)packed[bit >> 3] >> (bit & 7)) & ((1u << bs) - 1u);
+      v = (int)u - 128;   // q - cw, q = u + qmin, cw = qmin + 128
+      sum += v;
+    }
+    wp[(size_t)co * Kp + k] = (int8_t)v;
+  }
+  sum = (int)wave_sum_u32((uint32_t)sum);
+  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0, t = 0;
+    if (co < Co) {
+      float z = zp[co];
+      // any integer near the code range: |cwz| <= 384 keeps K * cwz inside int32
+      if (!(z == rintf(z) && z >= (float)(qmin - 256) && z <= (float)(qmin + 511))) {
+        atomicAdd(bad, 1u);
+        z = (float)qmin;
+      }
+      int total = 0;
+      for (int i = 0; i < kBlock / kWave; ++i) total += red[i];
+      c = qmin + 128 - (int)z;
+      t = total + (int)(Ci * RS) * c;
+    }
+    cwz[co] = c;
+    tt[co] = t;
+  }
+}
+
+// ---------------------------------------------------------------- K23 int8 implicit-GEMM conv
+struct QConvGeo {
+  uint32_t M, P, OW, H, W, Cp, Co, Kp, RS, S;
+  int stride, pad, az, padv;
+  FastDiv div_p, div_ow, div_cp, div_s;
+};
+
+__global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
+    const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ mask,
+    const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
+    const float* __restrict__ scale, QConvGeo g, float* __restrict__ y) {
+  __shared__ __attribute__((aligned(16))) int8_t lA[kQT * kQRow];
+  __shared__ __attribute__((aligned(16))) int8_t lB[(kQT + 1) * kQRow];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & (kWave - 1), wave = tid / kWave;
+  const uint32_t fr = lane & 15, fq = lane >> 4;
+
+  // staging role: one 16-byte chunk of each operand tile per thread
+  const uint32_t srow = tid >> 2, sc = tid & 3;
+  const uint32_t gm = blockIdx.x * kQT + srow;
+  const bool mval = gm < g.M;
+  const uint32_t gmc = mval ? gm : 0u;
+  const uint32_t sn = fdiv(gmc, g.div_p);
+  const uint32_t sp = gmc - sn * g.P;
+  const uint32_t soh = fdiv(sp, g.div_ow);
+  const uint32_t sow = sp - soh * g.OW;
+  const int ih0 = (int)soh * g.stride - g.pad, iw0 = (int)sow * g.stride - g.pad;
+  const int8_t* abase = act + (size_t)sn * g.H * g.W * g.Cp;
+  const int8_t* wrow = wp + (size_t)(blockIdx.y * kQT + srow) * g.Kp + sc * 16;
+  const int pv = (g.padv & 0xff) * 0x01010101;
+  const i32x4 padfill = {pv, pv, pv, pv};
+
+  auto load_a = [&](uint32_t kt) -> i32x4 {
+    const uint32_t k = kt * kQT + sc * 16;
+    const uint32_t tap = fdiv(k, g.div_cp);
+    const uint32_t ci0 = k - tap * g.Cp;
+    const uint32_t r = fdiv(tap, g.div_s);
+    const uint32_t s = tap - r * g.S;
+    const int ih = ih0 + (int)r, iw = iw0 + (int)s;
+    if (mval && tap < g.RS && (uint32_t)ih < g.H && (uint32_t)iw < g.W)
+      return *(const i32x4*)(abase + ((size_t)ih * g.W + (size_t)iw) * g.Cp + ci0);
+    return padfill;
+  };
+
+  i32x4 ra = load_a(0);
+  i32x4 rb = *(const i32x4*)wrow;
+  i32x4 rm = {0, 0, 0, 0};
+  if (tid < 4) rm = *(const i32x4*)(mask + tid * 16);
+
+  i32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = i32x4{0, 0, 0, 0};
+  i32x4 accs = {0, 0, 0, 0};
+
+  const uint32_t nk = g.Kp / kQT;
+  for (uint32_t kt = 0; kt < nk; ++kt) {
+    __syncthreads();   // the previous step's fragment reads are done
+    *(i32x4*)(lA + srow * kQRow + sc * 16) = ra;
+    *(i32x4*)(lB + srow * kQRow + sc * 16) = rb;
+    if (tid < 4) *(i32x4*)(lB + kQT * kQRow + tid * 16) = rm;
+    __syncthreads();
+    if (kt + 1 < nk) {
+      ra = load_a(kt + 1);
+      rb = *(const i32x4*)(wrow + (size_t)(kt + 1) * kQT);
+      if (tid < 4) rm = *(const i32x4*)(mask + (size_t)(kt + 1) * kQT + tid * 16);
+    }
+    const i32x4 af = *(const i32x4*)(lA + (wave * 16 + fr) * kQRow + fq * 16);
+    const i32x4 mf = *(const i32x4*)(lB + kQT * kQRow + fq * 16);
+    accs = __builtin_amdgcn_mfma_i32_16x16x64_i8(mf, af, accs, 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const i32x4 wf = *(const i32x4*)(lB + (j * 16 + fr) * kQRow + fq * 16);
+      acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, af, acc[j], 0, 0, 0);
+    }
+  }
+
+  // C/D map: column (pixel) = lane & 15, row (channel) = 4 * (lane >> 4) + reg
+  const uint32_t pixel = blockIdx.x * kQT + wave * 16 + fr;
+  if (pixel >= g.M) return;
+  const uint32_t n = fdiv(pixel, g.div_p);
+  const uint32_t p = pixel - n * g.P;
+  const long long sa = (long long)accs[0];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
+      if (co < g.Co) {
+        const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
+                            (long long)g.az * (long long)tt[co];
+        y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
+      }
+    }
+  }
+}
+
+static int qrange_ok(const char* what, int n_bits, int qmin) {
+  SSQ_REQUIRE(n_bits >= 1 && n_bits <= 8, SSQ_E_ARG, "%s: n_bits %d not in [1, 8]", what, n_bits);
+  SSQ_REQUIRE(qmin == 0 || qmin == -(1 << (n_bits - 1)), SSQ_E_ARG,
+              "%s: qmin %d is neither 0 nor -2^(n_bits-1)", what, qmin);
+  return SSQ_OK;
+}
+
+static int qgeo_ok(const char* what, int64_t Co, int64_t Ci, int64_t R, int64_t S) {
+  SSQ_REQUIRE(Co >= 1 && Ci >= 1 && R >= 1 && S >= 1 && R <= 7 && S <= 7, SSQ_E_ARG,
+              "%s: bad geometry (Co, Ci >= 1; R, S in [1, 7])", what);
+  SSQ_REQUIRE(Ci * R * S <= kQMaxK, SSQ_E_ARG,
+              "%s: K = Ci*R*S = %lld exceeds 65536 (int32 accumulator range)", what,
+              (long long)(Ci * R * S));
+  const QLayout L = qlayout(Co, Ci, R, S);
+  SSQ_REQUIRE(L.off_mask < (1ull << 31), SSQ_E_ARG, "%s: prepared weights exceed 2^31 bytes", what);
+  return SSQ_OK;
+}
+
+}  // namespace ssq
+
+using namespace ssq;
+
+extern "C" int64_t ssq_qinfer_cpad(int64_t C) { return C >= 1 ? rup(C, 16) : 0; }
+
+extern "C" size_t ssq_qweight_prepared_bytes(int64_t Co, int64_t Ci, int64_t R, int64_t S) {
+  if (Co < 1 || Ci < 1 || R < 1 || S < 1) return 0;
+  return qlayout(Co, Ci, R, S).bytes;
+}
+
+extern "C" int ssq_act_encode(const float* x, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                              float delta, float zero_point, int qmin, int qmax, int8_t* codes,
+                              uint32_t* bad, ssq_stream_t stream) {
+  SSQ_REQUIRE(x && codes && bad, SSQ_E_ARG, "ssq_act_encode: null pointer");
+  SSQ_REQUIRE(Nb >= 1 && C >= 1 && H >= 1 && W >= 1, SSQ_E_ARG, "ssq_act_encode: bad geometry");
+  SSQ_REQUIRE(qmin < qmax && qmax - qmin <= 255, SSQ_E_ARG,
+              "ssq_act_encode: code range [%d, %d] does not fit 8-bit codes", qmin, qmax);
+  SSQ_REQUIRE(delta > 0.0f && delta <= 3.0e38f, SSQ_E_ARG,
+              "ssq_act_encode: delta must be positive and finite");
+  // a padded tap stores zero_point - (qmin + 128) as an int8
+  SSQ_REQUIRE(zero_point == rintf(zero_point) && zero_point >= (float)qmin &&
+                  zero_point <= (float)(qmin + 255),
+              SSQ_E_ARG, "ssq_act_encode: zero point %g is not an integer in [%d, %d]",
+              (double)zero_point, qmin, qmin + 255);
+  const int64_t Cp = rup(C, 16);
+  SSQ_REQUIRE(Nb * H * W * Cp < (1ll << 31), SSQ_E_ARG,
+              "ssq_act_encode: tensor exceeds 2^31 elements");
+  const uint32_t npix = (uint32_t)(Nb * H * W), HW = (uint32_t)(H * W);
+  const dim3 grid(grid_for((int64_t)npix * (Cp / 16), kBlock, 8192));
+  hipLaunchKernelGGL(act_encode_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, x, npix, HW,
+                     (uint32_t)C, (uint32_t)Cp, make_fastdiv(npix), make_fastdiv(HW), delta,
+                     zero_point, (float)qmin, (float)qmax, codes, bad);
+  return check_launch("ssq_act_encode");
+}
+
+extern "C" int ssq_qweight_prepare(const void* packed, const float* zp, int64_t Co, int64_t Ci,
+                                   int64_t R, int64_t S, int n_bits, int qmin, void* prepared,
+                                   uint32_t* bad, ssq_stream_t stream) {
+  SSQ_REQUIRE(packed && zp && prepared && bad, SSQ_E_ARG, "ssq_qweight_prepare: null pointer");
+  int rc = qrange_ok("ssq_qweight_prepare", n_bits, qmin);
+  if (rc) return rc;
+  rc = qgeo_ok("ssq_qweight_prepare", Co, Ci, R, S);
+  if (rc) return rc;
+  const QLayout L = qlayout(Co, Ci, R, S);
+  int8_t* base = (int8_t*)prepared;
+  const int bs = n_bits <= 2 ? 2 : (n_bits <= 4 ? 4 : 8);
+  hipLaunchKernelGGL(qweight_prepare_kernel, dim3((uint32_t)L.Cop + 1), dim3(kBlock), 0,
+                     (hipStream_t)stream, (const uint8_t*)packed, zp, bs, qmin, (uint32_t)Co, (uint32_t)Ci, (uint32_t)(R * S),
+                     (uint32_t)L.Cp, (uint32_t)L.Kp, (uint32_t)L.Cop, make_fastdiv((uint32_t)L.Cp),
+                     base, base + L.off_mask, (int32_t*)(base + L.off_cwz),
+                     (int32_t*)(base + L.off_t), bad);
+  return check_launch("ssq_qweight_prepare");
+}
+
+extern "C" int ssq_qconv_i8_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                                float act_zero_point, int act_qmin, int act_qmax, float* y,
+                                ssq_stream_t stream) {
+  SSQ_REQUIRE(codes && prepared && scale && y, SSQ_E_ARG, "ssq_qconv_i8_fwd: null pointer");
+  SSQ_REQUIRE(groups == 1, SSQ_E_ARG, "ssq_qconv_i8_fwd: groups = %lld (only groups == 1)",
+              (long long)groups);
+  int rc = qgeo_ok("ssq_qconv_i8_fwd", Co, Ci, R, S);
+  if (rc) return rc;
+  SSQ_REQUIRE(Nb >= 1 && H >= 1 && W >= 1 && stride >= 1 && pad >= 0 &&
+                  H + 2 * pad >= R && W + 2 * pad >= S,
+              SSQ_E_ARG, "ssq_qconv_i8_fwd: bad geometry");
+  SSQ_REQUIRE(act_qmin < act_qmax && act_qmax - act_qmin <= 255, SSQ_E_ARG,
+              "ssq_qconv_i8_fwd: activation code range [%d, %d] does not fit 8-bit codes",
+              act_qmin, act_qmax);
+  // a padded tap stores act_zero_point - (act_qmin + 128) as an int8
+  SSQ_REQUIRE(act_zero_point == rintf(act_zero_point) && act_zero_point >= (float)act_qmin &&
+                  act_zero_point <= (float)(act_qmin + 255),
+              SSQ_E_ARG, "ssq_qconv_i8_fwd: zero point %g is not an integer in [%d, %d]",
+              (double)act_zero_point, act_qmin, act_qmin + 255);
+  const QLayout L = qlayout(Co, Ci, R, S);
+  const int64_t OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
+  SSQ_REQUIRE(Nb * H * W * L.Cp < (1ll << 31) && Nb * OH * OW * Co < (1ll << 31), SSQ_E_ARG,
+              "ssq_qconv_i8_fwd: tensor exceeds 2^31 elements");
+  QConvGeo g;
+  g.M = (uint32_t)(Nb * OH * OW);
+  g.P = (uint32_t)(OH * OW);
+  g.OW = (uint32_t)OW;
+  g.H = (uint32_t)H;
+  g.W = (uint32_t)W;
+  g.Cp = (uint32_t)L.Cp;
+  g.Co = (uint32_t)Co;
+  g.Kp = (uint32_t)L.Kp;
+  g.RS = (uint32_t)(R * S);
+  g.S = (uint32_t)S;
+  g.stride = (int)stride;
+  g.pad = (int)pad;
+  const int ca = act_qmin + 128, za = (int)act_zero_point;
+  g.az = ca - za;
+  g.padv = za - ca;   // a padded tap: (q_a - z_a) = 0
+  g.div_p = make_fastdiv(g.P);
+  g.div_ow = make_fastdiv(g.OW);
+  g.div_cp = make_fastdiv(g.Cp);
+  g.div_s = make_fastdiv(g.S);
+  const int8_t* base = (const int8_t*)prepared;
+  const dim3 grid((g.M + kQT - 1) / kQT, (uint32_t)(L.Cop / kQT));
+  hipLaunchKernelGGL(qconv_i8_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base,
+                     base + L.off_mask, (const int32_t*)(base + L.off_cwz),
+                     (const int32_t*)(base + L.off_t), scale, g, y);
+  return check_launch("ssq_qconv_i8_fwd");
+}

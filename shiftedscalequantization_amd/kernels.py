@@ -1834,6 +1834,110 @@ def pack_decode(packed, shape, zp, d1, per_ci, d2, n_bits, qmin):
     return out
 
 
+# ------------------------------------------------------------------ K21-K23 integer inference
+def code_offset(n_bits, sym):
+    """K21 / K22 store a code q as the int8 q - code_offset (= qmin + 128)."""
+    return qrange(n_bits, sym)[0] + 128
+
+
+def _i8_dev(t, name):
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise A.SSQError(f"{name}: ssq kernels run on the MI355X (HIP) device only")
+    return t.contiguous()
+
+
+def act_encode(x, delta, zp, n_bits, sym=False, bad=None):
+    """An act quantizer's output x = (q - zp) * delta (fp32 NCHW or (N, C); scalar delta, zp)
+    -> (int8 codes q - code_offset(n_bits, sym) in NHWC order, channels zero-padded to a
+    multiple of 16; the device int32 counter).  The counter -- `bad` when given (it is ADDED
+    to), else a fresh zero -- receives the number of elements that are not bit-identical to a
+    grid point (NaN / inf included, stored as qmin).  Nothing syncs."""
+    x, xp = fptr(x, "x")
+    if x.dim() not in (2, 4):
+        raise A.SSQError(f"act_encode: expected (N, C, H, W) or (N, C), got {tuple(x.shape)}")
+    N, Cc = int(x.shape[0]), int(x.shape[1])
+    H, W = (int(x.shape[2]), int(x.shape[3])) if x.dim() == 4 else (1, 1)
+    lo, hi = qrange(n_bits, sym)
+    Cp = query("ssq_qinfer_cpad", Cc)
+    codes = torch.empty((N, H, W, Cp) if x.dim() == 4 else (N, Cp), dtype=torch.int8,
+                        device=x.device)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=x.device)
+    call("ssq_act_encode", xp, N, Cc, H, W, float(delta), float(zp), lo, hi, _vp(codes), _vp(bad),
+         stream_of(x))
+    return codes, bad
+
+
+class QPrepared:
+    """A layer's weight as K23's operand (K22's output) with its (Co, Ci[, R, S]) shape; `bad`
+    counts the channels whose zero point is not an integer code (device int32)."""
+
+    def __init__(self, blob, shape, bad):
+        self.blob, self.shape, self.bad = blob, tuple(int(s) for s in shape), bad
+
+    def geometry(self):
+        Co, Ci = self.shape[:2]
+        R, S = (self.shape[2], self.shape[3]) if len(self.shape) == 4 else (1, 1)
+        return Co, Ci, R, S
+
+
+def qweight_prepare(packed, shape, zp, n_bits, qmin):
+    """Packed codes (pack_encode's layout) + zp[co] -> QPrepared."""
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
+        raise A.SSQError("qweight_prepare: packed codes must be a uint8 tensor")
+    packed = _i8_dev(packed, "qweight_prepare")
+    if len(shape) not in (2, 4):
+        raise A.SSQError(f"qweight_prepare: weight shape {tuple(shape)} is neither Linear nor Conv2d")
+    prep = QPrepared(None, shape, torch.zeros(1, dtype=torch.int32, device=packed.device))
+    Co, Ci, R, S = prep.geometry()
+    if packed.numel() < query("ssq_pack_bytes", Co * Ci * R * S, n_bits):
+        raise A.SSQError("qweight_prepare: packed buffer too small for the shape")
+    z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
+    if z.numel() != Co:
+        raise A.SSQError("qweight_prepare: zero point must have one entry per output channel")
+    prep.blob = torch.empty(max(query("ssq_qweight_prepared_bytes", Co, Ci, R, S), 1),
+                            dtype=torch.uint8, device=packed.device)
+    call("ssq_qweight_prepare", _vp(packed), zpp, Co, Ci, R, S, int(n_bits), int(qmin),
+         _vp(prep.blob), _vp(prep.bad), stream_of(packed))
+    return prep
+
+
+def qconv(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0, act_bits=8,
+          act_sym=False, act_delta=None, bad=None):
+    """y = fp32(I) * scale[co] (fp32 NCHW / (N, Co)), I the exact integer conv of the centred
+    codes.  `codes_or_x`: act_encode's int8 codes, or the fp32 activation itself, which is then
+    encoded with (act_delta, act_zp, act_bits, act_sym), off-grid elements ADDED to `bad`.
+    (act_zp, act_bits, act_sym) are the act quantizer's either way."""
+    stride, padding = _pair(stride), _pair(padding)
+    if stride[0] != stride[1] or padding[0] != padding[1]:
+        raise A.SSQError("qconv: square stride / padding only")
+    if codes_or_x.dtype == torch.float32:
+        if act_delta is None:
+            raise A.SSQError("qconv: an fp32 input needs act_delta to be encoded")
+        codes, _ = act_encode(codes_or_x, act_delta, act_zp, act_bits, act_sym, bad=bad)
+    elif codes_or_x.dtype == torch.int8:
+        codes = _i8_dev(codes_or_x, "qconv")
+    else:
+        raise A.SSQError(f"qconv: expected int8 codes or an fp32 activation, got {codes_or_x.dtype}")
+    Co, Ci, R, S = prepared.geometry()
+    Cp = query("ssq_qinfer_cpad", Ci)
+    if codes.dim() not in (2, 4) or codes.shape[-1] != Cp or (codes.dim() == 2) != (len(prepared.shape) == 2):
+        raise A.SSQError(f"qconv: codes {tuple(codes.shape)} do not match the weight {prepared.shape}")
+    N = int(codes.shape[0])
+    H, W = (int(codes.shape[1]), int(codes.shape[2])) if codes.dim() == 4 else (1, 1)
+    s, sp = fptr(scale.detach().reshape(-1), "scale")
+    if s.numel() != Co:
+        raise A.SSQError("qconv: scale must have one entry per output channel")
+    OH = (H + 2 * padding[0] - R) // stride[0] + 1
+    OW = (W + 2 * padding[0] - S) // stride[0] + 1
+    y = torch.empty((N, Co, max(OH, 0), max(OW, 0)) if codes.dim() == 4 else (N, Co),
+                    dtype=torch.float32, device=codes.device)
+    lo, hi = qrange(act_bits, act_sym)
+    call("ssq_qconv_i8_fwd", _vp(codes), _vp(prepared.blob), sp, N, Ci, H, W, Co, R, S,
+         int(stride[0]), int(padding[0]), int(groups), float(act_zp), lo, hi, _vp(y), stream_of(y))
+    return y
+
+
 # ------------------------------------------------------------------ K17 conv weight gradient
 def conv_wgrad_supported(x, weight, stride, padding, dilation, groups):
     """Shapes ssq_conv_wgrad handles: 4-D fp32 NCHW on the device, square stride /

@@ -18,3 +18,4 @@ from .layer_recon_shiftedScale import (LinearTempDecayShift, ScaleLossBlockFunct
                                        layer_recon_shiftedScale)
 from .data_utils import save_inp_oup_data, save_grad_data
 from .export import PackedWeight, dequant_form, export_quantized, load_quantized
+from .integer import disable_integer_inference, enable_integer_inference, integer_report

@@ -300,6 +300,7 @@ class QuantModule(nn.Module):
         self.selection = None
         self.selectionInited = False
         self.pathName = ''
+        self._int_plan = None           # integer route (quant/integer.py); None: decoded fp32
 
     def _cache(self, t):
         t = t.detach()
@@ -384,6 +385,15 @@ class QuantModule(nn.Module):
         """The layer's conv / linear; a conv whose weight needs a gradient goes through
         K.conv2d (deterministic K17 weight gradient, see kernels.WGRAD_POLICY; a LazyEpi
         input folded into its im2col GEMM there)."""
+        plan = getattr(self, '_int_plan', None)
+        if (plan is not None and not torch.is_grad_enabled() and self.use_weight_quant
+                and self.use_act_quant and self.cache_features == 'none'
+                and isinstance(input, torch.Tensor) and input.is_cuda
+                and input.dtype == torch.float32):
+            # the input is an act quantizer's output: int8 codes on the int8 MFMA (K21/K23);
+            # off-grid elements are counted on the device (quant.integer_report)
+            out = plan.run(input)
+            return out if bias is None else out + bias.view((1, -1) + (1,) * (out.dim() - 2))
         if self.fwd_func is F.conv2d and input.is_cuda and weight.requires_grad:
             out = K.conv2d(input, weight, **self.fwd_kwargs)
             return out if bias is None else out + bias.view(1, -1, 1, 1)
