@@ -702,6 +702,38 @@ int ssq_qconv_i8_fwd(const int8_t* codes, const void* prepared, const float* sca
                      int64_t stride, int64_t pad, int64_t groups, float act_zero_point,
                      int act_qmin, int act_qmax, float* y, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- K24-K26 grouped integer inference
+ * The same contract for a conv with groups = G >= 2, Cig = C/G, Cog = Co/G: output channel co
+ * belongs to group co / Cog and I runs over that group's K = Cig*R*S taps.  The activation
+ * operand is K21's, unchanged (dense NHWC int8, C padded to qinfer_cpad(C) at the end only),
+ * so one encode serves every consumer.
+ *
+ * qconv_grouped_kind(Co, Cig, groups): the kernel prepare and conv both take -- 1 the direct
+ * depthwise kernel (Cig == 1 and Co == groups), 2 the grouped int8-MFMA kernel (every other
+ * groups >= 2), 0 invalid (groups < 2, Co or Cig < 1, Co % groups != 0).
+ *
+ * K24 qweight_prepare_grouped (once per layer): the export's packed codes as stored, bit
+ * offset ((co*Cig + ci)*R*S + tap)*bs, + zp[co] -> qweight_prepared_bytes_grouped(Co, Cig, R,
+ * S, groups) bytes (0 on invalid geometry) in a layout private to the kind
+ * (csrc/qinfer_grouped.hip).  ADDS to *bad the number of channels whose zp is not an integer in
+ * [qmin-256, qmin+511], as K22 does.
+ *
+ * K25 / K26 qconv_i8_grouped_fwd: codes (K21, C channels) x prepared (K24) -> y, fp32 NCHW.
+ * Host-side checks before the launch (SSQ_E_ARG): null pointer, groups < 2 (groups == 1 is
+ * ssq_qconv_i8_fwd), C or Co not divisible by groups, R or S outside [1, 7], Cig*R*S > 65536,
+ * a tensor of 2^31 elements or more, a zero point that is not an integer in [qmin, qmin+255]. */
+int ssq_qconv_grouped_kind(int64_t Co, int64_t Cig, int64_t groups);
+size_t ssq_qweight_prepared_bytes_grouped(int64_t Co, int64_t Cig, int64_t R, int64_t S,
+                                          int64_t groups);
+int ssq_qweight_prepare_grouped(const void* packed, const float* zp, int64_t Co, int64_t Cig,
+                                int64_t R, int64_t S, int64_t groups, int n_bits, int qmin,
+                                void* prepared, uint32_t* bad, ssq_stream_t stream);
+int ssq_qconv_i8_grouped_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                             int64_t Nb, int64_t C, int64_t H, int64_t W, int64_t Co, int64_t R,
+                             int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                             float act_zero_point, int act_qmin, int act_qmax, float* y,
+                             ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- bandwidth probe
  * float4 device copy, used by bench.py to report the measured stream bandwidth.      */
 int ssq_stream_copy(const float* src, float* dst, int64_t n, ssq_stream_t stream);

@@ -154,7 +154,7 @@ def main(argv=None):
                                                                    validate_model(loader, qnn)))
     if args.int_infer and args.act_quant:
         from shiftedscalequantization_amd.quant import enable_integer_inference, integer_report
-        plan = enable_integer_inference(qnn, cali[:8])
+        plan = enable_integer_inference(qnn, cali[:8], grouped=args.int_infer_grouped)
         n_int = sum(v == 'int8' for v in plan.values())
         print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
         for name, why in plan.items():

@@ -73,6 +73,9 @@ def build_parser():
     p.add_argument('--int_infer', action='store_true',
                    help='after calibration, validate again with the interior layers on their '
                         'integer codes (int8 MFMA conv / linear) and print the per-layer report')
+    p.add_argument('--int_infer_grouped', action='store_true',
+                   help='--int_infer with the grouped and depthwise convs on integer codes too '
+                        '(depthwise direct kernel, grouped int8 MFMA conv); implies --int_infer')
     p.add_argument('--deterministic', default=1, type=int,
                    help='1 (reference): deterministic MIOpen conv solvers; 0: fastest solvers')
     # data parallel: one process per GPU, spawned by main_imagenet.py itself with --gpus N
@@ -90,6 +93,8 @@ def parse_args(argv=None):
     a = build_parser().parse_args(argv)
     if a.run_device:
         a.device_gpu = a.run_device
+    if a.int_infer_grouped:
+        a.int_infer = True
     return a
 
 

@@ -1,0 +1,528 @@
+// K24-K26: integer inference of grouped and depthwise convs (groups >= 2).
+//
+// Same contract as K23 (qinfer.hip): y[n, co, p] = fp32(I) * s[co] with
+//     I = sum over the K = Cig*R*S taps of co's group of (q_a - z_a)(q_w - z_w[co])
+// exact, one int -> fp32 conversion and one __fmul_rn.  The activation operand is K21's as it
+// stands: dense NHWC int8 a_s = q_a - ca with C padded to Cp = 16*ceil(C/16) at the end only.
+// One rule (qg_kind) picks the kernel in prepare and in the conv:
+//
+// kind 1, depthwise (groups == C == Co), K25 qconv_dw_kernel.  K is 1..49 taps: nothing for
+// the MFMA.  One thread per output pixel, the 64 lanes of a wave on 64 consecutive pixels; a
+// workgroup walks a run of consecutive 16-channel chunks for its 256 pixels, so the chunks
+// that share a cache line of the NHWC codes are read by one CU.  Per tap one 16-B code load
+// (a padded tap takes the pad value z_a - ca instead, its (q_a - z_a) = 0), 16 x
+// (a_s + az) * wc into int32 (|I| <= 49 * 255^2 < 2^24: exact, and so is the conversion);
+// 16 fp32 stores per chunk, each coalesced across the wave's pixels of one NCHW channel
+// plane.  The prepared blob is the centred weight wc = q_w - z_w[c] as int32 [R*S][Cp] (0 on
+// padded channels); its address is wave-uniform, so the 16 values of a (tap, chunk) come
+// through the scalar cache into SGPRs: no LDS, no barrier.
+//
+// kind 2, everything else, K26 qconv_grouped_kernel: K23's tile and shift-and-correct identity
+// per group,  I = D + cwz[co] * SA_g + az * T[co],  K = Cig*R*S.  A group's channels need not
+// start or end on a 16-B chunk, so group g reads the 16-aligned channel window that covers it,
+//     [w0_g, w0_g + Wc),  w0_g = 16*floor(g*Cig/16),  Wc = max_g (16*ceil((g+1)*Cig/16) - w0_g),
+// k = tap * Wc + (c - w0_g).  Its prepared weight rows and its own 0/1 row are zero on window
+// channels outside the group (and on the k tail), so D and SA_g see the group only whatever
+// the neighbouring channels hold; a chunk past Cp is not loaded.  A workgroup owns 64 output
+// pixels x one tile of up to 64 channels of one group; rows are stored per group padded to
+// Cogp = 16*ceil(Cog/16) and a tile runs only the 16-row fragments it has (Cog = 8: one MFMA
+// + the SA MFMA per k step, not four).
+// Blob: int8 [G*Cogp][Kp], Kp = 64*ceil(R*S*Wc/64); the 0/1 rows [G][Kp]; cwz[Co], T[Co] (int32).
+#include "ssq_common.h"
+
+namespace ssq {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kGT = 64;      // pixels, channel rows (at most) and k per tile step
+constexpr int kGRow = 80;    // LDS row stride in bytes (64 + 16), as K23
+constexpr int64_t kGMaxK = 65536;
+constexpr uint32_t kDwBlocks = 2048;   // workgroups K25 aims for: 8 per CU
+
+static inline int64_t rup(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+
+// 0 invalid, 1 depthwise direct, 2 grouped MFMA
+static inline int qg_kind(int64_t Co, int64_t Cig, int64_t groups) {
+  if (groups < 2 || Co < 1 || Cig < 1 || Co % groups != 0) return 0;
+  return (Cig == 1 && Co == groups) ? 1 : 2;
+}
+
+struct GLayout {
+  int kind;
+  int64_t C, Cp, Cog, Cogp, Wc, Kp, tiles;   // tiles: channel tiles per group
+  size_t off_mask, off_cwz, off_t, bytes;
+};
+
+static inline GLayout glayout(int64_t Co, int64_t Cig, int64_t R, int64_t S, int64_t groups) {
+  GLayout L = {};
+  L.kind = qg_kind(Co, Cig, groups);
+  if (!L.kind || R < 1 || S < 1) {
+    L.kind = 0;
+    return L;
+  }
+  L.C = Cig * groups;
+  L.Cp = rup(L.C, 16);
+  L.Cog = Co / groups;
+  if (L.kind == 1) {
+    L.bytes = (size_t)(R * S) * (size_t)L.Cp * 4;
+    return L;
+  }
+  L.Cogp = rup(L.Cog, 16);
+  L.tiles = (L.Cogp + kGT - 1) / kGT;
+  // the window width repeats with period 16 / gcd(Cig, 16) <= 16 groups
+  for (int64_t g = 0; g < groups && g < 16; ++g) {
+    const int64_t w = rup((g + 1) * Cig, 16) - g * Cig / 16 * 16;
+    if (w > L.Wc) L.Wc = w;
+  }
+  L.Kp = rup(R * S * L.Wc, kGT);
+  L.off_mask = (size_t)(groups * L.Cogp) * (size_t)L.Kp;
+  L.off_cwz = L.off_mask + (size_t)groups * (size_t)L.Kp;
+  L.off_t = L.off_cwz + (size_t)Co * 4;
+  L.bytes = L.off_t + (size_t)Co * 4;
+  return L;
+}
+
+__device__ __forceinline__ uint32_t gwave_sum_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, kWave);
+  return v;
+}
+
+// K22's zero-point rule: any integer near the code range, else counted and taken as qmin
+__device__ __forceinline__ bool zp_is_code(float z, int qmin) {
+  return z == rintf(z) && z >= (float)(qmin - 256) && z <= (float)(qmin + 511);
+}
+__device__ __forceinline__ int zp_or_qmin(float z, int qmin, uint32_t* bad) {
+  if (!zp_is_code(z, qmin)) {
+    atomicAdd(bad, 1u);
+    return qmin;
+  }
+  return (int)z;
+}
+
+__device__ __forceinline__ uint32_t packed_code(const uint8_t* packed, size_t idx, int bs) {
+  const size_t bit = idx * (size_t)bs;
+  return ((uint32_t)packed[bit >> 3] >> (bit & 7)) & ((1u << bs) - 1u);
+}
+
+// ---------------------------------------------------------------- K24 weight prepare
+// depthwise: one thread per (tap, padded channel)
+__global__ __launch_bounds__(kBlock) void qweight_prepare_dw_kernel(
+    const uint8_t* __restrict__ packed, const float* __restrict__ zp, int bs, int qmin, uint32_t C,
+    uint32_t RS, uint32_t Cp, FastDiv div_cp, int32_t* __restrict__ wc, uint32_t* __restrict__ bad) {
+  const uint32_t total = RS * Cp;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const uint32_t tap = fdiv(i, div_cp);
+    const uint32_t c = i - tap * Cp;
+    int v = 0;
+    if (c < C) {
+      const float zf = zp[c];
+      const bool ok = zp_is_code(zf, qmin);
+      const int z = ok ? (int)zf : qmin;
+      if (!ok && tap == 0) atomicAdd(bad, 1u);   // counted once per channel
+      v = (int)packed_code(packed, (size_t)c * RS + tap, bs) + qmin - z;
+    }
+    wc[i] = v;
+  }
+}
+
+// grouped: one workgroup per padded row (g, rl), then one per group for its 0/1 row
+__global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_kernel(
+    const uint8_t* __restrict__ packed, const float* __restrict__ zp, int bs, int qmin,
+    uint32_t groups, uint32_t Cig, uint32_t Cog, uint32_t Cogp, uint32_t RS, uint32_t Wc,
+    uint32_t Kp, FastDiv div_wc, FastDiv div_cogp, int8_t* __restrict__ wp,
+    int8_t* __restrict__ mask, int32_t* __restrict__ cwz, int32_t* __restrict__ tt,
+    uint32_t* __restrict__ bad) {
+  __shared__ int red[kBlock / kWave];
+  const uint32_t row = blockIdx.x;
+  const uint32_t nrows = groups * Cogp;
+  if (row >= nrows) {
+    const uint32_t g = row - nrows;
+    const uint32_t lo = g * Cig - g * Cig / 16 * 16;   // the group's offset inside its window
+    for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
+      const uint32_t tap = fdiv(k, div_wc);
+      const uint32_t cw = k - tap * Wc;
+      mask[(size_t)g * Kp + k] = (tap < RS && cw >= lo && cw < lo + Cig) ? 1 : 0;
+    }
+    return;
+  }
+  const uint32_t g = fdiv(row, div_cogp);
+  const uint32_t rl = row - g * Cogp;
+  const uint32_t co = g * Cog + rl;
+  const bool real = rl < Cog;
+  const uint32_t lo = g * Cig - g * Cig / 16 * 16;
+  int sum = 0;
+  for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
+    const uint32_t tap = fdiv(k, div_wc);
+    const uint32_t cw = k - tap * Wc;
+    int v = 0;
+    if (real && tap < RS && cw >= lo && cw < lo + Cig) {
+      v = (int)packed_code(packed, ((size_t)co * Cig + (cw - lo)) * RS + tap, bs) - 128;
+      sum += v;
+    }
+    wp[(size_t)row * Kp + k] = (int8_t)v;
+  }
+  sum = (int)gwave_sum_u32((uint32_t)sum);
+  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0 && real) {
+    const int z = zp_or_qmin(zp[co], qmin, bad);
+    int total = 0;
+    for (int i = 0; i < kBlock / kWave; ++i) total += red[i];
+    const int c = qmin + 128 - z;
+    cwz[co] = c;
+    tt[co] = total + (int)(Cig * RS) * c;
+  }
+}
+
+// ---------------------------------------------------------------- K25 depthwise direct conv
+struct QDwGeo {
+  uint32_t M, P, OW, H, W, C, Cp, R, S, nch, per;   // per: chunks per workgroup (blockIdx.y)
+  int stride, pad, az, padv;
+  FastDiv div_p, div_ow;
+};
+
+// KS: the square kernel size the s loop is unrolled for (its loads fly together); 0: any R x S
+template <int KS>
+__global__ __launch_bounds__(kBlock) void qconv_dw_kernel(const int8_t* __restrict__ act,
+                                                          const int32_t* __restrict__ wc,
+                                                          const float* __restrict__ scale,
+                                                          QDwGeo g, float* __restrict__ y) {
+  const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= g.M) return;
+  const uint32_t n = fdiv(pix, g.div_p);
+  const uint32_t p = pix - n * g.P;
+  const uint32_t oh = fdiv(p, g.div_ow);
+  const uint32_t ow = p - oh * g.OW;
+  const int ih0 = (int)oh * g.stride - g.pad, iw0 = (int)ow * g.stride - g.pad;
+  const uint32_t R = KS ? KS : g.R, S = KS ? KS : g.S;
+  const int pv = (g.padv & 0xff) * 0x01010101;
+  const i32x4 padfill = {pv, pv, pv, pv};
+  const uint32_t ch0 = blockIdx.y * g.per;
+  const uint32_t ch1 = min(ch0 + g.per, g.nch);
+  for (uint32_t ch = ch0; ch < ch1; ++ch) {
+    // byte offsets fit 32 bits: the host checked Nb*H*W*Cp < 2^31
+    const int8_t* abase = act + (n * g.H * g.W * g.Cp + ch * 16);
+    int acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0;
+#pragma unroll 1
+    for (uint32_t r = 0; r < R; ++r) {
+      const int ih = ih0 + (int)r;
+      const bool rok = (uint32_t)ih < g.H;
+      const int8_t* arow = abase + (uint32_t)(rok ? ih : 0) * g.W * g.Cp;
+      const int32_t* wr = wc + (r * S * g.Cp + ch * 16);   // wave-uniform
+#pragma unroll
+      for (uint32_t s = 0; s < S; ++s) {
+        const int iw = iw0 + (int)s;
+        const bool ok = rok && (uint32_t)iw < g.W;
+        i32x4 v = *(const i32x4*)(arow + (uint32_t)(ok ? iw : 0) * g.Cp);   // in bounds either way
+        if (!ok) v = padfill;
+        const int32_t* wt = wr + s * g.Cp;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t word = (uint32_t)v[q];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const int a = ((int)(word << (24 - 8 * b)) >> 24) + g.az;   // sign-extended byte + az
+            acc[q * 4 + b] += __mul24(a, wt[q * 4 + b]);   // |a| < 2^9, |wc| < 2^10
+          }
+        }
+      }
+    }
+    float* yo = y + (size_t)((n * g.C + ch * 16) * g.P + p);   // Nb*OH*OW*Co < 2^31, so is this
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const uint32_t c = ch * 16 + j;
+      if (c < g.C) yo[(size_t)(j * g.P)] = __fmul_rn((float)acc[j], scale[c]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- K26 grouped int8 MFMA conv
+struct QGConvGeo {
+  uint32_t M, P, OW, H, W, Cp, Co, Cig, Cog, Cogp, Wc, Kp, RS, S, tiles;
+  int stride, pad, az, padv;
+  FastDiv div_p, div_ow, div_wc, div_s, div_tiles;
+};
+
+__global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
+    const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ masks,
+    const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
+    const float* __restrict__ scale, QGConvGeo g, float* __restrict__ y) {
+  __shared__ __attribute__((aligned(16))) int8_t lA[kGT * kGRow];
+  __shared__ __attribute__((aligned(16))) int8_t lB[(kGT + 1) * kGRow];
+  const uint32_t tid = threadIdx.x;
+  const uint32_t lane = tid & (kWave - 1), wave = tid / kWave;
+  const uint32_t fr = lane & 15, fq = lane >> 4;
+
+  // the workgroup's group, channel tile and number of 16-row fragments (uniform)
+  const uint32_t grp = fdiv(blockIdx.y, g.div_tiles);
+  const uint32_t tile = blockIdx.y - grp * g.tiles;
+  const uint32_t row0 = tile * kGT;                       // first row inside the group
+  const uint32_t nrow = min(g.Cogp - row0, (uint32_t)kGT);   // multiple of 16
+  const uint32_t nf = nrow >> 4;
+  const uint32_t w0 = grp * g.Cig / 16 * 16;              // window start channel
+
+  // staging role: one 16-byte chunk of each operand tile per thread
+  const uint32_t srow = tid >> 2, sc = tid & 3;
+  const uint32_t gm = blockIdx.x * kGT + srow;
+  const bool mval = gm < g.M;
+  const uint32_t gmc = mval ? gm : 0u;
+  const uint32_t sn = fdiv(gmc, g.div_p);
+  const uint32_t sp = gmc - sn * g.P;
+  const uint32_t soh = fdiv(sp, g.div_ow);
+  const uint32_t sow = sp - soh * g.OW;
+  const int ih0 = (int)soh * g.stride - g.pad, iw0 = (int)sow * g.stride - g.pad;
+  const int8_t* abase = act + (size_t)sn * g.H * g.W * g.Cp;
+  const bool bval = srow < nrow;
+  const int8_t* wrow = wp + (size_t)(grp * g.Cogp + row0 + (bval ? srow : 0u)) * g.Kp + sc * 16;
+  const int8_t* mrow = masks + (size_t)grp * g.Kp;
+  const int pv = (g.padv & 0xff) * 0x01010101;
+  const i32x4 padfill = {pv, pv, pv, pv};
+  const i32x4 zero4 = {0, 0, 0, 0};
+
+  auto load_a = [&](uint32_t kt) -> i32x4 {
+    const uint32_t k = kt * kGT + sc * 16;
+    const uint32_t tap = fdiv(k, g.div_wc);
+    const uint32_t c0 = w0 + (k - tap * g.Wc);
+    const uint32_t r = fdiv(tap, g.div_s);
+    const uint32_t s = tap - r * g.S;
+    const int ih = ih0 + (int)r, iw = iw0 + (int)s;
+    if (mval && tap < g.RS && c0 < g.Cp && (uint32_t)ih < g.H && (uint32_t)iw < g.W)
+      return *(const i32x4*)(abase + ((size_t)ih * g.W + (size_t)iw) * g.Cp + c0);
+    return padfill;
+  };
+
+  i32x4 ra = load_a(0);
+  i32x4 rb = bval ? *(const i32x4*)wrow : zero4;
+  i32x4 rm = zero4;
+  if (tid < 4) rm = *(const i32x4*)(mrow + tid * 16);
+
+  i32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = zero4;
+  i32x4 accs = zero4;
+
+  const uint32_t nk = g.Kp / kGT;
+  for (uint32_t kt = 0; kt < nk; ++kt) {
+    __syncthreads();   // the previous step's fragment reads are done
+    *(i32x4*)(lA + srow * kGRow + sc * 16) = ra;
+    if (bval) *(i32x4*)(lB + srow * kGRow + sc * 16) = rb;
+    if (tid < 4) *(i32x4*)(lB + kGT * kGRow + tid * 16) = rm;
+    __syncthreads();
+    if (kt + 1 < nk) {
+      ra = load_a(kt + 1);
+      if (bval) rb = *(const i32x4*)(wrow + (size_t)(kt + 1) * kGT);
+      if (tid < 4) rm = *(const i32x4*)(mrow + (size_t)(kt + 1) * kGT + tid * 16);
+    }
+    const i32x4 af = *(const i32x4*)(lA + (wave * 16 + fr) * kGRow + fq * 16);
+    const i32x4 mf = *(const i32x4*)(lB + kGT * kGRow + fq * 16);
+    accs = __builtin_amdgcn_mfma_i32_16x16x64_i8(mf, af, accs, 0, 0, 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if ((uint32_t)j < nf) {
+        const i32x4 wf = *(const i32x4*)(lB + (j * 16 + fr) * kGRow + fq * 16);
+        acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, af, acc[j], 0, 0, 0);
+      }
+    }
+  }
+
+  // C/D map: column (pixel) = lane & 15, row (channel) = 4 * (lane >> 4) + reg
+  const uint32_t pixel = blockIdx.x * kGT + wave * 16 + fr;
+  if (pixel >= g.M) return;
+  const uint32_t n = fdiv(pixel, g.div_p);
+  const uint32_t p = pixel - n * g.P;
+  const long long sa = (long long)accs[0];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if ((uint32_t)j >= nf) continue;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t rl = row0 + j * 16 + fq * 4 + r;
+      if (rl < g.Cog) {
+        const uint32_t co = grp * g.Cog + rl;
+        const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
+                            (long long)g.az * (long long)tt[co];
+        y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
+      }
+    }
+  }
+}
+
+static int grange_ok(const char* what, int n_bits, int qmin) {
+  SSQ_REQUIRE(n_bits >= 1 && n_bits <= 8, SSQ_E_ARG, "%s: n_bits %d not in [1, 8]", what, n_bits);
+  SSQ_REQUIRE(qmin == 0 || qmin == -(1 << (n_bits - 1)), SSQ_E_ARG,
+              "%s: qmin %d is neither 0 nor -2^(n_bits-1)", what, qmin);
+  return SSQ_OK;
+}
+
+// C < 0: the caller has no C of its own (prepare); else C must be Cig * groups
+static int ggeo_ok(const char* what, const char* plain, int64_t C, int64_t Co, int64_t Cig,
+                   int64_t R, int64_t S, int64_t groups) {
+  SSQ_REQUIRE(groups >= 2, SSQ_E_ARG, "%s: groups = %lld (groups >= 2 only; groups == 1 is %s)",
+              what, (long long)groups, plain);
+  SSQ_REQUIRE(C < 0 || (C >= 1 && C % groups == 0), SSQ_E_ARG,
+              "%s: C = %lld is not divisible by groups = %lld", what, (long long)C,
+              (long long)groups);
+  SSQ_REQUIRE(Co >= 1 && Co % groups == 0, SSQ_E_ARG,
+              "%s: Co = %lld is not divisible by groups = %lld", what, (long long)Co,
+              (long long)groups);
+  SSQ_REQUIRE(Cig >= 1 && R >= 1 && S >= 1 && R <= 7 && S <= 7, SSQ_E_ARG,
+              "%s: bad geometry (Cig >= 1; R, S in [1, 7]; got R = %lld, S = %lld)", what,
+              (long long)R, (long long)S);
+  SSQ_REQUIRE(Cig * R * S <= kGMaxK, SSQ_E_ARG,
+              "%s: K = Cig*R*S = %lld exceeds 65536 (int32 accumulator range)", what,
+              (long long)(Cig * R * S));
+  SSQ_REQUIRE(Cig <= (1ll << 31) / groups, SSQ_E_ARG, "%s: C = Cig*groups exceeds 2^31", what);
+  const GLayout L = glayout(Co, Cig, R, S, groups);
+  SSQ_REQUIRE(L.kind != 0, SSQ_E_ARG, "%s: bad geometry", what);
+  SSQ_REQUIRE(L.bytes < (1ull << 31), SSQ_E_ARG, "%s: prepared weights exceed 2^31 bytes", what);
+  SSQ_REQUIRE(L.kind == 1 ? L.Cp / 16 <= 65535 : groups * L.tiles <= 65535, SSQ_E_ARG,
+              "%s: too many channel tiles for one launch", what);
+  return SSQ_OK;
+}
+
+}  // namespace ssq
+
+using namespace ssq;
+
+extern "C" int ssq_qconv_grouped_kind(int64_t Co, int64_t Cig, int64_t groups) {
+  return qg_kind(Co, Cig, groups);
+}
+
+extern "C" size_t ssq_qweight_prepared_bytes_grouped(int64_t Co, int64_t Cig, int64_t R, int64_t S,
+                                                     int64_t groups) {
+  if (R > 7 || S > 7 || Cig > kGMaxK || groups > (1ll << 31)) return 0;
+  return glayout(Co, Cig, R, S, groups).bytes;
+}
+
+extern "C" int ssq_qweight_prepare_grouped(const void* packed, const float* zp, int64_t Co,
+                                           int64_t Cig, int64_t R, int64_t S, int64_t groups,
+                                           int n_bits, int qmin, void* prepared, uint32_t* bad,
+                                           ssq_stream_t stream) {
+  const char* me = "ssq_qweight_prepare_grouped";
+  SSQ_REQUIRE(packed && zp && prepared && bad, SSQ_E_ARG, "%s: null pointer", me);
+  int rc = grange_ok(me, n_bits, qmin);
+  if (rc) return rc;
+  rc = ggeo_ok(me, "ssq_qweight_prepare", -1, Co, Cig, R, S, groups);
+  if (rc) return rc;
+  const GLayout L = glayout(Co, Cig, R, S, groups);
+  int8_t* base = (int8_t*)prepared;
+  const int bs = n_bits <= 2 ? 2 : (n_bits <= 4 ? 4 : 8);
+  const uint32_t RS = (uint32_t)(R * S);
+  if (L.kind == 1) {
+    hipLaunchKernelGGL(qweight_prepare_dw_kernel, dim3(grid_for((int64_t)RS * L.Cp, kBlock)),
+                       dim3(kBlock), 0, (hipStream_t)stream, (const uint8_t*)packed, zp, bs, qmin,
+                       (uint32_t)L.C, RS, (uint32_t)L.Cp, make_fastdiv((uint32_t)L.Cp),
+                       (int32_t*)base, bad);
+  } else {
+    hipLaunchKernelGGL(qweight_prepare_grouped_kernel,
+                       dim3((uint32_t)(groups * L.Cogp + groups)), dim3(kBlock), 0,
+                       (hipStream_t)stream, (const uint8_t*)packed, zp, bs, qmin, (uint32_t)groups,
+                       (uint32_t)Cig, (uint32_t)L.Cog, (uint32_t)L.Cogp, RS, (uint32_t)L.Wc,
+                       (uint32_t)L.Kp, make_fastdiv((uint32_t)L.Wc),
+                       make_fastdiv((uint32_t)L.Cogp), base, base + L.off_mask,
+                       (int32_t*)(base + L.off_cwz), (int32_t*)(base + L.off_t), bad);
+  }
+  return check_launch(me);
+}
+
+extern "C" int ssq_qconv_i8_grouped_fwd(const int8_t* codes, const void* prepared,
+                                        const float* scale, int64_t Nb, int64_t C, int64_t H,
+                                        int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
+                                        int64_t pad, int64_t groups, float act_zero_point,
+                                        int act_qmin, int act_qmax, float* y, ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_grouped_fwd";
+  SSQ_REQUIRE(codes && prepared && scale && y, SSQ_E_ARG, "%s: null pointer", me);
+  SSQ_REQUIRE(groups >= 2, SSQ_E_ARG,
+              "%s: groups = %lld (groups >= 2 only; groups == 1 is ssq_qconv_i8_fwd)", me,
+              (long long)groups);
+  SSQ_REQUIRE(C >= 1 && C % groups == 0, SSQ_E_ARG,
+              "%s: C = %lld is not divisible by groups = %lld", me, (long long)C,
+              (long long)groups);
+  const int64_t Cig = C / groups;
+  int rc = ggeo_ok(me, "ssq_qconv_i8_fwd", C, Co, Cig, R, S, groups);
+  if (rc) return rc;
+  SSQ_REQUIRE(Nb >= 1 && H >= 1 && W >= 1 && stride >= 1 && pad >= 0 && H + 2 * pad >= R &&
+                  W + 2 * pad >= S,
+              SSQ_E_ARG, "%s: bad geometry", me);
+  SSQ_REQUIRE(act_qmin < act_qmax && act_qmax - act_qmin <= 255, SSQ_E_ARG,
+              "%s: activation code range [%d, %d] does not fit 8-bit codes", me, act_qmin,
+              act_qmax);
+  // a padded tap stores act_zero_point - (act_qmin + 128) as an int8
+  SSQ_REQUIRE(act_zero_point == rintf(act_zero_point) && act_zero_point >= (float)act_qmin &&
+                  act_zero_point <= (float)(act_qmin + 255),
+              SSQ_E_ARG, "%s: zero point %g is not an integer in [%d, %d]", me,
+              (double)act_zero_point, act_qmin, act_qmin + 255);
+  const GLayout L = glayout(Co, Cig, R, S, groups);
+  const int64_t OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
+  SSQ_REQUIRE(Nb * H * W * L.Cp < (1ll << 31) && Nb * OH * OW * Co < (1ll << 31), SSQ_E_ARG,
+              "%s: tensor exceeds 2^31 elements", me);
+  const int ca = act_qmin + 128, za = (int)act_zero_point;
+  const int8_t* base = (const int8_t*)prepared;
+  if (L.kind == 1) {
+    QDwGeo g;
+    g.M = (uint32_t)(Nb * OH * OW);
+    g.P = (uint32_t)(OH * OW);
+    g.OW = (uint32_t)OW;
+    g.H = (uint32_t)H;
+    g.W = (uint32_t)W;
+    g.C = (uint32_t)C;
+    g.Cp = (uint32_t)L.Cp;
+    g.R = (uint32_t)R;
+    g.S = (uint32_t)S;
+    g.stride = (int)stride;
+    g.pad = (int)pad;
+    g.az = ca - za;
+    g.padv = za - ca;   // a padded tap: (q_a - z_a) = 0
+    g.div_p = make_fastdiv(g.P);
+    g.div_ow = make_fastdiv(g.OW);
+    // enough workgroups to fill the device, as few chunk runs per pixel block as that allows
+    const uint32_t pixblocks = (g.M + kBlock - 1) / kBlock;
+    g.nch = (uint32_t)(L.Cp / 16);
+    const uint32_t runs = min(g.nch, max(1u, (kDwBlocks + pixblocks - 1) / pixblocks));
+    g.per = (g.nch + runs - 1) / runs;
+    const dim3 grid(pixblocks, (g.nch + g.per - 1) / g.per);
+    const int32_t* wc = (const int32_t*)base;
+#define SSQ_DW_LAUNCH(KS)                                                                   \
+  hipLaunchKernelGGL(qconv_dw_kernel<KS>, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, wc, \
+                     scale, g, y)
+    if (R == S && R == 3) SSQ_DW_LAUNCH(3);
+    else if (R == S && R == 5) SSQ_DW_LAUNCH(5);
+    else if (R == S && R == 7) SSQ_DW_LAUNCH(7);
+    else SSQ_DW_LAUNCH(0);
+#undef SSQ_DW_LAUNCH
+    return check_launch(me);
+  }
+  QGConvGeo g;
+  g.M = (uint32_t)(Nb * OH * OW);
+  g.P = (uint32_t)(OH * OW);
+  g.OW = (uint32_t)OW;
+  g.H = (uint32_t)H;
+  g.W = (uint32_t)W;
+  g.Cp = (uint32_t)L.Cp;
+  g.Co = (uint32_t)Co;
+  g.Cig = (uint32_t)Cig;
+  g.Cog = (uint32_t)L.Cog;
+  g.Cogp = (uint32_t)L.Cogp;
+  g.Wc = (uint32_t)L.Wc;
+  g.Kp = (uint32_t)L.Kp;
+  g.RS = (uint32_t)(R * S);
+  g.S = (uint32_t)S;
+  g.tiles = (uint32_t)L.tiles;
+  g.stride = (int)stride;
+  g.pad = (int)pad;
+  g.az = ca - za;
+  g.padv = za - ca;   // a padded tap: (q_a - z_a) = 0
+  g.div_p = make_fastdiv(g.P);
+  g.div_ow = make_fastdiv(g.OW);
+  g.div_wc = make_fastdiv(g.Wc);
+  g.div_s = make_fastdiv(g.S);
+  g.div_tiles = make_fastdiv(g.tiles);
+  const dim3 grid((g.M + kGT - 1) / kGT, (uint32_t)(groups * L.tiles));
+  hipLaunchKernelGGL(qconv_grouped_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base,
+                     base + L.off_mask, (const int32_t*)(base + L.off_cwz),
+                     (const int32_t*)(base + L.off_t), scale, g, y);
+  return check_launch(me);
+}

@@ -1869,11 +1869,13 @@ def act_encode(x, delta, zp, n_bits, sym=False, bad=None):
 
 
 class QPrepared:
-    """A layer's weight as K23's operand (K22's output) with its (Co, Ci[, R, S]) shape; `bad`
-    counts the channels whose zero point is not an integer code (device int32)."""
+    """A layer's weight as K23's operand (K22's output) with its (Co, Ci[, R, S]) shape -- at
+    `groups` > 1 the grouped kernels' operand (K24's output), Ci then being the channels per
+    group; `bad` counts the channels whose zero point is not an integer code (device int32)."""
 
-    def __init__(self, blob, shape, bad):
+    def __init__(self, blob, shape, bad, groups=1):
         self.blob, self.shape, self.bad = blob, tuple(int(s) for s in shape), bad
+        self.groups = int(groups)
 
     def geometry(self):
         Co, Ci = self.shape[:2]
@@ -1881,25 +1883,50 @@ class QPrepared:
         return Co, Ci, R, S
 
 
-def qweight_prepare(packed, shape, zp, n_bits, qmin):
-    """Packed codes (pack_encode's layout) + zp[co] -> QPrepared."""
+def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1):
+    """Packed codes (pack_encode's layout) + zp[co] -> QPrepared.  `shape` is the weight's own
+    (Co, Cig, R, S); `groups` > 1 prepares for the grouped kernels (K24)."""
     if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
         raise A.SSQError("qweight_prepare: packed codes must be a uint8 tensor")
     packed = _i8_dev(packed, "qweight_prepare")
     if len(shape) not in (2, 4):
         raise A.SSQError(f"qweight_prepare: weight shape {tuple(shape)} is neither Linear nor Conv2d")
-    prep = QPrepared(None, shape, torch.zeros(1, dtype=torch.int32, device=packed.device))
+    groups = int(groups)
+    if groups < 1 or (groups > 1 and len(shape) != 4):
+        raise A.SSQError(f"qweight_prepare: groups = {groups} needs a Conv2d weight and groups >= 1")
+    prep = QPrepared(None, shape, torch.zeros(1, dtype=torch.int32, device=packed.device), groups)
     Co, Ci, R, S = prep.geometry()
     if packed.numel() < query("ssq_pack_bytes", Co * Ci * R * S, n_bits):
         raise A.SSQError("qweight_prepare: packed buffer too small for the shape")
     z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
     if z.numel() != Co:
         raise A.SSQError("qweight_prepare: zero point must have one entry per output channel")
+    if groups > 1:
+        prep.blob = torch.empty(max(query("ssq_qweight_prepared_bytes_grouped", Co, Ci, R, S, groups), 1),
+                                dtype=torch.uint8, device=packed.device)
+        call("ssq_qweight_prepare_grouped", _vp(packed), zpp, Co, Ci, R, S, groups, int(n_bits),
+             int(qmin), _vp(prep.blob), _vp(prep.bad), stream_of(packed))
+        return prep
     prep.blob = torch.empty(max(query("ssq_qweight_prepared_bytes", Co, Ci, R, S), 1),
                             dtype=torch.uint8, device=packed.device)
     call("ssq_qweight_prepare", _vp(packed), zpp, Co, Ci, R, S, int(n_bits), int(qmin),
          _vp(prep.blob), _vp(prep.bad), stream_of(packed))
     return prep
+
+
+QCONV_KINDS = {1: "depthwise", 2: "grouped"}
+
+
+def qconv_kind(prepared):
+    """The kernel `qconv` runs for a prepared weight: "dense" (K23), "depthwise" (K25) or
+    "grouped" (K26)."""
+    if prepared.groups == 1:
+        return "dense"
+    Co, Cig, _, _ = prepared.geometry()
+    kind = query("ssq_qconv_grouped_kind", Co, Cig, prepared.groups)
+    if kind not in QCONV_KINDS:
+        raise A.SSQError(f"qconv_kind: invalid grouped geometry {prepared.shape}, groups = {prepared.groups}")
+    return QCONV_KINDS[kind]
 
 
 def qconv(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0, act_bits=8,
@@ -1919,7 +1946,13 @@ def qconv(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0
         codes = _i8_dev(codes_or_x, "qconv")
     else:
         raise A.SSQError(f"qconv: expected int8 codes or an fp32 activation, got {codes_or_x.dtype}")
-    Co, Ci, R, S = prepared.geometry()
+    groups = int(groups)
+    pg = getattr(prepared, "groups", 1)
+    if groups != pg:
+        raise A.SSQError(f"qconv: groups = {groups}, but the weight was prepared with groups = {pg} "
+                         f"(qweight_prepare(..., groups=...))")
+    Co, Cig, R, S = prepared.geometry()
+    Ci = Cig * groups      # the activation's channels
     Cp = query("ssq_qinfer_cpad", Ci)
     if codes.dim() not in (2, 4) or codes.shape[-1] != Cp or (codes.dim() == 2) != (len(prepared.shape) == 2):
         raise A.SSQError(f"qconv: codes {tuple(codes.shape)} do not match the weight {prepared.shape}")
@@ -1933,6 +1966,10 @@ def qconv(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0
     y = torch.empty((N, Co, max(OH, 0), max(OW, 0)) if codes.dim() == 4 else (N, Co),
                     dtype=torch.float32, device=codes.device)
     lo, hi = qrange(act_bits, act_sym)
+    if groups > 1:
+        call("ssq_qconv_i8_grouped_fwd", _vp(codes), _vp(prepared.blob), sp, N, Ci, H, W, Co, R, S,
+             int(stride[0]), int(padding[0]), groups, float(act_zp), lo, hi, _vp(y), stream_of(y))
+        return y
     call("ssq_qconv_i8_fwd", _vp(codes), _vp(prepared.blob), sp, N, Ci, H, W, Co, R, S,
          int(stride[0]), int(padding[0]), int(groups), float(act_zp), lo, hi, _vp(y), stream_of(y))
     return y

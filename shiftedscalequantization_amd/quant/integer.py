@@ -1,4 +1,5 @@
-"""Integer inference of a calibrated model (K21-K23, csrc/qinfer.hip).
+"""Integer inference of a calibrated model (K21-K23, csrc/qinfer.hip; grouped and depthwise
+convs on K24-K26, csrc/qinfer_grouped.hip, with `grouped=True`).
 
 A QuantModule whose input is the direct output of an act quantizer (scalar delta, integer
 zero point) and whose hard weight is (q - zero_point[co]) * scale[co] runs its conv / linear
@@ -24,6 +25,8 @@ class IntPlan:
 
     def __init__(self, prepared, scale, delta, zp, n_bits, sym, stride, padding, counter):
         self.prepared, self.scale = prepared, scale
+        self.groups = prepared.groups
+        self.kind = K.qconv_kind(prepared)      # "dense" | "depthwise" | "grouped"
         self.delta, self.zp, self.n_bits, self.sym = delta, zp, n_bits, sym
         self.stride, self.padding = stride, padding
         self.counter = counter
@@ -31,7 +34,8 @@ class IntPlan:
 
     def run(self, x):
         self.calls += 1
-        return K.qconv(x, self.prepared, self.scale, self.stride, self.padding, act_zp=self.zp,
+        return K.qconv(x, self.prepared, self.scale, self.stride, self.padding,
+                       groups=self.groups, act_zp=self.zp,
                        act_bits=self.n_bits, act_sym=self.sym, act_delta=self.delta,
                        bad=self.counter)
 
@@ -124,10 +128,11 @@ def _weight_codes(m):
 
 
 @torch.no_grad()
-def enable_integer_inference(qnn, sample):
+def enable_integer_inference(qnn, sample, grouped=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
-    current quantization state with weight and act quantization expected on."""
+    current quantization state with weight and act quantization expected on.  `grouped`: also
+    plan grouped and depthwise convs (K24-K26); off, they are reported as refused."""
     disable_integer_inference(qnn)
     layers = _layers(qnn)
     if not layers:
@@ -143,7 +148,8 @@ def enable_integer_inference(qnn, sample):
             continue
         if m.fwd_func is F.conv2d:
             kw = m.fwd_kwargs
-            if kw["groups"] != 1:
+            groups = int(kw["groups"])
+            if groups != 1 and not grouped:
                 report[name] = f"grouped conv (groups = {kw['groups']})"
                 continue
             st, pd, dl = kw["stride"], kw["padding"], kw["dilation"]
@@ -155,7 +161,7 @@ def enable_integer_inference(qnn, sample):
                 continue
             stride, padding = int(st[0]), int(pd[0])
         elif m.fwd_func is F.linear:
-            stride, padding = 1, 0
+            stride, padding, groups = 1, 0, 1
         else:
             report[name] = "neither a conv nor a linear"
             continue
@@ -184,7 +190,7 @@ def enable_integer_inference(qnn, sample):
             report[name] = f"weight has a column scale ({f['kind']})"
             continue
         prep = K.qweight_prepare(packed, tuple(m.weight.shape), f["zero_point"], f["n_bits"],
-                                 f["qmin"])
+                                 f["qmin"], groups=groups)
         if int(prep.bad.item()):
             report[name] = "weight zero point is not an integer code"
             continue
