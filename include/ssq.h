@@ -734,6 +734,42 @@ int ssq_qconv_i8_grouped_fwd(const int8_t* codes, const void* prepared, const fl
                              float act_zero_point, int act_qmin, int act_qmax, float* y,
                              ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- carried codes (fused requantize)
+ * The integer convs with the consumer's operand as their output: for the exact sum I of
+ * channel co, in this fp32 operation order (csrc/qinfer_epi.h),
+ *     y = fp32(I) * scale[co];  pre = y + bias[co] (bias != NULL);
+ *     t = pre * gamma[co] + phi[co] (two roundings; gamma and phi both or neither);
+ *     t = act(t), act 0 identity / 1 ReLU / 2 ReLU6;
+ *     q = clamp(round_ste(t / out_delta) + out_zero_point, out_qmin, out_qmax)
+ * and out_codes receives q - (out_qmin + 128) in K21's layout, NHWC int8 with Co padded to
+ * qinfer_cpad(Co), padded channels 0: what ssq_act_encode derives from the K13 epilogue's
+ * fp32 output whenever it counts nothing off-grid.  A NaN q (a NaN bias, an infinite
+ * t / out_delta) is stored as out_qmin and ADDED to *bad (device u32), as K13 followed by K21
+ * leaves it.  The first sixteen arguments and their checks are those of ssq_qconv_i8_fwd /
+ * ssq_qconv_i8_grouped_fwd; the output quantizer is checked as ssq_act_encode checks its own
+ * (delta positive and finite, zero point an integer in [qmin, qmin + 255], qmax - qmin <= 255).
+ * No allocation, no sync, capturable.
+ *
+ * act_decode, K21's inverse: NHWC codes (C padded) -> fp32 NCHW (q - zero_point) * delta,
+ * q = code + qmin + 128.                                                                      */
+int ssq_qconv_i8_codes_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                           int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R,
+                           int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                           float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+                           const float* gamma, const float* phi, int act, float out_delta,
+                           float out_zero_point, int out_qmin, int out_qmax, int8_t* out_codes,
+                           uint32_t* bad, ssq_stream_t stream);
+int ssq_qconv_i8_grouped_codes_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                   int64_t Nb, int64_t C, int64_t H, int64_t W, int64_t Co,
+                                   int64_t R, int64_t S, int64_t stride, int64_t pad,
+                                   int64_t groups, float act_zero_point, int act_qmin,
+                                   int act_qmax, const float* bias, const float* gamma,
+                                   const float* phi, int act, float out_delta,
+                                   float out_zero_point, int out_qmin, int out_qmax,
+                                   int8_t* out_codes, uint32_t* bad, ssq_stream_t stream);
+int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W, float delta,
+                   float zero_point, int qmin, float* x, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- bandwidth probe
  * float4 device copy, used by bench.py to report the measured stream bandwidth.      */
 int ssq_stream_copy(const float* src, float* dst, int64_t n, ssq_stream_t stream);

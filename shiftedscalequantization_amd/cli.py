@@ -76,6 +76,10 @@ def build_parser():
     p.add_argument('--int_infer_grouped', action='store_true',
                    help='--int_infer with the grouped and depthwise convs on integer codes too '
                         '(depthwise direct kernel, grouped int8 MFMA conv); implies --int_infer')
+    p.add_argument('--int_infer_carry', action='store_true',
+                   help='--int_infer with int8 codes carried between the integer layers of a '
+                        'block (conv, epilogue and act quantizer in one kernel, no fp32 tensor '
+                        'in between); implies --int_infer')
     p.add_argument('--deterministic', default=1, type=int,
                    help='1 (reference): deterministic MIOpen conv solvers; 0: fastest solvers')
     # data parallel: one process per GPU, spawned by main_imagenet.py itself with --gpus N
@@ -93,7 +97,7 @@ def parse_args(argv=None):
     a = build_parser().parse_args(argv)
     if a.run_device:
         a.device_gpu = a.run_device
-    if a.int_infer_grouped:
+    if a.int_infer_grouped or a.int_infer_carry:
         a.int_infer = True
     return a
 

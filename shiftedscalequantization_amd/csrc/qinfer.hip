@@ -31,7 +31,10 @@
 // pixels: a store instruction writes 16 consecutive pixels per channel of the NCHW output)
 // plus one for SA.  Both operand fragments use the same lane map (row / column l & 15,
 // k chunk l >> 4), so the product does not depend on the k order inside a step.
+#include <type_traits>
+
 #include "ssq_common.h"
+#include "qinfer_epi.h"
 
 namespace ssq {
 
@@ -167,10 +170,15 @@ struct QConvGeo {
   FastDiv div_p, div_ow, div_cp, div_s;
 };
 
+// CODES: the code-emitting epilogue (qinfer_epi.h) instead of the fp32 NCHW store; `y` is then
+// the QEpi.  The 64 px x 64 ch code tile is transposed through the (then free) activation
+// tile and leaves as one 16-B chunk of a pixel's channels per thread.
+template <bool CODES>
 __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
     const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ mask,
     const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
-    const float* __restrict__ scale, QConvGeo g, float* __restrict__ y) {
+    const float* __restrict__ scale, QConvGeo g,
+    typename std::conditional<CODES, QEpi, float* __restrict__>::type y) {
   __shared__ __attribute__((aligned(16))) int8_t lA[kQT * kQRow];
   __shared__ __attribute__((aligned(16))) int8_t lB[(kQT + 1) * kQRow];
   const uint32_t tid = threadIdx.x;
@@ -238,19 +246,83 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
 
   // C/D map: column (pixel) = lane & 15, row (channel) = 4 * (lane >> 4) + reg
   const uint32_t pixel = blockIdx.x * kQT + wave * 16 + fr;
-  if (pixel >= g.M) return;
-  const uint32_t n = fdiv(pixel, g.div_p);
-  const uint32_t p = pixel - n * g.P;
   const long long sa = (long long)accs[0];
+  if constexpr (CODES) {
+    const QEpi& e = y;
+    const bool pval = pixel < g.M;
+    uint32_t nbad = 0;
+    __syncthreads();   // the last step's fragment reads are done: lA is free
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < 4; ++j) {
+      int c[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
-      if (co < g.Co) {
-        const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
-                            (long long)g.az * (long long)tt[co];
-        y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
+        c[r] = 0;
+        if (pval && co < g.Co) {
+          const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
+                              (long long)g.az * (long long)tt[co];
+          c[r] = qepi_code((float)I, co, scale, e, nbad);
+        }
+      }
+      *(int*)(lA + (wave * 16 + fr) * kQRow + j * 16 + fq * 4) = qepi_pack4(c[0], c[1], c[2], c[3]);
+    }
+    __syncthreads();
+    // the staging role's map again: thread (row, chunk) stores channels [16 chunk, 16 chunk + 16)
+    // of pixel row.  Recomputed from a thread id the compiler cannot tie to the one above, or
+    // srow / sc / gm / mval stay live across the K loop: 62 VGPRs and 5 waves per SIMD, not 56 and 6
+    uint32_t t2 = tid;
+    asm volatile("" : "+v"(t2));
+    const uint32_t row = t2 >> 2, chunk = t2 & 3;
+    const uint32_t gpix = blockIdx.x * kQT + row, ch0 = blockIdx.y * kQT + chunk * 16;
+    if (gpix < g.M && ch0 < e.Cpo)
+      *(i32x4*)(e.out + (size_t)gpix * e.Cpo + ch0) = *(const i32x4*)(lA + row * kQRow + chunk * 16);
+    qepi_count(nbad, e.bad);
+  } else {
+    if (pixel >= g.M) return;
+    const uint32_t n = fdiv(pixel, g.div_p);
+    const uint32_t p = pixel - n * g.P;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
+        if (co < g.Co) {
+          const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
+                              (long long)g.az * (long long)tt[co];
+          y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- K21's inverse
+// NHWC codes -> fp32 NCHW (q - z) * d: a carried tensor handed to an fp32 consumer.  K21's
+// thread map: one 16-B chunk of a pixel per thread, 16 stores each coalesced across pixels.
+__global__ __launch_bounds__(kBlock) void act_decode_kernel(const int8_t* __restrict__ codes,
+                                                            uint32_t npix, uint32_t HW, uint32_t C,
+                                                            uint32_t Cp, FastDiv div_npix,
+                                                            FastDiv div_hw, float d, float z,
+                                                            float lo, float* __restrict__ x) {
+  const uint32_t total = npix * (Cp / 16);
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const uint32_t ch = fdiv(i, div_npix);
+    const uint32_t pix = i - ch * npix;
+    const uint32_t n = fdiv(pix, div_hw);
+    const uint32_t p = pix - n * HW;
+    union {
+      i32x4 v;
+      int8_t b[16];
+    } in;
+    in.v = *(const i32x4*)(codes + (size_t)pix * Cp + (size_t)ch * 16);
+    float* dst = x + ((size_t)n * C + (size_t)ch * 16) * HW + p;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      if (ch * 16 + j < C) {
+        const float q = __fadd_rn((float)((int)in.b[j] + 128), lo);   // exact: |q| <= 255
+        dst[(size_t)j * HW] = __fmul_rn(__fsub_rn(q, z), d);
       }
     }
   }
@@ -329,31 +401,32 @@ extern "C" int ssq_qweight_prepare(const void* packed, const float* zp, int64_t 
   return check_launch("ssq_qweight_prepare");
 }
 
-extern "C" int ssq_qconv_i8_fwd(const int8_t* codes, const void* prepared, const float* scale,
-                                int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
-                                int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
-                                float act_zero_point, int act_qmin, int act_qmax, float* y,
-                                ssq_stream_t stream) {
-  SSQ_REQUIRE(codes && prepared && scale && y, SSQ_E_ARG, "ssq_qconv_i8_fwd: null pointer");
-  SSQ_REQUIRE(groups == 1, SSQ_E_ARG, "ssq_qconv_i8_fwd: groups = %lld (only groups == 1)",
+// y: the fp32 output (ssq_qconv_i8_fwd) or null with `epi` set (ssq_qconv_i8_codes_fwd)
+static int qconv_i8_launch(const char* me, const int8_t* codes, const void* prepared,
+                           const float* scale, int64_t Nb, int64_t Ci, int64_t H, int64_t W,
+                           int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+                           int64_t groups, float act_zero_point, int act_qmin, int act_qmax,
+                           float* y, QEpi* epi, ssq_stream_t stream) {
+  SSQ_REQUIRE(codes && prepared && scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
+  SSQ_REQUIRE(groups == 1, SSQ_E_ARG, "%s: groups = %lld (only groups == 1)", me,
               (long long)groups);
-  int rc = qgeo_ok("ssq_qconv_i8_fwd", Co, Ci, R, S);
+  int rc = qgeo_ok(me, Co, Ci, R, S);
   if (rc) return rc;
   SSQ_REQUIRE(Nb >= 1 && H >= 1 && W >= 1 && stride >= 1 && pad >= 0 &&
                   H + 2 * pad >= R && W + 2 * pad >= S,
-              SSQ_E_ARG, "ssq_qconv_i8_fwd: bad geometry");
+              SSQ_E_ARG, "%s: bad geometry", me);
   SSQ_REQUIRE(act_qmin < act_qmax && act_qmax - act_qmin <= 255, SSQ_E_ARG,
-              "ssq_qconv_i8_fwd: activation code range [%d, %d] does not fit 8-bit codes",
+              "%s: activation code range [%d, %d] does not fit 8-bit codes", me,
               act_qmin, act_qmax);
   // a padded tap stores act_zero_point - (act_qmin + 128) as an int8
   SSQ_REQUIRE(act_zero_point == rintf(act_zero_point) && act_zero_point >= (float)act_qmin &&
                   act_zero_point <= (float)(act_qmin + 255),
-              SSQ_E_ARG, "ssq_qconv_i8_fwd: zero point %g is not an integer in [%d, %d]",
+              SSQ_E_ARG, "%s: zero point %g is not an integer in [%d, %d]", me,
               (double)act_zero_point, act_qmin, act_qmin + 255);
   const QLayout L = qlayout(Co, Ci, R, S);
   const int64_t OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
   SSQ_REQUIRE(Nb * H * W * L.Cp < (1ll << 31) && Nb * OH * OW * Co < (1ll << 31), SSQ_E_ARG,
-              "ssq_qconv_i8_fwd: tensor exceeds 2^31 elements");
+              "%s: tensor exceeds 2^31 elements", me);
   QConvGeo g;
   g.M = (uint32_t)(Nb * OH * OW);
   g.P = (uint32_t)(OH * OW);
@@ -376,8 +449,71 @@ extern "C" int ssq_qconv_i8_fwd(const int8_t* codes, const void* prepared, const
   g.div_s = make_fastdiv(g.S);
   const int8_t* base = (const int8_t*)prepared;
   const dim3 grid((g.M + kQT - 1) / kQT, (uint32_t)(L.Cop / kQT));
-  hipLaunchKernelGGL(qconv_i8_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base,
-                     base + L.off_mask, (const int32_t*)(base + L.off_cwz),
+  if (epi) {
+    epi->Cpo = (uint32_t)rup(Co, 16);
+    SSQ_REQUIRE(Nb * OH * OW * (int64_t)epi->Cpo < (1ll << 31), SSQ_E_ARG,
+                "%s: tensor exceeds 2^31 elements", me);
+    hipLaunchKernelGGL(qconv_i8_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, codes,
+                       base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
+                       (const int32_t*)(base + L.off_t), scale, g, *epi);
+    return check_launch(me);
+  }
+  hipLaunchKernelGGL(qconv_i8_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, codes,
+                     base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
                      (const int32_t*)(base + L.off_t), scale, g, y);
-  return check_launch("ssq_qconv_i8_fwd");
+  return check_launch(me);
+}
+
+extern "C" int ssq_qconv_i8_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                                float act_zero_point, int act_qmin, int act_qmax, float* y,
+                                ssq_stream_t stream) {
+  SSQ_REQUIRE(y, SSQ_E_ARG, "ssq_qconv_i8_fwd: null pointer");
+  return qconv_i8_launch("ssq_qconv_i8_fwd", codes, prepared, scale, Nb, Ci, H, W, Co, R, S,
+                         stride, pad, groups, act_zero_point, act_qmin, act_qmax, y, nullptr,
+                         stream);
+}
+
+extern "C" int ssq_qconv_i8_codes_fwd(const int8_t* codes, const void* prepared,
+                                      const float* scale, int64_t Nb, int64_t Ci, int64_t H,
+                                      int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
+                                      int64_t pad, int64_t groups, float act_zero_point,
+                                      int act_qmin, int act_qmax, const float* bias,
+                                      const float* gamma, const float* phi, int act,
+                                      float out_delta, float out_zero_point, int out_qmin,
+                                      int out_qmax, int8_t* out_codes, uint32_t* bad,
+                                      ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_codes_fwd";
+  const int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
+                         out_codes, bad);
+  if (rc) return rc;
+  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
+            0u, out_codes, bad};
+  return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                         act_zero_point, act_qmin, act_qmax, nullptr, &e, stream);
+}
+
+extern "C" int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                              float delta, float zero_point, int qmin, float* x,
+                              ssq_stream_t stream) {
+  SSQ_REQUIRE(codes && x, SSQ_E_ARG, "ssq_act_decode: null pointer");
+  SSQ_REQUIRE(Nb >= 1 && C >= 1 && H >= 1 && W >= 1, SSQ_E_ARG, "ssq_act_decode: bad geometry");
+  SSQ_REQUIRE(qmin >= -128 && qmin <= 0, SSQ_E_ARG, "ssq_act_decode: qmin %d not in [-128, 0]",
+              qmin);
+  SSQ_REQUIRE(delta > 0.0f && delta <= 3.0e38f, SSQ_E_ARG,
+              "ssq_act_decode: delta must be positive and finite");
+  SSQ_REQUIRE(zero_point == rintf(zero_point) && zero_point >= (float)qmin &&
+                  zero_point <= (float)(qmin + 255),
+              SSQ_E_ARG, "ssq_act_decode: zero point %g is not an integer in [%d, %d]",
+              (double)zero_point, qmin, qmin + 255);
+  const int64_t Cp = rup(C, 16);
+  SSQ_REQUIRE(Nb * H * W * Cp < (1ll << 31), SSQ_E_ARG,
+              "ssq_act_decode: tensor exceeds 2^31 elements");
+  const uint32_t npix = (uint32_t)(Nb * H * W), HW = (uint32_t)(H * W);
+  const dim3 grid(grid_for((int64_t)npix * (Cp / 16), kBlock, 8192));
+  hipLaunchKernelGGL(act_decode_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, npix,
+                     HW, (uint32_t)C, (uint32_t)Cp, make_fastdiv(npix), make_fastdiv(HW), delta,
+                     zero_point, (float)qmin, x);
+  return check_launch("ssq_act_decode");
 }

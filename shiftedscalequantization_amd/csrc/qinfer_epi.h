@@ -1,0 +1,86 @@
+// The code-emitting epilogue of the integer conv kernels (K23 / K25 / K26 with CODES = true):
+// an output element leaves as the int8 code its consumer's K21 would re-derive, not as fp32.
+//
+// For the exact integer sum I of channel co, qepi_code runs the fp32 operations the uncarried
+// route runs between the conv and the next conv's operand, in their order:
+//     y    = fp32(I) * s[co]                       the conv kernel's own output
+//     pre  = y + bias[co]                          K13 (recon.hip epi / epi_elem), if bias
+//     t    = pre * gamma[co] + phi[co]             two roundings, if gamma / phi
+//     t    = act(t)                                act_fwd: 0 identity, 1 ReLU, 2 ReLU6
+//     v    = round_ste(t / d) + z                  IEEE divide; NaN at an infinite t / d
+//     q    = clamp(v, lo, hi)                      NaN stays NaN
+//     code = (int)(q - lo) - 128                   K21's stored form, q - (qmin + 128)
+// K13 would write (q - z) * d and K21 map it back to q; where K21 counts nothing off-grid that
+// round trip is the identity, and where q is NaN K21 stores qmin and counts the element: so
+// does this (the caller sums `nbad` over the wave into one atomic, as K21 does).
+//
+// The output is K21's layout: NHWC int8, channels padded to Cpo = 16*ceil(Co/16), padded
+// channels 0.
+#pragma once
+#include "ssq_common.h"
+
+namespace ssq {
+
+struct QEpi {
+  const float* bias;    // [Co] or null
+  const float* gamma;   // [Co] or null (with phi)
+  const float* phi;
+  float d, z, lo, hi;   // the output act quantizer
+  int act;              // 0 identity, 1 ReLU, 2 ReLU6
+  uint32_t Cpo;         // padded output channels
+  int8_t* out;          // [Nb*OH*OW][Cpo]
+  uint32_t* bad;
+};
+
+__device__ __forceinline__ int qepi_code(float fI, uint32_t co, const float* __restrict__ scale,
+                                         const QEpi& e, uint32_t& nbad) {
+  const float y = __fmul_rn(fI, scale[co]);
+  const float pre = e.bias ? __fadd_rn(y, e.bias[co]) : y;
+  float t = e.gamma ? __fadd_rn(__fmul_rn(pre, e.gamma[co]), e.phi[co]) : pre;
+  t = e.act == 1 ? act_fwd<1>(t) : (e.act == 2 ? act_fwd<2>(t) : t);
+  const float v = round_ste_zp(t / e.d, e.z);
+  float q = clampf(v, e.lo, e.hi);
+  if (q != q) {   // NaN: stored as qmin and counted, as K21 does with K13's NaN
+    q = e.lo;
+    nbad += 1u;
+  }
+  return (int)__fsub_rn(q, e.lo) - 128;
+}
+
+// four codes (each in [-128, 127]) as the bytes of one word, c0 lowest
+__device__ __forceinline__ int qepi_pack4(int c0, int c1, int c2, int c3) {
+  return (c0 & 0xff) | ((c1 & 0xff) << 8) | ((c2 & 0xff) << 16) | ((int)((uint32_t)c3 << 24));
+}
+
+__device__ __forceinline__ uint32_t qepi_wave_sum(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, kWave);
+  return v;
+}
+
+// every lane of the wave must be here
+__device__ __forceinline__ void qepi_count(uint32_t nbad, uint32_t* bad) {
+  nbad = qepi_wave_sum(nbad);
+  if ((threadIdx.x & (kWave - 1)) == 0 && nbad) atomicAdd(bad, nbad);
+}
+
+// the output quantizer, validated as ssq_act_encode validates its own
+static inline int qepi_ok(const char* what, const float* gamma, const float* phi, int act,
+                          float delta, float zero_point, int qmin, int qmax, const void* out,
+                          const void* bad) {
+  SSQ_REQUIRE(out && bad, SSQ_E_ARG, "%s: null pointer", what);
+  SSQ_REQUIRE((gamma == nullptr) == (phi == nullptr), SSQ_E_ARG,
+              "%s: gamma and phi go together", what);
+  SSQ_REQUIRE(act >= 0 && act <= 2, SSQ_E_ARG, "%s: activation code %d not in [0, 2]", what, act);
+  SSQ_REQUIRE(qmin < qmax && qmax - qmin <= 255, SSQ_E_ARG,
+              "%s: output code range [%d, %d] does not fit 8-bit codes", what, qmin, qmax);
+  SSQ_REQUIRE(delta > 0.0f && delta <= 3.0e38f, SSQ_E_ARG,
+              "%s: output delta must be positive and finite", what);
+  SSQ_REQUIRE(zero_point == rintf(zero_point) && zero_point >= (float)qmin &&
+                  zero_point <= (float)(qmin + 255),
+              SSQ_E_ARG, "%s: output zero point %g is not an integer in [%d, %d]", what,
+              (double)zero_point, qmin, qmin + 255);
+  return SSQ_OK;
+}
+
+}  // namespace ssq

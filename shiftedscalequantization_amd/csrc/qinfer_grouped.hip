@@ -28,7 +28,10 @@
 // Cogp = 16*ceil(Cog/16) and a tile runs only the 16-row fragments it has (Cog = 8: one MFMA
 // + the SA MFMA per k step, not four).
 // Blob: int8 [G*Cogp][Kp], Kp = 64*ceil(R*S*Wc/64); the 0/1 rows [G][Kp]; cwz[Co], T[Co] (int32).
+#include <type_traits>
+
 #include "ssq_common.h"
+#include "qinfer_epi.h"
 
 namespace ssq {
 
@@ -183,13 +186,18 @@ struct QDwGeo {
 };
 
 // KS: the square kernel size the s loop is unrolled for (its loads fly together); 0: any R x S
-template <int KS>
-__global__ __launch_bounds__(kBlock) void qconv_dw_kernel(const int8_t* __restrict__ act,
-                                                          const int32_t* __restrict__ wc,
-                                                          const float* __restrict__ scale,
-                                                          QDwGeo g, float* __restrict__ y) {
-  const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pix >= g.M) return;
+// CODES: the code-emitting epilogue (qinfer_epi.h), `y` then being the QEpi: the thread's 16
+// channels of its pixel leave as one 16-B store of the NHWC codes instead of 16 fp32 stores.
+template <int KS, bool CODES>
+__global__ __launch_bounds__(kBlock) void qconv_dw_kernel(
+    const int8_t* __restrict__ act, const int32_t* __restrict__ wc, const float* __restrict__ scale,
+    QDwGeo g, typename std::conditional<CODES, QEpi, float* __restrict__>::type y) {
+  const uint32_t pix0 = blockIdx.x * blockDim.x + threadIdx.x;
+  if (!CODES && pix0 >= g.M) return;
+  // CODES: a thread past M stays for the wave's count, computing pixel 0 and storing nothing
+  const bool pval = pix0 < g.M;
+  const uint32_t pix = pval ? pix0 : 0u;
+  uint32_t nbad = 0;
   const uint32_t n = fdiv(pix, g.div_p);
   const uint32_t p = pix - n * g.P;
   const uint32_t oh = fdiv(p, g.div_ow);
@@ -230,13 +238,30 @@ __global__ __launch_bounds__(kBlock) void qconv_dw_kernel(const int8_t* __restri
         }
       }
     }
-    float* yo = y + (size_t)((n * g.C + ch * 16) * g.P + p);   // Nb*OH*OW*Co < 2^31, so is this
+    if constexpr (CODES) {
+      const QEpi& e = y;
+      i32x4 o;
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const uint32_t c = ch * 16 + j;
-      if (c < g.C) yo[(size_t)(j * g.P)] = __fmul_rn((float)acc[j], scale[c]);
+      for (int q = 0; q < 4; ++q) {
+        int c4[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const uint32_t c = ch * 16 + q * 4 + b;
+          c4[b] = (pval && c < g.C) ? qepi_code((float)acc[q * 4 + b], c, scale, e, nbad) : 0;
+        }
+        o[q] = qepi_pack4(c4[0], c4[1], c4[2], c4[3]);
+      }
+      if (pval) *(i32x4*)(e.out + (size_t)pix * g.Cp + ch * 16) = o;
+    } else {
+      float* yo = y + (size_t)((n * g.C + ch * 16) * g.P + p);   // Nb*OH*OW*Co < 2^31, so is this
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const uint32_t c = ch * 16 + j;
+        if (c < g.C) yo[(size_t)(j * g.P)] = __fmul_rn((float)acc[j], scale[c]);
+      }
     }
   }
+  if constexpr (CODES) qepi_count(nbad, y.bad);
 }
 
 // ---------------------------------------------------------------- K26 grouped int8 MFMA conv
@@ -246,10 +271,25 @@ struct QGConvGeo {
   FastDiv div_p, div_ow, div_wc, div_s, div_tiles;
 };
 
+// one `T` per (pixel row, unit) of the transposed code tile, LDS -> the NHWC codes
+template <typename T>
+__device__ __forceinline__ void qg_store_units(const int8_t* lds, int8_t* out, uint32_t units,
+                                               uint32_t sub) {
+  for (uint32_t u = sub; u < units; u += 4) ((T*)out)[u] = ((const T*)lds)[u];
+}
+
+// CODES: the code-emitting epilogue (qinfer_epi.h), `y` then being the QEpi.  The workgroup's
+// code tile is transposed through the (then free) activation tile; it owns the bytes
+// [c0, c1) of every pixel, c0 = the tile's first channel, c1 one past its last real one -- or
+// Cpo when that is the layer's last channel (the zero padding is its to write) -- and stores
+// them at the widest power of two up to 16 B that divides both c0 and c1 - c0: two workgroups
+// may own different bytes of one 16-B chunk, none writes a byte of another's.
+template <bool CODES>
 __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
     const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ masks,
     const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
-    const float* __restrict__ scale, QGConvGeo g, float* __restrict__ y) {
+    const float* __restrict__ scale, QGConvGeo g,
+    typename std::conditional<CODES, QEpi, float* __restrict__>::type y) {
   __shared__ __attribute__((aligned(16))) int8_t lA[kGT * kGRow];
   __shared__ __attribute__((aligned(16))) int8_t lB[(kGT + 1) * kGRow];
   const uint32_t tid = threadIdx.x;
@@ -330,21 +370,64 @@ __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
 
   // C/D map: column (pixel) = lane & 15, row (channel) = 4 * (lane >> 4) + reg
   const uint32_t pixel = blockIdx.x * kGT + wave * 16 + fr;
-  if (pixel >= g.M) return;
-  const uint32_t n = fdiv(pixel, g.div_p);
-  const uint32_t p = pixel - n * g.P;
   const long long sa = (long long)accs[0];
+  if constexpr (CODES) {
+    const QEpi& e = y;
+    const bool pval = pixel < g.M;
+    uint32_t nbad = 0;
+    __syncthreads();   // the last step's fragment reads are done: lA is free
+    // chunks the codes below do not write: zero (the layer's channel padding lies there)
+    if (sc + 1 >= nf) *(i32x4*)(lA + srow * kGRow + (sc + 1) * 16) = zero4;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if ((uint32_t)j >= nf) continue;
+    for (int j = 0; j < 4; ++j) {
+      if ((uint32_t)j >= nf) continue;
+      int c[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const uint32_t rl = row0 + j * 16 + fq * 4 + r;
-      if (rl < g.Cog) {
-        const uint32_t co = grp * g.Cog + rl;
-        const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
-                            (long long)g.az * (long long)tt[co];
-        y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t rl = row0 + j * 16 + fq * 4 + r;
+        c[r] = 0;
+        if (pval && rl < g.Cog) {
+          const uint32_t co = grp * g.Cog + rl;
+          const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
+                              (long long)g.az * (long long)tt[co];
+          c[r] = qepi_code((float)I, co, scale, e, nbad);
+        }
+      }
+      *(int*)(lA + (wave * 16 + fr) * kGRow + j * 16 + fq * 4) = qepi_pack4(c[0], c[1], c[2], c[3]);
+    }
+    __syncthreads();
+    const uint32_t c0 = grp * g.Cog + row0;
+    uint32_t c1 = grp * g.Cog + min(row0 + nrow, g.Cog);
+    if (c1 == g.Co) c1 = e.Cpo;          // at most row0's 64 + 15 bytes: inside the 80-B row
+    const uint32_t len = c1 - c0;
+    const uint32_t a = (c0 | len | 16u);
+    const uint32_t w = a & (0u - a);     // lowest set bit: 1, 2, 4, 8 or 16
+    if (mval) {
+      const int8_t* src = lA + srow * kGRow;
+      int8_t* dst = e.out + (size_t)gm * e.Cpo + c0;
+      if (w == 16) qg_store_units<i32x4>(src, dst, len >> 4, sc);
+      else if (w == 8) qg_store_units<uint64_t>(src, dst, len >> 3, sc);
+      else if (w == 4) qg_store_units<uint32_t>(src, dst, len >> 2, sc);
+      else if (w == 2) qg_store_units<uint16_t>(src, dst, len >> 1, sc);
+      else qg_store_units<uint8_t>(src, dst, len, sc);
+    }
+    qepi_count(nbad, e.bad);
+  } else {
+    if (pixel >= g.M) return;
+    const uint32_t n = fdiv(pixel, g.div_p);
+    const uint32_t p = pixel - n * g.P;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if ((uint32_t)j >= nf) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t rl = row0 + j * 16 + fq * 4 + r;
+        if (rl < g.Cog) {
+          const uint32_t co = grp * g.Cog + rl;
+          const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
+                              (long long)g.az * (long long)tt[co];
+          y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
+        }
       }
     }
   }
@@ -428,13 +511,13 @@ extern "C" int ssq_qweight_prepare_grouped(const void* packed, const float* zp, 
   return check_launch(me);
 }
 
-extern "C" int ssq_qconv_i8_grouped_fwd(const int8_t* codes, const void* prepared,
-                                        const float* scale, int64_t Nb, int64_t C, int64_t H,
-                                        int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
-                                        int64_t pad, int64_t groups, float act_zero_point,
-                                        int act_qmin, int act_qmax, float* y, ssq_stream_t stream) {
-  const char* me = "ssq_qconv_i8_grouped_fwd";
-  SSQ_REQUIRE(codes && prepared && scale && y, SSQ_E_ARG, "%s: null pointer", me);
+// y: the fp32 output (ssq_qconv_i8_grouped_fwd) or null with `epi` set (..._codes_fwd)
+static int qconv_grouped_launch(const char* me, const int8_t* codes, const void* prepared,
+                                const float* scale, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                                int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+                                int64_t groups, float act_zero_point, int act_qmin, int act_qmax,
+                                float* y, QEpi* epi, ssq_stream_t stream) {
+  SSQ_REQUIRE(codes && prepared && scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
   SSQ_REQUIRE(groups >= 2, SSQ_E_ARG,
               "%s: groups = %lld (groups >= 2 only; groups == 1 is ssq_qconv_i8_fwd)", me,
               (long long)groups);
@@ -461,6 +544,11 @@ extern "C" int ssq_qconv_i8_grouped_fwd(const int8_t* codes, const void* prepare
               "%s: tensor exceeds 2^31 elements", me);
   const int ca = act_qmin + 128, za = (int)act_zero_point;
   const int8_t* base = (const int8_t*)prepared;
+  if (epi) {
+    epi->Cpo = (uint32_t)rup(Co, 16);
+    SSQ_REQUIRE(Nb * OH * OW * (int64_t)epi->Cpo < (1ll << 31), SSQ_E_ARG,
+                "%s: tensor exceeds 2^31 elements", me);
+  }
   if (L.kind == 1) {
     QDwGeo g;
     g.M = (uint32_t)(Nb * OH * OW);
@@ -485,9 +573,15 @@ extern "C" int ssq_qconv_i8_grouped_fwd(const int8_t* codes, const void* prepare
     g.per = (g.nch + runs - 1) / runs;
     const dim3 grid(pixblocks, (g.nch + g.per - 1) / g.per);
     const int32_t* wc = (const int32_t*)base;
-#define SSQ_DW_LAUNCH(KS)                                                                   \
-  hipLaunchKernelGGL(qconv_dw_kernel<KS>, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, wc, \
-                     scale, g, y)
+#define SSQ_DW_LAUNCH(KS)                                                                       \
+  do {                                                                                          \
+    if (epi)                                                                                    \
+      hipLaunchKernelGGL((qconv_dw_kernel<KS, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, \
+                         codes, wc, scale, g, *epi);                                            \
+    else                                                                                        \
+      hipLaunchKernelGGL((qconv_dw_kernel<KS, false>), grid, dim3(kBlock), 0,                   \
+                         (hipStream_t)stream, codes, wc, scale, g, y);                          \
+  } while (0)
     if (R == S && R == 3) SSQ_DW_LAUNCH(3);
     else if (R == S && R == 5) SSQ_DW_LAUNCH(5);
     else if (R == S && R == 7) SSQ_DW_LAUNCH(7);
@@ -521,8 +615,41 @@ extern "C" int ssq_qconv_i8_grouped_fwd(const int8_t* codes, const void* prepare
   g.div_s = make_fastdiv(g.S);
   g.div_tiles = make_fastdiv(g.tiles);
   const dim3 grid((g.M + kGT - 1) / kGT, (uint32_t)(groups * L.tiles));
-  hipLaunchKernelGGL(qconv_grouped_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base,
-                     base + L.off_mask, (const int32_t*)(base + L.off_cwz),
+  if (epi) {
+    hipLaunchKernelGGL(qconv_grouped_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream,
+                       codes, base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
+                       (const int32_t*)(base + L.off_t), scale, g, *epi);
+    return check_launch(me);
+  }
+  hipLaunchKernelGGL(qconv_grouped_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream,
+                     codes, base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
                      (const int32_t*)(base + L.off_t), scale, g, y);
   return check_launch(me);
+}
+
+extern "C" int ssq_qconv_i8_grouped_fwd(const int8_t* codes, const void* prepared,
+                                        const float* scale, int64_t Nb, int64_t C, int64_t H,
+                                        int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
+                                        int64_t pad, int64_t groups, float act_zero_point,
+                                        int act_qmin, int act_qmax, float* y, ssq_stream_t stream) {
+  SSQ_REQUIRE(y, SSQ_E_ARG, "ssq_qconv_i8_grouped_fwd: null pointer");
+  return qconv_grouped_launch("ssq_qconv_i8_grouped_fwd", codes, prepared, scale, Nb, C, H, W, Co,
+                              R, S, stride, pad, groups, act_zero_point, act_qmin, act_qmax, y,
+                              nullptr, stream);
+}
+
+extern "C" int ssq_qconv_i8_grouped_codes_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t C, int64_t H,
+    int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+    float act_zero_point, int act_qmin, int act_qmax, const float* bias, const float* gamma,
+    const float* phi, int act, float out_delta, float out_zero_point, int out_qmin, int out_qmax,
+    int8_t* out_codes, uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_grouped_codes_fwd";
+  const int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
+                         out_codes, bad);
+  if (rc) return rc;
+  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
+            0u, out_codes, bad};
+  return qconv_grouped_launch(me, codes, prepared, scale, Nb, C, H, W, Co, R, S, stride, pad,
+                              groups, act_zero_point, act_qmin, act_qmax, nullptr, &e, stream);
 }

@@ -1500,7 +1500,10 @@ def lazy_epilogue(y, bias, gamma, phi, relu, q):
 
 def materialize_epi(x):
     epi = getattr(x, "_ssq_epi", None)
-    return x if epi is None else epi.materialize()
+    if epi is None:
+        cc = getattr(x, "_ssq_codes", None)
+        return x if cc is None else cc.decode(x)
+    return epi.materialize()
 
 
 class EpiConvGemmFn(torch.autograd.Function):
@@ -1935,44 +1938,127 @@ def qconv(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0
     codes.  `codes_or_x`: act_encode's int8 codes, or the fp32 activation itself, which is then
     encoded with (act_delta, act_zp, act_bits, act_sym), off-grid elements ADDED to `bad`.
     (act_zp, act_bits, act_sym) are the act quantizer's either way."""
+    args, keep, (N, Co, OH, OW, conv) = _qconv_args(
+        "qconv", codes_or_x, prepared, scale, stride, padding, groups, act_zp, act_bits, act_sym,
+        act_delta, bad)
+    y = torch.empty((N, Co, OH, OW) if conv else (N, Co), dtype=torch.float32,
+                    device=keep[0].device)
+    fn = "ssq_qconv_i8_grouped_fwd" if int(groups) > 1 else "ssq_qconv_i8_fwd"
+    call(fn, *args, _vp(y), stream_of(y))
+    return y
+
+
+def _qconv_args(name, codes_or_x, prepared, scale, stride, padding, groups, act_zp, act_bits,
+                act_sym, act_delta, bad):
+    """qconv's and qconv_codes's shared front: the int8 operand (an fp32 input encoded first)
+    and the first sixteen arguments of the conv entry points, + (N, Co, OH, OW, 4-D?)."""
     stride, padding = _pair(stride), _pair(padding)
     if stride[0] != stride[1] or padding[0] != padding[1]:
-        raise A.SSQError("qconv: square stride / padding only")
+        raise A.SSQError(f"{name}: square stride / padding only")
     if codes_or_x.dtype == torch.float32:
         if act_delta is None:
-            raise A.SSQError("qconv: an fp32 input needs act_delta to be encoded")
+            raise A.SSQError(f"{name}: an fp32 input needs act_delta to be encoded")
         codes, _ = act_encode(codes_or_x, act_delta, act_zp, act_bits, act_sym, bad=bad)
     elif codes_or_x.dtype == torch.int8:
-        codes = _i8_dev(codes_or_x, "qconv")
+        codes = _i8_dev(codes_or_x, name)
     else:
-        raise A.SSQError(f"qconv: expected int8 codes or an fp32 activation, got {codes_or_x.dtype}")
+        raise A.SSQError(f"{name}: expected int8 codes or an fp32 activation, got {codes_or_x.dtype}")
     groups = int(groups)
     pg = getattr(prepared, "groups", 1)
     if groups != pg:
-        raise A.SSQError(f"qconv: groups = {groups}, but the weight was prepared with groups = {pg} "
+        raise A.SSQError(f"{name}: groups = {groups}, but the weight was prepared with groups = {pg} "
                          f"(qweight_prepare(..., groups=...))")
     Co, Cig, R, S = prepared.geometry()
     Ci = Cig * groups      # the activation's channels
     Cp = query("ssq_qinfer_cpad", Ci)
     if codes.dim() not in (2, 4) or codes.shape[-1] != Cp or (codes.dim() == 2) != (len(prepared.shape) == 2):
-        raise A.SSQError(f"qconv: codes {tuple(codes.shape)} do not match the weight {prepared.shape}")
+        raise A.SSQError(f"{name}: codes {tuple(codes.shape)} do not match the weight {prepared.shape}")
     N = int(codes.shape[0])
     H, W = (int(codes.shape[1]), int(codes.shape[2])) if codes.dim() == 4 else (1, 1)
     s, sp = fptr(scale.detach().reshape(-1), "scale")
     if s.numel() != Co:
-        raise A.SSQError("qconv: scale must have one entry per output channel")
+        raise A.SSQError(f"{name}: scale must have one entry per output channel")
     OH = (H + 2 * padding[0] - R) // stride[0] + 1
     OW = (W + 2 * padding[0] - S) // stride[0] + 1
-    y = torch.empty((N, Co, max(OH, 0), max(OW, 0)) if codes.dim() == 4 else (N, Co),
-                    dtype=torch.float32, device=codes.device)
     lo, hi = qrange(act_bits, act_sym)
-    if groups > 1:
-        call("ssq_qconv_i8_grouped_fwd", _vp(codes), _vp(prepared.blob), sp, N, Ci, H, W, Co, R, S,
-             int(stride[0]), int(padding[0]), groups, float(act_zp), lo, hi, _vp(y), stream_of(y))
-        return y
-    call("ssq_qconv_i8_fwd", _vp(codes), _vp(prepared.blob), sp, N, Ci, H, W, Co, R, S,
-         int(stride[0]), int(padding[0]), int(groups), float(act_zp), lo, hi, _vp(y), stream_of(y))
-    return y
+    args = (_vp(codes), _vp(prepared.blob), sp, N, Ci, H, W, Co, R, S, int(stride[0]),
+            int(padding[0]), groups, float(act_zp), lo, hi)
+    return args, (codes, s), (N, Co, max(OH, 0), max(OW, 0), codes.dim() == 4)
+
+
+class CarriedCodes:
+    """What an int8 code tensor carried between two integer layers stands for (the tensor's
+    `_ssq_codes`): the logical (N, C, H, W) -- (N, C) for a Linear's -- and the act quantizer
+    (delta, zp, n_bits, sym) whose output (q - zp) * delta the codes hold, q = code +
+    code_offset.  materialize_epi decodes it for a consumer that is not an integer layer."""
+
+    def __init__(self, shape, delta, zp, n_bits, sym):
+        self.shape = tuple(int(v) for v in shape)
+        self.delta, self.zp, self.n_bits, self.sym = float(delta), float(zp), int(n_bits), bool(sym)
+
+    def quantizer(self):
+        return self.delta, self.zp, self.n_bits, self.sym
+
+    def decode(self, codes):
+        x = act_decode(codes, self.shape[1], self.delta, self.zp, self.n_bits, self.sym)
+        return x.view(self.shape)
+
+
+def carried(codes, shape, delta, zp, n_bits, sym):
+    """`codes` tagged as a carried tensor (see CarriedCodes)."""
+    codes._ssq_codes = CarriedCodes(shape, delta, zp, n_bits, sym)
+    return codes
+
+
+def act_decode(codes, C, delta, zp, n_bits, sym=False):
+    """act_encode's inverse: int8 codes (N, H, W, Cpad) or (N, Cpad) with C real channels ->
+    fp32 (N, C, H, W) / (N, C), (q - zp) * delta."""
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int8:
+        raise A.SSQError("act_decode: expected int8 codes")
+    codes = _i8_dev(codes, "act_decode")
+    C = int(C)
+    if codes.dim() not in (2, 4) or codes.shape[-1] != query("ssq_qinfer_cpad", C):
+        raise A.SSQError(f"act_decode: codes {tuple(codes.shape)} do not hold {C} channels")
+    N = int(codes.shape[0])
+    H, W = (int(codes.shape[1]), int(codes.shape[2])) if codes.dim() == 4 else (1, 1)
+    x = torch.empty((N, C, H, W) if codes.dim() == 4 else (N, C), dtype=torch.float32,
+                    device=codes.device)
+    call("ssq_act_decode", _vp(codes), N, C, H, W, float(delta), float(zp),
+         qrange(n_bits, sym)[0], _vp(x), stream_of(x))
+    return x
+
+
+def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0, act_bits=8,
+                act_sym=False, act_delta=None, bias=None, gamma=None, phi=None, relu=0,
+                out_delta=None, out_zp=0.0, out_bits=8, out_sym=False, bad=None):
+    """qconv with the layer's epilogue and output act quantizer applied in the kernel
+    (csrc/qinfer_epi.h): returns the int8 codes of clamp(round(act((I * scale + bias) * gamma +
+    phi) / out_delta) + out_zp) in act_encode's layout (N, OH, OW, Cpad) -- what act_encode
+    derives from the K13 epilogue's output of qconv's.  `relu`: 0 identity, 1 ReLU, 2 ReLU6.
+    A NaN result is stored as qmin and ADDED to `bad`, as are the off-grid elements of an fp32
+    input; `bad` must be given (a device int32 word)."""
+    if out_delta is None or bad is None:
+        raise A.SSQError("qconv_codes: out_delta and bad are required")
+    if len(prepared.shape) != 4:
+        raise A.SSQError("qconv_codes: conv layers only")
+    if (gamma is None) != (phi is None):
+        raise A.SSQError("qconv_codes: gamma and phi go together")
+    args, keep, (N, Co, OH, OW, _) = _qconv_args(
+        "qconv_codes", codes_or_x, prepared, scale, stride, padding, groups, act_zp, act_bits,
+        act_sym, act_delta, bad)
+    vecs = []
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (phi, "phi")):
+        v, vp = (None, None) if t is None else fptr(t.detach().reshape(-1), nm)
+        if v is not None and v.numel() != Co:
+            raise A.SSQError(f"qconv_codes: {nm} must have one entry per output channel")
+        vecs.append((v, vp))
+    out = torch.empty((N, OH, OW, query("ssq_qinfer_cpad", Co)), dtype=torch.int8,
+                      device=keep[0].device)
+    olo, ohi = qrange(out_bits, out_sym)
+    fn = "ssq_qconv_i8_grouped_codes_fwd" if int(groups) > 1 else "ssq_qconv_i8_codes_fwd"
+    call(fn, *args, vecs[0][1], vecs[1][1], vecs[2][1], int(relu), float(out_delta), float(out_zp),
+         olo, ohi, _vp(out), _vp(bad), stream_of(out))
+    return out
 
 
 # ------------------------------------------------------------------ K17 conv weight gradient

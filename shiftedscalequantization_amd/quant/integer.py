@@ -9,13 +9,21 @@ fp32(I) * fp32(delta_a * scale[co]).  The raw output then takes the module's unc
 gamma^z, phi^z / activation / act-quant epilogue.  Every other layer keeps the decoded fp32
 path.  The switch is off until `enable_integer_inference` installs a plan; the plan holds the
 act quantizers' (delta, zero_point) as of that call, so re-enable after changing them.
+
+With `carry=True` the tensor between two integer layers of one block stays int8: the producer
+runs the code-emitting kernels (ssq_qconv_i8_codes_fwd / ssq_qconv_i8_grouped_codes_fwd:
+conv, bias, gamma^z / phi^z, activation and its act quantizer in one launch) and the consumer
+takes the codes as its operand, so the K13 epilogue pass and the K21 re-encode between them
+drop out.  Only the pairs a block declares (`BaseQuantBlock.interior_chain`) are carried: the
+planning trace sees module inputs, not residual adds or pooling, so the block's structure is
+what guarantees the producer's output has one reader.
 """
 import torch
 import torch.nn.functional as F
 
 from .. import kernels as K
 from .export import PackedWeight, dequant_form
-from .quant_layer import QuantModule, UniformAffineQuantizer
+from .quant_layer import QuantModule, UniformAffineQuantizer, fusable_act_quantizer
 
 INT8 = "int8"
 
@@ -31,6 +39,24 @@ class IntPlan:
         self.stride, self.padding = stride, padding
         self.counter = counter
         self.calls = 0
+        self.carry = None                       # a Carry when this layer emits codes
+
+    def accepts(self, cc):
+        """A carried tensor (K.CarriedCodes) holds this layer's planned operand."""
+        return cc.quantizer() == (self.delta, self.zp, self.n_bits, self.sym)
+
+    def run_codes(self, x, bias, gamma, phi, relu):
+        """The layer's whole forward as the consumer's int8 operand."""
+        c = self.carry
+        self.calls += 1
+        c.calls += 1
+        codes = K.qconv_codes(x, self.prepared, self.scale, self.stride, self.padding,
+                              groups=self.groups, act_zp=self.zp, act_bits=self.n_bits,
+                              act_sym=self.sym, act_delta=self.delta, bias=bias, gamma=gamma,
+                              phi=phi, relu=relu, out_delta=c.delta, out_zp=c.zp,
+                              out_bits=c.n_bits, out_sym=c.sym, bad=self.counter)
+        N, H, W, _ = codes.shape
+        return K.carried(codes, (N, self.prepared.shape[0], H, W), c.delta, c.zp, c.n_bits, c.sym)
 
     def run(self, x):
         self.calls += 1
@@ -38,6 +64,17 @@ class IntPlan:
                        groups=self.groups, act_zp=self.zp,
                        act_bits=self.n_bits, act_sym=self.sym, act_delta=self.delta,
                        bad=self.counter)
+
+
+class Carry:
+    """A producer's carried output: the consumer and the producer's act quantizer as the
+    consumer's plan holds it."""
+
+    def __init__(self, consumer):
+        p = consumer._int_plan
+        self.consumer = consumer
+        self.delta, self.zp, self.n_bits, self.sym = p.delta, p.zp, p.n_bits, p.sym
+        self.calls = 0
 
 
 def _layers(qnn):
@@ -128,11 +165,12 @@ def _weight_codes(m):
 
 
 @torch.no_grad()
-def enable_integer_inference(qnn, sample, grouped=False):
+def enable_integer_inference(qnn, sample, grouped=False, carry=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
-    plan grouped and depthwise convs (K24-K26); off, they are reported as refused."""
+    plan grouped and depthwise convs (K24-K26); off, they are reported as refused.  `carry`:
+    also carry int8 codes between the integer layers of a block (`carry_report`)."""
     disable_integer_inference(qnn)
     layers = _layers(qnn)
     if not layers:
@@ -200,7 +238,34 @@ def enable_integer_inference(qnn, sample, grouped=False):
                  * f["scale"].detach().reshape(-1).float()).contiguous()
         m._int_plan = IntPlan(prep, scale, delta, zp, n_bits, sym, stride, padding, counter)
         report[name] = INT8
+    if carry:
+        _plan_carry(qnn, source)
     return report
+
+
+def _plan_carry(qnn, source):
+    """Install a Carry on every producer of a block's interior chain whose pair can stay int8:
+    both planned, the consumer's traced input quantizer the producer's own act quantizer, the
+    producer's epilogue one the kernel applies (fusable quantizer and epilogue, no SE module),
+    and no hook that would see the tensor."""
+    from .quant_block import BaseQuantBlock
+    for blk in qnn.modules():
+        if not isinstance(blk, BaseQuantBlock):
+            continue
+        for prod, cons in blk.interior_chain():
+            if prod._int_plan is None or cons._int_plan is None:
+                continue
+            q = prod.act_quantizer
+            if source.get(cons) is not q or prod.disable_act_quant:
+                continue
+            if fusable_act_quantizer(q, True) is None or prod.se_module is not None:
+                continue
+            # (the weight stands in for the input: epilogue_fusable asks for its device only)
+            if not prod.epilogue_fusable(prod.weight) or prod.act_code() not in (0, 1, 2):
+                continue
+            if any(m._forward_hooks or m._forward_pre_hooks for m in (prod, cons)):
+                continue
+            prod._int_plan.carry = Carry(cons)
 
 
 def disable_integer_inference(qnn):
@@ -218,3 +283,16 @@ def integer_report(qnn):
     counter = getattr(qnn, "_int_counter", None)
     calls = {n: m._int_plan.calls for n, m in _layers(qnn) if getattr(m, "_int_plan", None) is not None}
     return {"off_grid": int(counter.item()) if counter is not None else 0, "calls": calls}
+
+
+def carry_report(qnn):
+    """{"pairs": [(producer name, consumer name), ...] the installed plan carries int8 codes
+    between, "calls": {producer name: forwards that emitted codes}}; empty without a plan."""
+    names = {m: n for n, m in _layers(qnn)}
+    pairs, calls = [], {}
+    for n, m in _layers(qnn):
+        c = getattr(getattr(m, "_int_plan", None), "carry", None)
+        if c is not None:
+            pairs.append((n, names[c.consumer]))
+            calls[n] = c.calls
+    return {"pairs": pairs, "calls": calls}

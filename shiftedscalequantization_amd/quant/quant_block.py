@@ -84,6 +84,12 @@ class BaseQuantBlock(nn.Module):
         residual add of the block's tail (_tail); None otherwise."""
         return None
 
+    def interior_chain(self):
+        """The (producer, consumer) QuantModule pairs where the block's own forward hands the
+        producer's output to the consumer and to nothing else (no residual, no pooling, no
+        second reader): the pairs between which quant.integer may carry int8 codes."""
+        return []
+
     def _residual(self, ds, x):
         """ds(x), the downsample branch.  For the block the recon loop fuses (K.TAIL_LAZY)
         and a downsample whose forward ends in its K13 epilogue alone (bias, gamma^z/phi^z,
@@ -180,6 +186,9 @@ class QuantBasicBlock(BaseQuantBlock):
     def identity_input_convs(self):
         return [self.conv1] if self.downsample is None else None
 
+    def interior_chain(self):
+        return [(self.conv1, self.conv2)]
+
     def toggleHardTarget(self):
         for m in (self.conv1, self.conv2, self.downsample):
             if m is not None:
@@ -207,6 +216,9 @@ class QuantBottleneck(BaseQuantBlock):
 
     def identity_input_convs(self):
         return [self.conv1] if self.downsample is None else None
+
+    def interior_chain(self):
+        return [(self.conv1, self.conv2), (self.conv2, self.conv3)]
 
     def forward(self, x):
         if self.cache_features == 'if':
@@ -239,6 +251,9 @@ class QuantResBottleneckBlock(BaseQuantBlock):
 
     def identity_input_convs(self):
         return None if self.proj_block else [self.conv1]
+
+    def interior_chain(self):
+        return [(self.conv1, self.conv2), (self.conv2, self.conv3)]
 
     def forward(self, x):
         if self.cache_features == 'if':
@@ -277,6 +292,10 @@ class QuantInvertedResidual(BaseQuantBlock):
 
     def identity_input_convs(self):
         return [self.conv[0]] if self.use_res_connect else None
+
+    def interior_chain(self):
+        convs = list(self.conv)
+        return list(zip(convs[:-1], convs[1:]))
 
     def forward(self, x):
         if self.cache_features == 'if':

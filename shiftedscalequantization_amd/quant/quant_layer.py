@@ -386,12 +386,18 @@ class QuantModule(nn.Module):
         K.conv2d (deterministic K17 weight gradient, see kernels.WGRAD_POLICY; a LazyEpi
         input folded into its im2col GEMM there)."""
         plan = getattr(self, '_int_plan', None)
-        if (plan is not None and not torch.is_grad_enabled() and self.use_weight_quant
-                and self.use_act_quant and self.cache_features == 'none'
-                and isinstance(input, torch.Tensor) and input.is_cuda
-                and input.dtype == torch.float32):
-            # the input is an act quantizer's output: int8 codes on the int8 MFMA (K21/K23);
-            # off-grid elements are counted on the device (quant.integer_report)
+        integer = (plan is not None and not torch.is_grad_enabled() and self.use_weight_quant
+                   and self.use_act_quant and self.cache_features == 'none')
+        cc = getattr(input, '_ssq_codes', None)
+        if cc is not None and not (integer and plan.accepts(cc)):
+            # a carrying producer's int8 codes (quant/integer.py) that are not this layer's
+            # planned operand: decoded to the fp32 tensor they stand for
+            input, cc = K.materialize_epi(input), None
+        if (integer and isinstance(input, torch.Tensor) and input.is_cuda
+                and (cc is not None or input.dtype == torch.float32)):
+            # the input is an act quantizer's output: int8 codes on the int8 MFMA (K21/K23;
+            # carried codes skip K21); off-grid elements are counted on the device
+            # (quant.integer_report)
             out = plan.run(input)
             return out if bias is None else out + bias.view((1, -1) + (1,) * (out.dim() - 2))
         if self.fwd_func is F.conv2d and input.is_cuda and weight.requires_grad:
@@ -413,9 +419,37 @@ class QuantModule(nn.Module):
                 return hit[4], bias
         return self._conv(input, weight), bias
 
+    def _carry(self, input):
+        """The forward as carried int8 codes (K.qconv_codes: conv, epilogue and act quantizer
+        in one kernel) when this layer is a planned carrying producer (quant/integer.py) and
+        the run-time state is still the planned one; None: take the usual route."""
+        plan = self._int_plan
+        c = None if plan is None else plan.carry
+        if (c is None or torch.is_grad_enabled() or self.disable_act_quant
+                or not (self.use_weight_quant and self.use_act_quant)
+                or self.cache_features != 'none' or _CONV_CACHE is not None
+                or self._forward_hooks or self._forward_pre_hooks
+                or not isinstance(input, torch.Tensor) or not self.epilogue_fusable(input)
+                or fusable_act_quantizer(self.act_quantizer, True) is None):
+            return None
+        m = c.consumer
+        if (m._int_plan is None or m._forward_hooks or m._forward_pre_hooks
+                or m.cache_features != 'none' or not (m.use_weight_quant and m.use_act_quant)):
+            return None
+        cc = getattr(input, '_ssq_codes', None)
+        if not (plan.accepts(cc) if cc is not None else input.dtype == torch.float32):
+            return None
+        gamma, phi = self.affine()
+        return plan.run_codes(input, self.bias, gamma, phi, self.act_code())
+
     def forward(self, input: torch.Tensor):
         if self.cache_features == 'if':
+            input = K.materialize_epi(input)
             self.cached_inp_features += [self._cache(input)]
+        elif getattr(self, '_int_plan', None) is not None:
+            out = self._carry(input)
+            if out is not None:
+                return out
         act_q = self.use_act_quant and not self.disable_act_quant
         if self.epilogue_fusable(input):
             out, bias = self.forward_raw(input)
