@@ -770,6 +770,30 @@ int ssq_qconv_i8_grouped_codes_fwd(const int8_t* codes, const void* prepared, co
 int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W, float delta,
                    float zero_point, int qmin, float* x, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- carried block tails
+ * ssq_qconv_i8_codes_fwd with K13's residual add: t = t + rv between the affine and the
+ * activation, one more fp32 rounding, so out_codes is what ssq_act_encode derives from the
+ * K13 epilogue run with that residual.  Exactly one residual pointer is non-null:
+ *   res_f32    fp32 NCHW [Nb, Co, OH, OW] (a downsample branch's output, an fp32 block input);
+ *              rv is the element itself, res_delta .. res_qmax are not read;
+ *   res_codes  int8 NHWC [Nb*OH*OW][qinfer_cpad(Co)] in K21's stored form (a carried block
+ *              input) with its own quantizer: rv = (q_r - res_zero_point) * res_delta,
+ *              q_r = code + res_qmin + 128, the value ssq_act_decode writes.
+ * groups must be 1 (the dense kernel K23).  The residual quantizer is checked as the output
+ * one: res_delta positive and finite, res_zero_point an integer in [res_qmin, res_qmin + 255],
+ * res_qmax - res_qmin <= 255.  A NaN q (now also from a NaN residual) is stored as out_qmin
+ * and ADDED to *bad.  Every refusal is SSQ_E_ARG before any launch.  No allocation, no sync,
+ * capturable.                                                                                 */
+int ssq_qconv_i8_codes_res_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                               int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                               int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                               float act_zero_point, int act_qmin, int act_qmax,
+                               const float* bias, const float* gamma, const float* phi, int act,
+                               float out_delta, float out_zero_point, int out_qmin, int out_qmax,
+                               int8_t* out_codes, uint32_t* bad, const float* res_f32,
+                               const int8_t* res_codes, float res_delta, float res_zero_point,
+                               int res_qmin, int res_qmax, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- bandwidth probe
  * float4 device copy, used by bench.py to report the measured stream bandwidth.      */
 int ssq_stream_copy(const float* src, float* dst, int64_t n, ssq_stream_t stream);

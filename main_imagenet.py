@@ -153,16 +153,21 @@ def main(argv=None):
             print('Full quantization (W{}A{}) accuracy: {}'.format(args.n_bits_w, args.n_bits_a,
                                                                    validate_model(loader, qnn)))
     if args.int_infer and args.act_quant:
-        from shiftedscalequantization_amd.quant import (carry_report, enable_integer_inference,
-                                                         integer_report)
+        from shiftedscalequantization_amd.quant import (block_carry_report, carry_report,
+                                                         enable_integer_inference, integer_report)
         plan = enable_integer_inference(qnn, cali[:8], grouped=args.int_infer_grouped,
-                                        carry=args.int_infer_carry)
+                                        carry=args.int_infer_carry,
+                                        carry_blocks=args.int_infer_carry_blocks)
         n_int = sum(v == 'int8' for v in plan.values())
         print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
         if args.int_infer_carry:
             pairs = carry_report(qnn)['pairs']
             print(f'integer inference: int8 codes carried between {len(pairs)} pairs: '
                   + ', '.join(f'{a} -> {b}' for a, b in pairs))
+        if args.int_infer_carry_blocks:
+            edges = block_carry_report(qnn)['edges']
+            print(f'integer inference: int8 codes carried across {len(edges)} block edges: '
+                  + ', '.join(f'{a} -> {b}' for a, b in edges))
         for name, why in plan.items():
             print(f'  {name}: {why}')
         if loader is not None:

@@ -80,6 +80,10 @@ def build_parser():
                    help='--int_infer with int8 codes carried between the integer layers of a '
                         'block (conv, epilogue and act quantizer in one kernel, no fp32 tensor '
                         'in between); implies --int_infer')
+    p.add_argument('--int_infer_carry_blocks', action='store_true',
+                   help='--int_infer_carry with the codes also carried across block tails '
+                        '(residual add in the conv kernel) and block boundaries; implies '
+                        '--int_infer_carry and --int_infer')
     p.add_argument('--deterministic', default=1, type=int,
                    help='1 (reference): deterministic MIOpen conv solvers; 0: fastest solvers')
     # data parallel: one process per GPU, spawned by main_imagenet.py itself with --gpus N
@@ -97,6 +101,8 @@ def parse_args(argv=None):
     a = build_parser().parse_args(argv)
     if a.run_device:
         a.device_gpu = a.run_device
+    if a.int_infer_carry_blocks:
+        a.int_infer_carry = True
     if a.int_infer_grouped or a.int_infer_carry:
         a.int_infer = True
     return a

@@ -173,12 +173,19 @@ struct QConvGeo {
 // CODES: the code-emitting epilogue (qinfer_epi.h) instead of the fp32 NCHW store; `y` is then
 // the QEpi.  The 64 px x 64 ch code tile is transposed through the (then free) activation
 // tile and leaves as one 16-B chunk of a pixel's channels per thread.
-template <bool CODES>
+// RES (with CODES): a block tail's residual, added where K13 adds it (qepi_code<true>).  1: fp32
+// NCHW, four loads per fragment, each 16 consecutive pixels of one channel plane (the fp32
+// form's store pattern); 2: int8 codes in the output's own layout, one aligned dword (the
+// lane's 4 channels of its pixel) per fragment.  `y` is then the QEpiRes.  The loads are issued
+// right after the K loop, so the cwz / T correction arithmetic covers their latency.
+template <bool CODES, int RES = 0>
 __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
     const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ mask,
     const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
     const float* __restrict__ scale, QConvGeo g,
-    typename std::conditional<CODES, QEpi, float* __restrict__>::type y) {
+    typename std::conditional<CODES, typename std::conditional<RES != 0, QEpiRes, QEpi>::type,
+                              float* __restrict__>::type y) {
+  static_assert(CODES || RES == 0, "a residual goes with the code-emitting epilogue");
   __shared__ __attribute__((aligned(16))) int8_t lA[kQT * kQRow];
   __shared__ __attribute__((aligned(16))) int8_t lB[(kQT + 1) * kQRow];
   const uint32_t tid = threadIdx.x;
@@ -248,9 +255,31 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
   const uint32_t pixel = blockIdx.x * kQT + wave * 16 + fr;
   const long long sa = (long long)accs[0];
   if constexpr (CODES) {
-    const QEpi& e = y;
+    const QEpi& e = qepi_of(y);
     const bool pval = pixel < g.M;
     uint32_t nbad = 0;
+    float rf[RES == 1 ? 16 : 1];
+    int rw[RES == 2 ? 4 : 1];
+    if constexpr (RES == 1) {
+      const uint32_t pc = pval ? pixel : 0u;
+      const uint32_t n = fdiv(pc, g.div_p);
+      const float* rp = y.r.f32 + (size_t)n * g.Co * g.P + (pc - n * g.P);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
+          rf[j * 4 + r] = (pval && co < g.Co) ? rp[(size_t)co * g.P] : 0.0f;
+        }
+      }
+    } else if constexpr (RES == 2) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        // co0 is a multiple of 4 below Co <= Cpo (a multiple of 16): the dword lies in the row
+        const uint32_t co0 = blockIdx.y * kQT + j * 16 + fq * 4;
+        rw[j] = (pval && co0 < g.Co) ? *(const int*)(y.r.codes + (size_t)pixel * e.Cpo + co0) : 0;
+      }
+    }
     __syncthreads();   // the last step's fragment reads are done: lA is free
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -262,7 +291,14 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
         if (pval && co < g.Co) {
           const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
                               (long long)g.az * (long long)tt[co];
-          c[r] = qepi_code((float)I, co, scale, e, nbad);
+          if constexpr (RES == 1) {
+            c[r] = qepi_code<true>((float)I, co, scale, e, nbad, rf[j * 4 + r]);
+          } else if constexpr (RES == 2) {
+            const int code = (int)(int8_t)((uint32_t)rw[j] >> (8 * r));
+            c[r] = qepi_code<true>((float)I, co, scale, e, nbad, qres_decode(code, y.r));
+          } else {
+            c[r] = qepi_code((float)I, co, scale, e, nbad);
+          }
         }
       }
       *(int*)(lA + (wave * 16 + fr) * kQRow + j * 16 + fq * 4) = qepi_pack4(c[0], c[1], c[2], c[3]);
@@ -401,12 +437,14 @@ extern "C" int ssq_qweight_prepare(const void* packed, const float* zp, int64_t 
   return check_launch("ssq_qweight_prepare");
 }
 
-// y: the fp32 output (ssq_qconv_i8_fwd) or null with `epi` set (ssq_qconv_i8_codes_fwd)
+// y: the fp32 output (ssq_qconv_i8_fwd) or null with `epi` set (ssq_qconv_i8_codes_fwd); `res`
+// with `epi`: the tail's residual (ssq_qconv_i8_codes_res_fwd)
 static int qconv_i8_launch(const char* me, const int8_t* codes, const void* prepared,
                            const float* scale, int64_t Nb, int64_t Ci, int64_t H, int64_t W,
                            int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
                            int64_t groups, float act_zero_point, int act_qmin, int act_qmax,
-                           float* y, QEpi* epi, ssq_stream_t stream) {
+                           float* y, QEpi* epi, ssq_stream_t stream,
+                           const QRes* res = nullptr) {
   SSQ_REQUIRE(codes && prepared && scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
   SSQ_REQUIRE(groups == 1, SSQ_E_ARG, "%s: groups = %lld (only groups == 1)", me,
               (long long)groups);
@@ -453,6 +491,18 @@ static int qconv_i8_launch(const char* me, const int8_t* codes, const void* prep
     epi->Cpo = (uint32_t)rup(Co, 16);
     SSQ_REQUIRE(Nb * OH * OW * (int64_t)epi->Cpo < (1ll << 31), SSQ_E_ARG,
                 "%s: tensor exceeds 2^31 elements", me);
+    if (res) {
+      const QEpiRes er = {*epi, *res};
+      if (res->f32)
+        hipLaunchKernelGGL((qconv_i8_kernel<true, 1>), grid, dim3(kBlock), 0, (hipStream_t)stream,
+                           codes, base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
+                           (const int32_t*)(base + L.off_t), scale, g, er);
+      else
+        hipLaunchKernelGGL((qconv_i8_kernel<true, 2>), grid, dim3(kBlock), 0, (hipStream_t)stream,
+                           codes, base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
+                           (const int32_t*)(base + L.off_t), scale, g, er);
+      return check_launch(me);
+    }
     hipLaunchKernelGGL(qconv_i8_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, codes,
                        base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
                        (const int32_t*)(base + L.off_t), scale, g, *epi);
@@ -492,6 +542,27 @@ extern "C" int ssq_qconv_i8_codes_fwd(const int8_t* codes, const void* prepared,
             0u, out_codes, bad};
   return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
                          act_zero_point, act_qmin, act_qmax, nullptr, &e, stream);
+}
+
+extern "C" int ssq_qconv_i8_codes_res_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t Ci,
+    int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+    int64_t groups, float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+    const float* gamma, const float* phi, int act, float out_delta, float out_zero_point,
+    int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad, const float* res_f32,
+    const int8_t* res_codes, float res_delta, float res_zero_point, int res_qmin, int res_qmax,
+    ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_codes_res_fwd";
+  int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax, out_codes,
+                   bad);
+  if (rc) return rc;
+  rc = qres_ok(me, res_f32, res_codes, res_delta, res_zero_point, res_qmin, res_qmax);
+  if (rc) return rc;
+  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
+            0u, out_codes, bad};
+  const QRes r = {res_f32, res_codes, res_delta, res_zero_point, (float)res_qmin};
+  return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                         act_zero_point, act_qmin, act_qmax, nullptr, &e, stream, &r);
 }
 
 extern "C" int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W,

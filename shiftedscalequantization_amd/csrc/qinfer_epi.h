@@ -6,6 +6,7 @@
 //     y    = fp32(I) * s[co]                       the conv kernel's own output
 //     pre  = y + bias[co]                          K13 (recon.hip epi / epi_elem), if bias
 //     t    = pre * gamma[co] + phi[co]             two roundings, if gamma / phi
+//     t    = t + rv                                K13's residual add, if a residual (RES)
 //     t    = act(t)                                act_fwd: 0 identity, 1 ReLU, 2 ReLU6
 //     v    = round_ste(t / d) + z                  IEEE divide; NaN at an infinite t / d
 //     q    = clamp(v, lo, hi)                      NaN stays NaN
@@ -32,11 +33,37 @@ struct QEpi {
   uint32_t* bad;
 };
 
+// A block tail's residual operand (K23 only): the fp32 NCHW tensor K13 would add, or the int8
+// codes (K21's stored form, the output's pixel and channel layout) of a carried block input
+// with that tensor's own act quantizer.  Exactly one pointer is set.
+struct QRes {
+  const float* f32;     // [Nb, Co, OH, OW] or null
+  const int8_t* codes;  // [Nb*OH*OW][Cpo] or null
+  float d, z, lo;       // the residual codes' quantizer
+};
+
+struct QEpiRes {
+  QEpi e;
+  QRes r;
+};
+
+__device__ __forceinline__ const QEpi& qepi_of(const QEpi& e) { return e; }
+__device__ __forceinline__ const QEpi& qepi_of(const QEpiRes& er) { return er.e; }
+
+// the fp32 value act_decode_kernel writes for a stored code: (q - z) * d, q = code + 128 + lo
+__device__ __forceinline__ float qres_decode(int code, const QRes& r) {
+  const float q = __fadd_rn((float)(code + 128), r.lo);   // exact: |q| <= 255
+  return __fmul_rn(__fsub_rn(q, r.z), r.d);
+}
+
+// RES: `rv` is the residual K13 adds between the affine and the activation
+template <bool RES = false>
 __device__ __forceinline__ int qepi_code(float fI, uint32_t co, const float* __restrict__ scale,
-                                         const QEpi& e, uint32_t& nbad) {
+                                         const QEpi& e, uint32_t& nbad, float rv = 0.0f) {
   const float y = __fmul_rn(fI, scale[co]);
   const float pre = e.bias ? __fadd_rn(y, e.bias[co]) : y;
   float t = e.gamma ? __fadd_rn(__fmul_rn(pre, e.gamma[co]), e.phi[co]) : pre;
+  if constexpr (RES) t = __fadd_rn(t, rv);
   t = e.act == 1 ? act_fwd<1>(t) : (e.act == 2 ? act_fwd<2>(t) : t);
   const float v = round_ste_zp(t / e.d, e.z);
   float q = clampf(v, e.lo, e.hi);
@@ -79,6 +106,23 @@ static inline int qepi_ok(const char* what, const float* gamma, const float* phi
   SSQ_REQUIRE(zero_point == rintf(zero_point) && zero_point >= (float)qmin &&
                   zero_point <= (float)(qmin + 255),
               SSQ_E_ARG, "%s: output zero point %g is not an integer in [%d, %d]", what,
+              (double)zero_point, qmin, qmin + 255);
+  return SSQ_OK;
+}
+
+// the residual codes' quantizer, held to the same rules
+static inline int qres_ok(const char* what, const float* res_f32, const int8_t* res_codes,
+                          float delta, float zero_point, int qmin, int qmax) {
+  SSQ_REQUIRE((res_f32 != nullptr) != (res_codes != nullptr), SSQ_E_ARG,
+              "%s: exactly one of res_f32 and res_codes must be set", what);
+  if (!res_codes) return SSQ_OK;
+  SSQ_REQUIRE(qmin < qmax && qmax - qmin <= 255, SSQ_E_ARG,
+              "%s: residual code range [%d, %d] does not fit 8-bit codes", what, qmin, qmax);
+  SSQ_REQUIRE(delta > 0.0f && delta <= 3.0e38f, SSQ_E_ARG,
+              "%s: residual delta must be positive and finite", what);
+  SSQ_REQUIRE(zero_point == rintf(zero_point) && zero_point >= (float)qmin &&
+                  zero_point <= (float)(qmin + 255),
+              SSQ_E_ARG, "%s: residual zero point %g is not an integer in [%d, %d]", what,
               (double)zero_point, qmin, qmin + 255);
   return SSQ_OK;
 }

@@ -2030,13 +2030,17 @@ def act_decode(codes, C, delta, zp, n_bits, sym=False):
 
 def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0, act_bits=8,
                 act_sym=False, act_delta=None, bias=None, gamma=None, phi=None, relu=0,
-                out_delta=None, out_zp=0.0, out_bits=8, out_sym=False, bad=None):
+                out_delta=None, out_zp=0.0, out_bits=8, out_sym=False, bad=None, residual=None):
     """qconv with the layer's epilogue and output act quantizer applied in the kernel
     (csrc/qinfer_epi.h): returns the int8 codes of clamp(round(act((I * scale + bias) * gamma +
     phi) / out_delta) + out_zp) in act_encode's layout (N, OH, OW, Cpad) -- what act_encode
     derives from the K13 epilogue's output of qconv's.  `relu`: 0 identity, 1 ReLU, 2 ReLU6.
     A NaN result is stored as qmin and ADDED to `bad`, as are the off-grid elements of an fp32
-    input; `bad` must be given (a device int32 word)."""
+    input; `bad` must be given (a device int32 word).
+    `residual` (dense convs only, ssq_qconv_i8_codes_res_fwd): a block tail's residual, added
+    between the affine and the activation as the K13 epilogue adds it -- an fp32 tensor of the
+    output's (N, Co, OH, OW), or a carried code tensor (`carried`) of that logical shape, which
+    enters as the fp32 value act_decode gives it."""
     if out_delta is None or bad is None:
         raise A.SSQError("qconv_codes: out_delta and bad are required")
     if len(prepared.shape) != 4:
@@ -2055,6 +2059,25 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
     out = torch.empty((N, OH, OW, query("ssq_qinfer_cpad", Co)), dtype=torch.int8,
                       device=keep[0].device)
     olo, ohi = qrange(out_bits, out_sym)
+    if residual is not None:
+        cc = getattr(residual, "_ssq_codes", None)
+        if cc is not None:
+            if (residual.dtype != torch.int8 or cc.shape != (N, Co, OH, OW)
+                    or tuple(residual.shape) != tuple(out.shape)):
+                raise A.SSQError(f"qconv_codes: residual codes {cc.shape} do not match the output "
+                                 f"{(N, Co, OH, OW)}")
+            res = _i8_dev(residual, "qconv_codes")
+            rlo, rhi = qrange(cc.n_bits, cc.sym)
+            rargs = (None, _vp(res), cc.delta, cc.zp, rlo, rhi)
+        else:
+            if residual.dtype != torch.float32 or tuple(residual.shape) != (N, Co, OH, OW):
+                raise A.SSQError(f"qconv_codes: residual must be fp32 {(N, Co, OH, OW)} or carried "
+                                 f"codes, got {residual.dtype} {tuple(residual.shape)}")
+            res, rp = fptr(residual.detach(), "residual")
+            rargs = (rp, None, 0.0, 0.0, 0, 0)
+        call("ssq_qconv_i8_codes_res_fwd", *args, vecs[0][1], vecs[1][1], vecs[2][1], int(relu),
+             float(out_delta), float(out_zp), olo, ohi, _vp(out), _vp(bad), *rargs, stream_of(out))
+        return out
     fn = "ssq_qconv_i8_grouped_codes_fwd" if int(groups) > 1 else "ssq_qconv_i8_codes_fwd"
     call(fn, *args, vecs[0][1], vecs[1][1], vecs[2][1], int(relu), float(out_delta), float(out_zp),
          olo, ohi, _vp(out), _vp(bad), stream_of(out))

@@ -102,6 +102,12 @@ class ResNet(nn.Module):
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
+    def stage_chain(self):
+        """The containers `forward` applies back to back with nothing in between: the last
+        child of one hands its output to the first child of the next and to nothing else
+        (quant.integer.block_edges)."""
+        return [self.layer1, self.layer2, self.layer3, self.layer4]
+
 
 def resnet18(**kw):
     return ResNet(BasicBlock, [2, 2, 2, 2], **kw)
@@ -271,6 +277,11 @@ class RegNet(nn.Module):
         for i in range(self.stages):
             x = getattr(self, f"s{i + 1}")(x)
         return self.fc(torch.flatten(self.avgpool(x), 1))
+
+    def stage_chain(self):
+        """The stages `forward` applies back to back with nothing in between (see
+        ResNet.stage_chain)."""
+        return [getattr(self, f"s{i + 1}") for i in range(self.stages)]
 
 
 def _regnet(name):

@@ -17,8 +17,18 @@ takes the codes as its operand, so the K13 epilogue pass and the K21 re-encode b
 drop out.  Only the pairs a block declares (`BaseQuantBlock.interior_chain`) are carried: the
 planning trace sees module inputs, not residual adds or pooling, so the block's structure is
 what guarantees the producer's output has one reader.
+
+With `carry_blocks=True` the codes also cross a block's tail and its boundary: the block's last
+conv runs ssq_qconv_i8_codes_res_fwd (the residual add, the block's activation and the block's
+act quantizer in the conv kernel; the residual an fp32 tensor or the carried block input) and
+the next block's readers, its identity residual among them, take the codes.  Which boundaries
+qualify is structural again (`block_edges`: neighbours in an nn.Sequential, and the stages a
+model declares with `stage_chain`); the trace confirms the readers' input quantizer.  A tagged
+tensor that arrives where it is not the planned operand is decoded (K.materialize_epi), so a
+condition that fails at run time costs time, never correctness.
 """
 import torch
+import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import kernels as K
@@ -45,16 +55,19 @@ class IntPlan:
         """A carried tensor (K.CarriedCodes) holds this layer's planned operand."""
         return cc.quantizer() == (self.delta, self.zp, self.n_bits, self.sym)
 
-    def run_codes(self, x, bias, gamma, phi, relu):
-        """The layer's whole forward as the consumer's int8 operand."""
-        c = self.carry
+    def run_codes(self, x, bias, gamma, phi, relu, c=None, residual=None):
+        """The layer's whole forward as the consumer's int8 operand.  `c`: the output quantizer
+        and call counter (the layer's own Carry, or a block's TailCarry with the block's
+        activation as `relu` and the tail's `residual`)."""
+        c = self.carry if c is None else c
         self.calls += 1
         c.calls += 1
         codes = K.qconv_codes(x, self.prepared, self.scale, self.stride, self.padding,
                               groups=self.groups, act_zp=self.zp, act_bits=self.n_bits,
                               act_sym=self.sym, act_delta=self.delta, bias=bias, gamma=gamma,
                               phi=phi, relu=relu, out_delta=c.delta, out_zp=c.zp,
-                              out_bits=c.n_bits, out_sym=c.sym, bad=self.counter)
+                              out_bits=c.n_bits, out_sym=c.sym, bad=self.counter,
+                              residual=residual)
         N, H, W, _ = codes.shape
         return K.carried(codes, (N, self.prepared.shape[0], H, W), c.delta, c.zp, c.n_bits, c.sym)
 
@@ -75,6 +88,18 @@ class Carry:
         self.consumer = consumer
         self.delta, self.zp, self.n_bits, self.sym = p.delta, p.zp, p.n_bits, p.sym
         self.calls = 0
+
+
+class TailCarry:
+    """A block's carried output (carry_blocks): the block's last conv, the successor and its
+    module readers, and the block's act quantizer as the readers' plans hold it."""
+
+    def __init__(self, last, successor, entry, readers):
+        p = readers[0]._int_plan
+        self.last, self.successor, self.entry, self.readers = last, successor, entry, readers
+        self.delta, self.zp, self.n_bits, self.sym = p.delta, p.zp, p.n_bits, p.sym
+        self.calls = 0
+        self.residual = None        # the kind the last emitting forward added
 
 
 def _layers(qnn):
@@ -165,12 +190,15 @@ def _weight_codes(m):
 
 
 @torch.no_grad()
-def enable_integer_inference(qnn, sample, grouped=False, carry=False):
+def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
     plan grouped and depthwise convs (K24-K26); off, they are reported as refused.  `carry`:
-    also carry int8 codes between the integer layers of a block (`carry_report`)."""
+    also carry int8 codes between the integer layers of a block (`carry_report`).
+    `carry_blocks`: `carry`, and the codes also cross block tails and block boundaries
+    (`block_carry_report`)."""
+    carry = carry or carry_blocks
     disable_integer_inference(qnn)
     layers = _layers(qnn)
     if not layers:
@@ -240,6 +268,8 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False):
         report[name] = INT8
     if carry:
         _plan_carry(qnn, source)
+    if carry_blocks:
+        _plan_block_carry(qnn, source)
     return report
 
 
@@ -268,10 +298,122 @@ def _plan_carry(qnn, source):
             prod._int_plan.carry = Carry(cons)
 
 
+def _edge_entry(m):
+    """The module a successor hands its input to and to nothing else: a quant block or a
+    QuantModule itself, the first child (recursively) of an nn.Sequential; None otherwise."""
+    from .quant_block import BaseQuantBlock
+    while not isinstance(m, (BaseQuantBlock, QuantModule)):
+        if not isinstance(m, nn.Sequential) or len(m) == 0:
+            return None
+        m = m[0]
+    return m
+
+
+def block_edges(qnn):
+    """The (producer block, successor) module pairs where the producer's output goes to the
+    successor and nowhere else, from the structure alone (no device, no forward): consecutive
+    children of an nn.Sequential, the first a quant block, the second a quant block, a
+    QuantModule or an nn.Sequential that starts with one; and, where the model declares the
+    containers its forward applies back to back (`stage_chain()` on `qnn.model`), the last
+    child of one stage and the first child of the next."""
+    from .quant_block import BaseQuantBlock
+    edges = []
+    for seq in qnn.modules():
+        if isinstance(seq, nn.Sequential):
+            kids = list(seq)
+            for a, b in zip(kids[:-1], kids[1:]):
+                if isinstance(a, BaseQuantBlock) and _edge_entry(b) is not None:
+                    edges.append((a, b))
+    chain = getattr(getattr(qnn, "model", qnn), "stage_chain", None)
+    stages = list(chain()) if callable(chain) else []
+    for s0, s1 in zip(stages[:-1], stages[1:]):
+        if not (isinstance(s0, nn.Sequential) and isinstance(s1, nn.Sequential) and len(s0) and len(s1)):
+            continue
+        if isinstance(s0[-1], BaseQuantBlock) and _edge_entry(s1[0]) is not None:
+            edges.append((s0[-1], s1[0]))
+    return edges
+
+
+def _hooked(*mods):
+    return any(m._forward_hooks or m._forward_pre_hooks for m in mods)
+
+
+def block_act_code(blk):
+    """The block activation as the kernels' code (0 identity, 1 ReLU, 2 ReLU6), None for any
+    other."""
+    from .quant_layer import StraightThrough
+    f = blk.activation_function
+    if isinstance(f, nn.ReLU6):
+        return 2
+    if isinstance(f, nn.ReLU):
+        return 1
+    return 0 if isinstance(f, StraightThrough) else None
+
+
+def edge_readers(successor):
+    """(entry module, the QuantModules that read the successor's input, whether the input is
+    also an identity residual); readers None when the input has a reader that is not known."""
+    from .quant_block import BaseQuantBlock
+    entry = _edge_entry(successor)
+    if isinstance(entry, QuantModule):
+        return entry, [entry], False
+    if isinstance(entry, BaseQuantBlock):
+        readers = entry.input_readers()
+        if readers is not None:
+            return entry, list(readers), False
+        readers = entry.identity_input_convs()
+        if readers is not None:
+            return entry, list(readers), True
+    return entry, None, False
+
+
+def _decoded_grouped(mod):
+    """`mod` holds a grouped or depthwise conv that is not planned."""
+    return any(isinstance(m, QuantModule) and m.fwd_kwargs.get("groups", 1) != 1
+               and m._int_plan is None for m in mod.modules())
+
+
+def _plan_block_carry(qnn, source):
+    """Install a TailCarry on every block of `block_edges` whose tail can emit codes: the last
+    conv a planned dense conv whose epilogue the kernel applies (no activation or act
+    quantizer of its own, no SE module), the block's activation and act quantizer ones the
+    kernel applies, every reader of the successor planned with the block's act quantizer as
+    its traced input, no grouped or depthwise conv of either side left on the decoded path
+    (without `grouped=True` a MobileNetV2 / RegNetX block has one in its middle: such a block
+    keeps its fp32 edges), and no hook that would see the tensor."""
+    from .quant_layer import StraightThrough
+    for blk, succ in block_edges(qnn):
+        last = blk.last_conv()
+        plan = None if last is None else last._int_plan
+        if plan is None or plan.kind != "dense":
+            continue
+        if not isinstance(last.activation_function, StraightThrough) or last.se_module is not None:
+            continue
+        if not last.disable_act_quant or not last.epilogue_fusable(last.weight):
+            continue
+        q = blk.act_quantizer
+        if block_act_code(blk) is None or fusable_act_quantizer(q, True) is None:
+            continue
+        if _input_reason(q)[0] is None:
+            continue
+        entry, readers, _ = edge_readers(succ)
+        if not readers or any(m._int_plan is None or source.get(m) is not q for m in readers):
+            continue
+        if any(_decoded_grouped(m) for m in (blk, entry)):
+            continue
+        if _hooked(blk, last, succ, entry, *readers):
+            continue
+        blk._int_tail = TailCarry(last, succ, entry, readers)
+
+
 def disable_integer_inference(qnn):
     """Every layer back on the decoded fp32 path."""
+    from .quant_block import BaseQuantBlock
     for _, m in _layers(qnn):
         m._int_plan = None
+    for m in qnn.modules():
+        if isinstance(m, BaseQuantBlock):
+            m._int_tail = None
     qnn._int_counter = None
 
 
@@ -296,3 +438,27 @@ def carry_report(qnn):
             pairs.append((n, names[c.consumer]))
             calls[n] = c.calls
     return {"pairs": pairs, "calls": calls}
+
+
+def block_carry_report(qnn):
+    """{"edges": [(block name, successor name), ...] whose block tail the installed plan lets
+    emit int8 codes, "calls": {block name: forwards whose tail emitted codes}, "residual":
+    {block name: "none" | "fp32" | "codes", the residual operand of the emitting tail: as the
+    last emitting forward had it, before one as the plan expects it}}; empty without a plan."""
+    from .quant_block import BaseQuantBlock
+    names = {m: n for n, m in qnn.named_modules()}
+    tails = [(n, m) for n, m in qnn.named_modules()
+             if isinstance(m, BaseQuantBlock) and getattr(m, "_int_tail", None) is not None]
+    fed = {m._int_tail.entry for _, m in tails}
+    edges, calls, residual = [], {}, {}
+    for n, blk in tails:
+        t = blk._int_tail
+        edges.append((n, names[t.successor]))
+        calls[n] = t.calls
+        kind = t.residual
+        if kind is None and blk.identity_input_convs() is not None:
+            kind = "codes" if blk in fed else "fp32"
+        elif kind is None:
+            kind = "none" if getattr(blk, "downsample", None) is None else "fp32"
+        residual[n] = kind
+    return {"edges": edges, "calls": calls, "residual": residual}

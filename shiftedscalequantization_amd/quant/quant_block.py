@@ -29,6 +29,7 @@ class BaseQuantBlock(nn.Module):
         self.cache_to_host = False
         self.selectionInited = False
         self.pathName = ''
+        self._int_tail = None           # carried tail (quant/integer.py, carry_blocks); None: fp32
 
     def set_quant_state(self, weight_quant: bool = False, act_quant: bool = False):
         self.use_weight_quant = weight_quant
@@ -90,6 +91,61 @@ class BaseQuantBlock(nn.Module):
         second reader): the pairs between which quant.integer may carry int8 codes."""
         return []
 
+    def last_conv(self):
+        """The QuantModule whose output (+ the residual) the block's activation and act
+        quantizer finish (_tail's `last`); None when the block declares none."""
+        return None
+
+    def _input(self, x):
+        """The block input; a carried code tensor (quant/integer.py) is decoded to the fp32
+        tensor it stands for when the block caches its input or carries hooks."""
+        if getattr(x, '_ssq_codes', None) is not None and (
+                self.cache_features != 'none' or self._forward_hooks or self._forward_pre_hooks):
+            return K.materialize_epi(x)
+        return x
+
+    def _tail_codes(self, last, inp, residual):
+        """The tail as carried int8 codes (K.qconv_codes with the residual: conv, bias,
+        gamma^z / phi^z, residual add, block activation and block act quantizer in one kernel)
+        when the block is a planned emitter (quant/integer.py, carry_blocks) and the run-time
+        state is still the planned one; None: take the usual route."""
+        from . import integer as I
+        from . import quant_layer as L
+        t = getattr(self, '_int_tail', None)
+        if t is None or t.last is not last or torch.is_grad_enabled():
+            return None
+        plan = last._int_plan
+        relu = I.block_act_code(self)
+        mods = [last, t.entry] + t.readers
+        if (plan is None or relu is None or L._CONV_CACHE is not None
+                or not (self.use_act_quant and self.cache_features == 'none')
+                or I._hooked(self, t.successor, *mods)
+                or any(m.cache_features != 'none' or not (m.use_weight_quant and m.use_act_quant)
+                       for m in mods)
+                or any(m._int_plan is None for m in t.readers)
+                or not last.disable_act_quant
+                or not isinstance(last.activation_function, StraightThrough)
+                or not isinstance(inp, torch.Tensor) or not last.epilogue_fusable(inp)
+                or fusable_act_quantizer(self.act_quantizer, True) is None):
+            return None
+        cc = getattr(inp, '_ssq_codes', None)
+        if not (plan.accepts(cc) if cc is not None else inp.dtype == torch.float32):
+            return None
+        if residual is None:
+            kind = "none"
+        elif not isinstance(residual, torch.Tensor):
+            return None
+        elif getattr(residual, '_ssq_codes', None) is not None:
+            kind = "codes"
+        elif residual.dtype == torch.float32 and residual.is_cuda:
+            kind = "fp32"
+        else:
+            return None
+        gamma, phi = last.affine()
+        out = plan.run_codes(inp, last.bias, gamma, phi, relu, c=t, residual=residual)
+        t.residual = kind
+        return out
+
     def _residual(self, ds, x):
         """ds(x), the downsample branch.  For the block the recon loop fuses (K.TAIL_LAZY)
         and a downsample whose forward ends in its K13 epilogue alone (bias, gamma^z/phi^z,
@@ -109,6 +165,13 @@ class BaseQuantBlock(nn.Module):
         """last(inp) (+ residual) -> block activation -> block act quant.  When `last` has
         no activation of its own and the block's is ReLU / identity, its bias add, the
         residual add and the activation run as one K13 epilogue pass (bit-identical)."""
+        if getattr(self, '_int_tail', None) is not None:
+            out = self._tail_codes(last, inp, residual)
+            if out is not None:
+                return out
+        # a carried block input as the identity residual of an fp32 tail: the tensor it stands for
+        if getattr(residual, '_ssq_codes', None) is not None:
+            residual = K.materialize_epi(residual)
         if (residual is not None
                 and isinstance(self.activation_function, (nn.ReLU, StraightThrough))
                 and isinstance(last.activation_function, StraightThrough)
@@ -161,6 +224,7 @@ class QuantBasicBlock(BaseQuantBlock):
         self.stride = basic_block.stride
 
     def forward(self, x):
+        x = self._input(x)
         if self.cache_features == 'if':
             self.cached_inp_features += [self._cache(x)]
         residual = x if self.downsample is None else self._residual(self.downsample, x)
@@ -188,6 +252,9 @@ class QuantBasicBlock(BaseQuantBlock):
 
     def interior_chain(self):
         return [(self.conv1, self.conv2)]
+
+    def last_conv(self):
+        return self.conv2
 
     def toggleHardTarget(self):
         for m in (self.conv1, self.conv2, self.downsample):
@@ -220,7 +287,11 @@ class QuantBottleneck(BaseQuantBlock):
     def interior_chain(self):
         return [(self.conv1, self.conv2), (self.conv2, self.conv3)]
 
+    def last_conv(self):
+        return self.conv3
+
     def forward(self, x):
+        x = self._input(x)
         if self.cache_features == 'if':
             self.cached_inp_features += [self._cache(x)]
         residual = x if self.downsample is None else self._residual(self.downsample, x)
@@ -255,7 +326,11 @@ class QuantResBottleneckBlock(BaseQuantBlock):
     def interior_chain(self):
         return [(self.conv1, self.conv2), (self.conv2, self.conv3)]
 
+    def last_conv(self):
+        return self.conv3
+
     def forward(self, x):
+        x = self._input(x)
         if self.cache_features == 'if':
             self.cached_inp_features += [self._cache(x)]
         residual = self._residual(self.downsample, x) if self.proj_block else x
@@ -297,7 +372,11 @@ class QuantInvertedResidual(BaseQuantBlock):
         convs = list(self.conv)
         return list(zip(convs[:-1], convs[1:]))
 
+    def last_conv(self):
+        return self.conv[-1]
+
     def forward(self, x):
+        x = self._input(x)
         if self.cache_features == 'if':
             self.cached_inp_features += [self._cache(x)]
         h = x
