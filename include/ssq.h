@@ -583,7 +583,13 @@ int ssq_flush_prep_fwd(ssq_stream_t stream);
  *                                                          ow*st + s - pad]
  * (the autograd of the reconstruction loops' F.conv2d weight, quant_layer.py:250, under
  * the reference's cudnn.deterministic = True, common.py:77-85).  Split-K partials in ws,
- * summed in a fixed order: bit-identical run to run.  OW <= 128, tensors < 2^31 elements. */
+ * summed in a fixed order: bit-identical run to run.  Tensors < 2^31 elements; H != W, R != S
+ * and any stride >= 1 are taken (the band kernel: 3x3 / pad 1 / stride 1-2 only).  There is
+ * no bound on OW as such: the 1x1, im2col-DMA and depthwise kernels take any width (depthwise:
+ * a padded plane <= 128 KiB), and the input-row-tile kernel refuses a shape -- workspace size
+ * 0, SSQ_E_ARG -- only when the (W + 2 pad)-wide input rows of one pixel chunk, for the input
+ * channels of one column tile, do not fit its 160 KiB LDS tile (a 3x3 / 64-channel conv:
+ * W about 150; 4 channels: about 1000). */
 /* A/B knob (returns the previous value; out-of-range values only query): non-depthwise
  * weight-gradient form, 0 auto, 1 input-row-tile kernel (+ 1x1 GEMM), 2 im2col-DMA kernel,
  * 3 band kernel (3x3 / pad 1 / stride 1-2 / Cin, Cout multiples of 32; others as 1), 4 the

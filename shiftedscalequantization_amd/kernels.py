@@ -1953,7 +1953,7 @@ def _qconv_args(name, codes_or_x, prepared, scale, stride, padding, groups, act_
     """qconv's and qconv_codes's shared front: the int8 operand (an fp32 input encoded first)
     and the first sixteen arguments of the conv entry points, + (N, Co, OH, OW, 4-D?)."""
     stride, padding = _pair(stride), _pair(padding)
-    if stride[0] != stride[1] or padding[0] != padding[1]:
+    if padding is None or stride[0] != stride[1] or padding[0] != padding[1]:
         raise A.SSQError(f"{name}: square stride / padding only")
     if codes_or_x.dtype == torch.float32:
         if act_delta is None:
@@ -2262,6 +2262,10 @@ class DwConv2dFn(torch.autograd.Function):
 
 
 def _pair(v):
+    """An int or (h, w) argument of F.conv2d as [h, w]; None for a string padding ('same' /
+    'valid'), which equals no list: every predicate comparing it keeps the library conv."""
+    if isinstance(v, str):
+        return None
     return [int(v), int(v)] if isinstance(v, int) else [int(t) for t in v]
 
 
