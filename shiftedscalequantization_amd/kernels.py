@@ -4,7 +4,9 @@ Each function states the reference op sequence it replaces.  All of them require
 tensors on the HIP device; nothing here falls back to eager PyTorch arithmetic.
 Weight geometry: W is (Co, Ci, kh, kw) -> (Co, Ci, K=kh*kw), Linear (Co, Ci) -> K = 1.
 """
+import collections
 import ctypes as C
+import functools
 import os
 
 import torch
@@ -1516,7 +1518,8 @@ class EpiConvGemmFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, bias, gamma, phi, delta, zp, weight, cfg):
         relu, n_bits, sym, stride, padding = cfg
-        Nb, C_, H, W, Co, R, S, st, pad, OH, OW = _gemm_geo(y.shape, weight.shape, stride, padding)
+        Nb, C_, H, W, Co, _, R, S, st, pad, _, _, OH, OW, _ = conv_geometry(
+            y.shape, weight.shape, stride, padding)
         y, yp = fptr(y.detach(), "conv output")
         flat = (lambda t, nm: (None, None) if t is None else fptr(t.detach().reshape(-1), nm))
         b, bp = flat(bias, "bias")
@@ -2084,36 +2087,66 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
     return out
 
 
+# ------------------------------------------------------------------ conv geometry
+# The numbers of one F.conv2d call, parsed once (conv_geometry).  single: the input and the
+# weight are 4-D and stride and padding each stand for one integer.  A tuple with unequal
+# entries or a string padding does not: every other field but dil and groups is then 0 and no
+# kernel of this file takes the conv.  dil: the one dilation, 0 for unequal entries.
+ConvGeo = collections.namedtuple("ConvGeo", "Nb C H W Co Cig R S st pad dil groups OH OW single")
+
+
+def _one(v):
+    """The integer an int-or-tuple argument of F.conv2d stands for; None for a string or a
+    tuple with unequal entries.  The one place that unpacks such an argument."""
+    if isinstance(v, int):
+        return v
+    return None if isinstance(v, str) or len(set(v)) != 1 else int(v[0])
+
+
+def conv_geometry(x_shape, w_shape, stride, padding, dilation=1, groups=1):
+    """ConvGeo of F.conv2d(x, w, None, stride, padding, dilation, groups); a layer asks for the
+    same one every iteration, so the hashable argument forms are remembered."""
+    try:
+        return _geometry(x_shape, w_shape, stride, padding, dilation, groups)
+    except TypeError:                                   # a list among the arguments
+        return _geometry.__wrapped__(x_shape, w_shape, stride, padding, dilation, groups)
+
+
+@functools.lru_cache(maxsize=1024)
+def _geometry(x_shape, w_shape, stride, padding, dilation, groups):
+    st, pad, dil = _one(stride), _one(padding), _one(dilation) or 0
+    if len(x_shape) != 4 or len(w_shape) != 4 or st is None or pad is None:
+        return ConvGeo(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, dil, groups, 0, 0, False)
+    Nb, C, H, W = x_shape
+    Co, Cig, R, S = w_shape
+    return ConvGeo(Nb, C, H, W, Co, Cig, R, S, st, pad, dil, groups,
+                   (H + 2 * pad - R) // st + 1, (W + 2 * pad - S) // st + 1, True)
+
+
+def _k17_dims(g):
+    """The ten shape arguments of ssq_conv_wgrad and of its planner queries."""
+    return g.Nb, g.C, g.H, g.W, g.Co, g.R, g.S, g.st, g.pad, g.groups
+
+
+def _dev_f32(x):
+    return x.is_cuda and x.dtype == torch.float32
+
+
 # ------------------------------------------------------------------ K17 conv weight gradient
-def conv_wgrad_supported(x, weight, stride, padding, dilation, groups):
+def conv_wgrad_supported(x, weight, stride, padding, dilation, groups, geo=None):
     """Shapes ssq_conv_wgrad handles: 4-D fp32 NCHW on the device, square stride /
     padding, dilation 1, and a plan whose LDS tile fits (nonzero workspace size)."""
-    if x.dim() != 4 or weight.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
-        return False
-    st = stride if isinstance(stride, int) else stride[0]
-    pad = padding if isinstance(padding, int) else padding[0]
-    if not isinstance(stride, int) and len(set(stride)) != 1:
-        return False
-    if not isinstance(padding, int) and (isinstance(padding, str) or len(set(padding)) != 1):
-        return False
-    if (dilation if isinstance(dilation, int) else max(dilation)) != 1:
-        return False
-    Nb, C, H, W = (int(v) for v in x.shape)
-    Co, _, R, S = (int(v) for v in weight.shape)
-    return query("ssq_conv_wgrad_workspace_size", Nb, C, H, W, Co, R, S, int(st), int(pad),
-                 int(groups)) > 0
+    g = geo or conv_geometry(x.shape, weight.shape, stride, padding, dilation, groups)
+    return (g.single and g.dil == 1 and _dev_f32(x)
+            and query("ssq_conv_wgrad_workspace_size", *_k17_dims(g)) > 0)
 
 
-def wgrad_kind(x_shape, w_shape, stride, padding, groups):
+def wgrad_kind(x_shape, w_shape, stride, padding, groups, geo=None):
     """The K17 kernel ssq_conv_wgrad runs for this shape (0 unsupported, 1 row tile,
     2 im2col-DMA, 3 band with 16-B staging, 4 1x1 GEMM, 5 depthwise, 6 band with 4-B
     staging)."""
-    st = stride if isinstance(stride, int) else stride[0]
-    pad = padding if isinstance(padding, int) else padding[0]
-    Nb, C, H, W = (int(v) for v in x_shape)
-    Co, _, R, S = (int(v) for v in w_shape)
-    return int(query("ssq_conv_wgrad_kind", Nb, C, H, W, Co, R, S, int(st), int(pad),
-                     int(groups)))
+    g = geo or conv_geometry(x_shape, w_shape, stride, padding, 1, groups)
+    return int(query("ssq_conv_wgrad_kind", *_k17_dims(g))) if g.single else 0
 
 
 def set_wgrad_form(form):
@@ -2125,43 +2158,28 @@ def set_wgrad_form(form):
 
 def conv_wgrad(x, dy, w_shape, stride, padding, groups):
     """d loss / d weight of F.conv2d(x, w, stride, padding, groups) given dy (K17)."""
-    st = stride if isinstance(stride, int) else stride[0]
-    pad = padding if isinstance(padding, int) else padding[0]
+    dims = _k17_dims(conv_geometry(x.shape, w_shape, stride, padding, 1, groups))
     x, xp = fptr(x.detach(), "x")
     dy, dp = fptr(dy.detach(), "dy")
-    Nb, C, H, W = (int(v) for v in x.shape)
-    Co, _, R, S = (int(v) for v in w_shape)
-    dims = (Nb, C, H, W, Co, R, S, int(st), int(pad), int(groups))
     ws, wsn = workspace(query("ssq_conv_wgrad_workspace_size", *dims), x.device)
     dw = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
     call("ssq_conv_wgrad", xp, dp, *dims, _vp(dw), ws, wsn, stream_of(x))
     return dw
 
 
-def _gemm_geo(x_shape, w_shape, stride, padding):
-    st = stride if isinstance(stride, int) else stride[0]
-    pad = padding if isinstance(padding, int) else padding[0]
-    Nb, C_, H, W = (int(v) for v in x_shape)
-    Co, _, R, S = (int(v) for v in w_shape)
-    OH, OW = (H + 2 * pad - R) // st + 1, (W + 2 * pad - S) // st + 1
-    return Nb, C_, H, W, Co, R, S, int(st), int(pad), OH, OW
-
-
 def gemm_operands(x, dy, w_shape, stride, padding, want_col=True, want_dy2=True):
     """ssq_wgrad_gemm_operands: the im2col matrix col (N*P x C*R*S) of x and/or the
     permuted gradient dy2 (Co x N*P), in one launch."""
-    shape = x.shape if x is not None else None
-    Nb, C_, H, W, Co, R, S, st, pad, OH, OW = _gemm_geo(shape, w_shape, stride, padding)
-    NP = Nb * OH * OW
-    dev_ = (x if x is not None else dy).device
-    col = torch.empty(NP, C_ * R * S, dtype=torch.float32, device=dev_) if want_col else None
-    dy2 = torch.empty(Co, NP, dtype=torch.float32, device=dev_) if want_dy2 else None
+    g = conv_geometry(x.shape, w_shape, stride, padding)
+    NP, dev_ = g.Nb * g.OH * g.OW, x.device
+    col = torch.empty(NP, g.C * g.R * g.S, dtype=torch.float32, device=dev_) if want_col else None
+    dy2 = torch.empty(g.Co, NP, dtype=torch.float32, device=dev_) if want_dy2 else None
     # (the contiguous tensors are held to the launch: a copy made here must not be freed
     # and its block reused by the next one before the kernel has read it)
     xt, xp = fptr(x.detach(), "x") if want_col else (None, None)
     dt, dp = fptr(dy.detach(), "dy") if want_dy2 else (None, None)
-    call("ssq_wgrad_gemm_operands", xp, dp, Nb, C_, H, W, Co, R, S, st, pad, _vp(col), _vp(dy2),
-         stream_of(col if want_col else dy2))
+    call("ssq_wgrad_gemm_operands", xp, dp, g.Nb, g.C, g.H, g.W, g.Co, g.R, g.S, g.st, g.pad,
+         _vp(col), _vp(dy2), stream_of(col if want_col else dy2))
     return col, dy2
 
 
@@ -2170,8 +2188,7 @@ def conv_wgrad_gemm(x, dy, w_shape, stride, padding, col=None):
     (torch.matmul -> hipBLASLt; one kernel per shape, bit-identical run to run), the
     operands from ssq_wgrad_gemm_operands (col may be the forward's, saved).  Ungrouped
     convs.  Faster than the band kernel on small output planes."""
-    c2, dy2 = gemm_operands(x if col is None else x, dy, w_shape, stride, padding,
-                            want_col=col is None, want_dy2=True)
+    c2, dy2 = gemm_operands(x, dy, w_shape, stride, padding, want_col=col is None, want_dy2=True)
     col = c2 if col is None else col
     return torch.matmul(dy2, col).view(tuple(w_shape))
 
@@ -2182,59 +2199,48 @@ def conv_fwd_gemm(x, weight, stride, padding):
     NCHW directly.  Bit-identical to the one-GEMM y2 = W @ col^T + permute form it replaced
     and 1-4 us faster per ResNet-18 layer3/4 conv (tools/fwd_gemm_layout_probe.py,
     profiles/r3_fwd_gemm_layout.json).  Returns (y, col); col serves the weight gradient."""
-    Nb, C_, H, W, Co, R, S, st, pad, OH, OW = _gemm_geo(x.shape, weight.shape, stride, padding)
+    g = conv_geometry(x.shape, weight.shape, stride, padding)
     col, _ = gemm_operands(x, None, weight.shape, stride, padding, want_col=True, want_dy2=False)
-    y = torch.matmul(weight.detach().reshape(Co, C_ * R * S),
-                     col.view(Nb, OH * OW, C_ * R * S).transpose(1, 2))
-    return y.view(Nb, Co, OH, OW), col
+    crs = g.C * g.R * g.S
+    y = torch.matmul(weight.detach().reshape(g.Co, crs),
+                     col.view(g.Nb, g.OH * g.OW, crs).transpose(1, 2))
+    return y.view(g.Nb, g.Co, g.OH, g.OW), col
 
 
 # ------------------------------------------------------------------ K18 depthwise conv
-def dwconv_supported(x, weight, stride, padding, dilation, groups):
+def dwconv_supported(x, weight, stride, padding, dilation, groups, geo=None):
     """Depthwise shapes K18 handles: fp32 NCHW on the device, groups == C == Co, square
     stride / padding, dilation 1, R*S <= 25, and forward AND input-gradient LDS stages
     (weight rows + padded planes) within the 128 KiB opt-in (ssq_dwconv_supported)."""
-    if x.dim() != 4 or weight.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
+    g = geo or conv_geometry(x.shape, weight.shape, stride, padding, dilation, groups)
+    if not g.single or g.dil != 1 or not _dev_f32(x):
         return False
-    if groups <= 1 or groups != x.shape[1] or groups != weight.shape[0] or weight.shape[1] != 1:
+    if groups <= 1 or groups != g.C or groups != g.Co or g.Cig != 1:
         return False
-    if not isinstance(stride, int) and len(set(stride)) != 1:
-        return False
-    if not isinstance(padding, int) and (isinstance(padding, str) or len(set(padding)) != 1):
-        return False
-    if (dilation if isinstance(dilation, int) else max(dilation)) != 1:
-        return False
-    pad = padding if isinstance(padding, int) else padding[0]
-    st = stride if isinstance(stride, int) else stride[0]
-    Nb, C, H, W = (int(v) for v in x.shape)
-    R, S = int(weight.shape[2]), int(weight.shape[3])
     # both the forward and the input-gradient stage must fit (the planner's own sizes)
-    return R * S <= 25 and bool(query("ssq_dwconv_supported", Nb, C, H, W, R, S, int(st), int(pad)))
+    return g.R * g.S <= 25 and bool(query("ssq_dwconv_supported", *_dw_dims(g)))
 
 
-def _dw_dims(x_shape, w_shape, stride, padding):
-    st = stride if isinstance(stride, int) else stride[0]
-    pad = padding if isinstance(padding, int) else padding[0]
-    Nb, C, H, W = (int(v) for v in x_shape)
-    return Nb, C, H, W, int(w_shape[2]), int(w_shape[3]), int(st), int(pad)
+def _dw_dims(g):
+    """The eight shape arguments of the K18 launches and their planner query."""
+    return g.Nb, g.C, g.H, g.W, g.R, g.S, g.st, g.pad
 
 
 def dwconv_fwd(x, weight, stride, padding):
-    Nb, C, H, W, R, S, st, pad = _dw_dims(x.shape, weight.shape, stride, padding)
+    g = conv_geometry(x.shape, weight.shape, stride, padding)
     x, xp = fptr(x.detach(), "x")
     w, wp = fptr(weight.detach(), "weight")
-    y = torch.empty((Nb, C, (H + 2 * pad - R) // st + 1, (W + 2 * pad - S) // st + 1),
-                    dtype=torch.float32, device=x.device)
-    call("ssq_dwconv_fwd", xp, wp, _vp(y), Nb, C, H, W, R, S, st, pad, stream_of(x))
+    y = torch.empty((g.Nb, g.C, g.OH, g.OW), dtype=torch.float32, device=x.device)
+    call("ssq_dwconv_fwd", xp, wp, _vp(y), *_dw_dims(g), stream_of(x))
     return y
 
 
 def dwconv_bwd_data(dy, weight, x_shape, stride, padding):
-    Nb, C, H, W, R, S, st, pad = _dw_dims(x_shape, weight.shape, stride, padding)
+    g = conv_geometry(x_shape, weight.shape, stride, padding)
     dy, dp = fptr(dy.detach(), "dy")
     w, wp = fptr(weight.detach(), "weight")
     dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    call("ssq_dwconv_bwd_data", dp, wp, _vp(dx), Nb, C, H, W, R, S, st, pad, stream_of(dy))
+    call("ssq_dwconv_bwd_data", dp, wp, _vp(dx), *_dw_dims(g), stream_of(dy))
     return dx
 
 
@@ -2263,7 +2269,8 @@ class DwConv2dFn(torch.autograd.Function):
 
 def _pair(v):
     """An int or (h, w) argument of F.conv2d as [h, w]; None for a string padding ('same' /
-    'valid'), which equals no list: every predicate comparing it keeps the library conv."""
+    'valid'): no rule takes such a conv (ConvGeo.single), so none reaches the
+    aten.convolution_backward calls, which take this form."""
     if isinstance(v, str):
         return None
     return [int(v), int(v)] if isinstance(v, int) else [int(t) for t in v]
@@ -2275,63 +2282,51 @@ class Conv2dFn(torch.autograd.Function):
     faster (small-plane im2col forwards, 1x1 stride-2 forwards, 1x1 stride-1 input gradients)."""
 
     @staticmethod
-    def forward(ctx, x, weight, stride, padding, dilation, groups, lib_wgrad=False):
-        # lib_wgrad: a 1x1 conv taken for its GEMM input gradient only; its weight gradient
-        # (if any) stays on MIOpen
-        ctx.cfg = (stride, padding, dilation, groups)
-        ctx.lib_wgrad = lib_wgrad
-        if not lib_wgrad and _use_fwd_gemm(x, weight, stride, padding, groups):
-            # small planes: the forward as one library GEMM over the im2col matrix, kept
-            # for the weight gradient's GEMM
-            y, col = conv_fwd_gemm(x, weight, stride, padding)
-            ctx.save_for_backward(x, weight, col)
-            return y
-        if not lib_wgrad and ctx.needs_input_grad[1] and GROUPED_GEMM_FWD and \
-                _use_wgrad_grouped_gemm(x, weight, stride, padding, groups):
-            # the im2col matrix the grouped weight gradient reads, built once, forward first
-            y, col = conv_fwd_grouped_gemm(x, weight, stride, padding, groups)
-            ctx.save_for_backward(x, weight, col)
-            return y
-        if _use_fwd_1x1(x, weight, stride, padding, dilation, groups):
+    def forward(ctx, x, weight, stride, padding, dilation, groups, route):
+        """route: conv_route's answer for this call; the backward runs what it names.  kept:
+        the forward's im2col matrix (im2col_gemm, grouped_gemm) or its subsampled input
+        (gemm_1x1, where the weight gradient is bmm_s2)."""
+        ctx.cfg, ctx.route, kept = (stride, padding, dilation, groups), route, None
+        if route.fwd == "im2col_gemm":
+            y, kept = conv_fwd_gemm(x, weight, stride, padding)
+        elif route.fwd == "grouped_gemm":
+            y, kept = conv_fwd_grouped_gemm(x, weight, stride, padding, groups)
+        elif route.fwd == "gemm_1x1":
             y, xs = conv1x1_fwd_gemm(x, weight, stride, keep_xs=True)
-            keep = (not lib_wgrad and ctx.needs_input_grad[1]
-                    and _use_wgrad_bmm_s2(x, weight, stride, padding, groups))
-            ctx.save_for_backward(x, weight, xs if keep else None)
-            return y
-        ctx.save_for_backward(x, weight, None)
-        return torch.nn.functional.conv2d(x, weight, None, stride, padding, dilation, groups)
+            kept = xs if route.dw == "bmm_s2" else None
+        else:
+            y = torch.nn.functional.conv2d(x, weight, None, stride, padding, dilation, groups)
+        ctx.save_for_backward(x, weight, kept)
+        return y
 
     @staticmethod
     def backward(ctx, g):
-        x, weight, col = ctx.saved_tensors
+        x, weight, kept = ctx.saved_tensors
         stride, padding, dilation, groups = ctx.cfg
+        route, need = ctx.route, ctx.needs_input_grad
         g = g.contiguous()
         gx = gw = None
-        if ctx.needs_input_grad[0] and _use_dgrad_1x1(x, weight, stride, padding, groups):
-            gx = conv1x1_dgrad_gemm(g, weight)
-        elif ctx.needs_input_grad[0]:
+
+        def lib(which):
             # the saved input itself, not torch.nn.grad.conv2d_input's expanded dummy: the
             # MIOpen backend makes an expanded input contiguous first (one activation-sized
             # copy per call, 8.4 us on a ResNet-18 layer1 batch)
-            gx = torch.ops.aten.convolution_backward(
+            return torch.ops.aten.convolution_backward(
                 g, x, weight, None, _pair(stride), _pair(padding), _pair(dilation), False,
-                [0, 0], groups, (True, False, False))[0]
-        if ctx.needs_input_grad[1] and ctx.lib_wgrad:
-            gw = torch.ops.aten.convolution_backward(
-                g, x, weight, None, _pair(stride), _pair(padding), _pair(dilation), False,
-                [0, 0], groups, (False, True, False))[1]
-        elif ctx.needs_input_grad[1]:
-            if _use_wgrad_gemm(x, weight, stride, padding, groups):
-                gw = conv_wgrad_gemm(x, g, weight.shape, stride, padding, col=col)
-            elif _use_wgrad_bmm(x, weight, stride, padding, groups):
-                gw = conv_wgrad_1x1_bmm(x, g, weight.shape)
-            elif col is not None and _use_wgrad_bmm_s2(x, weight, stride, padding, groups):
-                gw = conv_wgrad_1x1_bmm(col, g, weight.shape)   # col: the forward's xs
-            elif _use_wgrad_grouped_gemm(x, weight, stride, padding, groups):
-                gw = conv_wgrad_grouped_gemm(x, g, weight.shape, stride, padding, groups,
-                                             col=col)
-            else:
-                gw = conv_wgrad(x, g, weight.shape, stride, padding, groups)
+                [0, 0], groups, tuple(i == which for i in range(3)))[which]
+        if need[0]:
+            gx = conv1x1_dgrad_gemm(g, weight) if route.dx == "gemm_1x1" else lib(0)
+        if need[1] and route.dw == "im2col_gemm":
+            gw = conv_wgrad_gemm(x, g, weight.shape, stride, padding, col=kept)
+        elif need[1] and route.dw == "bmm_1x1":
+            gw = conv_wgrad_1x1_bmm(x, g, weight.shape)
+        elif need[1] and route.dw == "bmm_s2":
+            gw = conv_wgrad_1x1_bmm(kept, g, weight.shape)
+        elif need[1] and route.dw == "grouped_gemm":
+            gw = conv_wgrad_grouped_gemm(x, g, weight.shape, stride, padding, groups, col=kept)
+        elif need[1]:
+            gw = conv_wgrad(x, g, weight.shape, stride, padding, groups) if route.dw == "k17" \
+                else lib(1)
         return gx, gw, None, None, None, None, None
 
 
@@ -2357,41 +2352,26 @@ WGRAD_POLICY = "auto"
 # profiles/r2_wgrad_gemm.log: the GEMM runs at 94-115 TF there, the band kernel at 57 TF
 # on 14x14 planes).  'never' keeps K17 / MIOpen (A/B).
 WGRAD_GEMM = "auto"
-# ... and the forward of those convs too (MIOpen's deterministic forward takes 99 / 173 us
-# on layer3.0 / layer4.0's stride-2 convs where the GEMM takes 42 / 38,
-# profiles/r2_wgrad_gemm.log); the im2col matrix is then shared with the weight gradient
-WGRAD_GEMM_FWD = True
 
 
-def _out_plane(x, weight, stride, padding):
-    st = stride if isinstance(stride, int) else stride[0]
-    pad = padding if isinstance(padding, int) else padding[0]
-    oh = (x.shape[2] + 2 * pad - weight.shape[2]) // st + 1
-    ow = (x.shape[3] + 2 * pad - weight.shape[3]) // st + 1
-    return oh, ow
-
-
-def _use_wgrad_gemm(x, weight, stride, padding, groups=1):
+# The rules conv_route consults, each at most once per call.  Called on their own they parse
+# the arguments themselves; conv_route hands them its ConvGeo (geo).
+def _use_wgrad_gemm(x, weight, stride, padding, groups=1, geo=None):
     # WGRAD_POLICY 'never' is the all-MIOpen A/B mode: no GEMM convs either
-    if WGRAD_GEMM != "auto" or WGRAD_POLICY == "never" or groups != 1:
+    g = geo or conv_geometry(x.shape, weight.shape, stride, padding, 1, groups)
+    if WGRAD_GEMM != "auto" or WGRAD_POLICY == "never" or groups != 1 or not g.single:
         return False
-    if isinstance(stride, (tuple, list)) and len(set(stride)) != 1:
+    NP, crs = g.Nb * g.OH * g.OW, g.Cig * g.R * g.S
+    if NP * crs >= (1 << 31) or g.Co * NP >= (1 << 31) or g.OH * g.OW > 196:
         return False
-    if isinstance(padding, str) or (isinstance(padding, (tuple, list)) and len(set(padding)) != 1):
-        return False
-    oh, ow = _out_plane(x, weight, stride, padding)
-    Co, C_, R, S = (int(v) for v in weight.shape)
-    NP = x.shape[0] * oh * ow
-    if NP * C_ * R * S >= (1 << 31) or Co * NP >= (1 << 31) or oh * ow > 196:
-        return False
-    if R * S == 1:
+    if g.R * g.S == 1:
         # 1x1 (the ResNet downsamples): layer3.0 / layer4.0 33 / 23 us vs K17's 1x1 kernel
         # 44 / 44; layer2.0's (28x28 plane) stays on K17 (84 vs 42; tools/ds_gemm_probe.py).
         # Under cudnn.deterministic also every 1x1 on a 7x7 plane: MIOpen's deterministic
         # weight gradient takes 74-137 us there (MobileNetV2 960 -> 160: GEMM 25, K17 45;
         # tools/conv1x1_probe.py, profiles/r6_conv1x1_probe.jsonl)
-        return Co >= 256 or (oh * ow <= 49 and torch.backends.cudnn.deterministic)
-    return Co >= 128 and C_ * R * S >= 1152
+        return g.Co >= 256 or (g.OH * g.OW <= 49 and torch.backends.cudnn.deterministic)
+    return g.Co >= 128 and crs >= 1152
 
 
 # 1x1 stride-1 convs on large planes (OH*OW >= 400: ResNet-50's bottleneck 1x1s and layer1
@@ -2402,19 +2382,14 @@ def _use_wgrad_gemm(x, weight, stride, padding, groups=1):
 # (profiles/r6_wgrad1x1_probe.jsonl), batch 32: ResNet-50 layer1.0 conv1 / conv3 / downsample
 # 74.6 / 120.8 / 120.9 -> 20.9 / 35.3 / 35.0 us, RegNetX-3200M s3.b1 'a' 133.7 -> 54.3 us;
 # bit-identical run to run, within 1e-6 of float64 (K17: 3e-7).  Planes <= 196 pixels keep
-# the im2col GEMM (_use_wgrad_gemm) or K17.  A/B knob: SSQ_WGRAD_1X1_BMM=0.
-WGRAD_1X1_BMM = os.environ.get("SSQ_WGRAD_1X1_BMM", "1") != "0"
-
-
-def _use_wgrad_bmm(x, weight, stride, padding, groups=1):
-    if not WGRAD_1X1_BMM or WGRAD_POLICY != "auto" or groups != 1 \
-            or tuple(weight.shape[2:]) != (1, 1):
-        return False
-    if _pair(stride) != [1, 1] or _pair(padding) != [0, 0]:
+# the im2col GEMM (_use_wgrad_gemm) or K17.
+def _use_wgrad_bmm(x, weight, stride, padding, groups=1, geo=None):
+    g = geo or conv_geometry(x.shape, weight.shape, stride, padding, 1, groups)
+    if WGRAD_POLICY != "auto" or groups != 1 or (g.R, g.S, g.st, g.pad) != (1, 1, 1, 0):
         return False
     # 14x14 planes too under cudnn.deterministic (MobileNetV2's 14x14 1x1s: 16-27 us vs K17's
     # 39-44; tools/conv1x1_probe.py) where the im2col GEMM does not take them
-    p = x.shape[2] * x.shape[3] if x.dim() == 4 else 0
+    p = g.H * g.W
     return p >= 400 or (p >= 100 and torch.backends.cudnn.deterministic)
 
 
@@ -2428,20 +2403,13 @@ def _use_wgrad_bmm(x, weight, stride, padding, groups=1):
 #   14x14 / 28x28 planes with C >= 128 and Co >= C, and Co >= 2 C on 14x14 (ResNet-50
 #       256 -> 1024: 53 -> 35; RegNetX 192 -> 432: 103 -> 51; 432 -> 432 on 14x14 is not);
 #   56x56 planes never (the GEMM is 1.3-2.5x slower there).
-# A/B knob: SSQ_DGRAD_1X1_GEMM=0.
-DGRAD_1X1_GEMM = os.environ.get("SSQ_DGRAD_1X1_GEMM", "1") != "0"
-
-
-def _use_dgrad_1x1(x, weight, stride, padding, groups=1):
-    if not DGRAD_1X1_GEMM or WGRAD_POLICY == "never" or groups != 1 \
-            or tuple(weight.shape[2:]) != (1, 1) or not torch.backends.cudnn.deterministic:
+def _use_dgrad_1x1(x, weight, stride, padding, groups=1, geo=None):
+    g = geo or conv_geometry(x.shape, weight.shape, stride, padding, 1, groups)
+    if WGRAD_POLICY == "never" or groups != 1 or not torch.backends.cudnn.deterministic:
         return False
-    if _pair(stride) != [1, 1] or _pair(padding) != [0, 0]:
+    if (g.R, g.S, g.st, g.pad) != (1, 1, 1, 0) or not _dev_f32(x):
         return False
-    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
-        return False
-    co, c = int(weight.shape[0]), int(weight.shape[1])
-    p = x.shape[2] * x.shape[3]
+    co, c, p = g.Co, g.Cig, g.H * g.W
     if p >= 12544:
         return True
     if p <= 49:
@@ -2477,26 +2445,16 @@ def conv_wgrad_1x1_bmm(x, dy, w_shape):
 # (profiles/r6_wgrad_grouped_probe.jsonl), batch 32: s3.b1 268.6 -> 115.5 us, s3.b2 205.4 ->
 # 91.0, s4.b1 243.9 -> 70.3, s4.b2 121.7 -> 57.6; on the larger planes of stages 1-2 (g = 2,
 # 4) K17 stays faster and keeps them.  Bit-identical run to run, within 1e-6 of float64.
-# A/B knob: SSQ_WGRAD_GROUPED_GEMM=0.
-WGRAD_GROUPED_GEMM = os.environ.get("SSQ_WGRAD_GROUPED_GEMM", "1") != "0"
 # ... and the forward of those convs as one GEMM over the groups on the same im2col matrix,
-# built once, in the forward (conv_fwd_grouped_gemm).  A/B knob: SSQ_GROUPED_GEMM_FWD=0.
-GROUPED_GEMM_FWD = os.environ.get("SSQ_GROUPED_GEMM_FWD", "1") != "0"
-
-
-def _use_wgrad_grouped_gemm(x, weight, stride, padding, groups=1):
-    if not WGRAD_GROUPED_GEMM or WGRAD_POLICY != "auto" or groups <= 1 or weight.shape[1] <= 1:
+# built once, in the forward (conv_fwd_grouped_gemm).
+def _use_wgrad_grouped_gemm(x, weight, stride, padding, groups=1, geo=None):
+    g = geo or conv_geometry(x.shape, weight.shape, stride, padding, 1, groups)
+    if WGRAD_POLICY != "auto" or groups <= 1 or g.Cig <= 1:
         return False
-    if isinstance(stride, (tuple, list)) and len(set(stride)) != 1:
+    NP = g.Nb * g.OH * g.OW
+    if NP * g.Cig * groups * g.R * g.S >= (1 << 31) or g.Co * NP >= (1 << 31):
         return False
-    if isinstance(padding, str) or (isinstance(padding, (tuple, list)) and len(set(padding)) != 1):
-        return False
-    oh, ow = _out_plane(x, weight, stride, padding)
-    Co, Cig, R, S = (int(v) for v in weight.shape)
-    NP = x.shape[0] * oh * ow
-    if NP * Cig * groups * R * S >= (1 << 31) or Co * NP >= (1 << 31):
-        return False
-    return oh * ow <= 196
+    return g.OH * g.OW <= 196
 
 
 def conv_wgrad_grouped_gemm(x, dy, w_shape, stride, padding, groups, col=None):
@@ -2521,23 +2479,26 @@ def conv_fwd_grouped_gemm(x, weight, stride, padding, groups):
     then permuted to NCHW.  RegNetX-3200M s3.b1's 'b' conv (g = 9, stride 2): MIOpen's
     deterministic forward 102.5 us; here the im2col build moves from the backward to the
     forward (tools/recon_configs_trace.py).  Returns (y, col)."""
-    Nb, C_, H, W, Co, R, S, st, pad, OH, OW = _gemm_geo(x.shape, weight.shape, stride, padding)
-    C_ = int(weight.shape[1]) * groups
-    k = int(weight.shape[1]) * R * S
-    col, _ = gemm_operands(x, None, (Co, C_, R, S), stride, padding, want_col=True,
-                           want_dy2=False)
-    y = torch.matmul(weight.detach().reshape(groups, Co // groups, k),
+    g = conv_geometry(x.shape, weight.shape, stride, padding, 1, groups)
+    k = g.Cig * g.R * g.S
+    col, _ = gemm_operands(x, None, (g.Co, g.Cig * groups, g.R, g.S), stride, padding,
+                           want_col=True, want_dy2=False)
+    y = torch.matmul(weight.detach().reshape(groups, g.Co // groups, k),
                      col.view(-1, groups, k).permute(1, 2, 0))
-    y = y.view(groups, Co // groups, Nb, OH * OW).permute(2, 0, 1, 3).contiguous()
-    return y.view(Nb, Co, OH, OW), col
+    y = y.view(groups, g.Co // groups, g.Nb, g.OH * g.OW).permute(2, 0, 1, 3).contiguous()
+    return y.view(g.Nb, g.Co, g.OH, g.OW), col
 
 
 def _use_fwd_gemm(x, weight, stride, padding, groups=1):
-    """The forward as the im2col GEMM on the weight-gradient GEMM's shapes.  Extending it to
-    layer2.0's stride-2 conv (MIOpen's deterministic forward 99 us standalone, the GEMM 40
-    + the 58 MB im2col pass) measured no gain in the loop (1639 -> 1617 it/s,
-    profiles/r2_wgrad_gemm.log), so it is not."""
-    return (WGRAD_GEMM_FWD and weight.shape[2] * weight.shape[3] > 1
+    """The forward as the im2col GEMM on the weight-gradient GEMM's 3x3 (or larger) shapes:
+    MIOpen's deterministic forward takes 99 / 173 us on layer3.0 / layer4.0's stride-2 convs
+    where the GEMM takes 42 / 38 (profiles/r2_wgrad_gemm.log), and the im2col matrix is then
+    shared with the weight gradient.  Extending it to layer2.0's stride-2 conv (MIOpen's
+    deterministic forward 99 us standalone, the GEMM 40 + the 58 MB im2col pass) measured no
+    gain in the loop (1639 -> 1617 it/s, profiles/r2_wgrad_gemm.log), so it is not.
+    conv_route, which has _use_wgrad_gemm's answer already, applies the kernel-size test to
+    it instead of calling this."""
+    return (weight.shape[2] * weight.shape[3] > 1
             and _use_wgrad_gemm(x, weight, stride, padding, groups))
 
 
@@ -2553,25 +2514,21 @@ def _use_fwd_gemm(x, weight, stride, padding, groups=1):
 FWD_1X1_GEMM = os.environ.get("SSQ_FWD_1X1_GEMM", "1") != "0"
 
 
-def _use_fwd_1x1(x, weight, stride, padding, dilation, groups):
+def _use_fwd_1x1(x, weight, stride, padding, dilation, groups, geo=None):
     # WGRAD_POLICY 'never' is the all-MIOpen A/B mode: no GEMM convs there either
-    if not FWD_1X1_GEMM or WGRAD_POLICY == "never" or groups != 1 or weight.shape[2] != 1 \
-            or weight.shape[3] != 1:
+    g = geo or conv_geometry(x.shape, weight.shape, stride, padding, dilation, groups)
+    if not FWD_1X1_GEMM or WGRAD_POLICY == "never" or groups != 1 or not _dev_f32(x):
         return False
-    if x.dim() != 4 or not x.is_cuda or x.dtype != torch.float32:
+    if (g.R, g.S, g.pad, g.dil) != (1, 1, 0, 1) or g.st < 2:
         return False
-    st, pad, dil = (_pair(v) for v in (stride, padding, dilation))
-    if st[0] != st[1] or st[0] < 2 or pad != [0, 0] or dil != [1, 1]:
-        return False
-    oh, ow = _out_plane(x, weight, st[0], 0)
-    return not (100 < oh * ow < 400 and x.shape[0] < 128)
+    return not (100 < g.OH * g.OW < 400 and g.Nb < 128)
 
 
 def conv1x1_fwd_gemm(x, weight, stride, keep_xs=False):
     """F.conv2d of a 1x1 / pad 0 / stride s conv as one strided-batched GEMM on the
     subsampled input (see FWD_1X1_GEMM); keep_xs: also return that input, contiguous (the
     weight gradient's operand, conv_wgrad_1x1_bmm)."""
-    st = stride if isinstance(stride, int) else stride[0]
+    st = conv_geometry(x.shape, weight.shape, stride, 0).st
     xs = x[:, :, ::st, ::st].contiguous()
     n, c, oh, ow = xs.shape
     co = int(weight.shape[0])
@@ -2586,76 +2543,87 @@ def conv1x1_fwd_gemm(x, weight, stride, keep_xs=False):
 # tools/ds_wgrad_probe.py (profiles/r6_ds_wgrad_probe.jsonl), batch 32: ResNet-18 layer2.0
 # 41.1 -> 31.6 us, ResNet-50 layer2.0 138.9 -> 65.3; RegNetX s2.b1 (96 -> 192) is slower as
 # the GEMM (79.3 vs 43.6) and keeps K17; on 14x14 and 7x7 planes the im2col GEMM stays.
-# A/B knob: SSQ_WGRAD_S2_BMM=0.
-WGRAD_S2_BMM = os.environ.get("SSQ_WGRAD_S2_BMM", "1") != "0"
-
-
-def _use_wgrad_bmm_s2(x, weight, stride, padding, groups=1):
-    if not WGRAD_S2_BMM or WGRAD_POLICY != "auto" or groups != 1 \
-            or tuple(weight.shape[2:]) != (1, 1) or _pair(padding) != [0, 0]:
+def _use_wgrad_bmm_s2(x, weight, stride, padding, groups=1, geo=None):
+    g = geo or conv_geometry(x.shape, weight.shape, stride, padding, 1, groups)
+    if WGRAD_POLICY != "auto" or groups != 1 or (g.R, g.S, g.pad) != (1, 1, 0) or g.st < 2:
         return False
-    st = _pair(stride)
-    if st[0] != st[1] or st[0] < 2:
-        return False
-    oh, ow = _out_plane(x, weight, st[0], 0)
-    co, c = int(weight.shape[0]), int(weight.shape[1])
-    return oh * ow >= 400 and c % 64 == 0 and co % 64 == 0
+    return g.OH * g.OW >= 400 and g.Cig % 64 == 0 and g.Co % 64 == 0
 
 
-def _use_k17(x, weight, stride, padding, groups=1):
-    if WGRAD_POLICY == "always":
-        return True
+# ------------------------------------------------------------------ the conv router
+# What one conv2d call runs: the forward, the input gradient and the weight gradient kernel
+# (None: not needed), decided once by conv_route and carried to the backward.
+#   fwd  lib (MIOpen) | k18 | im2col_gemm | grouped_gemm | gemm_1x1 | epi_gemm
+#   dx   lib | k18 | gemm_1x1 | None
+#   dw   lib | k17 | im2col_gemm | bmm_1x1 | bmm_s2 | grouped_gemm | None
+ConvRoute = collections.namedtuple("ConvRoute", "geo fwd dx dw")
+
+
+def conv_route(x, weight, stride, padding, dilation, groups, need_dx, need_dw):
+    """The ConvRoute of conv2d(x, weight, stride, padding, dilation, groups) when the input /
+    the weight needs a gradient: a function of shapes, device, dtype, contiguity, WGRAD_POLICY,
+    WGRAD_GEMM, FWD_1X1_GEMM and cudnn.deterministic.  Launches and allocates nothing.  The
+    rules' order of precedence is the order of this function."""
+    g = conv_geometry(x.shape, weight.shape, stride, padding, dilation, groups)
+    a = (x, weight, stride, padding)
+    ours = need_dw and g.dil == 1       # K17 and the GEMM weight gradients: dilation 1 only
+    gemm = ours and _use_wgrad_gemm(*a, groups, g)
+    if getattr(x, "_ssq_epi", None) is not None and gemm and g.R * g.S > 1:
+        # a LazyEpi input (a BasicBlock's conv1 epilogue) on _use_fwd_gemm's shapes: folded
+        # into the im2col build (EpiConvGemmFn); any other route materialises it
+        return ConvRoute(g, "epi_gemm", "lib" if need_dx else None, "im2col_gemm")
+    # depthwise convs on K18 + K17 (MIOpen runs them on naive direct kernels)
+    if groups > 1 and dwconv_supported(*a, dilation, groups, g) and x.is_contiguous():
+        return ConvRoute(g, "k18", "k18" if need_dx else None, "k17" if need_dw else None)
+    if ours:
+        grouped = not gemm and _use_wgrad_grouped_gemm(*a, groups, g)
+        if gemm or grouped or (conv_wgrad_supported(*a, dilation, groups, g) and _k17_rule(g)):
+            # small planes: the forward as one library GEMM over the im2col matrix, kept for
+            # the weight gradient's GEMM (_use_fwd_gemm; grouped: conv_fwd_grouped_gemm)
+            fwd = "im2col_gemm" if gemm and g.R * g.S > 1 else "grouped_gemm" if grouped else \
+                "gemm_1x1" if _use_fwd_1x1(*a, dilation, groups, g) else "lib"
+            dw = "im2col_gemm" if gemm else "bmm_1x1" if _use_wgrad_bmm(*a, groups, g) else \
+                "bmm_s2" if fwd == "gemm_1x1" and _use_wgrad_bmm_s2(*a, groups, g) else \
+                "grouped_gemm" if grouped else "k17"
+            dx = None if not need_dx else "gemm_1x1" if _use_dgrad_1x1(*a, groups, g) else "lib"
+            return ConvRoute(g, fwd, dx, dw)
+    if need_dx and _use_dgrad_1x1(*a, groups, g):
+        # a 1x1 conv K17 does not take (an activation-phase conv, or a small plane): its
+        # input gradient as a GEMM, its weight gradient (if any) on MIOpen as before
+        return ConvRoute(g, "lib", "gemm_1x1", "lib" if need_dw else None)
+    fwd = "gemm_1x1" if not (need_dx or need_dw) and _use_fwd_1x1(*a, dilation, groups, g) \
+        else "lib"
+    return ConvRoute(g, fwd, "lib" if need_dx else None, "lib" if need_dw else None)
+
+
+def _k17_rule(g):
+    """WGRAD_POLICY (above) for a conv K17 supports and no GEMM form took."""
     if WGRAD_POLICY != "auto":
-        return False
-    if groups > 1:
+        return WGRAD_POLICY == "always"
+    if g.groups > 1 or wgrad_kind(g[:4], g[4:8], g.st, g.pad, g.groups, g) == 3:
         return True
-    if _use_wgrad_gemm(x, weight, stride, padding, groups):
-        return True
-    if wgrad_kind(x.shape, weight.shape, stride, padding, groups) == 3:
-        return True
-    if torch.backends.cudnn.deterministic:
-        st = stride if isinstance(stride, int) else stride[0]
-        pad = padding if isinstance(padding, int) else padding[0]
-        oh = (x.shape[2] + 2 * pad - weight.shape[2]) // st + 1
-        ow = (x.shape[3] + 2 * pad - weight.shape[3]) // st + 1
-        return st > 1 or oh * ow >= 100
-    return False
-
-
-# Depthwise convs on K18 + K17 ('auto'; MIOpen runs them on naive direct kernels) or on
-# MIOpen ('never').
-DWCONV_POLICY = "auto"
+    return torch.backends.cudnn.deterministic and (g.st > 1 or g.OH * g.OW >= 100)
 
 
 def conv2d(x, weight, stride=1, padding=0, dilation=1, groups=1):
-    """F.conv2d without bias: depthwise convs on K18/K17 (DWCONV_POLICY), otherwise MIOpen
-    with the K17 weight gradient when the weight needs one (WGRAD_POLICY); 1x1 stride-2
-    forwards as one batched GEMM (FWD_1X1_GEMM); a LazyEpi input (a BasicBlock's conv1
-    epilogue) folded into the im2col GEMM of conv_fwd_gemm's shapes, else materialised."""
-    if getattr(x, "_ssq_epi", None) is not None:
-        if (weight.requires_grad and torch.is_grad_enabled() and groups == 1 and
-                (dilation if isinstance(dilation, int) else max(dilation)) == 1 and
-                _use_fwd_gemm(x, weight, stride, padding, groups)):
-            return epi_conv_gemm(x, weight, stride, padding)
+    """F.conv2d without bias on the kernels conv_route names: depthwise convs on K18/K17,
+    otherwise MIOpen with the K17 or a GEMM weight gradient when the weight needs one
+    (WGRAD_POLICY); 1x1 stride-2 forwards as one batched GEMM (FWD_1X1_GEMM); a LazyEpi input
+    folded into the im2col GEMM of conv_fwd_gemm's shapes, else materialised."""
+    grad, lazy = torch.is_grad_enabled(), getattr(x, "_ssq_epi", None) is not None
+    # (a LazyEpi placeholder exists only inside the graph of a block being trained)
+    route = conv_route(x, weight, stride, padding, dilation, groups,
+                       grad and (lazy or x.requires_grad), grad and weight.requires_grad)
+    if route.fwd == "epi_gemm":
+        return epi_conv_gemm(x, weight, stride, padding)
+    if lazy:
         x = materialize_epi(x)
-    if DWCONV_POLICY == "auto" and dwconv_supported(x, weight, stride, padding, dilation, groups) \
-            and x.is_contiguous():
-        if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
+    if route.fwd == "k18":
+        if route.dx or route.dw:
             return DwConv2dFn.apply(x, weight, stride, padding)
         return dwconv_fwd(x, weight, stride, padding)
-    if weight.requires_grad and torch.is_grad_enabled() and \
-            (dilation if isinstance(dilation, int) else max(dilation)) == 1 and \
-            (_use_wgrad_gemm(x, weight, stride, padding, groups) or
-             _use_wgrad_grouped_gemm(x, weight, stride, padding, groups) or
-             (conv_wgrad_supported(x, weight, stride, padding, dilation, groups) and
-              _use_k17(x, weight, stride, padding, groups))):
-        return Conv2dFn.apply(x, weight, stride, padding, dilation, groups)
-    if torch.is_grad_enabled() and x.requires_grad and \
-            _use_dgrad_1x1(x, weight, stride, padding, groups):
-        # a 1x1 conv K17 does not take (an activation-phase conv, or a small plane): its
-        # input gradient as a GEMM, its weight gradient (if any) on MIOpen as before
-        return Conv2dFn.apply(x, weight, stride, padding, dilation, groups, True)
-    if _use_fwd_1x1(x, weight, stride, padding, dilation, groups) and \
-            not (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)):
+    if route.dw not in (None, "lib") or route.dx == "gemm_1x1":
+        return Conv2dFn.apply(x, weight, stride, padding, dilation, groups, route)
+    if route.fwd == "gemm_1x1":
         return conv1x1_fwd_gemm(x, weight, stride)
     return torch.nn.functional.conv2d(x, weight, None, stride, padding, dilation, groups)

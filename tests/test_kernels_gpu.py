@@ -1110,7 +1110,7 @@ def test_conv1x1_stride2_forward_gemm(K, cfg):
         torch.backends.cudnn.deterministic = old_det
     np.testing.assert_array_equal(host(xg.grad).view(np.int32), host(xm.grad).view(np.int32))
     if use and K._use_wgrad_bmm_s2(xd, wd, 2, 0):
-        # the weight gradient then runs on the forward's subsampled input (WGRAD_S2_BMM,
+        # the weight gradient then runs on the forward's subsampled input (route dw bmm_s2,
         # test_conv_wgrad_s2_bmm_matches_fp64): another summation order, same bound
         rw = torch.nn.grad.conv2d_weight(x.double(), w.shape, dy.double().cpu(), 2, 0)
         mw = torch.nn.grad.conv2d_weight(x.double().abs(), w.shape, dy.double().abs().cpu(), 2, 0)
@@ -1127,7 +1127,7 @@ def test_conv1x1_stride2_forward_gemm(K, cfg):
     (4, 16, 19, 8)])
 def test_conv_wgrad_1x1_bmm_matches_fp64(K, cfg):
     """The 1x1 stride-1 weight gradient on planes >= 400 pixels as one strided-batched GEMM
-    and an in-order batch sum (K.conv_wgrad_1x1_bmm, WGRAD_1X1_BMM): vs the fp64 CPU gradient
+    and an in-order batch sum (K.conv_wgrad_1x1_bmm, route dw bmm_1x1): vs the fp64 CPU gradient
     within the fp32 accumulation bound, bit-identical run to run, and what K.conv2d's
     training path (Conv2dFn under cudnn.deterministic) hands the weight -- below 400 pixels,
     or with the policy forced, K17 / the im2col GEMM as before."""
@@ -1166,7 +1166,7 @@ def test_conv_wgrad_1x1_bmm_matches_fp64(K, cfg):
     (4, 128, 28, 256, False)])
 def test_conv_wgrad_s2_bmm_matches_fp64(K, cfg):
     """1x1 stride-2 weight gradients as one batched GEMM + batch sum over the subsampled
-    input the forward GEMM made contiguous (WGRAD_S2_BMM): K.conv2d's training path under
+    input the forward GEMM made contiguous (route dw bmm_s2): K.conv2d's training path under
     cudnn.deterministic hands the weight exactly K.conv_wgrad_1x1_bmm(xs)'s bits where the
     rule takes the shape, and every route is within the fp32 bound of the fp64 gradient."""
     Nb, C, H, Co, bmm = cfg
@@ -1221,7 +1221,7 @@ def test_gemm_operands_noncontiguous_inputs(K):
 @pytest.mark.parametrize("weight_grad", [True, False], ids=["weight_phase", "act_phase"])
 def test_conv1x1_dgrad_gemm_matches_fp64(K, cfg, weight_grad):
     """The input gradient of 1x1 stride-1 convs as one strided-batched GEMM
-    (K.conv1x1_dgrad_gemm, DGRAD_1X1_GEMM, on the shapes its rule names): vs the fp64 CPU
+    (K.conv1x1_dgrad_gemm, route dx gemm_1x1, on the shapes its rule names): vs the fp64 CPU
     gradient within the fp32 accumulation bound, bit-identical run to run, and what K.conv2d's
     autograd hands the input under cudnn.deterministic, with the weight trained (Conv2dFn) and
     fixed (an activation-phase conv): the GEMM's bits where the rule takes the shape, else
@@ -1265,7 +1265,7 @@ def test_conv1x1_dgrad_gemm_matches_fp64(K, cfg, weight_grad):
 def test_conv_wgrad_grouped_gemm_matches_fp64(K, cfg):
     """Grouped-conv weight gradients on output planes <= 196 pixels as the im2col operands of
     every channel and one strided-batched GEMM over the groups (K.conv_wgrad_grouped_gemm,
-    WGRAD_GROUPED_GEMM): vs the fp64 CPU gradient within the fp32 accumulation bound,
+    route dw grouped_gemm): vs the fp64 CPU gradient within the fp32 accumulation bound,
     bit-identical run to run, and what K.conv2d's training path hands the weight (larger
     planes: K17 as before); the forward as one GEMM over the groups on the same im2col
     matrix (K.conv_fwd_grouped_gemm) likewise, and the weight gradient from its saved
@@ -1287,7 +1287,7 @@ def test_conv_wgrad_grouped_gemm_matches_fp64(K, cfg):
     np.testing.assert_array_equal(host(dw1).view(np.int32), host(dw2).view(np.int32))
     err = (dw1.double().cpu() - ref).abs()
     assert bool((err <= 1e-5 * mag + 1e-30).all()), float((err / mag.clamp_min(1e-30)).max())
-    # the forward as one GEMM over the groups on the same im2col matrix (GROUPED_GEMM_FWD)
+    # the forward as one GEMM over the groups on the same im2col matrix (route fwd grouped_gemm)
     yref = torch.nn.functional.conv2d(x.double(), w.double(), None, st, 1, 1, G)
     ymag = torch.nn.functional.conv2d(x.double().abs(), w.double().abs(), None, st, 1, 1, G)
     if small:
@@ -1354,7 +1354,7 @@ def test_conv_wgrad_gemm_matches_fp64(K, cfg):
     wd = w.cuda().requires_grad_(True)
     assert K._use_wgrad_gemm(xd, wd, st, pad) and K._use_fwd_gemm(xd, wd, st, pad) == (k > 1)
     out = K.conv2d(xd, wd, st, pad)
-    # the forward runs as the GEMM too (K.WGRAD_GEMM_FWD): vs the fp64 conv
+    # the forward runs as the GEMM too (route fwd im2col_gemm): vs the fp64 conv
     yref = torch.nn.functional.conv2d(x.double(), w.double(), None, st, pad)
     ymag = torch.nn.functional.conv2d(x.double().abs(), w.double().abs(), None, st, pad)
     assert out.shape == yref.shape and out.is_contiguous()
