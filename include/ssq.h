@@ -800,6 +800,30 @@ int ssq_qconv_i8_codes_res_fwd(const int8_t* codes, const void* prepared, const 
                                const int8_t* res_codes, float res_delta, float res_zero_point,
                                int res_qmin, int res_qmax, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- carried stem (K27, K28)
+ * ssq_epilogue_codes_fwd (K27): the K13 epilogue of an fp32 conv output y (NCHW [Nb, C, H, W])
+ * leaving as K21's stored codes: the operation list above from `pre = y + bias[c]` on, the same
+ * device function the integer kernels' code epilogue runs.  out_codes is NHWC int8
+ * [Nb*H*W][qinfer_cpad(C)], padded channels 0, every byte written: what ssq_act_encode derives
+ * from K13's fp32 output whenever it counts nothing off-grid; a NaN q is stored as out_qmin
+ * and ADDED to *bad.  The output quantizer is checked as by ssq_qconv_i8_codes_fwd.
+ *
+ * ssq_maxpool_i8_fwd (K28): max-pool on stored codes, codes NHWC [Nb, H, W, qinfer_cpad(C)] ->
+ * out [Nb, OH, OW, qinfer_cpad(C)], ssq_maxpool2d_fwd's geometry (square window K <= 7,
+ * 2 * pad <= K, stride >= 1, floor mode, no dilation).  The per-channel signed byte maximum
+ * over the in-bounds taps; since the stored form is the code shifted by one constant and
+ * (q - z) * delta is non-decreasing in q, out is what ssq_act_encode derives from the fp32
+ * max-pool of the decoded tensor.  Padded channels stay 0.
+ *
+ * Every refusal (null pointer, bad geometry or quantizer, an empty output, a tensor of 2^31
+ * bytes or more) is SSQ_E_ARG before any launch.  No allocation, no sync, capturable.         */
+int ssq_epilogue_codes_fwd(const float* y, const float* bias, const float* gamma, const float* phi,
+                           int64_t Nb, int64_t C, int64_t H, int64_t W, int act, float out_delta,
+                           float out_zero_point, int out_qmin, int out_qmax, int8_t* out_codes,
+                           uint32_t* bad, ssq_stream_t stream);
+int ssq_maxpool_i8_fwd(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W, int64_t K,
+                       int64_t stride, int64_t pad, int8_t* out, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- bandwidth probe
  * float4 device copy, used by bench.py to report the measured stream bandwidth.      */
 int ssq_stream_copy(const float* src, float* dst, int64_t n, ssq_stream_t stream);

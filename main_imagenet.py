@@ -154,10 +154,12 @@ def main(argv=None):
                                                                    validate_model(loader, qnn)))
     if args.int_infer and args.act_quant:
         from shiftedscalequantization_amd.quant import (block_carry_report, carry_report,
-                                                         enable_integer_inference, integer_report)
+                                                         enable_integer_inference, integer_report,
+                                                         stem_carry_report)
         plan = enable_integer_inference(qnn, cali[:8], grouped=args.int_infer_grouped,
                                         carry=args.int_infer_carry,
-                                        carry_blocks=args.int_infer_carry_blocks)
+                                        carry_blocks=args.int_infer_carry_blocks,
+                                        carry_stem=args.int_infer_carry_stem)
         n_int = sum(v == 'int8' for v in plan.values())
         print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
         if args.int_infer_carry:
@@ -168,6 +170,10 @@ def main(argv=None):
             edges = block_carry_report(qnn)['edges']
             print(f'integer inference: int8 codes carried across {len(edges)} block edges: '
                   + ', '.join(f'{a} -> {b}' for a, b in edges))
+        if args.int_infer_carry_stem:
+            edges = stem_carry_report(qnn)['edges']
+            print(f'integer inference: int8 codes carried from {len(edges)} stem edges: '
+                  + ', '.join(' -> '.join([a] + pools + [b]) for a, pools, b in edges))
         for name, why in plan.items():
             print(f'  {name}: {why}')
         if loader is not None:

@@ -146,6 +146,9 @@ SIGNATURES = {
     "ssq_qconv_i8_codes_res_fwd": (_i, [_p, _p, _p] + [_i64] * 10 + [_f, _i, _i, _p, _p, _p, _i, _f,
                                                                   _f, _i, _i, _p, _p, _p, _p, _f,
                                                                   _f, _i, _i, _p]),
+    "ssq_epilogue_codes_fwd": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _f, _f, _i, _i, _p,
+                                    _p, _p]),
+    "ssq_maxpool_i8_fwd": (_i, [_p] + [_i64] * 7 + [_p, _p]),
     "ssq_stream_copy": (_i, [_p, _p, _i64, _p]),
     "ssq_stream_probe": (_i, [_p, _p, _i64, _i, _p]),
 }

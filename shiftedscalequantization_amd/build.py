@@ -19,7 +19,8 @@ LIB = os.path.join(HERE, "libssq.so")
 ARCH = os.environ.get("SSQ_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["fq.hip", "adashift.hip", "adashift_prep.hip", "scale_init.hip", "recon.hip", "pack.hip", "conv_wgrad.hip",
-           "dwconv.hip", "fc_recon.hip", "fisher.hip", "qinfer.hip", "qinfer_grouped.hip"]
+           "dwconv.hip", "fc_recon.hip", "fisher.hip", "qinfer.hip", "qinfer_grouped.hip",
+           "qinfer_stem.hip"]
 HEADERS = ["ssq_common.h", "adashift_common.h", "fin_tasks.h", "prep_ride.h", "qinfer_epi.h", os.path.join("..", "..", "include", "ssq.h")]
 CFLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-ffp-contract=off",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]

@@ -56,11 +56,12 @@ __device__ __forceinline__ float qres_decode(int code, const QRes& r) {
   return __fmul_rn(__fsub_rn(q, r.z), r.d);
 }
 
+// The epilogue from the conv's fp32 output y on (the list above from `pre`): what K27
+// (qinfer_stem.hip) runs on an fp32 conv's output and the integer kernels after their own product.
 // RES: `rv` is the residual K13 adds between the affine and the activation
 template <bool RES = false>
-__device__ __forceinline__ int qepi_code(float fI, uint32_t co, const float* __restrict__ scale,
-                                         const QEpi& e, uint32_t& nbad, float rv = 0.0f) {
-  const float y = __fmul_rn(fI, scale[co]);
+__device__ __forceinline__ int qepi_code_y(float y, uint32_t co, const QEpi& e, uint32_t& nbad,
+                                           float rv = 0.0f) {
   const float pre = e.bias ? __fadd_rn(y, e.bias[co]) : y;
   float t = e.gamma ? __fadd_rn(__fmul_rn(pre, e.gamma[co]), e.phi[co]) : pre;
   if constexpr (RES) t = __fadd_rn(t, rv);
@@ -72,6 +73,12 @@ __device__ __forceinline__ int qepi_code(float fI, uint32_t co, const float* __r
     nbad += 1u;
   }
   return (int)__fsub_rn(q, e.lo) - 128;
+}
+
+template <bool RES = false>
+__device__ __forceinline__ int qepi_code(float fI, uint32_t co, const float* __restrict__ scale,
+                                         const QEpi& e, uint32_t& nbad, float rv = 0.0f) {
+  return qepi_code_y<RES>(__fmul_rn(fI, scale[co]), co, e, nbad, rv);
 }
 
 // four codes (each in [-128, 127]) as the bytes of one word, c0 lowest

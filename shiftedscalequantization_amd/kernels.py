@@ -242,7 +242,9 @@ MAXPOOL_HIP = os.environ.get("SSQ_MAXPOOL", "1") != "0"
 class SsqMaxPool2d(torch.nn.MaxPool2d):
     """nn.MaxPool2d whose forward runs on ssq_maxpool2d_fwd where it applies (a square
     window of <= 7, padding <= K // 2, no dilation / ceil mode / indices, a 4-D fp32 device
-    input that needs no gradient); torch's pooling otherwise.  Same results either way."""
+    input that needs no gradient); torch's pooling otherwise.  Same results either way.
+    A carried int8 code tensor (`carried`) is pooled as codes (ssq_maxpool_i8_fwd) when the
+    integer plan marks this pool, and decoded to the fp32 tensor it stands for otherwise."""
 
     @staticmethod
     def wrap(m):
@@ -263,8 +265,21 @@ class SsqMaxPool2d(torch.nn.MaxPool2d):
             return None
         return k, st, pad
 
+    _int_stem = None    # the StemCarry that marks a planned pool (quant/integer.py, carry_stem)
+
     def forward(self, x):
         plan = self._plan()
+        cc = getattr(x, "_ssq_codes", None)
+        if cc is not None:
+            # a carried code tensor: pooled as codes (K28) by a planned pool, decoded otherwise
+            stem = self._int_stem
+            if (stem is not None and plan is not None and not self._forward_hooks
+                    and not self._forward_pre_hooks):
+                out = maxpool_codes(x, *plan)
+                stem.pooled[self] += 1
+                N, OH, OW, _ = (int(v) for v in out.shape)
+                return carried(out, (N, cc.shape[1], OH, OW), *cc.quantizer())
+            x = materialize_epi(x)
         if (plan is not None and x.dim() == 4 and x.is_cuda and x.dtype == torch.float32
                 and not (torch.is_grad_enabled() and x.requires_grad)):
             return maxpool2d(x, *plan)
@@ -2084,6 +2099,52 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
     fn = "ssq_qconv_i8_grouped_codes_fwd" if int(groups) > 1 else "ssq_qconv_i8_codes_fwd"
     call(fn, *args, vecs[0][1], vecs[1][1], vecs[2][1], int(relu), float(out_delta), float(out_zp),
          olo, ohi, _vp(out), _vp(bad), stream_of(out))
+    return out
+
+
+def epilogue_codes(y, bias, gamma, phi, relu, out_delta, out_zp, out_bits, out_sym, bad):
+    """The K13 epilogue of an fp32 conv output y (N, C, H, W) leaving as int8 codes
+    (ssq_epilogue_codes_fwd): clamp(round(act((y + bias) * gamma + phi) / out_delta) + out_zp) in
+    act_encode's layout (N, H, W, Cpad) -- what act_encode derives from the fp32 epilogue's
+    output.  `relu`: 0 identity, 1 ReLU, 2 ReLU6.  A NaN result is stored as qmin and ADDED to
+    `bad` (a device int32 word)."""
+    if bad is None:
+        raise A.SSQError("epilogue_codes: bad is required")
+    if (gamma is None) != (phi is None):
+        raise A.SSQError("epilogue_codes: gamma and phi go together")
+    y, yp = fptr(y, "y")
+    if y.dim() != 4:
+        raise A.SSQError(f"epilogue_codes: expected (N, C, H, W), got {tuple(y.shape)}")
+    N, Cc, H, W = (int(v) for v in y.shape)
+    vecs = []
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (phi, "phi")):
+        v, vp = (None, None) if t is None else fptr(t.detach().reshape(-1), nm)
+        if v is not None and v.numel() != Cc:
+            raise A.SSQError(f"epilogue_codes: {nm} must have one entry per channel")
+        vecs.append((v, vp))
+    out = torch.empty((N, H, W, query("ssq_qinfer_cpad", Cc)), dtype=torch.int8, device=y.device)
+    olo, ohi = qrange(out_bits, out_sym)
+    call("ssq_epilogue_codes_fwd", yp, vecs[0][1], vecs[1][1], vecs[2][1], N, Cc, H, W, int(relu),
+         float(out_delta), float(out_zp), olo, ohi, _vp(out), _vp(bad), stream_of(out))
+    return out
+
+
+def maxpool_codes(codes, k, stride, padding):
+    """Max-pool (ssq_maxpool2d_fwd's geometry) on act_encode's int8 codes (N, H, W, Cpad) ->
+    (N, OH, OW, Cpad) (ssq_maxpool_i8_fwd): the codes act_encode derives from the fp32 max-pool
+    of the tensor the codes stand for."""
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int8:
+        raise A.SSQError("maxpool_codes: expected int8 codes")
+    codes = _i8_dev(codes, "maxpool_codes")
+    if codes.dim() != 4 or codes.shape[-1] % 16:
+        raise A.SSQError(f"maxpool_codes: codes {tuple(codes.shape)} are not (N, H, W, Cpad)")
+    N, H, W, Cp = (int(v) for v in codes.shape)
+    k, stride, padding = int(k), int(stride), int(padding)
+    OH = (H + 2 * padding - k) // max(stride, 1) + 1
+    OW = (W + 2 * padding - k) // max(stride, 1) + 1
+    out = torch.empty((N, max(OH, 0), max(OW, 0), Cp), dtype=torch.int8, device=codes.device)
+    call("ssq_maxpool_i8_fwd", _vp(codes), N, Cp, H, W, k, stride, padding, _vp(out),
+         stream_of(codes))
     return out
 
 

@@ -108,6 +108,11 @@ class ResNet(nn.Module):
         (quant.integer.block_edges)."""
         return [self.layer1, self.layer2, self.layer3, self.layer4]
 
+    def stem_chain(self):
+        """The modules `forward` applies back to back from the stem conv to the first stage,
+        each handing its output to the next and to nothing else (quant.integer.stem_edges)."""
+        return [self.conv1, self.bn1, self.relu, self.maxpool, self.layer1]
+
 
 def resnet18(**kw):
     return ResNet(BasicBlock, [2, 2, 2, 2], **kw)
@@ -175,6 +180,10 @@ class MobileNetV2(nn.Module):
 
     def forward(self, x):
         return self.classifier(self.features(x).mean([2, 3]))
+
+    def stem_chain(self):
+        """The stem and the first block (see ResNet.stem_chain)."""
+        return [self.features[0], self.features[1]]
 
 
 def mobilenetv2(**kw):
@@ -282,6 +291,10 @@ class RegNet(nn.Module):
         """The stages `forward` applies back to back with nothing in between (see
         ResNet.stage_chain)."""
         return [getattr(self, f"s{i + 1}") for i in range(self.stages)]
+
+    def stem_chain(self):
+        """The stem and the first stage (see ResNet.stem_chain)."""
+        return [self.stem, self.s1]
 
 
 def _regnet(name):

@@ -26,6 +26,14 @@ qualify is structural again (`block_edges`: neighbours in an nn.Sequential, and 
 model declares with `stage_chain`); the trace confirms the readers' input quantizer.  A tagged
 tensor that arrives where it is not the planned operand is decoded (K.materialize_epi), so a
 condition that fails at run time costs time, never correctness.
+
+With `carry_stem=True` the codes start at the model's front: the stem conv stays on the fp32
+route (its input is an unquantized image), but its K13 epilogue leaves as codes
+(ssq_epilogue_codes_fwd), a max-pool behind it pools the codes (ssq_maxpool_i8_fwd: a max-pool
+commutes with the decode, which is non-decreasing in the code) and the first block's readers
+take them.  The chain is structural once more (`stem_edges`, from the `stem_chain` a model
+declares); the planning trace follows an act quantizer's output through such a pool, so the
+layers behind it become eligible.
 """
 import torch
 import torch.nn as nn
@@ -102,6 +110,33 @@ class TailCarry:
         self.residual = None        # the kind the last emitting forward added
 
 
+class StemCarry:
+    """The stem's carried output (carry_stem): the producing conv, the pools its codes pass, the
+    successor with its entry and module readers, and the producer's act quantizer as the
+    readers' plans hold it."""
+
+    def __init__(self, producer, pools, successor, entry, readers):
+        p = readers[0]._int_plan
+        self.producer, self.pools, self.successor = producer, list(pools), successor
+        self.entry, self.readers = entry, readers
+        self.delta, self.zp, self.n_bits, self.sym = p.delta, p.zp, p.n_bits, p.sym
+        self.counter = p.counter
+        self.calls = 0
+        self.pooled = {m: 0 for m in self.pools}    # forwards in which a pool pooled codes
+
+    def live(self):
+        """The run-time state behind the producer is still the planned one."""
+        mods = [self.entry] + self.readers
+        if _hooked(self.successor, *self.pools, *mods):
+            return False
+        if any(m._int_stem is not self or m._plan() is None for m in self.pools):
+            return False
+        if any(m.cache_features != 'none' for m in mods):
+            return False
+        return all(m._int_plan is not None and m.use_weight_quant and m.use_act_quant
+                   for m in self.readers)
+
+
 def _layers(qnn):
     return [(n, m) for n, m in qnn.named_modules() if isinstance(m, QuantModule)]
 
@@ -117,16 +152,24 @@ def _act_quantizers(qnn):
 
 
 @torch.no_grad()
-def _trace_inputs(qnn, sample):
+def _trace_inputs(qnn, sample, pools=False):
     """{QuantModule: the act quantizer whose output tensor is that module's input} from one
     forward of `sample`.  A hooked act quantizer runs unfused (fusable_act_quantizer), so its
-    output is the very tensor object the next layer receives."""
+    output is the very tensor object the next layer receives.  `pools` (carry_stem): the output
+    of a max-pool the code kernel can run (SsqMaxPool2d with a plan) whose input is an act
+    quantizer's output counts as that quantizer's: the same grid, delta and zero point."""
     produced, keep, source, hooks = {}, [], {}, []
 
     def post(q, args, out):
         if isinstance(out, torch.Tensor):
             produced[id(out)] = q
             keep.append(out)          # ids stay unique while the trace runs
+
+    def post_pool(m, args, out):
+        x = args[0] if args else None
+        q = produced.get(id(x)) if isinstance(x, torch.Tensor) else None
+        if q is not None:
+            post(q, args, out)
 
     def pre(m, args):
         x = args[0] if args else None
@@ -141,6 +184,9 @@ def _trace_inputs(qnn, sample):
     layers = [m for _, m in _layers(qnn)]
     for q in _act_quantizers(qnn):
         hooks.append(q.register_forward_hook(post))
+    for m in qnn.modules() if pools else ():
+        if isinstance(m, K.SsqMaxPool2d) and m._plan() is not None:
+            hooks.append(m.register_forward_hook(post_pool))
     for m in layers:
         hooks.append(m.register_forward_pre_hook(pre))
         m.forward_raw = raw_of(m)
@@ -190,20 +236,24 @@ def _weight_codes(m):
 
 
 @torch.no_grad()
-def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False):
+def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
+                             carry_stem=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
     plan grouped and depthwise convs (K24-K26); off, they are reported as refused.  `carry`:
     also carry int8 codes between the integer layers of a block (`carry_report`).
     `carry_blocks`: `carry`, and the codes also cross block tails and block boundaries
-    (`block_carry_report`)."""
+    (`block_carry_report`).  `carry_stem`: `carry_blocks`, and the stem's epilogue emits codes
+    that a max-pool behind it pools as codes (`stem_carry_report`); the layers behind such a
+    pool are planned too."""
+    carry_blocks = carry_blocks or carry_stem
     carry = carry or carry_blocks
     disable_integer_inference(qnn)
     layers = _layers(qnn)
     if not layers:
         return {}
-    source = _trace_inputs(qnn, sample)
+    source = _trace_inputs(qnn, sample, pools=carry_stem)
     dev = layers[0][1].weight.device
     counter = torch.zeros(1, dtype=torch.int32, device=dev)
     qnn._int_counter = counter
@@ -270,6 +320,8 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         _plan_carry(qnn, source)
     if carry_blocks:
         _plan_block_carry(qnn, source)
+    if carry_stem:
+        _plan_stem_carry(qnn, source)
     return report
 
 
@@ -406,14 +458,78 @@ def _plan_block_carry(qnn, source):
         blk._int_tail = TailCarry(last, succ, entry, readers)
 
 
+def stem_edges(qnn):
+    """The (producer QuantModule, [max-pools], successor) chains from the stem conv to the first
+    stage, from the structure alone (no device, no forward): the `stem_chain()` the model
+    declares on `qnn.model`, whose first entry is a QuantModule -- itself, or an nn.Sequential
+    of one followed by StraightThrough only --, whose entries in between are StraightThrough or
+    a max-pool the code kernel can run (SsqMaxPool2d with a plan), and whose last entry has an
+    `_edge_entry`.  Empty for any other chain and for a model that declares none."""
+    from .fold_bn import StraightThrough as FoldedBN
+    from .quant_layer import StraightThrough as MovedAct
+    StraightThrough = (FoldedBN, MovedAct)      # a folded BN's and a moved activation's identity
+    chain = getattr(getattr(qnn, "model", qnn), "stem_chain", None)
+    mods = list(chain()) if callable(chain) else []
+    if len(mods) < 2:
+        return []
+    prod = mods[0]
+    if isinstance(prod, nn.Sequential):
+        kids = list(prod)
+        if not kids or not all(isinstance(k, StraightThrough) for k in kids[1:]):
+            return []
+        prod = kids[0]
+    if not isinstance(prod, QuantModule):
+        return []
+    pools = []
+    for m in mods[1:-1]:
+        if isinstance(m, K.SsqMaxPool2d) and m._plan() is not None:
+            pools.append(m)
+        elif not isinstance(m, StraightThrough):
+            return []
+    if _edge_entry(mods[-1]) is None:
+        return []
+    return [(prod, pools, mods[-1])]
+
+
+def _plan_stem_carry(qnn, source):
+    """Install a StemCarry on the producer of every `stem_edges` chain that can emit codes: a
+    conv on the fp32 route whose epilogue and act quantizer K27 applies (no SE module), every
+    reader of the successor planned with that act quantizer as its traced input (through the
+    pools), no grouped or depthwise conv of the entry left on the decoded path (the block-edge
+    rule), and no hook that would see the tensor.  The pools are marked with the same object."""
+    for prod, pools, succ in stem_edges(qnn):
+        if prod._int_plan is not None or prod.fwd_func is not F.conv2d:
+            continue
+        if prod.se_module is not None or prod.disable_act_quant:
+            continue
+        if not prod.epilogue_fusable(prod.weight) or prod.act_code() not in (0, 1, 2):
+            continue
+        q = prod.act_quantizer
+        if fusable_act_quantizer(q, True) is None or _input_reason(q)[0] is None:
+            continue
+        entry, readers, _ = edge_readers(succ)
+        if not readers or any(m._int_plan is None or source.get(m) is not q for m in readers):
+            continue
+        if _decoded_grouped(entry):
+            continue
+        if _hooked(prod, succ, entry, *pools, *readers):
+            continue
+        prod._int_stem = StemCarry(prod, pools, succ, entry, readers)
+        for m in pools:
+            m._int_stem = prod._int_stem
+
+
 def disable_integer_inference(qnn):
     """Every layer back on the decoded fp32 path."""
     from .quant_block import BaseQuantBlock
     for _, m in _layers(qnn):
         m._int_plan = None
+        m._int_stem = None
     for m in qnn.modules():
         if isinstance(m, BaseQuantBlock):
             m._int_tail = None
+        elif isinstance(m, K.SsqMaxPool2d):
+            m._int_stem = None
     qnn._int_counter = None
 
 
@@ -450,6 +566,7 @@ def block_carry_report(qnn):
     tails = [(n, m) for n, m in qnn.named_modules()
              if isinstance(m, BaseQuantBlock) and getattr(m, "_int_tail", None) is not None]
     fed = {m._int_tail.entry for _, m in tails}
+    fed |= {m._int_stem.entry for _, m in _layers(qnn) if getattr(m, "_int_stem", None) is not None}
     edges, calls, residual = [], {}, {}
     for n, blk in tails:
         t = blk._int_tail
@@ -462,3 +579,18 @@ def block_carry_report(qnn):
             kind = "none" if getattr(blk, "downsample", None) is None else "fp32"
         residual[n] = kind
     return {"edges": edges, "calls": calls, "residual": residual}
+
+
+def stem_carry_report(qnn):
+    """{"edges": [(producer name, [pool names], successor name), ...] whose producer the
+    installed plan lets emit int8 codes, "calls": {producer name: forwards that emitted codes},
+    "pooled": {pool name: forwards that pooled codes}}; empty without a plan."""
+    names = {m: n for n, m in qnn.named_modules()}
+    edges, calls, pooled = [], {}, {}
+    for n, m in _layers(qnn):
+        s = getattr(m, "_int_stem", None)
+        if s is not None:
+            edges.append((n, [names[p] for p in s.pools], names[s.successor]))
+            calls[n] = s.calls
+            pooled.update({names[p]: k for p, k in s.pooled.items()})
+    return {"edges": edges, "calls": calls, "pooled": pooled}

@@ -301,6 +301,7 @@ class QuantModule(nn.Module):
         self.selectionInited = False
         self.pathName = ''
         self._int_plan = None           # integer route (quant/integer.py); None: decoded fp32
+        self._int_stem = None           # carried stem output (quant/integer.py, carry_stem)
 
     def _cache(self, t):
         t = t.detach()
@@ -442,12 +443,38 @@ class QuantModule(nn.Module):
         gamma, phi = self.affine()
         return plan.run_codes(input, self.bias, gamma, phi, self.act_code())
 
+    def _stem_codes(self, input):
+        """The forward as carried int8 codes when this layer is the planned producer of a stem
+        edge (quant/integer.py, carry_stem): the conv on its fp32 route, then K.epilogue_codes
+        (bias, gamma^z / phi^z, activation and the act quantizer, leaving as the readers'
+        operand) when the run-time state is still the planned one; None: take the usual route."""
+        s = self._int_stem
+        if (torch.is_grad_enabled() or self.disable_act_quant
+                or not (self.use_weight_quant and self.use_act_quant)
+                or self.cache_features != 'none' or _CONV_CACHE is not None
+                or self._forward_hooks or self._forward_pre_hooks
+                or not isinstance(input, torch.Tensor) or input.dtype != torch.float32
+                or input.dim() != 4 or not self.epilogue_fusable(input)
+                or self.act_code() not in (0, 1, 2)
+                or fusable_act_quantizer(self.act_quantizer, True) is None or not s.live()):
+            return None
+        out, bias = self.forward_raw(input)
+        gamma, phi = self.affine()
+        s.calls += 1
+        codes = K.epilogue_codes(out, bias, gamma, phi, self.act_code(), s.delta, s.zp, s.n_bits,
+                                 s.sym, s.counter)
+        return K.carried(codes, tuple(out.shape), s.delta, s.zp, s.n_bits, s.sym)
+
     def forward(self, input: torch.Tensor):
         if self.cache_features == 'if':
             input = K.materialize_epi(input)
             self.cached_inp_features += [self._cache(input)]
         elif getattr(self, '_int_plan', None) is not None:
             out = self._carry(input)
+            if out is not None:
+                return out
+        elif getattr(self, '_int_stem', None) is not None:
+            out = self._stem_codes(input)
             if out is not None:
                 return out
         act_q = self.use_act_quant and not self.disable_act_quant
