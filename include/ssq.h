@@ -824,6 +824,38 @@ int ssq_epilogue_codes_fwd(const float* y, const float* bias, const float* gamma
 int ssq_maxpool_i8_fwd(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W, int64_t K,
                        int64_t stride, int64_t pad, int8_t* out, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- pooling head on codes (K29, K30)
+ * The global average pool and the fc behind it on stored codes, with a numerics contract of
+ * their own (the fc has no input quantizer, so the pooled value is never re-quantized):
+ *     P[n,c]  = sum_hw (q_a - z_a)                     exact integer
+ *     I[n,co] = sum_c P[n,c] (q_w[co,c] - z_w[co])     exact integer (int64)
+ *     y[n,co] = fp32(I) * scale_h[co]                  one conversion (RNE), one multiply
+ * scale_h[co] = fp32(fp32(delta_a * d1[co]) / fp32(HW)) is the caller's.  No bias, no FMA.  y is a
+ * function of the codes alone and reproducible bit for bit from a host int64 restatement; it is
+ * NOT bit-equal to an fp32 mean followed by an fp32 GEMM.
+ *
+ * ssq_avgpool_i8_digits_fwd (K29): codes NHWC [Nb, H, W, qinfer_cpad(C)] (ssq_act_encode's
+ * stored form a_s) -> the plane sums P_s[n,c] = sum_hw a_s as two int8 digits
+ * hi = (P_s + 64) >> 7, lo = P_s - 128 * hi in [-64, 63], each [Nb][qinfer_cpad(C)] with padded
+ * channels 0, and sp[n] = sum_c P_s[n,c] (int32).  H * W <= 126 (|hi| <= 126), C <= 65536.
+ *
+ * ssq_qlinear_pooled_fwd (K30): y [Nb, Co] fp32 from K29's hi, lo, sp and the fc's prepared
+ * weight (ssq_qweight_prepare's blob for (Co, Ci, 1, 1), unchanged): D = 128 * D_hi + D_lo on
+ * v_mfma_i32_16x16x64_i8, I = D + cwz[co] * sp[n] + HW * az * T[co] in int64.  HW is the pooled
+ * plane's H * W (1..126), (act_zero_point, act_qmin, act_qmax) the pooled codes' quantizer.
+ *
+ * Every refusal (null pointer, bad geometry or quantizer, H * W > 126, C > 65536, a tensor of
+ * 2^31 bytes or more) is SSQ_E_ARG before any launch.  No allocation, no sync, capturable.
+ * ssq_qlinear_pooled_set_tile: measurement plumbing only, K30's image tile (16, the default, or
+ * 64); returns the previous value, any other argument only queries.                           */
+int ssq_avgpool_i8_digits_fwd(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                              int8_t* hi, int8_t* lo, int32_t* sp, ssq_stream_t stream);
+int ssq_qlinear_pooled_fwd(const int8_t* hi, const int8_t* lo, const int32_t* sp,
+                           const void* prepared, const float* scale_h, int64_t Nb, int64_t Ci,
+                           int64_t Co, int64_t HW, float act_zero_point, int act_qmin,
+                           int act_qmax, float* y, ssq_stream_t stream);
+int ssq_qlinear_pooled_set_tile(int tile);
+
 /* ---------------------------------------------------------------- bandwidth probe
  * float4 device copy, used by bench.py to report the measured stream bandwidth.      */
 int ssq_stream_copy(const float* src, float* dst, int64_t n, ssq_stream_t stream);

@@ -154,12 +154,14 @@ def main(argv=None):
                                                                    validate_model(loader, qnn)))
     if args.int_infer and args.act_quant:
         from shiftedscalequantization_amd.quant import (block_carry_report, carry_report,
-                                                         enable_integer_inference, integer_report,
+                                                         enable_integer_inference,
+                                                         head_carry_report, integer_report,
                                                          stem_carry_report)
         plan = enable_integer_inference(qnn, cali[:8], grouped=args.int_infer_grouped,
                                         carry=args.int_infer_carry,
                                         carry_blocks=args.int_infer_carry_blocks,
-                                        carry_stem=args.int_infer_carry_stem)
+                                        carry_stem=args.int_infer_carry_stem,
+                                        carry_head=args.int_infer_carry_head)
         n_int = sum(v == 'int8' for v in plan.values())
         print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
         if args.int_infer_carry:
@@ -174,6 +176,10 @@ def main(argv=None):
             edges = stem_carry_report(qnn)['edges']
             print(f'integer inference: int8 codes carried from {len(edges)} stem edges: '
                   + ', '.join(' -> '.join([a] + pools + [b]) for a, pools, b in edges))
+        if args.int_infer_carry_head:
+            edges = head_carry_report(qnn)['edges']
+            print(f'integer inference: int8 codes carried to the logits along {len(edges)} head '
+                  'edges: ' + ', '.join(' -> '.join(e) for e in edges))
         for name, why in plan.items():
             print(f'  {name}: {why}')
         if loader is not None:

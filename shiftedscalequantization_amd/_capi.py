@@ -149,6 +149,9 @@ SIGNATURES = {
     "ssq_epilogue_codes_fwd": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _f, _f, _i, _i, _p,
                                     _p, _p]),
     "ssq_maxpool_i8_fwd": (_i, [_p] + [_i64] * 7 + [_p, _p]),
+    "ssq_avgpool_i8_digits_fwd": (_i, [_p] + [_i64] * 4 + [_p, _p, _p, _p]),
+    "ssq_qlinear_pooled_fwd": (_i, [_p] * 5 + [_i64] * 4 + [_f, _i, _i, _p, _p]),
+    "ssq_qlinear_pooled_set_tile": (_i, [_i]),
     "ssq_stream_copy": (_i, [_p, _p, _i64, _p]),
     "ssq_stream_probe": (_i, [_p, _p, _i64, _i, _p]),
 }

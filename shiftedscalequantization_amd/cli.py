@@ -88,6 +88,10 @@ def build_parser():
                    help='--int_infer_carry_blocks with the codes starting at the stem: its '
                         'epilogue emits int8 codes and a max-pool behind it pools them; implies '
                         '--int_infer_carry_blocks')
+    p.add_argument('--int_infer_carry_head', action='store_true',
+                   help='--int_infer_carry_stem with the codes running to the logits: the global '
+                        'average pool sums the int8 codes and the fc runs on the sums (a numerics '
+                        'contract of its own, DESIGN 4); implies --int_infer_carry_stem')
     p.add_argument('--deterministic', default=1, type=int,
                    help='1 (reference): deterministic MIOpen conv solvers; 0: fastest solvers')
     # data parallel: one process per GPU, spawned by main_imagenet.py itself with --gpus N
@@ -105,6 +109,8 @@ def parse_args(argv=None):
     a = build_parser().parse_args(argv)
     if a.run_device:
         a.device_gpu = a.run_device
+    if a.int_infer_carry_head:
+        a.int_infer_carry_stem = True
     if a.int_infer_carry_stem:
         a.int_infer_carry_blocks = True
     if a.int_infer_carry_blocks:

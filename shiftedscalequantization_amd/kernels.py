@@ -13,6 +13,7 @@ import torch
 
 from . import _capi as A
 from ._capi import call, fptr, query, stream_of, workspace
+from .nets import GlobalMeanPool
 
 
 def qrange(n_bits, sym):
@@ -284,6 +285,43 @@ class SsqMaxPool2d(torch.nn.MaxPool2d):
                 and not (torch.is_grad_enabled() and x.requires_grad)):
             return maxpool2d(x, *plan)
         return super().forward(x)
+
+
+class SsqGlobalAvgPool(torch.nn.AdaptiveAvgPool2d):
+    """The global average pool in front of the fc -- nn.AdaptiveAvgPool2d with output size 1
+    ((N, C, 1, 1)), or with `flat` a GlobalMeanPool ((N, C)) -- whose forward is the wrapped
+    module's on any untagged input.  A carried int8 code tensor (`carried`) is pooled as codes
+    (ssq_avgpool_i8_digits_fwd, leaving as `pooled` digits for the planned fc) while the
+    integer plan's HeadCarry marks this pool and is live, and decoded to the fp32 tensor it
+    stands for otherwise."""
+
+    @staticmethod
+    def wraps(m):
+        if isinstance(m, GlobalMeanPool):
+            return True
+        return type(m) is torch.nn.AdaptiveAvgPool2d and m.output_size in (1, (1, 1))
+
+    @staticmethod
+    def wrap(m):
+        s = SsqGlobalAvgPool(1)
+        s.flat = isinstance(m, GlobalMeanPool)
+        return s
+
+    flat = False
+    _int_head = None    # the HeadCarry that marks a planned pool (quant/integer.py, carry_head)
+
+    def forward(self, x):
+        cc = getattr(x, "_ssq_codes", None)
+        if cc is not None:
+            head = self._int_head
+            if (head is not None and x.dim() == 4 and x.shape[1] * x.shape[2] <= HEAD_MAX_HW
+                    and head.live()):
+                hi, lo, sp = avgpool_codes(x)
+                head.pooled += 1
+                return pooled(hi, lo, sp, (cc.shape[0], cc.shape[1]),
+                              int(x.shape[1] * x.shape[2]), *cc.quantizer())
+            x = materialize_epi(x)
+        return x.mean([2, 3]) if self.flat else super().forward(x)
 
 
 class deferred_fq_multi:
@@ -1518,6 +1556,9 @@ def lazy_epilogue(y, bias, gamma, phi, relu, q):
 def materialize_epi(x):
     epi = getattr(x, "_ssq_epi", None)
     if epi is None:
+        if getattr(x, "_ssq_pooled", None) is not None:
+            # digits of plane sums (`pooled`) stand for no fp32 tensor another route computes
+            raise A.SSQError("pooled code digits reached a consumer that is not the planned fc")
         cc = getattr(x, "_ssq_codes", None)
         return x if cc is None else cc.decode(x)
     return epi.materialize()
@@ -2146,6 +2187,96 @@ def maxpool_codes(codes, k, stride, padding):
     call("ssq_maxpool_i8_fwd", _vp(codes), N, Cp, H, W, k, stride, padding, _vp(out),
          stream_of(codes))
     return out
+
+
+# ------------------------------------------------------------------ K29-K30 pooling head on codes
+HEAD_MAX_HW = 126   # the pooled plane's H * W: keeps the high digit of a plane sum inside int8
+
+
+def avgpool_codes(codes):
+    """The plane sums of act_encode's int8 codes (N, H, W, Cpad), H * W <= 126
+    (ssq_avgpool_i8_digits_fwd): P_s[n, c] = sum_hw code as two int8 digits (N, Cpad),
+    hi = (P_s + 64) >> 7 and lo = P_s - 128 * hi in [-64, 63], padded channels 0, and
+    sp[n] = sum_c P_s[n, c] (int32) -> (hi, lo, sp)."""
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int8:
+        raise A.SSQError("avgpool_codes: expected int8 codes")
+    codes = _i8_dev(codes, "avgpool_codes")
+    if codes.dim() != 4 or codes.shape[-1] % 16:
+        raise A.SSQError(f"avgpool_codes: codes {tuple(codes.shape)} are not (N, H, W, Cpad)")
+    N, H, W, Cp = (int(v) for v in codes.shape)
+    digits = torch.empty((2, N, Cp), dtype=torch.int8, device=codes.device)
+    sp = torch.empty((N,), dtype=torch.int32, device=codes.device)
+    call("ssq_avgpool_i8_digits_fwd", _vp(codes), N, Cp, H, W, _vp(digits[0]), _vp(digits[1]),
+         _vp(sp), stream_of(codes))
+    return digits[0], digits[1], sp
+
+
+def head_scale(scale, HW):
+    """K30's scale_h[co] = fp32(scale[co] / fp32(HW)) from a layer's s[co] = fp32(delta_a *
+    d1[co]): the mean's 1 / HW folded into the scale by one correctly rounded fp32 division
+    (made on the host; one copy each way)."""
+    import numpy as np
+    s = scale.detach().reshape(-1).float().cpu().numpy()
+    return torch.from_numpy((s / np.float32(int(HW))).astype(np.float32)).to(scale.device)
+
+
+def qlinear_pooled(hi, lo, sp, prepared, scale_h, HW, act_zp=0.0, act_bits=8, act_sym=False):
+    """The fc on avgpool_codes's digits (ssq_qlinear_pooled_fwd): y[n, co] = fp32(I) *
+    scale_h[co] (fp32 (N, Co)), I = sum_c P[n, c] (q_w[co, c] - z_w[co]) the exact integer with
+    P[n, c] = sum_hw (q_a - z_a) over the HW pooled pixels.  `prepared`: the Linear's
+    qweight_prepare output; `scale_h`: head_scale(s, HW); (act_zp, act_bits, act_sym): the
+    pooled codes' act quantizer.  No bias."""
+    for t, nm in ((hi, "hi"), (lo, "lo")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int8:
+            raise A.SSQError(f"qlinear_pooled: {nm} must be int8 digits")
+    if not isinstance(sp, torch.Tensor) or sp.dtype != torch.int32:
+        raise A.SSQError("qlinear_pooled: sp must be an int32 tensor")
+    hi, lo, sp = (_i8_dev(t, "qlinear_pooled") for t in (hi, lo, sp))
+    if len(prepared.shape) != 2 or getattr(prepared, "groups", 1) != 1:
+        raise A.SSQError("qlinear_pooled: the weight must be a prepared Linear")
+    Co, Ci, _, _ = prepared.geometry()
+    Cp = query("ssq_qinfer_cpad", Ci)
+    if hi.dim() != 2 or hi.shape[1] != Cp or tuple(lo.shape) != tuple(hi.shape):
+        raise A.SSQError(f"qlinear_pooled: digits {tuple(hi.shape)}, {tuple(lo.shape)} do not "
+                         f"match the weight {prepared.shape} (Cpad = {Cp})")
+    N = int(hi.shape[0])
+    if sp.dim() != 1 or sp.numel() != N:
+        raise A.SSQError("qlinear_pooled: sp must have one entry per image")
+    s, shp = fptr(scale_h.detach().reshape(-1), "scale_h")
+    if s.numel() != Co:
+        raise A.SSQError("qlinear_pooled: scale_h must have one entry per output channel")
+    alo, ahi = qrange(act_bits, act_sym)
+    y = torch.empty((N, Co), dtype=torch.float32, device=hi.device)
+    call("ssq_qlinear_pooled_fwd", _vp(hi), _vp(lo), _vp(sp), _vp(prepared.blob), shp, N, Ci, Co,
+         int(HW), float(act_zp), alo, ahi, _vp(y), stream_of(y))
+    return y
+
+
+def qlinear_pooled_tile(tile=0):
+    """Measurement plumbing: set K30's image tile (16, the default, or 64); returns the previous
+    one (any other value only queries)."""
+    return query("ssq_qlinear_pooled_set_tile", int(tile))
+
+
+class PooledCodes:
+    """What a pooled digit tensor stands for (the hi tensor's `_ssq_pooled`): the lo digits and
+    the per-image sums that go with it, the logical (N, C), the HW pixels that were summed and
+    the act quantizer (delta, zp, n_bits, sym) of the pooled codes.  Only the planned fc reads
+    it; it stands for no fp32 tensor, so materialize_epi refuses it."""
+
+    def __init__(self, lo, sp, shape, HW, delta, zp, n_bits, sym):
+        self.lo, self.sp = lo, sp
+        self.shape, self.HW = tuple(int(v) for v in shape), int(HW)
+        self.delta, self.zp, self.n_bits, self.sym = float(delta), float(zp), int(n_bits), bool(sym)
+
+    def quantizer(self):
+        return self.delta, self.zp, self.n_bits, self.sym
+
+
+def pooled(hi, lo, sp, shape, HW, delta, zp, n_bits, sym):
+    """`hi` tagged as a pooled digit tensor (see PooledCodes)."""
+    hi._ssq_pooled = PooledCodes(lo, sp, shape, HW, delta, zp, n_bits, sym)
+    return hi
 
 
 # ------------------------------------------------------------------ conv geometry

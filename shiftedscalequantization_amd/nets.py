@@ -113,6 +113,12 @@ class ResNet(nn.Module):
         each handing its output to the next and to nothing else (quant.integer.stem_edges)."""
         return [self.conv1, self.bn1, self.relu, self.maxpool, self.layer1]
 
+    def head_chain(self):
+        """[last stage, global average pool, classifier]: `forward` hands the stage's output to
+        the pool and to nothing else, and the pool's output -- through a flatten only -- to the
+        classifier (quant.integer.head_edges)."""
+        return [self.layer4, self.avgpool, self.fc]
+
 
 def resnet18(**kw):
     return ResNet(BasicBlock, [2, 2, 2, 2], **kw)
@@ -148,6 +154,14 @@ class InvertedResidual(nn.Module):
         return x + self.conv(x) if self.use_res_connect else self.conv(x)
 
 
+class GlobalMeanPool(nn.Module):
+    """x.mean([2, 3]) as a parameterless module: MobileNetV2's pooling between `features` and
+    `classifier`, so the model's structure names it (MobileNetV2.head_chain)."""
+
+    def forward(self, x):
+        return x.mean([2, 3])
+
+
 class MobileNetV2(nn.Module):
     SETTING = [[1, 16, 1, 1], [6, 24, 2, 2], [6, 32, 3, 2], [6, 64, 4, 2], [6, 96, 3, 1],
                [6, 160, 3, 2], [6, 320, 1, 1]]
@@ -167,6 +181,7 @@ class MobileNetV2(nn.Module):
                                    nn.BatchNorm2d(self.last_channel), nn.ReLU6(inplace=True)))
         self.features = nn.Sequential(*feats)
         self.classifier = nn.Sequential(nn.Dropout(dropout), nn.Linear(self.last_channel, n_class))
+        self.pool = GlobalMeanPool()
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 n = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
@@ -179,11 +194,15 @@ class MobileNetV2(nn.Module):
                 m.bias.data.zero_()
 
     def forward(self, x):
-        return self.classifier(self.features(x).mean([2, 3]))
+        return self.classifier(self.pool(self.features(x)))
 
     def stem_chain(self):
         """The stem and the first block (see ResNet.stem_chain)."""
         return [self.features[0], self.features[1]]
+
+    def head_chain(self):
+        """The features, the pool and the classifier (see ResNet.head_chain)."""
+        return [self.features, self.pool, self.classifier]
 
 
 def mobilenetv2(**kw):
@@ -295,6 +314,10 @@ class RegNet(nn.Module):
     def stem_chain(self):
         """The stem and the first stage (see ResNet.stem_chain)."""
         return [self.stem, self.s1]
+
+    def head_chain(self):
+        """The last stage, the pool and the fc (see ResNet.head_chain)."""
+        return [getattr(self, f"s{self.stages}"), self.avgpool, self.fc]
 
 
 def _regnet(name):

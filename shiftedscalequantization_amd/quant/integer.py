@@ -34,6 +34,15 @@ commutes with the decode, which is non-decreasing in the code) and the first blo
 take them.  The chain is structural once more (`stem_edges`, from the `stem_chain` a model
 declares); the planning trace follows an act quantizer's output through such a pool, so the
 layers behind it become eligible.
+
+With `carry_head=True` the codes run to the logits: the global average pool in front of the
+fc sums the carried codes of its input (ssq_avgpool_i8_digits_fwd: exact integers, stored as two
+int8 digits) and the fc multiplies the sums with its prepared int8 weight
+(ssq_qlinear_pooled_fwd), one int -> fp32 conversion and one multiply per logit.  The head has a
+numerics contract of its own: its logits are a function of the codes alone, not bit
+for bit those of an fp32 mean and an fp32 GEMM.  The chain is structural (`head_edges`, from
+the `head_chain` a model declares); the fc is planned for the pooled operand only, so whenever
+the pool does not pool codes the head is the fp32 one of the other routes.
 """
 import torch
 import torch.nn as nn
@@ -58,6 +67,7 @@ class IntPlan:
         self.counter = counter
         self.calls = 0
         self.carry = None                       # a Carry when this layer emits codes
+        self.head = None                        # a HeadCarry: the fc, on pooled digits only
 
     def accepts(self, cc):
         """A carried tensor (K.CarriedCodes) holds this layer's planned operand."""
@@ -137,6 +147,43 @@ class StemCarry:
                    for m in self.readers)
 
 
+class HeadCarry:
+    """The carried head (carry_head): the producer (the last quant block, or a trailing
+    QuantModule) whose codes the marked pool sums and the fc that reads the sums; the fc's plan
+    holds the producer's act quantizer."""
+
+    def __init__(self, producer, pool, fc):
+        self.producer, self.pool, self.fc = producer, pool, fc
+        self.calls = 0          # fc forwards on ssq_qlinear_pooled_fwd
+        self.pooled = 0         # forwards in which the pool summed codes
+        self._scale_h = {}      # HW -> K.head_scale(plan.scale, HW)
+        self.emitter = None     # the producer's TailCarry / Carry: counts its emitting forwards
+
+    def live(self):
+        """The run-time state behind the pool is still the planned one."""
+        fc, p = self.fc, self.fc._int_plan
+        if torch.is_grad_enabled() or _hooked(self.pool, fc):
+            return False
+        if self.pool._int_head is not self or p is None or p.head is not self:
+            return False
+        return fc.cache_features == 'none' and fc.use_weight_quant and fc.use_act_quant
+
+    def accepts(self, pc):
+        """A pooled digit tensor (K.PooledCodes) holds the fc's planned operand."""
+        p = self.fc._int_plan
+        return (pc.quantizer() == (p.delta, p.zp, p.n_bits, p.sym)
+                and pc.shape[1] == p.prepared.shape[1] and 1 <= pc.HW <= K.HEAD_MAX_HW)
+
+    def run(self, hi, pc):
+        p = self.fc._int_plan
+        sh = self._scale_h.get(pc.HW)
+        if sh is None:
+            sh = self._scale_h[pc.HW] = K.head_scale(p.scale, pc.HW)
+        self.calls += 1
+        p.calls += 1
+        return K.qlinear_pooled(hi, pc.lo, pc.sp, p.prepared, sh, pc.HW, p.zp, p.n_bits, p.sym)
+
+
 def _layers(qnn):
     return [(n, m) for n, m in qnn.named_modules() if isinstance(m, QuantModule)]
 
@@ -152,13 +199,18 @@ def _act_quantizers(qnn):
 
 
 @torch.no_grad()
-def _trace_inputs(qnn, sample, pools=False):
+def _trace_inputs(qnn, sample, pools=False, heads=()):
     """{QuantModule: the act quantizer whose output tensor is that module's input} from one
     forward of `sample`.  A hooked act quantizer runs unfused (fusable_act_quantizer), so its
     output is the very tensor object the next layer receives.  `pools` (carry_stem): the output
     of a max-pool the code kernel can run (SsqMaxPool2d with a plan) whose input is an act
-    quantizer's output counts as that quantizer's: the same grid, delta and zero point."""
+    quantizer's output counts as that quantizer's: the same grid, delta and zero point.
+    `heads` (carry_head): `head_edges`' (producer, pool, fc); a pool whose input is an act
+    quantizer's output makes that quantizer the fc's source -- the structure guarantees that
+    only a flatten lies between them, which makes a new tensor object -- and the pooled plane's
+    H * W is left in `source[pool]`."""
     produced, keep, source, hooks = {}, [], {}, []
+    via_pool = {}
 
     def post(q, args, out):
         if isinstance(out, torch.Tensor):
@@ -170,6 +222,14 @@ def _trace_inputs(qnn, sample, pools=False):
         q = produced.get(id(x)) if isinstance(x, torch.Tensor) else None
         if q is not None:
             post(q, args, out)
+
+    def post_head(fc):
+        def hook(m, args, out):
+            x = args[0] if args else None
+            if isinstance(x, torch.Tensor) and x.dim() == 4:
+                via_pool[fc] = produced.get(id(x))
+                source[m] = int(x.shape[2] * x.shape[3])
+        return hook
 
     def pre(m, args):
         x = args[0] if args else None
@@ -187,11 +247,16 @@ def _trace_inputs(qnn, sample, pools=False):
     for m in qnn.modules() if pools else ():
         if isinstance(m, K.SsqMaxPool2d) and m._plan() is not None:
             hooks.append(m.register_forward_hook(post_pool))
+    for _, pool, fc in heads:
+        hooks.append(pool.register_forward_hook(post_head(fc)))
     for m in layers:
         hooks.append(m.register_forward_pre_hook(pre))
         m.forward_raw = raw_of(m)
     try:
         qnn(sample)
+        for fc, q in via_pool.items():
+            if fc in source and source[fc] is None:
+                source[fc] = q
     finally:
         for h in hooks:
             h.remove()
@@ -237,7 +302,7 @@ def _weight_codes(m):
 
 @torch.no_grad()
 def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
-                             carry_stem=False):
+                             carry_stem=False, carry_head=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
@@ -246,14 +311,19 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     `carry_blocks`: `carry`, and the codes also cross block tails and block boundaries
     (`block_carry_report`).  `carry_stem`: `carry_blocks`, and the stem's epilogue emits codes
     that a max-pool behind it pools as codes (`stem_carry_report`); the layers behind such a
-    pool are planned too."""
+    pool are planned too.  `carry_head`: `carry_stem`, and the global average pool in front of
+    the fc sums the codes and the fc runs on the sums (`head_carry_report`); the fc is planned
+    for that operand only, and reported with the reason when the head edge is not installed."""
+    carry_stem = carry_stem or carry_head
     carry_blocks = carry_blocks or carry_stem
     carry = carry or carry_blocks
     disable_integer_inference(qnn)
     layers = _layers(qnn)
     if not layers:
         return {}
-    source = _trace_inputs(qnn, sample, pools=carry_stem)
+    heads = head_edges(qnn) if carry_head else []
+    source = _trace_inputs(qnn, sample, pools=carry_stem, heads=heads)
+    head_fc = {fc: pool for _, pool, fc in heads}
     dev = layers[0][1].weight.device
     counter = torch.zeros(1, dtype=torch.int32, device=dev)
     qnn._int_counter = counter
@@ -291,6 +361,9 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         if act is None:
             report[name] = why
             continue
+        if m in head_fc and not 1 <= source.get(head_fc[m], 0) <= K.HEAD_MAX_HW:
+            report[name] = f"pooled plane H*W exceeds {K.HEAD_MAX_HW} (int8 digit range)"
+            continue
         if not m.weight.is_cuda:
             report[name] = "weight is not on the HIP device"
             continue
@@ -322,6 +395,8 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         _plan_block_carry(qnn, source)
     if carry_stem:
         _plan_stem_carry(qnn, source)
+    if carry_head:
+        _plan_head_carry(qnn, source, heads, report, sample)
     return report
 
 
@@ -425,6 +500,25 @@ def _decoded_grouped(mod):
                and m._int_plan is None for m in mod.modules())
 
 
+def _emitting_tail(blk):
+    """The block's last conv when its tail can emit codes (see _plan_block_carry), else None."""
+    from .quant_layer import StraightThrough
+    last = blk.last_conv()
+    plan = None if last is None else last._int_plan
+    if plan is None or plan.kind != "dense":
+        return None
+    if not isinstance(last.activation_function, StraightThrough) or last.se_module is not None:
+        return None
+    if not last.disable_act_quant or not last.epilogue_fusable(last.weight):
+        return None
+    q = blk.act_quantizer
+    if block_act_code(blk) is None or fusable_act_quantizer(q, True) is None:
+        return None
+    if _input_reason(q)[0] is None:
+        return None
+    return last
+
+
 def _plan_block_carry(qnn, source):
     """Install a TailCarry on every block of `block_edges` whose tail can emit codes: the last
     conv a planned dense conv whose epilogue the kernel applies (no activation or act
@@ -433,21 +527,11 @@ def _plan_block_carry(qnn, source):
     its traced input, no grouped or depthwise conv of either side left on the decoded path
     (without `grouped=True` a MobileNetV2 / RegNetX block has one in its middle: such a block
     keeps its fp32 edges), and no hook that would see the tensor."""
-    from .quant_layer import StraightThrough
     for blk, succ in block_edges(qnn):
-        last = blk.last_conv()
-        plan = None if last is None else last._int_plan
-        if plan is None or plan.kind != "dense":
-            continue
-        if not isinstance(last.activation_function, StraightThrough) or last.se_module is not None:
-            continue
-        if not last.disable_act_quant or not last.epilogue_fusable(last.weight):
+        last = _emitting_tail(blk)
+        if last is None:
             continue
         q = blk.act_quantizer
-        if block_act_code(blk) is None or fusable_act_quantizer(q, True) is None:
-            continue
-        if _input_reason(q)[0] is None:
-            continue
         entry, readers, _ = edge_readers(succ)
         if not readers or any(m._int_plan is None or source.get(m) is not q for m in readers):
             continue
@@ -519,6 +603,128 @@ def _plan_stem_carry(qnn, source):
             m._int_stem = prod._int_stem
 
 
+def head_edges(qnn):
+    """The (producer, pool, fc) chains of the pooling head, from the structure alone (no device,
+    no forward): the `head_chain()` the model declares on `qnn.model`, [last stage, pool,
+    classifier].  The producer is the stage's last child when that is a quant block, or -- an
+    nn.Sequential there -- a trailing QuantModule followed by StraightThrough only (MobileNetV2's
+    `features.18`); the pool is a K.SsqGlobalAvgPool; the classifier a Linear QuantModule, or an
+    nn.Sequential that ends in one behind nn.Dropout / nn.Flatten / identities only.  Empty for
+    any other chain and for a model that declares none."""
+    from .fold_bn import StraightThrough as FoldedBN
+    from .quant_block import BaseQuantBlock
+    from .quant_layer import StraightThrough as MovedAct
+    ident = (FoldedBN, MovedAct, nn.Identity)
+    chain = getattr(getattr(qnn, "model", qnn), "head_chain", None)
+    mods = list(chain()) if callable(chain) else []
+    if len(mods) != 3:
+        return []
+    prod, pool, fc = mods
+    while isinstance(prod, nn.Sequential) and len(prod):
+        kids = list(prod)
+        while len(kids) > 1 and isinstance(kids[-1], ident):
+            kids.pop()
+        prod = kids[-1]
+    if not isinstance(prod, (BaseQuantBlock, QuantModule)):
+        return []
+    if isinstance(prod, QuantModule) and prod.fwd_func is not F.conv2d:
+        return []
+    if not isinstance(pool, K.SsqGlobalAvgPool):
+        return []
+    if isinstance(fc, nn.Sequential):
+        kids = list(fc)
+        if not kids or not all(isinstance(k, ident + (nn.Dropout, nn.Flatten)) for k in kids[:-1]):
+            return []
+        fc = kids[-1]
+    if not isinstance(fc, QuantModule) or fc.fwd_func is not F.linear:
+        return []
+    return [(prod, pool, fc)]
+
+
+def _reset_calls(qnn):
+    """Zero every forward counter of the installed plan (after the head's dry forward)."""
+    from .quant_block import BaseQuantBlock
+    for m in qnn.modules():
+        p = getattr(m, "_int_plan", None) if isinstance(m, QuantModule) else None
+        if p is not None:
+            p.calls = 0
+            if p.carry is not None:
+                p.carry.calls = 0
+        s = getattr(m, "_int_stem", None) if isinstance(m, QuantModule) else None
+        if s is not None:
+            s.calls = 0
+            s.pooled = {k: 0 for k in s.pooled}
+        t = getattr(m, "_int_tail", None) if isinstance(m, BaseQuantBlock) else None
+        if t is not None:
+            t.calls, t.residual = 0, None
+        h = getattr(m, "_int_head", None) if isinstance(m, K.SsqGlobalAvgPool) else None
+        if h is not None:
+            h.calls = h.pooled = 0
+    if getattr(qnn, "_int_counter", None) is not None:
+        qnn._int_counter.zero_()
+
+
+def _plan_head_carry(qnn, source, heads, report, sample):
+    """Install a HeadCarry on every `head_edges` chain whose producer can emit codes for the
+    pool: a quant block whose tail emits under the block-edge rules with the fc as its reader
+    (ssq_qconv_i8_codes[_res]_fwd; a carried block input is then the RES = 2 residual), or a
+    trailing QuantModule under the interior-pair rules (ssq_qconv_i8_codes_fwd); the fc planned
+    with the producer's act quantizer as its traced input (through the pool); no hook that would
+    see the tensors; and a dry forward of `sample` under the installed plan that shows the
+    pooled digits arriving at the fc.  An fc whose edge is not installed loses its plan -- it
+    is planned for pooled digits only -- and is reported with the reason."""
+    from .quant_block import BaseQuantBlock
+    names = {m: n for n, m in qnn.named_modules()}
+    for prod, pool, fc in heads:
+        if fc._int_plan is None:
+            continue        # refused by the weight / input rules: the report says why
+        why = None
+        if isinstance(prod, BaseQuantBlock):
+            q, last = prod.act_quantizer, _emitting_tail(prod)
+            if last is None:
+                why = "the last block's tail cannot emit codes"
+            elif _decoded_grouped(prod):
+                why = "the last block holds a grouped conv on the decoded path"
+            elif getattr(prod, "_int_tail", None) is not None:
+                why = "the last block already emits codes for another edge"
+        else:
+            q = prod.act_quantizer
+            if (prod._int_plan is None or prod.disable_act_quant or prod.se_module is not None
+                    or fusable_act_quantizer(q, True) is None
+                    or not prod.epilogue_fusable(prod.weight) or prod.act_code() not in (0, 1, 2)
+                    or prod._int_plan.carry is not None):
+                why = "the last layer cannot emit codes"
+        if why is None and source.get(fc) is not q:
+            why = "the pool's input is not the last block's act quantizer output"
+        if why is None and _hooked(prod, pool, fc, *([last] if isinstance(prod, BaseQuantBlock) else [])):
+            why = "a forward hook on the last block, the pool or the fc"
+        if why is None:
+            head = HeadCarry(prod, pool, fc)
+            fc._int_plan.head = pool._int_head = head
+            if isinstance(prod, BaseQuantBlock):
+                head.emitter = prod._int_tail = TailCarry(last, pool, fc, [fc])
+            else:
+                head.emitter = prod._int_plan.carry = Carry(fc)
+            head.emitter.head = head
+            try:
+                qnn(sample)
+            except K.A.SSQError as e:
+                why = f"the dry forward failed: {e}"
+            else:
+                if not head.calls:
+                    why = "the dry forward did not bring pooled codes to the fc"
+            _reset_calls(qnn)
+            if why is not None:
+                pool._int_head = None
+                if isinstance(prod, BaseQuantBlock):
+                    prod._int_tail = None
+                else:
+                    prod._int_plan.carry = None
+        if why is not None:
+            fc._int_plan = None
+            report[names[fc]] = f"no head edge: {why}"
+
+
 def disable_integer_inference(qnn):
     """Every layer back on the decoded fp32 path."""
     from .quant_block import BaseQuantBlock
@@ -530,6 +736,8 @@ def disable_integer_inference(qnn):
             m._int_tail = None
         elif isinstance(m, K.SsqMaxPool2d):
             m._int_stem = None
+        elif isinstance(m, K.SsqGlobalAvgPool):
+            m._int_head = None
     qnn._int_counter = None
 
 
@@ -550,7 +758,7 @@ def carry_report(qnn):
     pairs, calls = [], {}
     for n, m in _layers(qnn):
         c = getattr(getattr(m, "_int_plan", None), "carry", None)
-        if c is not None:
+        if c is not None and getattr(c, "head", None) is None:
             pairs.append((n, names[c.consumer]))
             calls[n] = c.calls
     return {"pairs": pairs, "calls": calls}
@@ -564,7 +772,8 @@ def block_carry_report(qnn):
     from .quant_block import BaseQuantBlock
     names = {m: n for n, m in qnn.named_modules()}
     tails = [(n, m) for n, m in qnn.named_modules()
-             if isinstance(m, BaseQuantBlock) and getattr(m, "_int_tail", None) is not None]
+             if isinstance(m, BaseQuantBlock) and getattr(m, "_int_tail", None) is not None
+             and getattr(m._int_tail, "head", None) is None]
     fed = {m._int_tail.entry for _, m in tails}
     fed |= {m._int_stem.entry for _, m in _layers(qnn) if getattr(m, "_int_stem", None) is not None}
     edges, calls, residual = [], {}, {}
@@ -594,3 +803,20 @@ def stem_carry_report(qnn):
             calls[n] = s.calls
             pooled.update({names[p]: k for p, k in s.pooled.items()})
     return {"edges": edges, "calls": calls, "pooled": pooled}
+
+
+def head_carry_report(qnn):
+    """{"edges": [(producer name, pool name, fc name), ...] the installed plan carries int8
+    codes along, "calls": {producer name: forwards that emitted codes for the pool}, "pooled":
+    {pool name: forwards that summed codes (ssq_avgpool_i8_digits_fwd)}, "fc": {fc name: forwards
+    on ssq_qlinear_pooled_fwd}}; empty without a plan."""
+    names = {m: n for n, m in qnn.named_modules()}
+    out = {"edges": [], "calls": {}, "pooled": {}, "fc": {}}
+    for m in qnn.modules():
+        h = getattr(m, "_int_head", None) if isinstance(m, K.SsqGlobalAvgPool) else None
+        if h is not None:
+            out["edges"].append((names[h.producer], names[h.pool], names[h.fc]))
+            out["calls"][names[h.producer]] = h.emitter.calls
+            out["pooled"][names[h.pool]] = h.pooled
+            out["fc"][names[h.fc]] = h.calls
+    return out

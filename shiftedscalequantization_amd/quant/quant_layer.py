@@ -389,6 +389,18 @@ class QuantModule(nn.Module):
         plan = getattr(self, '_int_plan', None)
         integer = (plan is not None and not torch.is_grad_enabled() and self.use_weight_quant
                    and self.use_act_quant and self.cache_features == 'none')
+        pc = getattr(input, '_ssq_pooled', None)
+        if pc is not None:
+            # a carried head's pooled digits (quant/integer.py, carry_head): the planned fc's
+            # operand and nothing else's -- they stand for no fp32 tensor, so never decoded
+            head = plan.head if integer else None
+            if head is None or not head.accepts(pc):
+                raise K.A.SSQError(f"{self.pathName or 'layer'}: pooled code digits reached a "
+                                   f"layer that is not their planned fc")
+            out = head.run(input, pc)
+            return out if bias is None else out + bias.view(1, -1)
+        # (an fc planned for pooled digits only takes any other input on the decoded path)
+        integer = integer and plan.head is None
         cc = getattr(input, '_ssq_codes', None)
         if cc is not None and not (integer and plan.accepts(cc)):
             # a carrying producer's int8 codes (quant/integer.py) that are not this layer's

@@ -42,6 +42,10 @@ class QuantModel(nn.Module):
             elif type(child_module) is nn.MaxPool2d and K.MAXPOOL_HIP:
                 # the stem's pool on ssq_maxpool2d_fwd (same results as torch's)
                 setattr(module, name, K.SsqMaxPool2d.wrap(child_module))
+            elif K.SsqGlobalAvgPool.wraps(child_module):
+                # the pool in front of the fc: the wrapped module's forward, and the code pool
+                # of a carried head (quant/integer.py, carry_head)
+                setattr(module, name, K.SsqGlobalAvgPool.wrap(child_module))
             else:
                 self.quant_module_refactor(child_module, weight_quant_params, act_quant_params,
                                            depth + 1, moduleName=curName)

@@ -1,0 +1,256 @@
+"""Carried pooling head (quant/integer.py, carry_head), host side: `head_edges` decides from the
+structure of a CPU-built model alone, the two new entry points (ssq_avgpool_i8_digits_fwd,
+ssq_qlinear_pooled_fwd) are declared, exported, bound and refuse bad arguments without a GPU,
+--int_infer_carry_head implies the flags below it, and MobileNetV2's `pool` module leaves its
+fp32 forward bit for bit what it was."""
+import ctypes as C
+import os
+import re
+
+import pytest
+import torch
+import torch.nn as nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("ssq_avgpool_i8_digits_fwd", "ssq_qlinear_pooled_fwd")
+EMPTY = {"edges": [], "calls": {}, "pooled": {}, "fc": {}}
+
+
+def cpu_qnn(arch):
+    from shiftedscalequantization_amd import drivers as D
+    return D.build_qnn(arch, 2, 4, device="cpu")
+
+
+def named(qnn):
+    from shiftedscalequantization_amd.quant import head_edges
+    names = {m: n for n, m in qnn.named_modules()}
+    return [tuple(names[m] for m in e) for e in head_edges(qnn)]
+
+
+# ---------------------------------------------------------------- structure
+@pytest.mark.parametrize("arch,edge", [
+    ("resnet18", ("model.layer4.1", "model.avgpool", "model.fc")),
+    ("resnet34", ("model.layer4.2", "model.avgpool", "model.fc")),
+    ("resnet50", ("model.layer4.2", "model.avgpool", "model.fc")),
+    ("mobilenetv2", ("model.features.18.0", "model.pool", "model.classifier.1")),
+    ("regnetx_600m", ("model.s4.b7", "model.avgpool", "model.fc"))])
+def test_head_edges_of_the_model_zoo(arch, edge):
+    import torch.nn.functional as F
+    from shiftedscalequantization_amd import kernels as K
+    from shiftedscalequantization_amd.quant import QuantModule
+    from shiftedscalequantization_amd.quant.quant_block import BaseQuantBlock
+    qnn = cpu_qnn(arch)
+    assert named(qnn) == [edge]
+    mods = dict(qnn.named_modules())
+    prod, pool, fc = (mods[n] for n in edge)
+    assert isinstance(prod, QuantModule if arch == "mobilenetv2" else BaseQuantBlock)
+    assert isinstance(pool, K.SsqGlobalAvgPool) and pool.flat == (arch == "mobilenetv2")
+    assert isinstance(fc, QuantModule) and fc.fwd_func is F.linear
+    # the producer is the last layer in front of the pool: the model's last conv is its own
+    convs = [m for m in qnn.modules() if isinstance(m, QuantModule) and m.fwd_func is F.conv2d]
+    assert convs[-1] in list(prod.modules())
+
+
+def test_no_head_edge_without_head_chain():
+    qnn = cpu_qnn("resnet18")
+    assert callable(qnn.model.head_chain) and len(qnn.model.head_chain()) == 3
+    qnn.model.head_chain = None               # the instance no longer declares its head
+    assert named(qnn) == []
+
+
+@pytest.mark.parametrize("arch", ["resnet18", "mobilenetv2"])
+def test_no_head_edge_with_another_module_between_pool_and_fc(arch):
+    qnn = cpu_qnn(arch)
+    if arch == "resnet18":
+        chain = qnn.model.head_chain()
+        qnn.model.head_chain = lambda: chain[:2] + [nn.Sequential(nn.Hardswish(), chain[2])]
+    else:
+        qnn.model.classifier[0] = nn.Hardswish()      # where the Dropout stood
+    assert named(qnn) == []
+
+
+def test_dropout_flatten_and_identities_may_stand_between_pool_and_fc():
+    qnn = cpu_qnn("resnet18")
+    chain = qnn.model.head_chain()
+    qnn.model.head_chain = lambda: chain[:2] + [nn.Sequential(nn.Flatten(), nn.Identity(),
+                                                               nn.Dropout(0.2), chain[2])]
+    assert named(qnn) == [("model.layer4.1", "model.avgpool", "model.fc")]
+
+
+def test_no_head_edge_for_a_pool_that_is_not_the_global_average():
+    qnn = cpu_qnn("resnet18")
+    qnn.model.avgpool = nn.AdaptiveAvgPool2d(2)
+    assert named(qnn) == []
+    qnn = cpu_qnn("resnet18")
+    chain = qnn.model.head_chain()
+    qnn.model.head_chain = lambda: [chain[1], chain[1], chain[2]]     # no producer
+    assert named(qnn) == []
+
+
+def test_quant_model_wraps_the_global_pools_only():
+    from shiftedscalequantization_amd import kernels as K
+    from shiftedscalequantization_amd import nets
+    assert K.SsqGlobalAvgPool.wraps(nn.AdaptiveAvgPool2d(1))
+    assert K.SsqGlobalAvgPool.wraps(nn.AdaptiveAvgPool2d((1, 1)))
+    assert K.SsqGlobalAvgPool.wraps(nets.GlobalMeanPool())
+    assert not K.SsqGlobalAvgPool.wraps(nn.AdaptiveAvgPool2d(2))
+    assert not K.SsqGlobalAvgPool.wraps(nn.AdaptiveAvgPool2d((1, 2)))
+    assert not K.SsqGlobalAvgPool.wraps(nn.AvgPool2d(7))
+    x = torch.randn(2, 5, 3, 4, generator=torch.Generator().manual_seed(3))
+    a = K.SsqGlobalAvgPool.wrap(nn.AdaptiveAvgPool2d((1, 1)))
+    assert torch.equal(a(x), nn.AdaptiveAvgPool2d((1, 1))(x)) and a(x).shape == (2, 5, 1, 1)
+    b = K.SsqGlobalAvgPool.wrap(nets.GlobalMeanPool())
+    assert torch.equal(b(x), x.mean([2, 3])) and b(x).shape == (2, 5)
+
+
+def test_mobilenetv2_fp32_forward_is_unchanged_by_the_pool_module():
+    from shiftedscalequantization_amd import nets
+    torch.manual_seed(7)
+    m = nets.mobilenetv2().eval()
+    assert isinstance(m.pool, nets.GlobalMeanPool) and not list(m.pool.parameters())
+    assert not any(k.startswith("pool") for k in m.state_dict())
+    x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(8))
+    with torch.no_grad():
+        y = m(x)
+        ref = m.classifier(m.features(x).mean([2, 3]))
+    assert torch.equal(y, ref) and y.shape == (2, 1000)
+
+
+# ---------------------------------------------------------------- ABI
+def test_new_symbols_declared_exported_and_bound():
+    from shiftedscalequantization_amd import _capi
+    from shiftedscalequantization_amd.build import HEADERS, SOURCES
+    src = open(os.path.join(ROOT, "include", "ssq.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    lib = _capi.load()
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for s in NEW + ("ssq_qlinear_pooled_set_tile",):
+        m = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % s, src)
+        assert m and hasattr(lib, s) and s in _capi.SIGNATURES, s
+        assert len(_capi.SIGNATURES[s][1]) == m.group(1).count(",") + 1, s
+        assert s in doc, s
+    assert "qinfer_head.hip" in SOURCES and "qinfer_layout.h" in HEADERS
+
+
+def _fake():
+    return C.c_void_p(256)     # non-null, never dereferenced: the checks return before any launch
+
+
+def _avg(lib, codes=True, hi=True, lo=True, sp=True, shape=(1, 16, 7, 7)):
+    f = _fake
+    return lib.ssq_avgpool_i8_digits_fwd(f() if codes else None, *shape, f() if hi else None,
+                                         f() if lo else None, f() if sp else None, None)
+
+
+def test_avgpool_digits_refuses_bad_arguments_without_gpu():
+    from shiftedscalequantization_amd import _capi
+    lib = _capi.load()
+    err = lib.ssq_last_error
+    for kw in (dict(codes=False), dict(hi=False), dict(lo=False), dict(sp=False)):
+        assert _avg(lib, **kw) == -1 and b"null" in err()
+    assert _avg(lib, shape=(0, 16, 7, 7)) == -1 and b"geometry" in err()
+    assert _avg(lib, shape=(1, 0, 7, 7)) == -1 and b"geometry" in err()
+    assert _avg(lib, shape=(1, 16, 0, 7)) == -1 and b"geometry" in err()
+    assert _avg(lib, shape=(1, 16, 1, 127)) == -1 and b"exceeds 126" in err()
+    assert _avg(lib, shape=(1, 16, 127, 1)) == -1 and b"exceeds 126" in err()
+    assert _avg(lib, shape=(1, 16, 12, 11)) == -1 and b"exceeds 126" in err()
+    assert _avg(lib, shape=(1, 16, 1 << 31, 1 << 31)) == -1 and b"exceeds 126" in err()
+    assert _avg(lib, shape=(1, 65537, 7, 7)) == -1 and b"65536" in err()
+    assert _avg(lib, shape=(1 << 20, 64, 9, 14)) == -1 and b"2^31" in err()
+    assert _avg(lib, shape=(1 << 40, 64, 9, 14)) == -1 and b"2^31" in err()
+
+
+def _fc(lib, hi=True, lo=True, sp=True, prep=True, sh=True, y=True, N=2, Ci=16, Co=10, HW=49,
+        z=0.0, qmin=0, qmax=255):
+    f = _fake
+    return lib.ssq_qlinear_pooled_fwd(f() if hi else None, f() if lo else None,
+                                      f() if sp else None, f() if prep else None,
+                                      f() if sh else None, N, Ci, Co, HW, z, qmin, qmax,
+                                      f() if y else None, None)
+
+
+def test_qlinear_pooled_refuses_bad_arguments_without_gpu():
+    from shiftedscalequantization_amd import _capi
+    lib = _capi.load()
+    err = lib.ssq_last_error
+    for kw in (dict(hi=False), dict(lo=False), dict(sp=False), dict(prep=False), dict(sh=False),
+               dict(y=False)):
+        assert _fc(lib, **kw) == -1 and b"null" in err()
+    for kw in (dict(N=0), dict(Ci=0), dict(Co=0)):
+        assert _fc(lib, **kw) == -1 and b"geometry" in err()
+    for hw in (0, 127, -1, 1 << 40):
+        assert _fc(lib, HW=hw) == -1 and b"digit range" in err()
+    assert _fc(lib, Ci=65537) == -1 and b"65536" in err()
+    assert _fc(lib, qmin=0, qmax=256) == -1 and b"8-bit" in err()
+    assert _fc(lib, qmin=3, qmax=3) == -1 and b"8-bit" in err()
+    for z in (0.5, 256.0, -1.0, float("nan")):
+        assert _fc(lib, z=z) == -1 and b"zero point" in err()
+    assert _fc(lib, N=1 << 30, Ci=64) == -1 and b"2^31" in err()
+    assert _fc(lib, Ci=65536, Co=1 << 16) == -1 and b"2^31" in err()
+
+
+def test_tile_knob_keeps_16_or_64():
+    from shiftedscalequantization_amd import kernels as K
+    assert K.qlinear_pooled_tile() == 16           # the default; 0 only queries
+    assert K.qlinear_pooled_tile(64) == 16 and K.qlinear_pooled_tile(32) == 64
+    assert K.qlinear_pooled_tile(16) == 64 and K.qlinear_pooled_tile() == 16
+
+
+def test_wrappers_refuse_without_gpu():
+    from shiftedscalequantization_amd import kernels as K
+    from shiftedscalequantization_amd._capi import SSQError
+    with pytest.raises(SSQError, match="int8"):
+        K.avgpool_codes(torch.zeros(1, 7, 7, 16))                            # not int8
+    with pytest.raises(SSQError, match="HIP"):
+        K.avgpool_codes(torch.zeros(1, 7, 7, 16, dtype=torch.int8))          # a CPU tensor
+    d = torch.zeros(2, 16, dtype=torch.int8)
+    sp = torch.zeros(2, dtype=torch.int32)
+    with pytest.raises(SSQError, match="int8 digits"):
+        K.qlinear_pooled(d.float(), d, sp, None, torch.ones(10), 49)
+    with pytest.raises(SSQError, match="int32"):
+        K.qlinear_pooled(d, d, sp.float(), None, torch.ones(10), 49)
+    with pytest.raises(SSQError, match="HIP"):
+        K.qlinear_pooled(d, d, sp, None, torch.ones(10), 49)
+    # pooled digits stand for no fp32 tensor: nothing decodes them
+    t = K.pooled(d, d, sp, (2, 16), 49, 0.1, 0.0, 8, False)
+    assert t is d and t._ssq_pooled.HW == 49 and not hasattr(t, "_ssq_codes")
+    with pytest.raises(SSQError, match="planned fc"):
+        K.materialize_epi(t)
+
+
+def test_head_scale_is_one_rounded_fp32_division():
+    import numpy as np
+    from shiftedscalequantization_amd import kernels as K
+    s = torch.rand(37, generator=torch.Generator().manual_seed(5)) * 1e-3 + 1e-6
+    for hw in (1, 3, 49, 126):
+        want = (s.numpy().astype(np.float64) / hw).astype(np.float32)
+        assert np.array_equal(K.head_scale(s, hw).numpy().view(np.int32), want.view(np.int32))
+
+
+# ---------------------------------------------------------------- CLI, API
+def test_cli_int_infer_carry_head_implies_the_flags_below_it():
+    from shiftedscalequantization_amd.cli import parse_args
+    a = parse_args(["--int_infer_carry_head"])
+    assert (a.int_infer_carry_head and a.int_infer_carry_stem and a.int_infer_carry_blocks
+            and a.int_infer_carry and a.int_infer and not a.int_infer_grouped)
+    a = parse_args(["--int_infer_carry_stem"])
+    assert a.int_infer_carry_stem and not a.int_infer_carry_head
+    assert not parse_args([]).int_infer_carry_head
+
+
+def test_reports_are_empty_without_a_plan():
+    from shiftedscalequantization_amd import quant as Q
+    qnn = cpu_qnn("resnet18")
+    assert Q.head_carry_report(qnn) == EMPTY
+    Q.disable_integer_inference(qnn)
+    assert Q.head_carry_report(qnn) == EMPTY and qnn.model.avgpool._int_head is None
+
+
+def test_a_pooled_tensor_at_an_unplanned_layer_raises():
+    from shiftedscalequantization_amd import kernels as K
+    from shiftedscalequantization_amd._capi import SSQError
+    qnn = cpu_qnn("resnet18")
+    d = torch.zeros(2, 512, dtype=torch.int8)
+    t = K.pooled(d, d, torch.zeros(2, dtype=torch.int32), (2, 512), 49, 0.1, 0.0, 8, False)
+    with torch.no_grad(), pytest.raises(SSQError, match="planned fc"):
+        qnn.model.fc(t)
