@@ -824,6 +824,59 @@ int ssq_epilogue_codes_fwd(const float* y, const float* bias, const float* gamma
 int ssq_maxpool_i8_fwd(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W, int64_t K,
                        int64_t stride, int64_t pad, int8_t* out, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- column-scaled weights
+ * A weight with a per-column input scale on a common integer grid,
+ *     W_hat[co, j] = ((q_w - z_w[co]) * d1[co]) * c[j],  c[j] = fp32(kcol[j] / L),  j = (ci, r, s)
+ * (ChannelQuantMSE; kcol[j] in 1..L, L <= 127 found by the caller), runs on the same kernels
+ * with the centred integer m[co, j] = (q_w - z_w[co]) * kcol[j] as the int8 operand:
+ *     I = sum_j (q_a - z_a) m[co, j] = D + az * T[co],  D = sum a_s m,  T[co] = sum_j m[co, j]
+ * exact for K <= 65536 (|a_s| <= 128, |m| <= 127), and y = fp32(I) * scale[co] with the caller's
+ * scale[co] = fp32(fp32(delta_a * d1[co]) / fp32(L)): one conversion, one multiply, as above.
+ *
+ * ssq_qweight_prepare_colscale / ssq_qweight_prepare_grouped_colscale: ssq_qweight_prepare /
+ * ssq_qweight_prepare_grouped with kcol (device int32 [Ci*R*S], [Cig*R*S] shared by all groups):
+ * the same byte count and layout, holding m, cwz = 0, T[co] = sum m and the 0/1 row(s) (the
+ * depthwise int32 blob is the centred weight times kcol[tap]), so every reader of a prepared
+ * blob (ssq_qconv_i8_*_fwd, ssq_qconv_i8_grouped_*_fwd, ssq_qlinear_pooled_fwd) runs it as it
+ * stands.  *bad also receives the number of real elements with |m| > 127 (stored saturated) or
+ * with kcol[j] outside [1, 127]: a blob prepared with *bad != 0 must not be used.
+ *
+ * ssq_qconv_i8_centred_fwd / _codes_fwd / _codes_res_fwd: ssq_qconv_i8_fwd / _codes_fwd /
+ * _codes_res_fwd (same arguments, checks and results bit for bit) for a blob whose cwz is 0,
+ * i.e. one of ssq_qweight_prepare_colscale: the 0/1 row and cwz are not read and the window-sum
+ * MFMA is not issued (four per k step instead of five).  On any other blob the result is wrong. */
+int ssq_qweight_prepare_colscale(const void* packed, const float* zp, const int32_t* kcol,
+                                 int64_t Co, int64_t Ci, int64_t R, int64_t S, int n_bits,
+                                 int qmin, void* prepared, uint32_t* bad, ssq_stream_t stream);
+int ssq_qweight_prepare_grouped_colscale(const void* packed, const float* zp, const int32_t* kcol,
+                                         int64_t Co, int64_t Cig, int64_t R, int64_t S,
+                                         int64_t groups, int n_bits, int qmin, void* prepared,
+                                         uint32_t* bad, ssq_stream_t stream);
+int ssq_qconv_i8_centred_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                             int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R,
+                             int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                             float act_zero_point, int act_qmin, int act_qmax, float* y,
+                             ssq_stream_t stream);
+int ssq_qconv_i8_centred_codes_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                   int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                   int64_t R, int64_t S, int64_t stride, int64_t pad,
+                                   int64_t groups, float act_zero_point, int act_qmin,
+                                   int act_qmax, const float* bias, const float* gamma,
+                                   const float* phi, int act, float out_delta,
+                                   float out_zero_point, int out_qmin, int out_qmax,
+                                   int8_t* out_codes, uint32_t* bad, ssq_stream_t stream);
+int ssq_qconv_i8_centred_codes_res_fwd(const int8_t* codes, const void* prepared,
+                                       const float* scale, int64_t Nb, int64_t Ci, int64_t H,
+                                       int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
+                                       int64_t pad, int64_t groups, float act_zero_point,
+                                       int act_qmin, int act_qmax, const float* bias,
+                                       const float* gamma, const float* phi, int act,
+                                       float out_delta, float out_zero_point, int out_qmin,
+                                       int out_qmax, int8_t* out_codes, uint32_t* bad,
+                                       const float* res_f32, const int8_t* res_codes,
+                                       float res_delta, float res_zero_point, int res_qmin,
+                                       int res_qmax, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- pooling head on codes (K29, K30)
  * The global average pool and the fc behind it on stored codes, with a numerics contract of
  * their own (the fc has no input quantizer, so the pooled value is never re-quantized):

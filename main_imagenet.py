@@ -65,6 +65,48 @@ def val_loader(val, bs=256):
     return [(images[i:i + bs], labels[i:i + bs]) for i in range(0, len(images), bs)]
 
 
+def run_integer_inference(qnn, args, cali, loader, bs=32):
+    """Install the integer route the --int_infer* flags ask for, print the plan and validate
+    (or run one batch) on it."""
+    from shiftedscalequantization_amd.quant import (block_carry_report, carry_report,
+                                                     enable_integer_inference,
+                                                     head_carry_report, integer_report,
+                                                     stem_carry_report)
+    plan = enable_integer_inference(qnn, cali[:8], grouped=args.int_infer_grouped,
+                                    carry=args.int_infer_carry,
+                                    carry_blocks=args.int_infer_carry_blocks,
+                                    carry_stem=args.int_infer_carry_stem,
+                                    carry_head=args.int_infer_carry_head,
+                                    colscale=args.int_infer_colscale)
+    n_int = sum(v == 'int8' for v in plan.values())
+    print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
+    if args.int_infer_carry:
+        pairs = carry_report(qnn)['pairs']
+        print(f'integer inference: int8 codes carried between {len(pairs)} pairs: '
+              + ', '.join(f'{a} -> {b}' for a, b in pairs))
+    if args.int_infer_carry_blocks:
+        edges = block_carry_report(qnn)['edges']
+        print(f'integer inference: int8 codes carried across {len(edges)} block edges: '
+              + ', '.join(f'{a} -> {b}' for a, b in edges))
+    if args.int_infer_carry_stem:
+        edges = stem_carry_report(qnn)['edges']
+        print(f'integer inference: int8 codes carried from {len(edges)} stem edges: '
+              + ', '.join(' -> '.join([a] + pools + [b]) for a, pools, b in edges))
+    if args.int_infer_carry_head:
+        edges = head_carry_report(qnn)['edges']
+        print(f'integer inference: int8 codes carried to the logits along {len(edges)} head '
+              'edges: ' + ', '.join(' -> '.join(e) for e in edges))
+    for name, why in plan.items():
+        print(f'  {name}: {why}')
+    if loader is not None:
+        print('Integer inference (W{}A{}) accuracy: {}'.format(args.n_bits_w, args.n_bits_a,
+                                                               validate_model(loader, qnn)))
+    else:
+        with torch.no_grad():
+            qnn(cali[:bs])
+    print(f'integer inference: {integer_report(qnn)["off_grid"]} off-grid activations')
+
+
 def main(argv=None):
     args = parse_args(argv)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -101,6 +143,16 @@ def main(argv=None):
         acc = validate_model(loader, qnn) if loader is not None else None
         print(f'channelShift_wMSE (level {args.mse_level}, threshold {args.mse_threshold}) '
               f'finished in {time.time() - t0:.1f}s; accuracy of qnn_hard: {acc}')
+        if args.int_infer_colscale:
+            # the shipped path on integer codes: the column-scaled weights on their common
+            # integer grid, the act quantizers initialised on the calibration head
+            qnn.set_quant_state(True, True)
+            with torch.no_grad():
+                qnn(cali[:64])
+            if world > 1:
+                qnn.synchorize_activation_statistics()
+            qnn.disable_network_output_quantization()
+            run_integer_inference(qnn, args, cali, loader)
         if world > 1:
             dist.destroy_process_group()
         return qnn
@@ -153,42 +205,7 @@ def main(argv=None):
             print('Full quantization (W{}A{}) accuracy: {}'.format(args.n_bits_w, args.n_bits_a,
                                                                    validate_model(loader, qnn)))
     if args.int_infer and args.act_quant:
-        from shiftedscalequantization_amd.quant import (block_carry_report, carry_report,
-                                                         enable_integer_inference,
-                                                         head_carry_report, integer_report,
-                                                         stem_carry_report)
-        plan = enable_integer_inference(qnn, cali[:8], grouped=args.int_infer_grouped,
-                                        carry=args.int_infer_carry,
-                                        carry_blocks=args.int_infer_carry_blocks,
-                                        carry_stem=args.int_infer_carry_stem,
-                                        carry_head=args.int_infer_carry_head)
-        n_int = sum(v == 'int8' for v in plan.values())
-        print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
-        if args.int_infer_carry:
-            pairs = carry_report(qnn)['pairs']
-            print(f'integer inference: int8 codes carried between {len(pairs)} pairs: '
-                  + ', '.join(f'{a} -> {b}' for a, b in pairs))
-        if args.int_infer_carry_blocks:
-            edges = block_carry_report(qnn)['edges']
-            print(f'integer inference: int8 codes carried across {len(edges)} block edges: '
-                  + ', '.join(f'{a} -> {b}' for a, b in edges))
-        if args.int_infer_carry_stem:
-            edges = stem_carry_report(qnn)['edges']
-            print(f'integer inference: int8 codes carried from {len(edges)} stem edges: '
-                  + ', '.join(' -> '.join([a] + pools + [b]) for a, pools, b in edges))
-        if args.int_infer_carry_head:
-            edges = head_carry_report(qnn)['edges']
-            print(f'integer inference: int8 codes carried to the logits along {len(edges)} head '
-                  'edges: ' + ', '.join(' -> '.join(e) for e in edges))
-        for name, why in plan.items():
-            print(f'  {name}: {why}')
-        if loader is not None:
-            print('Integer inference (W{}A{}) accuracy: {}'.format(args.n_bits_w, args.n_bits_a,
-                                                                   validate_model(loader, qnn)))
-        else:
-            with torch.no_grad():
-                qnn(cali[:bs])
-        print(f'integer inference: {integer_report(qnn)["off_grid"]} off-grid activations')
+        run_integer_inference(qnn, args, cali, loader, bs)
     print(f'calibration finished in {time.time() - t0:.1f}s '
           f'({", ".join(f"{k} {v:.1f}s" for k, v in phases.items())}); block rec losses: '
           f'{ {k: v for k, v in report.items()} }')

@@ -155,6 +155,12 @@ SIGNATURES = {
     "ssq_stream_copy": (_i, [_p, _p, _i64, _p]),
     "ssq_stream_probe": (_i, [_p, _p, _i64, _i, _p]),
 }
+# the column-scaled prepares take kcol after zp; the centred convs take their plain twins' arguments
+SIGNATURES["ssq_qweight_prepare_colscale"] = (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _i, _i, _p, _p, _p])
+SIGNATURES["ssq_qweight_prepare_grouped_colscale"] = (_i, [_p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i, _i,
+                                                           _p, _p, _p])
+for _n in ("fwd", "codes_fwd", "codes_res_fwd"):
+    SIGNATURES[f"ssq_qconv_i8_centred_{_n}"] = SIGNATURES[f"ssq_qconv_i8_{_n}"]
 
 _lib = None
 

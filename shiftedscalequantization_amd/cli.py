@@ -92,6 +92,11 @@ def build_parser():
                    help='--int_infer_carry_stem with the codes running to the logits: the global '
                         'average pool sums the int8 codes and the fc runs on the sums (a numerics '
                         'contract of its own, DESIGN 4); implies --int_infer_carry_stem')
+    p.add_argument('--int_infer_colscale', action='store_true',
+                   help='--int_infer with column-scaled weights (ChannelQuantMSE, the --test path) '
+                        'on integer codes too: the column scale as integers k / L, L <= 127, folded '
+                        'into the int8 weight operand; with --test the act quantizers are '
+                        'initialised and the route runs after channelShift_wMSE; implies --int_infer')
     p.add_argument('--deterministic', default=1, type=int,
                    help='1 (reference): deterministic MIOpen conv solvers; 0: fastest solvers')
     # data parallel: one process per GPU, spawned by main_imagenet.py itself with --gpus N
@@ -115,7 +120,7 @@ def parse_args(argv=None):
         a.int_infer_carry_blocks = True
     if a.int_infer_carry_blocks:
         a.int_infer_carry = True
-    if a.int_infer_grouped or a.int_infer_carry:
+    if a.int_infer_grouped or a.int_infer_carry or a.int_infer_colscale:
         a.int_infer = True
     return a
 

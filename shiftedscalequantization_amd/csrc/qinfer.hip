@@ -31,6 +31,11 @@
 // pixels: a store instruction writes 16 consecutive pixels per channel of the NCHW output)
 // plus one for SA.  Both operand fragments use the same lane map (row / column l & 15,
 // k chunk l >> 4), so the product does not depend on the k order inside a step.
+//
+// Column-scaled weights, W_hat = ((q_w - z_w[co]) * d1[co]) * (kcol[j] / L), j = (ci, r, s): the
+// prepared operand is the centred integer m = (q_w - z_w[co]) * kcol[j] itself (|m| <= 127), so
+// cwz = 0, I = D + az * T[co] with T[co] = sum m, and the CENTRED instantiation of K23 drops the
+// 0/1 row and the SA MFMA; the caller's s[co] = fp32(fp32(delta_a * d1[co]) / fp32(L)).
 #include <type_traits>
 
 #include "ssq_common.h"
@@ -141,12 +146,88 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_kernel(
   }
 }
 
+// K22 for a column-scaled weight W_hat = ((q - z_w[co]) * d1[co]) * (kcol[j] / L), j = (ci, r, s):
+// the operand is the centred integer m = (q - z_w[co]) * kcol[j] itself (zero on padded channels
+// and on the K tail), so cwz = 0 and T[co] = sum m; the 0/1 row is written as above, so every
+// reader of the layout runs the blob as it stands.  *bad also counts the real elements whose m
+// leaves [-127, 127] (stored saturated) and those whose kcol[j] is not in [1, 127].
+__global__ __launch_bounds__(kBlock) void qweight_prepare_colscale_kernel(
+    const uint8_t* __restrict__ packed, const float* __restrict__ zp,
+    const int32_t* __restrict__ kcol, int bs, int qmin, uint32_t Co, uint32_t Ci, uint32_t RS,
+    uint32_t Cp, uint32_t Kp, uint32_t Cop, FastDiv div_cp, int8_t* __restrict__ wp,
+    int8_t* __restrict__ mask, int32_t* __restrict__ cwz, int32_t* __restrict__ tt,
+    uint32_t* __restrict__ bad) {
+  __shared__ int red[kBlock / kWave];
+  const uint32_t co = blockIdx.x;
+  if (co == Cop) {
+    for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
+      const uint32_t tap = fdiv(k, div_cp);
+      mask[k] = (tap < RS && k - tap * Cp < Ci) ? 1 : 0;
+    }
+    return;
+  }
+  int z = qmin;
+  bool zok = true;
+  if (co < Co) {
+    const float zf = zp[co];
+    zok = zf == rintf(zf) && zf >= (float)(qmin - 256) && zf <= (float)(qmin + 511);
+    if (zok) z = (int)zf;
+  }
+  int sum = 0;
+  uint32_t nbad = 0;
+  for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
+    const uint32_t tap = fdiv(k, div_cp);
+    const uint32_t ci = k - tap * Cp;
+    int v = 0;
+    if (co < Co && tap < RS && ci < Ci) {
+      const size_t j = (size_t)ci * RS + tap;
+      const size_t bit = ((size_t)co * Ci * RS + j) * (size_t)bs;
+      const uint32_t u = ((uint32_t)packed[bit >> 3] >> (bit & 7)) & ((1u << bs) - 1u);
+      int kj = kcol[j];
+      if (kj < 1 || kj > 127) {
+        ++nbad;
+        kj = 0;
+      }
+      v = ((int)u + qmin - z) * kj;   // |q - z| <= 767, kj <= 127: no overflow
+      if (v > 127 || v < -127) {
+        ++nbad;
+        v = v > 0 ? 127 : -127;
+      }
+      sum += v;
+    }
+    wp[(size_t)co * Kp + k] = (int8_t)v;
+  }
+  sum = (int)wave_sum_u32((uint32_t)sum);
+  nbad = wave_sum_u32(nbad);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    red[threadIdx.x / kWave] = sum;
+    if (nbad) atomicAdd(bad, nbad);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int total = 0;
+    for (int i = 0; i < kBlock / kWave; ++i) total += red[i];
+    if (!zok) atomicAdd(bad, 1u);
+    cwz[co] = 0;
+    tt[co] = co < Co ? total : 0;
+  }
+}
+
 // ---------------------------------------------------------------- K23 int8 implicit-GEMM conv
 struct QConvGeo {
   uint32_t M, P, OW, H, W, Cp, Co, Kp, RS, S;
   int stride, pad, az, padv;
   FastDiv div_p, div_ow, div_cp, div_s;
 };
+
+// the epilogue's integer sum of channel co: I = D + cwz[co] * SA + az * T[co]; centred, cwz = 0
+template <bool CENTRED>
+__device__ __forceinline__ long long qconv_sum(int d, const int32_t* __restrict__ cwz,
+                                               long long sa, int az,
+                                               const int32_t* __restrict__ tt, uint32_t co) {
+  if constexpr (CENTRED) return (long long)d + (long long)az * (long long)tt[co];
+  else return (long long)d + (long long)cwz[co] * sa + (long long)az * (long long)tt[co];
+}
 
 // CODES: the code-emitting epilogue (qinfer_epi.h) instead of the fp32 NCHW store; `y` is then
 // the QEpi.  The 64 px x 64 ch code tile is transposed through the (then free) activation
@@ -156,7 +237,10 @@ struct QConvGeo {
 // form's store pattern); 2: int8 codes in the output's own layout, one aligned dword (the
 // lane's 4 channels of its pixel) per fragment.  `y` is then the QEpiRes.  The loads are issued
 // right after the K loop, so the cwz / T correction arithmetic covers their latency.
-template <bool CODES, int RES = 0>
+// CENTRED: the blob holds a centred operand (ssq_qweight_prepare_colscale: cwz = 0), so SA is
+// not needed: no 0/1 row load, LDS store or fragment read, no SA MFMA (four per k step, not
+// five) and I = D + az * T[co].  `mask` and `cwz` are not read.
+template <bool CODES, int RES = 0, bool CENTRED = false>
 __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
     const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ mask,
     const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
@@ -200,7 +284,9 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
   i32x4 ra = load_a(0);
   i32x4 rb = *(const i32x4*)wrow;
   i32x4 rm = {0, 0, 0, 0};
-  if (tid < 4) rm = *(const i32x4*)(mask + tid * 16);
+  if constexpr (!CENTRED) {
+    if (tid < 4) rm = *(const i32x4*)(mask + tid * 16);
+  }
 
   i32x4 acc[4];
 #pragma unroll
@@ -212,16 +298,22 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
     __syncthreads();   // the previous step's fragment reads are done
     *(i32x4*)(lA + srow * kQRow + sc * 16) = ra;
     *(i32x4*)(lB + srow * kQRow + sc * 16) = rb;
-    if (tid < 4) *(i32x4*)(lB + kQT * kQRow + tid * 16) = rm;
+    if constexpr (!CENTRED) {
+      if (tid < 4) *(i32x4*)(lB + kQT * kQRow + tid * 16) = rm;
+    }
     __syncthreads();
     if (kt + 1 < nk) {
       ra = load_a(kt + 1);
       rb = *(const i32x4*)(wrow + (size_t)(kt + 1) * kQT);
-      if (tid < 4) rm = *(const i32x4*)(mask + (size_t)(kt + 1) * kQT + tid * 16);
+      if constexpr (!CENTRED) {
+        if (tid < 4) rm = *(const i32x4*)(mask + (size_t)(kt + 1) * kQT + tid * 16);
+      }
     }
     const i32x4 af = *(const i32x4*)(lA + (wave * 16 + fr) * kQRow + fq * 16);
-    const i32x4 mf = *(const i32x4*)(lB + kQT * kQRow + fq * 16);
-    accs = __builtin_amdgcn_mfma_i32_16x16x64_i8(mf, af, accs, 0, 0, 0);
+    if constexpr (!CENTRED) {
+      const i32x4 mf = *(const i32x4*)(lB + kQT * kQRow + fq * 16);
+      accs = __builtin_amdgcn_mfma_i32_16x16x64_i8(mf, af, accs, 0, 0, 0);
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const i32x4 wf = *(const i32x4*)(lB + (j * 16 + fr) * kQRow + fq * 16);
@@ -267,8 +359,7 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
         const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
         c[r] = 0;
         if (pval && co < g.Co) {
-          const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
-                              (long long)g.az * (long long)tt[co];
+          const long long I = qconv_sum<CENTRED>(acc[j][r], cwz, sa, g.az, tt, co);
           if constexpr (RES == 1) {
             c[r] = qepi_code<true>((float)I, co, scale, e, nbad, rf[j * 4 + r]);
           } else if constexpr (RES == 2) {
@@ -302,8 +393,7 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
       for (int r = 0; r < 4; ++r) {
         const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
         if (co < g.Co) {
-          const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
-                              (long long)g.az * (long long)tt[co];
+          const long long I = qconv_sum<CENTRED>(acc[j][r], cwz, sa, g.az, tt, co);
           y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
         }
       }
@@ -415,6 +505,27 @@ extern "C" int ssq_qweight_prepare(const void* packed, const float* zp, int64_t 
   return check_launch("ssq_qweight_prepare");
 }
 
+extern "C" int ssq_qweight_prepare_colscale(const void* packed, const float* zp,
+                                            const int32_t* kcol, int64_t Co, int64_t Ci, int64_t R,
+                                            int64_t S, int n_bits, int qmin, void* prepared,
+                                            uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_qweight_prepare_colscale";
+  SSQ_REQUIRE(packed && zp && kcol && prepared && bad, SSQ_E_ARG, "%s: null pointer", me);
+  int rc = qrange_ok(me, n_bits, qmin);
+  if (rc) return rc;
+  rc = qgeo_ok(me, Co, Ci, R, S);
+  if (rc) return rc;
+  const QLayout L = qlayout(Co, Ci, R, S);
+  int8_t* base = (int8_t*)prepared;
+  const int bs = n_bits <= 2 ? 2 : (n_bits <= 4 ? 4 : 8);
+  hipLaunchKernelGGL(qweight_prepare_colscale_kernel, dim3((uint32_t)L.Cop + 1), dim3(kBlock), 0,
+                     (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, bs, qmin, (uint32_t)Co,
+                     (uint32_t)Ci, (uint32_t)(R * S), (uint32_t)L.Cp, (uint32_t)L.Kp,
+                     (uint32_t)L.Cop, make_fastdiv((uint32_t)L.Cp), base, base + L.off_mask,
+                     (int32_t*)(base + L.off_cwz), (int32_t*)(base + L.off_t), bad);
+  return check_launch(me);
+}
+
 // y: the fp32 output (ssq_qconv_i8_fwd) or null with `epi` set (ssq_qconv_i8_codes_fwd); `res`
 // with `epi`: the tail's residual (ssq_qconv_i8_codes_res_fwd)
 static int qconv_i8_launch(const char* me, const int8_t* codes, const void* prepared,
@@ -422,7 +533,7 @@ static int qconv_i8_launch(const char* me, const int8_t* codes, const void* prep
                            int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
                            int64_t groups, float act_zero_point, int act_qmin, int act_qmax,
                            float* y, QEpi* epi, ssq_stream_t stream,
-                           const QRes* res = nullptr) {
+                           const QRes* res = nullptr, bool centred = false) {
   SSQ_REQUIRE(codes && prepared && scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
   SSQ_REQUIRE(groups == 1, SSQ_E_ARG, "%s: groups = %lld (only groups == 1)", me,
               (long long)groups);
@@ -465,30 +576,35 @@ static int qconv_i8_launch(const char* me, const int8_t* codes, const void* prep
   g.div_s = make_fastdiv(g.S);
   const int8_t* base = (const int8_t*)prepared;
   const dim3 grid((g.M + kQT - 1) / kQT, (uint32_t)(L.Cop / kQT));
+  // a centred blob (ssq_qweight_prepare_colscale) on the CENTRED instantiation of the same form
+#define SSQ_QCONV_LAUNCH(CODES_, RES_, OUT_)                                                      \
+  do {                                                                                            \
+    if (centred)                                                                                  \
+      hipLaunchKernelGGL((qconv_i8_kernel<CODES_, RES_, true>), grid, dim3(kBlock), 0,            \
+                         (hipStream_t)stream, codes, base, base + L.off_mask,                     \
+                         (const int32_t*)(base + L.off_cwz), (const int32_t*)(base + L.off_t),    \
+                         scale, g, OUT_);                                                         \
+    else                                                                                          \
+      hipLaunchKernelGGL((qconv_i8_kernel<CODES_, RES_>), grid, dim3(kBlock), 0,                  \
+                         (hipStream_t)stream, codes, base, base + L.off_mask,                     \
+                         (const int32_t*)(base + L.off_cwz), (const int32_t*)(base + L.off_t),    \
+                         scale, g, OUT_);                                                         \
+  } while (0)
   if (epi) {
     epi->Cpo = (uint32_t)rup(Co, 16);
     SSQ_REQUIRE(Nb * OH * OW * (int64_t)epi->Cpo < (1ll << 31), SSQ_E_ARG,
                 "%s: tensor exceeds 2^31 elements", me);
     if (res) {
       const QEpiRes er = {*epi, *res};
-      if (res->f32)
-        hipLaunchKernelGGL((qconv_i8_kernel<true, 1>), grid, dim3(kBlock), 0, (hipStream_t)stream,
-                           codes, base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
-                           (const int32_t*)(base + L.off_t), scale, g, er);
-      else
-        hipLaunchKernelGGL((qconv_i8_kernel<true, 2>), grid, dim3(kBlock), 0, (hipStream_t)stream,
-                           codes, base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
-                           (const int32_t*)(base + L.off_t), scale, g, er);
+      if (res->f32) SSQ_QCONV_LAUNCH(true, 1, er);
+      else SSQ_QCONV_LAUNCH(true, 2, er);
       return check_launch(me);
     }
-    hipLaunchKernelGGL(qconv_i8_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream, codes,
-                       base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
-                       (const int32_t*)(base + L.off_t), scale, g, *epi);
+    SSQ_QCONV_LAUNCH(true, 0, *epi);
     return check_launch(me);
   }
-  hipLaunchKernelGGL(qconv_i8_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream, codes,
-                     base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
-                     (const int32_t*)(base + L.off_t), scale, g, y);
+  SSQ_QCONV_LAUNCH(false, 0, y);
+#undef SSQ_QCONV_LAUNCH
   return check_launch(me);
 }
 
@@ -541,6 +657,59 @@ extern "C" int ssq_qconv_i8_codes_res_fwd(
   const QRes r = {res_f32, res_codes, res_delta, res_zero_point, (float)res_qmin};
   return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
                          act_zero_point, act_qmin, act_qmax, nullptr, &e, stream, &r);
+}
+
+// The same three entry points for a centred blob (ssq_qweight_prepare_colscale), on the CENTRED
+// instantiations: bit-identical to the ones above on such a blob, one MFMA per k step less.
+extern "C" int ssq_qconv_i8_centred_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                                float act_zero_point, int act_qmin, int act_qmax, float* y,
+                                ssq_stream_t stream) {
+  SSQ_REQUIRE(y, SSQ_E_ARG, "ssq_qconv_i8_centred_fwd: null pointer");
+  return qconv_i8_launch("ssq_qconv_i8_centred_fwd", codes, prepared, scale, Nb, Ci, H, W, Co, R, S,
+                         stride, pad, groups, act_zero_point, act_qmin, act_qmax, y, nullptr,
+                         stream, nullptr, true);
+}
+
+extern "C" int ssq_qconv_i8_centred_codes_fwd(const int8_t* codes, const void* prepared,
+                                      const float* scale, int64_t Nb, int64_t Ci, int64_t H,
+                                      int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
+                                      int64_t pad, int64_t groups, float act_zero_point,
+                                      int act_qmin, int act_qmax, const float* bias,
+                                      const float* gamma, const float* phi, int act,
+                                      float out_delta, float out_zero_point, int out_qmin,
+                                      int out_qmax, int8_t* out_codes, uint32_t* bad,
+                                      ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_centred_codes_fwd";
+  const int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
+                         out_codes, bad);
+  if (rc) return rc;
+  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
+            0u, out_codes, bad};
+  return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                         act_zero_point, act_qmin, act_qmax, nullptr, &e, stream, nullptr, true);
+}
+
+extern "C" int ssq_qconv_i8_centred_codes_res_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t Ci,
+    int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+    int64_t groups, float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+    const float* gamma, const float* phi, int act, float out_delta, float out_zero_point,
+    int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad, const float* res_f32,
+    const int8_t* res_codes, float res_delta, float res_zero_point, int res_qmin, int res_qmax,
+    ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_centred_codes_res_fwd";
+  int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax, out_codes,
+                   bad);
+  if (rc) return rc;
+  rc = qres_ok(me, res_f32, res_codes, res_delta, res_zero_point, res_qmin, res_qmax);
+  if (rc) return rc;
+  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
+            0u, out_codes, bad};
+  const QRes r = {res_f32, res_codes, res_delta, res_zero_point, (float)res_qmin};
+  return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                         act_zero_point, act_qmin, act_qmax, nullptr, &e, stream, &r, true);
 }
 
 extern "C" int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W,

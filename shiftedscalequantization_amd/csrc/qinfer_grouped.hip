@@ -178,6 +178,107 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_kernel(
   }
 }
 
+// K24 for a column-scaled weight W_hat = ((q - z_w[co]) * d1[co]) * (kcol[j] / L), j = (ci, r, s)
+// within the group (J = Cig*R*S, shared by all groups): the operand is the centred integer
+// m = (q - z_w[co]) * kcol[j].  *bad also counts the real elements whose m leaves [-127, 127]
+// (stored saturated) and those whose kcol[j] is not in [1, 127].
+__device__ __forceinline__ int colscaled(int centred, int kj, uint32_t& nbad) {
+  if (kj < 1 || kj > 127) {
+    ++nbad;
+    kj = 0;
+  }
+  int v = centred * kj;   // |q - z| <= 767, kj <= 127: no overflow
+  if (v > 127 || v < -127) {
+    ++nbad;
+    v = v > 0 ? 127 : -127;
+  }
+  return v;
+}
+
+// depthwise: K25's centred int32 blob [R*S][Cp] multiplied by kcol[tap]
+__global__ __launch_bounds__(kBlock) void qweight_prepare_dw_colscale_kernel(
+    const uint8_t* __restrict__ packed, const float* __restrict__ zp,
+    const int32_t* __restrict__ kcol, int bs, int qmin, uint32_t C, uint32_t RS, uint32_t Cp,
+    FastDiv div_cp, int32_t* __restrict__ wc, uint32_t* __restrict__ bad) {
+  const uint32_t total = RS * Cp;
+  uint32_t nbad = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const uint32_t tap = fdiv(i, div_cp);
+    const uint32_t c = i - tap * Cp;
+    int v = 0;
+    if (c < C) {
+      const float zf = zp[c];
+      const bool ok = zp_is_code(zf, qmin);
+      const int z = ok ? (int)zf : qmin;
+      if (!ok && tap == 0) ++nbad;   // counted once per channel
+      v = colscaled((int)packed_code(packed, (size_t)c * RS + tap, bs) + qmin - z, kcol[tap], nbad);
+    }
+    wc[i] = v;
+  }
+  if (nbad) atomicAdd(bad, nbad);
+}
+
+// grouped: K26's blob with m as the int8 operand, cwz = 0, T[co] = sum m, the 0/1 rows as above
+__global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_colscale_kernel(
+    const uint8_t* __restrict__ packed, const float* __restrict__ zp,
+    const int32_t* __restrict__ kcol, int bs, int qmin, uint32_t groups, uint32_t Cig,
+    uint32_t Cog, uint32_t Cogp, uint32_t RS, uint32_t Wc, uint32_t Kp, FastDiv div_wc,
+    FastDiv div_cogp, int8_t* __restrict__ wp, int8_t* __restrict__ mask,
+    int32_t* __restrict__ cwz, int32_t* __restrict__ tt, uint32_t* __restrict__ bad) {
+  __shared__ int red[kBlock / kWave];
+  const uint32_t row = blockIdx.x;
+  const uint32_t nrows = groups * Cogp;
+  if (row >= nrows) {
+    const uint32_t g = row - nrows;
+    const uint32_t lo = g * Cig - g * Cig / 16 * 16;   // the group's offset inside its window
+    for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
+      const uint32_t tap = fdiv(k, div_wc);
+      const uint32_t cw = k - tap * Wc;
+      mask[(size_t)g * Kp + k] = (tap < RS && cw >= lo && cw < lo + Cig) ? 1 : 0;
+    }
+    return;
+  }
+  const uint32_t g = fdiv(row, div_cogp);
+  const uint32_t rl = row - g * Cogp;
+  const uint32_t co = g * Cog + rl;
+  const bool real = rl < Cog;
+  const uint32_t lo = g * Cig - g * Cig / 16 * 16;
+  int z = qmin;
+  bool zok = true;
+  if (real) {
+    zok = zp_is_code(zp[co], qmin);
+    if (zok) z = (int)zp[co];
+  }
+  int sum = 0;
+  uint32_t nbad = 0;
+  for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
+    const uint32_t tap = fdiv(k, div_wc);
+    const uint32_t cw = k - tap * Wc;
+    int v = 0;
+    if (real && tap < RS && cw >= lo && cw < lo + Cig) {
+      const size_t j = (size_t)(cw - lo) * RS + tap;
+      v = colscaled((int)packed_code(packed, (size_t)co * Cig * RS + j, bs) + qmin - z, kcol[j],
+                    nbad);
+      sum += v;
+    }
+    wp[(size_t)row * Kp + k] = (int8_t)v;
+  }
+  sum = (int)gwave_sum_u32((uint32_t)sum);
+  nbad = gwave_sum_u32(nbad);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    red[threadIdx.x / kWave] = sum;
+    if (nbad) atomicAdd(bad, nbad);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && real) {
+    int total = 0;
+    for (int i = 0; i < kBlock / kWave; ++i) total += red[i];
+    if (!zok) atomicAdd(bad, 1u);
+    cwz[co] = 0;
+    tt[co] = total;
+  }
+}
+
 // ---------------------------------------------------------------- K25 depthwise direct conv
 struct QDwGeo {
   uint32_t M, P, OW, H, W, C, Cp, R, S, nch, per;   // per: chunks per workgroup (blockIdx.y)
@@ -505,6 +606,39 @@ extern "C" int ssq_qweight_prepare_grouped(const void* packed, const float* zp, 
                        (hipStream_t)stream, (const uint8_t*)packed, zp, bs, qmin, (uint32_t)groups,
                        (uint32_t)Cig, (uint32_t)L.Cog, (uint32_t)L.Cogp, RS, (uint32_t)L.Wc,
                        (uint32_t)L.Kp, make_fastdiv((uint32_t)L.Wc),
+                       make_fastdiv((uint32_t)L.Cogp), base, base + L.off_mask,
+                       (int32_t*)(base + L.off_cwz), (int32_t*)(base + L.off_t), bad);
+  }
+  return check_launch(me);
+}
+
+extern "C" int ssq_qweight_prepare_grouped_colscale(const void* packed, const float* zp,
+                                                    const int32_t* kcol, int64_t Co, int64_t Cig,
+                                                    int64_t R, int64_t S, int64_t groups,
+                                                    int n_bits, int qmin, void* prepared,
+                                                    uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_qweight_prepare_grouped_colscale";
+  SSQ_REQUIRE(packed && zp && kcol && prepared && bad, SSQ_E_ARG, "%s: null pointer", me);
+  int rc = grange_ok(me, n_bits, qmin);
+  if (rc) return rc;
+  rc = ggeo_ok(me, "ssq_qweight_prepare_colscale", -1, Co, Cig, R, S, groups);
+  if (rc) return rc;
+  const GLayout L = glayout(Co, Cig, R, S, groups);
+  int8_t* base = (int8_t*)prepared;
+  const int bs = n_bits <= 2 ? 2 : (n_bits <= 4 ? 4 : 8);
+  const uint32_t RS = (uint32_t)(R * S);
+  if (L.kind == 1) {
+    hipLaunchKernelGGL(qweight_prepare_dw_colscale_kernel,
+                       dim3(grid_for((int64_t)RS * L.Cp, kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, bs, qmin,
+                       (uint32_t)L.C, RS, (uint32_t)L.Cp, make_fastdiv((uint32_t)L.Cp),
+                       (int32_t*)base, bad);
+  } else {
+    hipLaunchKernelGGL(qweight_prepare_grouped_colscale_kernel,
+                       dim3((uint32_t)(groups * L.Cogp + groups)), dim3(kBlock), 0,
+                       (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, bs, qmin,
+                       (uint32_t)groups, (uint32_t)Cig, (uint32_t)L.Cog, (uint32_t)L.Cogp, RS,
+                       (uint32_t)L.Wc, (uint32_t)L.Kp, make_fastdiv((uint32_t)L.Wc),
                        make_fastdiv((uint32_t)L.Cogp), base, base + L.off_mask,
                        (int32_t*)(base + L.off_cwz), (int32_t*)(base + L.off_t), bad);
   }

@@ -1933,11 +1933,15 @@ def act_encode(x, delta, zp, n_bits, sym=False, bad=None):
 class QPrepared:
     """A layer's weight as K23's operand (K22's output) with its (Co, Ci[, R, S]) shape -- at
     `groups` > 1 the grouped kernels' operand (K24's output), Ci then being the channels per
-    group; `bad` counts the channels whose zero point is not an integer code (device int32)."""
+    group; `bad` counts the channels whose zero point is not an integer code (device int32).
+    `centred`: the blob holds a column-scaled weight's centred operand m = (q - z) * kcol[j]
+    (qweight_prepare(..., kcol=...)), cwz = 0: the dense convs run it without the window sum,
+    and `bad` also counts the elements whose |m| exceeds 127."""
 
-    def __init__(self, blob, shape, bad, groups=1):
+    def __init__(self, blob, shape, bad, groups=1, centred=False):
         self.blob, self.shape, self.bad = blob, tuple(int(s) for s in shape), bad
         self.groups = int(groups)
+        self.centred = bool(centred)
 
     def geometry(self):
         Co, Ci = self.shape[:2]
@@ -1945,9 +1949,34 @@ class QPrepared:
         return Co, Ci, R, S
 
 
-def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1):
+COLSCALE_MAX_L = 127
+
+
+def colscale_grid(col_scale):
+    """The common integer grid of a column scale (ChannelQuantMSE's c[j] = k[j] / level): the
+    smallest L in 1..127 with, for every j, k[j] = rint(c[j] * L) an integer >= 1 and
+    fp32(k[j] / L) == c[j] bit for bit -> (L, k as an int32 CPU tensor); None when there is no
+    such L with every k[j] <= 127 (a zero, negative or non-finite entry included).  Host
+    arithmetic on a CPU copy of the J floats; L may be smaller than the level the search ran
+    with."""
+    import numpy as np
+    c = np.ascontiguousarray(col_scale.detach().reshape(-1).float().cpu().numpy(), dtype=np.float32)
+    if c.size == 0 or not np.all(np.isfinite(c)) or not np.all(c > 0):
+        return None
+    for L in range(1, COLSCALE_MAX_L + 1):
+        k = np.rint(c.astype(np.float64) * L)      # exact product: 24 + 7 bits
+        if k.min() < 1 or k.max() > COLSCALE_MAX_L:
+            continue
+        if np.array_equal((k.astype(np.float32) / np.float32(L)).view(np.int32), c.view(np.int32)):
+            return L, torch.from_numpy(k.astype(np.int32))
+    return None
+
+
+def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None):
     """Packed codes (pack_encode's layout) + zp[co] -> QPrepared.  `shape` is the weight's own
-    (Co, Cig, R, S); `groups` > 1 prepares for the grouped kernels (K24)."""
+    (Co, Cig, R, S); `groups` > 1 prepares for the grouped kernels (K24).  `kcol`: the int32
+    column factors k[j], j = (ci, r, s) (colscale_grid), of a column-scaled weight: the blob then
+    holds the centred operand (q - zp[co]) * k[j] (`centred`)."""
     if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
         raise A.SSQError("qweight_prepare: packed codes must be a uint8 tensor")
     packed = _i8_dev(packed, "qweight_prepare")
@@ -1963,6 +1992,24 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1):
     z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
     if z.numel() != Co:
         raise A.SSQError("qweight_prepare: zero point must have one entry per output channel")
+    if kcol is not None:
+        kc = torch.as_tensor(kcol).detach().reshape(-1)
+        if kc.dtype.is_floating_point or kc.numel() != Ci * R * S:
+            raise A.SSQError("qweight_prepare: kcol must hold one integer per (ci, r, s) column")
+        if int(kc.min()) < 1 or int(kc.max()) > COLSCALE_MAX_L:
+            raise A.SSQError(f"qweight_prepare: kcol must lie in [1, {COLSCALE_MAX_L}]")
+        kc = kc.to(device=packed.device, dtype=torch.int32).contiguous()
+        prep.centred = True
+        nbytes = (query("ssq_qweight_prepared_bytes_grouped", Co, Ci, R, S, groups) if groups > 1
+                  else query("ssq_qweight_prepared_bytes", Co, Ci, R, S))
+        prep.blob = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=packed.device)
+        if groups > 1:
+            call("ssq_qweight_prepare_grouped_colscale", _vp(packed), zpp, _vp(kc), Co, Ci, R, S,
+                 groups, int(n_bits), int(qmin), _vp(prep.blob), _vp(prep.bad), stream_of(packed))
+        else:
+            call("ssq_qweight_prepare_colscale", _vp(packed), zpp, _vp(kc), Co, Ci, R, S,
+                 int(n_bits), int(qmin), _vp(prep.blob), _vp(prep.bad), stream_of(packed))
+        return prep
     if groups > 1:
         prep.blob = torch.empty(max(query("ssq_qweight_prepared_bytes_grouped", Co, Ci, R, S, groups), 1),
                                 dtype=torch.uint8, device=packed.device)
@@ -1977,6 +2024,20 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1):
 
 
 QCONV_KINDS = {1: "depthwise", 2: "grouped"}
+
+# A centred blob (a column-scaled weight's, QPrepared.centred) on K23's CENTRED instantiations:
+# no window-sum MFMA, no 0/1-row traffic; bit-identical to the shift-and-correct ones on such a
+# blob (profiles/int_infer_colscale_rate.txt).  A/B knob: SSQ_QCONV_CENTRED=0.
+QCONV_CENTRED = os.environ.get("SSQ_QCONV_CENTRED", "1") != "0"
+
+
+def _qconv_fn(prepared, groups, form):
+    """The entry point of `form` ("fwd" | "codes_fwd" | "codes_res_fwd") for a prepared weight."""
+    if int(groups) > 1:
+        return f"ssq_qconv_i8_grouped_{form}"
+    if QCONV_CENTRED and getattr(prepared, "centred", False):
+        return f"ssq_qconv_i8_centred_{form}"
+    return f"ssq_qconv_i8_{form}"
 
 
 def qconv_kind(prepared):
@@ -2002,8 +2063,7 @@ def qconv(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0
         act_delta, bad)
     y = torch.empty((N, Co, OH, OW) if conv else (N, Co), dtype=torch.float32,
                     device=keep[0].device)
-    fn = "ssq_qconv_i8_grouped_fwd" if int(groups) > 1 else "ssq_qconv_i8_fwd"
-    call(fn, *args, _vp(y), stream_of(y))
+    call(_qconv_fn(prepared, groups, "fwd"), *args, _vp(y), stream_of(y))
     return y
 
 
@@ -2134,11 +2194,12 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
                                  f"codes, got {residual.dtype} {tuple(residual.shape)}")
             res, rp = fptr(residual.detach(), "residual")
             rargs = (rp, None, 0.0, 0.0, 0, 0)
-        call("ssq_qconv_i8_codes_res_fwd", *args, vecs[0][1], vecs[1][1], vecs[2][1], int(relu),
+        call(_qconv_fn(prepared, 1, "codes_res_fwd"), *args, vecs[0][1], vecs[1][1], vecs[2][1],
+             int(relu),
              float(out_delta), float(out_zp), olo, ohi, _vp(out), _vp(bad), *rargs, stream_of(out))
         return out
-    fn = "ssq_qconv_i8_grouped_codes_fwd" if int(groups) > 1 else "ssq_qconv_i8_codes_fwd"
-    call(fn, *args, vecs[0][1], vecs[1][1], vecs[2][1], int(relu), float(out_delta), float(out_zp),
+    call(_qconv_fn(prepared, groups, "codes_fwd"), *args, vecs[0][1], vecs[1][1], vecs[2][1],
+         int(relu), float(out_delta), float(out_zp),
          olo, ohi, _vp(out), _vp(bad), stream_of(out))
     return out
 

@@ -104,7 +104,10 @@ def maybe_spawn(script, argv=None, flag="--gpus"):
     if "WORLD_SIZE" in os.environ:
         if os.environ.get(DRYRUN_ENV):
             keys = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", LAUNCHER_ENV)
-            print(json.dumps({"rank_env": {k: os.environ.get(k) for k in keys}}), flush=True)
+            # one write per rank: the ranks share the parent's stdout, and an unbuffered
+            # stream (PYTHONUNBUFFERED) would emit the newline apart from the line
+            sys.stdout.write(json.dumps({"rank_env": {k: os.environ.get(k) for k in keys}}) + "\n")
+            sys.stdout.flush()
             sys.exit(0)
         return
     n = requested_gpus(argv, flag)

@@ -43,6 +43,15 @@ numerics contract of its own: its logits are a function of the codes 
 for bit those of an fp32 mean and an fp32 GEMM.  The chain is structural (`head_edges`, from
 the `head_chain` a model declares); the fc is planned for the pooled operand only, so whenever
 the pool does not pool codes the head is the fp32 one of the other routes.
+
+With `colscale=True` a column-scaled weight ((q - zero_point[co]) * scale[co]) * c[j]
+(ChannelQuantMSE, the form channelShift_wMSE puts on every conv) is planned too when its column
+scale lies on an integer grid c[j] = k[j] / L, L <= 127 (K.colscale_grid, host arithmetic on the
+J stored floats): the prepared int8 operand is the centred integer (q - zero_point[co]) * k[j]
+(ssq_qweight_prepare_colscale; every element must fit int8, counted on the device otherwise),
+the output scale fp32(fp32(delta * scale[co]) / fp32(L)), and the dense convs run the kernel
+instantiation without the window-sum MFMA.  Such a layer carries and consumes codes
+like any other; an all-ones column scale is a plain weight on the plain route.
 """
 import torch
 import torch.nn as nn
@@ -283,14 +292,15 @@ def _input_reason(q):
     return (delta, zp, q.n_bits, q.sym), None
 
 
-def _weight_codes(m):
+def _weight_codes(m, colscale=False):
     """(packed codes, fields) of the module's hard weight: a restored model's PackedWeight as
-    stored, a live quantizer through dequant_form + pack_encode (soft state is refused there)."""
+    stored, a live quantizer through dequant_form + pack_encode (soft state is refused there).
+    A column-scaled weight is encoded only with `colscale` (its caller refuses it otherwise)."""
     q = m.weight_quantizer
     if isinstance(q, PackedWeight):
         return q.packed, q.fields()
     what, f = dequant_form(m)
-    if f["per_ci"] or f["col_scale"] is not None:
+    if f["per_ci"] or (f["col_scale"] is not None and not colscale):
         return None, f
     packed, bad = K.pack_encode(what, f["zero_point"], f["scale"], f["per_ci"], f["col_scale"],
                                 f["n_bits"], f["qmin"], f["qmax"])
@@ -302,7 +312,7 @@ def _weight_codes(m):
 
 @torch.no_grad()
 def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
-                             carry_stem=False, carry_head=False):
+                             carry_stem=False, carry_head=False, colscale=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
@@ -313,7 +323,11 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     that a max-pool behind it pools as codes (`stem_carry_report`); the layers behind such a
     pool are planned too.  `carry_head`: `carry_stem`, and the global average pool in front of
     the fc sums the codes and the fc runs on the sums (`head_carry_report`); the fc is planned
-    for that operand only, and reported with the reason when the head edge is not installed."""
+    for that operand only, and reported with the reason when the head edge is not installed.
+    `colscale`: also plan column-scaled weights (ChannelQuantMSE) whose column scale lies on an
+    integer grid k[j] / L, L <= 127 (K.colscale_grid), with the centred integer (q - z) * k[j] as
+    the int8 operand; off, they are reported as refused.  An all-ones column scale is
+    a plain weight and takes the plain route."""
     carry_stem = carry_stem or carry_head
     carry_blocks = carry_blocks or carry_stem
     carry = carry or carry_blocks
@@ -368,25 +382,41 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
             report[name] = "weight is not on the HIP device"
             continue
         try:
-            packed, f = _weight_codes(m)
+            packed, f = _weight_codes(m, colscale)
         except TypeError as e:
             report[name] = str(e)
             continue
         if f["per_ci"]:
             report[name] = f"weight scale is per (co, ci) ({f['kind']})"
             continue
+        kcol, L = None, 1
         if f["col_scale"] is not None:
-            report[name] = f"weight has a column scale ({f['kind']})"
-            continue
+            grid = K.colscale_grid(f["col_scale"]) if colscale else None
+            if grid is None:
+                report[name] = f"weight has a column scale ({f['kind']})" + (
+                    f" that is not on an integer grid k / L, L <= {K.COLSCALE_MAX_L}" if colscale else "")
+                continue
+            L, kcol = grid
+            if L == 1 and int(kcol.max()) == 1:
+                kcol = None                     # all ones: a plain weight, the plain K22 blob
+            elif m in head_fc:
+                report[name] = (f"weight has a column scale ({f['kind']}): the pooled-operand fc "
+                                "takes plain weights only")
+                continue
         prep = K.qweight_prepare(packed, tuple(m.weight.shape), f["zero_point"], f["n_bits"],
-                                 f["qmin"], groups=groups)
+                                 f["qmin"], groups=groups, kcol=kcol)
         if int(prep.bad.item()):
-            report[name] = "weight zero point is not an integer code"
+            report[name] = ("weight zero point is not an integer code" if kcol is None else
+                            "scaled weight (q - z) * k leaves int8 (|m| > 127), or a zero point "
+                            "is not an integer code")
             continue
         delta, zp, n_bits, sym = act
         # s[co] = fp32(delta_a * d1[co]): one fp32 product of the two stored fp32 values
         scale = (torch.full((1,), delta, dtype=torch.float32, device=dev)
                  * f["scale"].detach().reshape(-1).float()).contiguous()
+        if kcol is not None:
+            # ... / fp32(L): the column grid's common denominator, one more rounding
+            scale = (scale / torch.full((1,), float(L), dtype=torch.float32, device=dev)).contiguous()
         m._int_plan = IntPlan(prep, scale, delta, zp, n_bits, sym, stride, padding, counter)
         report[name] = INT8
     if carry:
