@@ -267,9 +267,10 @@ int ssq_adaround_bwd(const float* gWhat, const float* W, const float* beta,
                      const float* delta, int delta_per_ci, const float* zp, float scale,
                      int64_t Co, int64_t Ci, int64_t K, int qmin, int qmax, float reg_lambda,
                      float reg_b, const float* reg_dev, float* gbeta, ssq_stream_t stream);
-/* Several AdaRound weights (a block's quantizers) in one launch each way: arrays of nseg
- * (<= 8) per-weight arguments as in ssq_adaround_fwd / _bwd (scale, qmin, qmax per weight);
- * results bit-identical to one call per weight. */
+/* Several AdaRound weights (a block's quantizers) in one launch each way (up to 8 per
+ * launch, further launches beyond that): arrays of nseg per-weight arguments as in
+ * ssq_adaround_fwd / _bwd (scale, qmin, qmax per weight); results bit-identical to one
+ * call per weight. */
 int ssq_adaround_fwd_multi(int nseg, const float* const* W, const float* const* beta,
                            const float* const* delta, const int* delta_per_ci,
                            const float* const* zp, const float* scale, const int64_t* Co,

@@ -184,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void adaround_bwd_kernel(
 // Several weights in one launch (the AdaRound quantizers of a block, BRECQ's weight phase):
 // a table of segments, each a contiguous run of kAdaTile-element tiles; every element runs
 // the single-weight kernels' exact ops, so the results are bit-identical to one launch per
-// weight.
+// weight.  More than kMaxAdaSeg weights take further launches.
 constexpr int kMaxAdaSeg = 8;
 constexpr uint32_t kAdaTile = 512;   // 2 elements per thread: as many workgroups as the single launches
 struct AdaSeg {
@@ -846,14 +846,22 @@ extern "C" int ssq_adaround_fwd_multi(int nseg, const float* const* W, const flo
                                       const int64_t* Co, const int64_t* Ci, const int64_t* K,
                                       int hard_round, const int* qmin, const int* qmax,
                                       float* const* What, ssq_stream_t stream) {
-  AdaTable tab;
-  uint32_t nblk = 0;
-  const int rc = ada_table("ssq_adaround_fwd_multi", nseg, nullptr, W, beta, delta, delta_per_ci,
-                           zp, scale, Co, Ci, K, qmin, qmax, What, tab, nblk);
-  if (rc) return rc;
-  hipLaunchKernelGGL(adaround_fwd_multi_kernel, dim3(nblk), dim3(kBlock), 0, (hipStream_t)stream,
-                     tab, hard_round);
-  return check_launch("ssq_adaround_fwd_multi");
+  const char* what = "ssq_adaround_fwd_multi";
+  SSQ_REQUIRE(nseg >= 1 && W && beta && delta && delta_per_ci && zp && scale && Co && Ci && K &&
+              qmin && qmax && What, SSQ_E_ARG, "%s: bad arrays", what);
+  // more than kMaxAdaSeg weights: further launches, one table each
+  for (int base = 0; base < nseg; base += kMaxAdaSeg) {
+    const int cnt = nseg - base < kMaxAdaSeg ? nseg - base : kMaxAdaSeg;
+    AdaTable tab;
+    uint32_t nblk = 0;
+    const int rc = ada_table(what, cnt, nullptr, W + base, beta + base, delta + base,
+                             delta_per_ci + base, zp + base, scale + base, Co + base, Ci + base,
+                             K + base, qmin + base, qmax + base, What + base, tab, nblk);
+    if (rc) return rc;
+    hipLaunchKernelGGL(adaround_fwd_multi_kernel, dim3(nblk), dim3(kBlock), 0,
+                       (hipStream_t)stream, tab, hard_round);
+  }
+  return check_launch(what);
 }
 
 extern "C" int ssq_adaround_bwd_multi(int nseg, const float* const* gWhat, const float* const* W,
@@ -863,15 +871,21 @@ extern "C" int ssq_adaround_bwd_multi(int nseg, const float* const* gWhat, const
                                       const int64_t* K, const int* qmin, const int* qmax,
                                       float reg_lambda, float reg_b, const float* reg_dev,
                                       float* const* gbeta, ssq_stream_t stream) {
-  SSQ_REQUIRE(gWhat, SSQ_E_ARG, "ssq_adaround_bwd_multi: null gWhat");
-  AdaTable tab;
-  uint32_t nblk = 0;
-  const int rc = ada_table("ssq_adaround_bwd_multi", nseg, gWhat, W, beta, delta, delta_per_ci,
-                           zp, scale, Co, Ci, K, qmin, qmax, gbeta, tab, nblk);
-  if (rc) return rc;
-  hipLaunchKernelGGL(adaround_bwd_multi_kernel, dim3(nblk), dim3(kBlock), 0, (hipStream_t)stream,
-                     tab, reg_lambda, reg_b, reg_dev);
-  return check_launch("ssq_adaround_bwd_multi");
+  const char* what = "ssq_adaround_bwd_multi";
+  SSQ_REQUIRE(nseg >= 1 && gWhat && W && beta && delta && delta_per_ci && zp && scale && Co && Ci &&
+              K && qmin && qmax && gbeta, SSQ_E_ARG, "%s: bad arrays", what);
+  for (int base = 0; base < nseg; base += kMaxAdaSeg) {
+    const int cnt = nseg - base < kMaxAdaSeg ? nseg - base : kMaxAdaSeg;
+    AdaTable tab;
+    uint32_t nblk = 0;
+    const int rc = ada_table(what, cnt, gWhat + base, W + base, beta + base, delta + base,
+                             delta_per_ci + base, zp + base, scale + base, Co + base, Ci + base,
+                             K + base, qmin + base, qmax + base, gbeta + base, tab, nblk);
+    if (rc) return rc;
+    hipLaunchKernelGGL(adaround_bwd_multi_kernel, dim3(nblk), dim3(kBlock), 0,
+                       (hipStream_t)stream, tab, reg_lambda, reg_b, reg_dev);
+  }
+  return check_launch(what);
 }
 
 extern "C" int ssq_rect_init(const float* W, const float* delta, int delta_per_ci, int64_t Co,
