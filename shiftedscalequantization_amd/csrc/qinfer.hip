@@ -41,16 +41,11 @@
 #include "ssq_common.h"
 #include "qinfer_epi.h"
 #include "qinfer_layout.h"
+#include "qinfer_prepare.h"
 
 namespace ssq {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, kWave);
-  return v;
-}
 
 // ---------------------------------------------------------------- K21 activation encode
 __global__ __launch_bounds__(kBlock) void act_encode_kernel(const float* __restrict__ x,
@@ -91,67 +86,20 @@ __global__ __launch_bounds__(kBlock) void act_encode_kernel(const float* __restr
     }
     *(i32x4*)(out + (size_t)pix * Cp + (size_t)ch * 16) = o.v;
   }
-  nbad = wave_sum_u32(nbad);
+  nbad = wave_sum(nbad);
   if ((threadIdx.x & (kWave - 1)) == 0 && nbad) atomicAdd(bad, nbad);
 }
 
 // ---------------------------------------------------------------- K22 weight prepare
 // One workgroup per padded output channel, one more (blockIdx.x == Cop) for the 0/1 row.
+// Plain: the operand is q - cw, cwz[co] = cw - z_w[co], T[co] = sum + K * cwz[co].
+// COLSCALE, a column-scaled weight W_hat = ((q - z_w[co]) * d1[co]) * (kcol[j] / L), j = (ci, r, s):
+// the operand is the centred integer m = (q - z_w[co]) * kcol[j] itself (qinfer_prepare.h), so
+// cwz = 0 and T[co] = sum m; the 0/1 row is written all the same, so every reader of the layout
+// runs the blob as it stands.  *bad counts the real channels whose zero point breaks zp_is_code
+// and, COLSCALE, the real elements colscaled() counts.
+template <bool COLSCALE>
 __global__ __launch_bounds__(kBlock) void qweight_prepare_kernel(
-    const uint8_t* __restrict__ packed, const float* __restrict__ zp, int bs, int qmin,
-    uint32_t Co, uint32_t Ci, uint32_t RS, uint32_t Cp, uint32_t Kp, uint32_t Cop, FastDiv div_cp,
-    int8_t* __restrict__ wp, int8_t* __restrict__ mask, int32_t* __restrict__ cwz,
-    int32_t* __restrict__ tt, uint32_t* __restrict__ bad) {
-  __shared__ int red[kBlock / kWave];
-  const uint32_t co = blockIdx.x;
-  if (co == Cop) {
-    for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
-      const uint32_t tap = fdiv(k, div_cp);
-      mask[k] = (tap < RS && k - tap * Cp < Ci) ? 1 : 0;
-    }
-    return;
-  }
-  int sum = 0;
-  for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
-    const uint32_t tap = fdiv(k, div_cp);
-    const uint32_t ci = k - tap * Cp;
-    int v = 0;
-    if (co < Co && tap < RS && ci < Ci) {
-      const size_t bit = (((size_t)co * Ci + ci) * RS + tap) * (size_t)bs;
-      const uint32_t u = ((uint32_t)packed[bit >> 3] >> (bit & 7)) & ((1u << bs) - 1u);
-      v = (int)u - 128;   // q - cw, q = u + qmin, cw = qmin + 128
-      sum += v;
-    }
-    wp[(size_t)co * Kp + k] = (int8_t)v;
-  }
-  sum = (int)wave_sum_u32((uint32_t)sum);
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0, t = 0;
-    if (co < Co) {
-      float z = zp[co];
-      // any integer near the code range: |cwz| <= 384 keeps K * cwz inside int32
-      if (!(z == rintf(z) && z >= (float)(qmin - 256) && z <= (float)(qmin + 511))) {
-        atomicAdd(bad, 1u);
-        z = (float)qmin;
-      }
-      int total = 0;
-      for (int i = 0; i < kBlock / kWave; ++i) total += red[i];
-      c = qmin + 128 - (int)z;
-      t = total + (int)(Ci * RS) * c;
-    }
-    cwz[co] = c;
-    tt[co] = t;
-  }
-}
-
-// K22 for a column-scaled weight W_hat = ((q - z_w[co]) * d1[co]) * (kcol[j] / L), j = (ci, r, s):
-// the operand is the centred integer m = (q - z_w[co]) * kcol[j] itself (zero on padded channels
-// and on the K tail), so cwz = 0 and T[co] = sum m; the 0/1 row is written as above, so every
-// reader of the layout runs the blob as it stands.  *bad also counts the real elements whose m
-// leaves [-127, 127] (stored saturated) and those whose kcol[j] is not in [1, 127].
-__global__ __launch_bounds__(kBlock) void qweight_prepare_colscale_kernel(
     const uint8_t* __restrict__ packed, const float* __restrict__ zp,
     const int32_t* __restrict__ kcol, int bs, int qmin, uint32_t Co, uint32_t Ci, uint32_t RS,
     uint32_t Cp, uint32_t Kp, uint32_t Cop, FastDiv div_cp, int8_t* __restrict__ wp,
@@ -166,39 +114,26 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_colscale_kernel(
     }
     return;
   }
-  int z = qmin;
-  bool zok = true;
-  if (co < Co) {
-    const float zf = zp[co];
-    zok = zf == rintf(zf) && zf >= (float)(qmin - 256) && zf <= (float)(qmin + 511);
-    if (zok) z = (int)zf;
-  }
+  const bool real = co < Co;
+  const bool zok = !real || zp_is_code(zp[co], qmin);
+  const int z = real && zok ? (int)zp[co] : qmin;
   int sum = 0;
   uint32_t nbad = 0;
   for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
     const uint32_t tap = fdiv(k, div_cp);
     const uint32_t ci = k - tap * Cp;
     int v = 0;
-    if (co < Co && tap < RS && ci < Ci) {
+    if (real && tap < RS && ci < Ci) {
       const size_t j = (size_t)ci * RS + tap;
-      const size_t bit = ((size_t)co * Ci * RS + j) * (size_t)bs;
-      const uint32_t u = ((uint32_t)packed[bit >> 3] >> (bit & 7)) & ((1u << bs) - 1u);
-      int kj = kcol[j];
-      if (kj < 1 || kj > 127) {
-        ++nbad;
-        kj = 0;
-      }
-      v = ((int)u + qmin - z) * kj;   // |q - z| <= 767, kj <= 127: no overflow
-      if (v > 127 || v < -127) {
-        ++nbad;
-        v = v > 0 ? 127 : -127;
-      }
+      const int u = (int)packed_code(packed, (size_t)co * Ci * RS + j, bs);   // q - qmin
+      if constexpr (COLSCALE) v = colscaled(u + qmin - z, kcol[j], nbad);
+      else v = u - 128;   // q - cw, cw = qmin + 128
       sum += v;
     }
     wp[(size_t)co * Kp + k] = (int8_t)v;
   }
-  sum = (int)wave_sum_u32((uint32_t)sum);
-  nbad = wave_sum_u32(nbad);
+  sum = (int)wave_sum((uint32_t)sum);
+  nbad = wave_sum(nbad);
   if ((threadIdx.x & (kWave - 1)) == 0) {
     red[threadIdx.x / kWave] = sum;
     if (nbad) atomicAdd(bad, nbad);
@@ -208,8 +143,9 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_colscale_kernel(
     int total = 0;
     for (int i = 0; i < kBlock / kWave; ++i) total += red[i];
     if (!zok) atomicAdd(bad, 1u);
-    cwz[co] = 0;
-    tt[co] = co < Co ? total : 0;
+    const int c = (COLSCALE || !real) ? 0 : qmin + 128 - z;
+    cwz[co] = c;
+    tt[co] = total + (int)(Ci * RS) * c;   // a padded channel: 0
   }
 }
 
@@ -432,13 +368,6 @@ __global__ __launch_bounds__(kBlock) void act_decode_kernel(const int8_t* __rest
   }
 }
 
-static int qrange_ok(const char* what, int n_bits, int qmin) {
-  SSQ_REQUIRE(n_bits >= 1 && n_bits <= 8, SSQ_E_ARG, "%s: n_bits %d not in [1, 8]", what, n_bits);
-  SSQ_REQUIRE(qmin == 0 || qmin == -(1 << (n_bits - 1)), SSQ_E_ARG,
-              "%s: qmin %d is neither 0 nor -2^(n_bits-1)", what, qmin);
-  return SSQ_OK;
-}
-
 static int qgeo_ok(const char* what, int64_t Co, int64_t Ci, int64_t R, int64_t S) {
   SSQ_REQUIRE(Co >= 1 && Ci >= 1 && R >= 1 && S >= 1 && R <= 7 && S <= 7, SSQ_E_ARG,
               "%s: bad geometry (Co, Ci >= 1; R, S in [1, 7])", what);
@@ -466,15 +395,8 @@ extern "C" int ssq_act_encode(const float* x, int64_t Nb, int64_t C, int64_t H, 
                               uint32_t* bad, ssq_stream_t stream) {
   SSQ_REQUIRE(x && codes && bad, SSQ_E_ARG, "ssq_act_encode: null pointer");
   SSQ_REQUIRE(Nb >= 1 && C >= 1 && H >= 1 && W >= 1, SSQ_E_ARG, "ssq_act_encode: bad geometry");
-  SSQ_REQUIRE(qmin < qmax && qmax - qmin <= 255, SSQ_E_ARG,
-              "ssq_act_encode: code range [%d, %d] does not fit 8-bit codes", qmin, qmax);
-  SSQ_REQUIRE(delta > 0.0f && delta <= 3.0e38f, SSQ_E_ARG,
-              "ssq_act_encode: delta must be positive and finite");
-  // a padded tap stores zero_point - (qmin + 128) as an int8
-  SSQ_REQUIRE(zero_point == rintf(zero_point) && zero_point >= (float)qmin &&
-                  zero_point <= (float)(qmin + 255),
-              SSQ_E_ARG, "ssq_act_encode: zero point %g is not an integer in [%d, %d]",
-              (double)zero_point, qmin, qmin + 255);
+  const int rc = qquant_ok("ssq_act_encode", "", &delta, zero_point, qmin, qmax);
+  if (rc) return rc;
   const int64_t Cp = rup(C, 16);
   SSQ_REQUIRE(Nb * H * W * Cp < (1ll << 31), SSQ_E_ARG,
               "ssq_act_encode: tensor exceeds 2^31 elements");
@@ -486,72 +408,87 @@ extern "C" int ssq_act_encode(const float* x, int64_t Nb, int64_t C, int64_t H, 
   return check_launch("ssq_act_encode");
 }
 
-extern "C" int ssq_qweight_prepare(const void* packed, const float* zp, int64_t Co, int64_t Ci,
-                                   int64_t R, int64_t S, int n_bits, int qmin, void* prepared,
-                                   uint32_t* bad, ssq_stream_t stream) {
-  SSQ_REQUIRE(packed && zp && prepared && bad, SSQ_E_ARG, "ssq_qweight_prepare: null pointer");
-  int rc = qrange_ok("ssq_qweight_prepare", n_bits, qmin);
-  if (rc) return rc;
-  rc = qgeo_ok("ssq_qweight_prepare", Co, Ci, R, S);
-  if (rc) return rc;
-  const QLayout L = qlayout(Co, Ci, R, S);
-  int8_t* base = (int8_t*)prepared;
-  const int bs = n_bits <= 2 ? 2 : (n_bits <= 4 ? 4 : 8);
-  hipLaunchKernelGGL(qweight_prepare_kernel, dim3((uint32_t)L.Cop + 1), dim3(kBlock), 0,
-                     (hipStream_t)stream, (const uint8_t*)packed, zp, bs, qmin, (uint32_t)Co, (uint32_t)Ci, (uint32_t)(R * S),
-                     (uint32_t)L.Cp, (uint32_t)L.Kp, (uint32_t)L.Cop, make_fastdiv((uint32_t)L.Cp),
-                     base, base + L.off_mask, (int32_t*)(base + L.off_cwz),
-                     (int32_t*)(base + L.off_t), bad);
-  return check_launch("ssq_qweight_prepare");
-}
-
-extern "C" int ssq_qweight_prepare_colscale(const void* packed, const float* zp,
-                                            const int32_t* kcol, int64_t Co, int64_t Ci, int64_t R,
-                                            int64_t S, int n_bits, int qmin, void* prepared,
-                                            uint32_t* bad, ssq_stream_t stream) {
-  const char* me = "ssq_qweight_prepare_colscale";
-  SSQ_REQUIRE(packed && zp && kcol && prepared && bad, SSQ_E_ARG, "%s: null pointer", me);
+// kcol: the column factors of a column-scaled weight (the COLSCALE kernel), or null
+static int qweight_prepare_launch(const char* me, bool colscale, const void* packed,
+                                  const float* zp, const int32_t* kcol, int64_t Co, int64_t Ci,
+                                  int64_t R, int64_t S, int n_bits, int qmin, void* prepared,
+                                  uint32_t* bad, ssq_stream_t stream) {
+  SSQ_REQUIRE(packed && zp && (kcol || !colscale) && prepared && bad, SSQ_E_ARG,
+              "%s: null pointer", me);
   int rc = qrange_ok(me, n_bits, qmin);
   if (rc) return rc;
   rc = qgeo_ok(me, Co, Ci, R, S);
   if (rc) return rc;
   const QLayout L = qlayout(Co, Ci, R, S);
   int8_t* base = (int8_t*)prepared;
-  const int bs = n_bits <= 2 ? 2 : (n_bits <= 4 ? 4 : 8);
-  hipLaunchKernelGGL(qweight_prepare_colscale_kernel, dim3((uint32_t)L.Cop + 1), dim3(kBlock), 0,
-                     (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, bs, qmin, (uint32_t)Co,
+  auto* kernel = colscale ? qweight_prepare_kernel<true> : qweight_prepare_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((uint32_t)L.Cop + 1), dim3(kBlock), 0, (hipStream_t)stream,
+                     (const uint8_t*)packed, zp, kcol, packed_bits(n_bits), qmin, (uint32_t)Co,
                      (uint32_t)Ci, (uint32_t)(R * S), (uint32_t)L.Cp, (uint32_t)L.Kp,
                      (uint32_t)L.Cop, make_fastdiv((uint32_t)L.Cp), base, base + L.off_mask,
                      (int32_t*)(base + L.off_cwz), (int32_t*)(base + L.off_t), bad);
   return check_launch(me);
 }
 
+extern "C" int ssq_qweight_prepare(const void* packed, const float* zp, int64_t Co, int64_t Ci,
+                                   int64_t R, int64_t S, int n_bits, int qmin, void* prepared,
+                                   uint32_t* bad, ssq_stream_t stream) {
+  return qweight_prepare_launch("ssq_qweight_prepare", false, packed, zp, nullptr, Co, Ci, R, S,
+                                n_bits, qmin, prepared, bad, stream);
+}
+
+extern "C" int ssq_qweight_prepare_colscale(const void* packed, const float* zp,
+                                            const int32_t* kcol, int64_t Co, int64_t Ci, int64_t R,
+                                            int64_t S, int n_bits, int qmin, void* prepared,
+                                            uint32_t* bad, ssq_stream_t stream) {
+  return qweight_prepare_launch("ssq_qweight_prepare_colscale", true, packed, zp, kcol, Co, Ci, R,
+                                S, n_bits, qmin, prepared, bad, stream);
+}
+
+// One form of K23 on a blob: CENTRED for a centred one (ssq_qweight_prepare_colscale), which is
+// bit-identical to the plain instantiation there, one MFMA per k step less.
+template <bool CENTRED>
+static void qconv_i8_run(dim3 grid, ssq_stream_t stream, const int8_t* codes, const int8_t* base,
+                         const QLayout& L, const float* scale, const QConvGeo& g, float* y,
+                         const QEpi* epi, const QRes* res) {
+  auto run = [&](auto* kernel, auto out) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base,
+                       base + L.off_mask, (const int32_t*)(base + L.off_cwz),
+                       (const int32_t*)(base + L.off_t), scale, g, out);
+  };
+  if (!epi) run(qconv_i8_kernel<false, 0, CENTRED>, y);
+  else if (!res) run(qconv_i8_kernel<true, 0, CENTRED>, *epi);
+  else if (res->f32) run(qconv_i8_kernel<true, 1, CENTRED>, QEpiRes{*epi, *res});
+  else run(qconv_i8_kernel<true, 2, CENTRED>, QEpiRes{*epi, *res});
+}
+
+// The arguments every dense conv entry point hands to the launch as they came
+struct QConvIn {
+  const int8_t* codes;
+  const void* prepared;
+  const float* scale;
+  int64_t Nb, Ci, H, W, Co, R, S, stride, pad, groups;
+  float act_zero_point;
+  int act_qmin, act_qmax;
+};
+
 // y: the fp32 output (ssq_qconv_i8_fwd) or null with `epi` set (ssq_qconv_i8_codes_fwd); `res`
-// with `epi`: the tail's residual (ssq_qconv_i8_codes_res_fwd)
-static int qconv_i8_launch(const char* me, const int8_t* codes, const void* prepared,
-                           const float* scale, int64_t Nb, int64_t Ci, int64_t H, int64_t W,
-                           int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
-                           int64_t groups, float act_zero_point, int act_qmin, int act_qmax,
-                           float* y, QEpi* epi, ssq_stream_t stream,
-                           const QRes* res = nullptr, bool centred = false) {
-  SSQ_REQUIRE(codes && prepared && scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
-  SSQ_REQUIRE(groups == 1, SSQ_E_ARG, "%s: groups = %lld (only groups == 1)", me,
-              (long long)groups);
-  int rc = qgeo_ok(me, Co, Ci, R, S);
+// with `epi`: the tail's residual (ssq_qconv_i8_codes_res_fwd); centred: the *_centred_* forms
+static int qconv_i8_launch(const char* me, bool centred, const QConvIn& a, float* y, QEpi* epi,
+                           const QRes* res, ssq_stream_t stream) {
+  SSQ_REQUIRE(a.codes && a.prepared && a.scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
+  SSQ_REQUIRE(a.groups == 1, SSQ_E_ARG, "%s: groups = %lld (only groups == 1)", me,
+              (long long)a.groups);
+  const int64_t Nb = a.Nb, H = a.H, W = a.W, Co = a.Co, R = a.R, S = a.S, pad = a.pad;
+  int rc = qgeo_ok(me, Co, a.Ci, R, S);
   if (rc) return rc;
-  SSQ_REQUIRE(Nb >= 1 && H >= 1 && W >= 1 && stride >= 1 && pad >= 0 &&
+  SSQ_REQUIRE(Nb >= 1 && H >= 1 && W >= 1 && a.stride >= 1 && pad >= 0 &&
                   H + 2 * pad >= R && W + 2 * pad >= S,
               SSQ_E_ARG, "%s: bad geometry", me);
-  SSQ_REQUIRE(act_qmin < act_qmax && act_qmax - act_qmin <= 255, SSQ_E_ARG,
-              "%s: activation code range [%d, %d] does not fit 8-bit codes", me,
-              act_qmin, act_qmax);
-  // a padded tap stores act_zero_point - (act_qmin + 128) as an int8
-  SSQ_REQUIRE(act_zero_point == rintf(act_zero_point) && act_zero_point >= (float)act_qmin &&
-                  act_zero_point <= (float)(act_qmin + 255),
-              SSQ_E_ARG, "%s: zero point %g is not an integer in [%d, %d]", me,
-              (double)act_zero_point, act_qmin, act_qmin + 255);
-  const QLayout L = qlayout(Co, Ci, R, S);
-  const int64_t OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
+  rc = qquant_ok(me, "activation ", nullptr, a.act_zero_point, a.act_qmin, a.act_qmax);
+  if (rc) return rc;
+  const QLayout L = qlayout(Co, a.Ci, R, S);
+  const int64_t OH = (H + 2 * pad - R) / a.stride + 1, OW = (W + 2 * pad - S) / a.stride + 1;
   SSQ_REQUIRE(Nb * H * W * L.Cp < (1ll << 31) && Nb * OH * OW * Co < (1ll << 31), SSQ_E_ARG,
               "%s: tensor exceeds 2^31 elements", me);
   QConvGeo g;
@@ -565,58 +502,52 @@ static int qconv_i8_launch(const char* me, const int8_t* codes, const void* prep
   g.Kp = (uint32_t)L.Kp;
   g.RS = (uint32_t)(R * S);
   g.S = (uint32_t)S;
-  g.stride = (int)stride;
+  g.stride = (int)a.stride;
   g.pad = (int)pad;
-  const int ca = act_qmin + 128, za = (int)act_zero_point;
+  const int ca = a.act_qmin + 128, za = (int)a.act_zero_point;
   g.az = ca - za;
   g.padv = za - ca;   // a padded tap: (q_a - z_a) = 0
   g.div_p = make_fastdiv(g.P);
   g.div_ow = make_fastdiv(g.OW);
   g.div_cp = make_fastdiv(g.Cp);
   g.div_s = make_fastdiv(g.S);
-  const int8_t* base = (const int8_t*)prepared;
-  const dim3 grid((g.M + kQT - 1) / kQT, (uint32_t)(L.Cop / kQT));
-  // a centred blob (ssq_qweight_prepare_colscale) on the CENTRED instantiation of the same form
-#define SSQ_QCONV_LAUNCH(CODES_, RES_, OUT_)                                                      \
-  do {                                                                                            \
-    if (centred)                                                                                  \
-      hipLaunchKernelGGL((qconv_i8_kernel<CODES_, RES_, true>), grid, dim3(kBlock), 0,            \
-                         (hipStream_t)stream, codes, base, base + L.off_mask,                     \
-                         (const int32_t*)(base + L.off_cwz), (const int32_t*)(base + L.off_t),    \
-                         scale, g, OUT_);                                                         \
-    else                                                                                          \
-      hipLaunchKernelGGL((qconv_i8_kernel<CODES_, RES_>), grid, dim3(kBlock), 0,                  \
-                         (hipStream_t)stream, codes, base, base + L.off_mask,                     \
-                         (const int32_t*)(base + L.off_cwz), (const int32_t*)(base + L.off_t),    \
-                         scale, g, OUT_);                                                         \
-  } while (0)
   if (epi) {
     epi->Cpo = (uint32_t)rup(Co, 16);
     SSQ_REQUIRE(Nb * OH * OW * (int64_t)epi->Cpo < (1ll << 31), SSQ_E_ARG,
                 "%s: tensor exceeds 2^31 elements", me);
-    if (res) {
-      const QEpiRes er = {*epi, *res};
-      if (res->f32) SSQ_QCONV_LAUNCH(true, 1, er);
-      else SSQ_QCONV_LAUNCH(true, 2, er);
-      return check_launch(me);
-    }
-    SSQ_QCONV_LAUNCH(true, 0, *epi);
-    return check_launch(me);
   }
-  SSQ_QCONV_LAUNCH(false, 0, y);
-#undef SSQ_QCONV_LAUNCH
+  const dim3 grid((g.M + kQT - 1) / kQT, (uint32_t)(L.Cop / kQT));
+  const int8_t* base = (const int8_t*)a.prepared;
+  if (centred) qconv_i8_run<true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res);
+  else qconv_i8_run<false>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res);
   return check_launch(me);
 }
 
+// The six dense entry points: {plain, centred blob} x {fp32 out, codes out, codes out + residual},
+// each its own checks (y; the epilogue; the residual, in that order) and one launch.
 extern "C" int ssq_qconv_i8_fwd(const int8_t* codes, const void* prepared, const float* scale,
                                 int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
                                 int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
                                 float act_zero_point, int act_qmin, int act_qmax, float* y,
                                 ssq_stream_t stream) {
   SSQ_REQUIRE(y, SSQ_E_ARG, "ssq_qconv_i8_fwd: null pointer");
-  return qconv_i8_launch("ssq_qconv_i8_fwd", codes, prepared, scale, Nb, Ci, H, W, Co, R, S,
-                         stride, pad, groups, act_zero_point, act_qmin, act_qmax, y, nullptr,
-                         stream);
+  return qconv_i8_launch("ssq_qconv_i8_fwd", false,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         y, nullptr, nullptr, stream);
+}
+
+extern "C" int ssq_qconv_i8_centred_fwd(const int8_t* codes, const void* prepared,
+                                        const float* scale, int64_t Nb, int64_t Ci, int64_t H,
+                                        int64_t W, int64_t Co, int64_t R, int64_t S,
+                                        int64_t stride, int64_t pad, int64_t groups,
+                                        float act_zero_point, int act_qmin, int act_qmax, float* y,
+                                        ssq_stream_t stream) {
+  SSQ_REQUIRE(y, SSQ_E_ARG, "ssq_qconv_i8_centred_fwd: null pointer");
+  return qconv_i8_launch("ssq_qconv_i8_centred_fwd", true,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         y, nullptr, nullptr, stream);
 }
 
 extern "C" int ssq_qconv_i8_codes_fwd(const int8_t* codes, const void* prepared,
@@ -629,13 +560,35 @@ extern "C" int ssq_qconv_i8_codes_fwd(const int8_t* codes, const void* prepared,
                                       int out_qmax, int8_t* out_codes, uint32_t* bad,
                                       ssq_stream_t stream) {
   const char* me = "ssq_qconv_i8_codes_fwd";
-  const int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
-                         out_codes, bad);
+  QEpi e;
+  const int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin,
+                           out_qmax, out_codes, bad, &e);
   if (rc) return rc;
-  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
-            0u, out_codes, bad};
-  return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
-                         act_zero_point, act_qmin, act_qmax, nullptr, &e, stream);
+  return qconv_i8_launch(me, false,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         nullptr, &e, nullptr, stream);
+}
+
+extern "C" int ssq_qconv_i8_centred_codes_fwd(const int8_t* codes, const void* prepared,
+                                              const float* scale, int64_t Nb, int64_t Ci,
+                                              int64_t H, int64_t W, int64_t Co, int64_t R,
+                                              int64_t S, int64_t stride, int64_t pad,
+                                              int64_t groups, float act_zero_point, int act_qmin,
+                                              int act_qmax, const float* bias, const float* gamma,
+                                              const float* phi, int act, float out_delta,
+                                              float out_zero_point, int out_qmin, int out_qmax,
+                                              int8_t* out_codes, uint32_t* bad,
+                                              ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_centred_codes_fwd";
+  QEpi e;
+  const int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin,
+                           out_qmax, out_codes, bad, &e);
+  if (rc) return rc;
+  return qconv_i8_launch(me, true,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         nullptr, &e, nullptr, stream);
 }
 
 extern "C" int ssq_qconv_i8_codes_res_fwd(
@@ -647,48 +600,16 @@ extern "C" int ssq_qconv_i8_codes_res_fwd(
     const int8_t* res_codes, float res_delta, float res_zero_point, int res_qmin, int res_qmax,
     ssq_stream_t stream) {
   const char* me = "ssq_qconv_i8_codes_res_fwd";
-  int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax, out_codes,
-                   bad);
+  QEpi e;
+  QRes r;
+  int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
+                     out_codes, bad, &e);
+  if (!rc) rc = qres_init(me, res_f32, res_codes, res_delta, res_zero_point, res_qmin, res_qmax, &r);
   if (rc) return rc;
-  rc = qres_ok(me, res_f32, res_codes, res_delta, res_zero_point, res_qmin, res_qmax);
-  if (rc) return rc;
-  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
-            0u, out_codes, bad};
-  const QRes r = {res_f32, res_codes, res_delta, res_zero_point, (float)res_qmin};
-  return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
-                         act_zero_point, act_qmin, act_qmax, nullptr, &e, stream, &r);
-}
-
-// The same three entry points for a centred blob (ssq_qweight_prepare_colscale), on the CENTRED
-// instantiations: bit-identical to the ones above on such a blob, one MFMA per k step less.
-extern "C" int ssq_qconv_i8_centred_fwd(const int8_t* codes, const void* prepared, const float* scale,
-                                int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
-                                int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
-                                float act_zero_point, int act_qmin, int act_qmax, float* y,
-                                ssq_stream_t stream) {
-  SSQ_REQUIRE(y, SSQ_E_ARG, "ssq_qconv_i8_centred_fwd: null pointer");
-  return qconv_i8_launch("ssq_qconv_i8_centred_fwd", codes, prepared, scale, Nb, Ci, H, W, Co, R, S,
-                         stride, pad, groups, act_zero_point, act_qmin, act_qmax, y, nullptr,
-                         stream, nullptr, true);
-}
-
-extern "C" int ssq_qconv_i8_centred_codes_fwd(const int8_t* codes, const void* prepared,
-                                      const float* scale, int64_t Nb, int64_t Ci, int64_t H,
-                                      int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
-                                      int64_t pad, int64_t groups, float act_zero_point,
-                                      int act_qmin, int act_qmax, const float* bias,
-                                      const float* gamma, const float* phi, int act,
-                                      float out_delta, float out_zero_point, int out_qmin,
-                                      int out_qmax, int8_t* out_codes, uint32_t* bad,
-                                      ssq_stream_t stream) {
-  const char* me = "ssq_qconv_i8_centred_codes_fwd";
-  const int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
-                         out_codes, bad);
-  if (rc) return rc;
-  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
-            0u, out_codes, bad};
-  return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
-                         act_zero_point, act_qmin, act_qmax, nullptr, &e, stream, nullptr, true);
+  return qconv_i8_launch(me, false,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         nullptr, &e, &r, stream);
 }
 
 extern "C" int ssq_qconv_i8_centred_codes_res_fwd(
@@ -700,16 +621,16 @@ extern "C" int ssq_qconv_i8_centred_codes_res_fwd(
     const int8_t* res_codes, float res_delta, float res_zero_point, int res_qmin, int res_qmax,
     ssq_stream_t stream) {
   const char* me = "ssq_qconv_i8_centred_codes_res_fwd";
-  int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax, out_codes,
-                   bad);
+  QEpi e;
+  QRes r;
+  int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
+                     out_codes, bad, &e);
+  if (!rc) rc = qres_init(me, res_f32, res_codes, res_delta, res_zero_point, res_qmin, res_qmax, &r);
   if (rc) return rc;
-  rc = qres_ok(me, res_f32, res_codes, res_delta, res_zero_point, res_qmin, res_qmax);
-  if (rc) return rc;
-  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
-            0u, out_codes, bad};
-  const QRes r = {res_f32, res_codes, res_delta, res_zero_point, (float)res_qmin};
-  return qconv_i8_launch(me, codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
-                         act_zero_point, act_qmin, act_qmax, nullptr, &e, stream, &r, true);
+  return qconv_i8_launch(me, true,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         nullptr, &e, &r, stream);
 }
 
 extern "C" int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W,
@@ -719,12 +640,9 @@ extern "C" int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_
   SSQ_REQUIRE(Nb >= 1 && C >= 1 && H >= 1 && W >= 1, SSQ_E_ARG, "ssq_act_decode: bad geometry");
   SSQ_REQUIRE(qmin >= -128 && qmin <= 0, SSQ_E_ARG, "ssq_act_decode: qmin %d not in [-128, 0]",
               qmin);
-  SSQ_REQUIRE(delta > 0.0f && delta <= 3.0e38f, SSQ_E_ARG,
-              "ssq_act_decode: delta must be positive and finite");
-  SSQ_REQUIRE(zero_point == rintf(zero_point) && zero_point >= (float)qmin &&
-                  zero_point <= (float)(qmin + 255),
-              SSQ_E_ARG, "ssq_act_decode: zero point %g is not an integer in [%d, %d]",
-              (double)zero_point, qmin, qmin + 255);
+  // decode has no qmax of its own: the widest range from qmin, which always fits
+  const int rc = qquant_ok("ssq_act_decode", "", &delta, zero_point, qmin, qmin + 255);
+  if (rc) return rc;
   const int64_t Cp = rup(C, 16);
   SSQ_REQUIRE(Nb * H * W * Cp < (1ll << 31), SSQ_E_ARG,
               "ssq_act_decode: tensor exceeds 2^31 elements");

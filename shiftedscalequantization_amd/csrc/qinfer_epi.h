@@ -19,6 +19,7 @@
 // channels 0.
 #pragma once
 #include "ssq_common.h"
+#include "qinfer_check.h"
 
 namespace ssq {
 
@@ -86,51 +87,35 @@ __device__ __forceinline__ int qepi_pack4(int c0, int c1, int c2, int c3) {
   return (c0 & 0xff) | ((c1 & 0xff) << 8) | ((c2 & 0xff) << 16) | ((int)((uint32_t)c3 << 24));
 }
 
-__device__ __forceinline__ uint32_t qepi_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, kWave);
-  return v;
-}
-
 // every lane of the wave must be here
 __device__ __forceinline__ void qepi_count(uint32_t nbad, uint32_t* bad) {
-  nbad = qepi_wave_sum(nbad);
+  nbad = wave_sum(nbad);
   if ((threadIdx.x & (kWave - 1)) == 0 && nbad) atomicAdd(bad, nbad);
 }
 
-// the output quantizer, validated as ssq_act_encode validates its own
-static inline int qepi_ok(const char* what, const float* gamma, const float* phi, int act,
-                          float delta, float zero_point, int qmin, int qmax, const void* out,
-                          const void* bad) {
+// The epilogue's arguments checked (the output quantizer as ssq_act_encode checks its own) and
+// gathered; the caller sets Cpo.
+static inline int qepi_init(const char* what, const float* bias, const float* gamma,
+                            const float* phi, int act, float delta, float zero_point, int qmin,
+                            int qmax, int8_t* out, uint32_t* bad, QEpi* e) {
   SSQ_REQUIRE(out && bad, SSQ_E_ARG, "%s: null pointer", what);
   SSQ_REQUIRE((gamma == nullptr) == (phi == nullptr), SSQ_E_ARG,
               "%s: gamma and phi go together", what);
   SSQ_REQUIRE(act >= 0 && act <= 2, SSQ_E_ARG, "%s: activation code %d not in [0, 2]", what, act);
-  SSQ_REQUIRE(qmin < qmax && qmax - qmin <= 255, SSQ_E_ARG,
-              "%s: output code range [%d, %d] does not fit 8-bit codes", what, qmin, qmax);
-  SSQ_REQUIRE(delta > 0.0f && delta <= 3.0e38f, SSQ_E_ARG,
-              "%s: output delta must be positive and finite", what);
-  SSQ_REQUIRE(zero_point == rintf(zero_point) && zero_point >= (float)qmin &&
-                  zero_point <= (float)(qmin + 255),
-              SSQ_E_ARG, "%s: output zero point %g is not an integer in [%d, %d]", what,
-              (double)zero_point, qmin, qmin + 255);
+  const int rc = qquant_ok(what, "output ", &delta, zero_point, qmin, qmax);
+  if (rc) return rc;
+  *e = {bias, gamma, phi, delta, zero_point, (float)qmin, (float)qmax, act, 0u, out, bad};
   return SSQ_OK;
 }
 
-// the residual codes' quantizer, held to the same rules
-static inline int qres_ok(const char* what, const float* res_f32, const int8_t* res_codes,
-                          float delta, float zero_point, int qmin, int qmax) {
+// A tail's residual likewise: exactly one operand, the codes' quantizer held to the same rules
+static inline int qres_init(const char* what, const float* res_f32, const int8_t* res_codes,
+                            float delta, float zero_point, int qmin, int qmax, QRes* r) {
   SSQ_REQUIRE((res_f32 != nullptr) != (res_codes != nullptr), SSQ_E_ARG,
               "%s: exactly one of res_f32 and res_codes must be set", what);
-  if (!res_codes) return SSQ_OK;
-  SSQ_REQUIRE(qmin < qmax && qmax - qmin <= 255, SSQ_E_ARG,
-              "%s: residual code range [%d, %d] does not fit 8-bit codes", what, qmin, qmax);
-  SSQ_REQUIRE(delta > 0.0f && delta <= 3.0e38f, SSQ_E_ARG,
-              "%s: residual delta must be positive and finite", what);
-  SSQ_REQUIRE(zero_point == rintf(zero_point) && zero_point >= (float)qmin &&
-                  zero_point <= (float)(qmin + 255),
-              SSQ_E_ARG, "%s: residual zero point %g is not an integer in [%d, %d]", what,
-              (double)zero_point, qmin, qmin + 255);
+  const int rc = res_codes ? qquant_ok(what, "residual ", &delta, zero_point, qmin, qmax) : SSQ_OK;
+  if (rc) return rc;
+  *r = {res_f32, res_codes, delta, zero_point, (float)qmin};
   return SSQ_OK;
 }
 

@@ -32,171 +32,25 @@
 
 #include "ssq_common.h"
 #include "qinfer_epi.h"
+#include "qinfer_layout.h"
+#include "qinfer_prepare.h"
 
 namespace ssq {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kGT = 64;      // pixels, channel rows (at most) and k per tile step
 constexpr int kGRow = 80;    // LDS row stride in bytes (64 + 16), as K23
-constexpr int64_t kGMaxK = 65536;
 constexpr uint32_t kDwBlocks = 2048;   // workgroups K25 aims for: 8 per CU
 
-static inline int64_t rup(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
-// 0 invalid, 1 depthwise direct, 2 grouped MFMA
-static inline int qg_kind(int64_t Co, int64_t Cig, int64_t groups) {
-  if (groups < 2 || Co < 1 || Cig < 1 || Co % groups != 0) return 0;
-  return (Cig == 1 && Co == groups) ? 1 : 2;
-}
-
-struct GLayout {
-  int kind;
-  int64_t C, Cp, Cog, Cogp, Wc, Kp, tiles;   // tiles: channel tiles per group
-  size_t off_mask, off_cwz, off_t, bytes;
-};
-
-static inline GLayout glayout(int64_t Co, int64_t Cig, int64_t R, int64_t S, int64_t groups) {
-  GLayout L = {};
-  L.kind = qg_kind(Co, Cig, groups);
-  if (!L.kind || R < 1 || S < 1) {
-    L.kind = 0;
-    return L;
-  }
-  L.C = Cig * groups;
-  L.Cp = rup(L.C, 16);
-  L.Cog = Co / groups;
-  if (L.kind == 1) {
-    L.bytes = (size_t)(R * S) * (size_t)L.Cp * 4;
-    return L;
-  }
-  L.Cogp = rup(L.Cog, 16);
-  L.tiles = (L.Cogp + kGT - 1) / kGT;
-  // the window width repeats with period 16 / gcd(Cig, 16) <= 16 groups
-  for (int64_t g = 0; g < groups && g < 16; ++g) {
-    const int64_t w = rup((g + 1) * Cig, 16) - g * Cig / 16 * 16;
-    if (w > L.Wc) L.Wc = w;
-  }
-  L.Kp = rup(R * S * L.Wc, kGT);
-  L.off_mask = (size_t)(groups * L.Cogp) * (size_t)L.Kp;
-  L.off_cwz = L.off_mask + (size_t)groups * (size_t)L.Kp;
-  L.off_t = L.off_cwz + (size_t)Co * 4;
-  L.bytes = L.off_t + (size_t)Co * 4;
-  return L;
-}
-
-__device__ __forceinline__ uint32_t gwave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, kWave);
-  return v;
-}
-
-// K22's zero-point rule: any integer near the code range, else counted and taken as qmin
-__device__ __forceinline__ bool zp_is_code(float z, int qmin) {
-  return z == rintf(z) && z >= (float)(qmin - 256) && z <= (float)(qmin + 511);
-}
-__device__ __forceinline__ int zp_or_qmin(float z, int qmin, uint32_t* bad) {
-  if (!zp_is_code(z, qmin)) {
-    atomicAdd(bad, 1u);
-    return qmin;
-  }
-  return (int)z;
-}
-
-__device__ __forceinline__ uint32_t packed_code(const uint8_t* packed, size_t idx, int bs) {
-  const size_t bit = idx * (size_t)bs;
-  return ((uint32_t)packed[bit >> 3] >> (bit & 7)) & ((1u << bs) - 1u);
-}
-
 // ---------------------------------------------------------------- K24 weight prepare
-// depthwise: one thread per (tap, padded channel)
+// Plain and COLSCALE as K22 (qinfer.hip): COLSCALE stores the centred integer
+// m = (q - z_w[co]) * kcol[j], j = (ci, r, s) within the group (J = Cig*R*S, shared by all groups),
+// and *bad also counts what colscaled() counts (qinfer_prepare.h).
+//
+// depthwise: one thread per (tap, padded channel) of K25's centred int32 blob [R*S][Cp],
+// wc = q - z_w[c]; COLSCALE multiplies it by kcol[tap]
+template <bool COLSCALE>
 __global__ __launch_bounds__(kBlock) void qweight_prepare_dw_kernel(
-    const uint8_t* __restrict__ packed, const float* __restrict__ zp, int bs, int qmin, uint32_t C,
-    uint32_t RS, uint32_t Cp, FastDiv div_cp, int32_t* __restrict__ wc, uint32_t* __restrict__ bad) {
-  const uint32_t total = RS * Cp;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const uint32_t tap = fdiv(i, div_cp);
-    const uint32_t c = i - tap * Cp;
-    int v = 0;
-    if (c < C) {
-      const float zf = zp[c];
-      const bool ok = zp_is_code(zf, qmin);
-      const int z = ok ? (int)zf : qmin;
-      if (!ok && tap == 0) atomicAdd(bad, 1u);   // counted once per channel
-      v = (int)packed_code(packed, (size_t)c * RS + tap, bs) + qmin - z;
-    }
-    wc[i] = v;
-  }
-}
-
-// grouped: one workgroup per padded row (g, rl), then one per group for its 0/1 row
-__global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_kernel(
-    const uint8_t* __restrict__ packed, const float* __restrict__ zp, int bs, int qmin,
-    uint32_t groups, uint32_t Cig, uint32_t Cog, uint32_t Cogp, uint32_t RS, uint32_t Wc,
-    uint32_t Kp, FastDiv div_wc, FastDiv div_cogp, int8_t* __restrict__ wp,
-    int8_t* __restrict__ mask, int32_t* __restrict__ cwz, int32_t* __restrict__ tt,
-    uint32_t* __restrict__ bad) {
-  __shared__ int red[kBlock / kWave];
-  const uint32_t row = blockIdx.x;
-  const uint32_t nrows = groups * Cogp;
-  if (row >= nrows) {
-    const uint32_t g = row - nrows;
-    const uint32_t lo = g * Cig - g * Cig / 16 * 16;   // the group's offset inside its window
-    for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
-      const uint32_t tap = fdiv(k, div_wc);
-      const uint32_t cw = k - tap * Wc;
-      mask[(size_t)g * Kp + k] = (tap < RS && cw >= lo && cw < lo + Cig) ? 1 : 0;
-    }
-    return;
-  }
-  const uint32_t g = fdiv(row, div_cogp);
-  const uint32_t rl = row - g * Cogp;
-  const uint32_t co = g * Cog + rl;
-  const bool real = rl < Cog;
-  const uint32_t lo = g * Cig - g * Cig / 16 * 16;
-  int sum = 0;
-  for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
-    const uint32_t tap = fdiv(k, div_wc);
-    const uint32_t cw = k - tap * Wc;
-    int v = 0;
-    if (real && tap < RS && cw >= lo && cw < lo + Cig) {
-      v = (int)packed_code(packed, ((size_t)co * Cig + (cw - lo)) * RS + tap, bs) - 128;
-      sum += v;
-    }
-    wp[(size_t)row * Kp + k] = (int8_t)v;
-  }
-  sum = (int)gwave_sum_u32((uint32_t)sum);
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0 && real) {
-    const int z = zp_or_qmin(zp[co], qmin, bad);
-    int total = 0;
-    for (int i = 0; i < kBlock / kWave; ++i) total += red[i];
-    const int c = qmin + 128 - z;
-    cwz[co] = c;
-    tt[co] = total + (int)(Cig * RS) * c;
-  }
-}
-
-// K24 for a column-scaled weight W_hat = ((q - z_w[co]) * d1[co]) * (kcol[j] / L), j = (ci, r, s)
-// within the group (J = Cig*R*S, shared by all groups): the operand is the centred integer
-// m = (q - z_w[co]) * kcol[j].  *bad also counts the real elements whose m leaves [-127, 127]
-// (stored saturated) and those whose kcol[j] is not in [1, 127].
-__device__ __forceinline__ int colscaled(int centred, int kj, uint32_t& nbad) {
-  if (kj < 1 || kj > 127) {
-    ++nbad;
-    kj = 0;
-  }
-  int v = centred * kj;   // |q - z| <= 767, kj <= 127: no overflow
-  if (v > 127 || v < -127) {
-    ++nbad;
-    v = v > 0 ? 127 : -127;
-  }
-  return v;
-}
-
-// depthwise: K25's centred int32 blob [R*S][Cp] multiplied by kcol[tap]
-__global__ __launch_bounds__(kBlock) void qweight_prepare_dw_colscale_kernel(
     const uint8_t* __restrict__ packed, const float* __restrict__ zp,
     const int32_t* __restrict__ kcol, int bs, int qmin, uint32_t C, uint32_t RS, uint32_t Cp,
     FastDiv div_cp, int32_t* __restrict__ wc, uint32_t* __restrict__ bad) {
@@ -211,15 +65,18 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_dw_colscale_kernel(
       const bool ok = zp_is_code(zf, qmin);
       const int z = ok ? (int)zf : qmin;
       if (!ok && tap == 0) ++nbad;   // counted once per channel
-      v = colscaled((int)packed_code(packed, (size_t)c * RS + tap, bs) + qmin - z, kcol[tap], nbad);
+      v = (int)packed_code(packed, (size_t)c * RS + tap, bs) + qmin - z;
+      if constexpr (COLSCALE) v = colscaled(v, kcol[tap], nbad);
     }
     wc[i] = v;
   }
   if (nbad) atomicAdd(bad, nbad);
 }
 
-// grouped: K26's blob with m as the int8 operand, cwz = 0, T[co] = sum m, the 0/1 rows as above
-__global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_colscale_kernel(
+// grouped: one workgroup per padded row (g, rl), then one per group for its 0/1 row.  K26's blob;
+// COLSCALE: m as the int8 operand, cwz = 0, T[co] = sum m, the 0/1 rows all the same
+template <bool COLSCALE>
+__global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_kernel(
     const uint8_t* __restrict__ packed, const float* __restrict__ zp,
     const int32_t* __restrict__ kcol, int bs, int qmin, uint32_t groups, uint32_t Cig,
     uint32_t Cog, uint32_t Cogp, uint32_t RS, uint32_t Wc, uint32_t Kp, FastDiv div_wc,
@@ -228,9 +85,9 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_colscale_kerne
   __shared__ int red[kBlock / kWave];
   const uint32_t row = blockIdx.x;
   const uint32_t nrows = groups * Cogp;
+  const uint32_t g = row >= nrows ? row - nrows : fdiv(row, div_cogp);
+  const uint32_t lo = g * Cig - g * Cig / 16 * 16;   // the group's offset inside its window
   if (row >= nrows) {
-    const uint32_t g = row - nrows;
-    const uint32_t lo = g * Cig - g * Cig / 16 * 16;   // the group's offset inside its window
     for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
       const uint32_t tap = fdiv(k, div_wc);
       const uint32_t cw = k - tap * Wc;
@@ -238,17 +95,11 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_colscale_kerne
     }
     return;
   }
-  const uint32_t g = fdiv(row, div_cogp);
   const uint32_t rl = row - g * Cogp;
   const uint32_t co = g * Cog + rl;
   const bool real = rl < Cog;
-  const uint32_t lo = g * Cig - g * Cig / 16 * 16;
-  int z = qmin;
-  bool zok = true;
-  if (real) {
-    zok = zp_is_code(zp[co], qmin);
-    if (zok) z = (int)zp[co];
-  }
+  const bool zok = !real || zp_is_code(zp[co], qmin);
+  const int z = real && zok ? (int)zp[co] : qmin;
   int sum = 0;
   uint32_t nbad = 0;
   for (uint32_t k = threadIdx.x; k < Kp; k += blockDim.x) {
@@ -257,25 +108,27 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_colscale_kerne
     int v = 0;
     if (real && tap < RS && cw >= lo && cw < lo + Cig) {
       const size_t j = (size_t)(cw - lo) * RS + tap;
-      v = colscaled((int)packed_code(packed, (size_t)co * Cig * RS + j, bs) + qmin - z, kcol[j],
-                    nbad);
+      const int u = (int)packed_code(packed, (size_t)co * Cig * RS + j, bs);   // q - qmin
+      if constexpr (COLSCALE) v = colscaled(u + qmin - z, kcol[j], nbad);
+      else v = u - 128;   // q - cw, cw = qmin + 128
       sum += v;
     }
     wp[(size_t)row * Kp + k] = (int8_t)v;
   }
-  sum = (int)gwave_sum_u32((uint32_t)sum);
-  nbad = gwave_sum_u32(nbad);
+  sum = (int)wave_sum((uint32_t)sum);
+  nbad = wave_sum(nbad);
   if ((threadIdx.x & (kWave - 1)) == 0) {
     red[threadIdx.x / kWave] = sum;
     if (nbad) atomicAdd(bad, nbad);
   }
   __syncthreads();
-  if (threadIdx.x == 0 && real) {
+  if (threadIdx.x == 0 && real) {   // cwz and T have no padded rows
     int total = 0;
     for (int i = 0; i < kBlock / kWave; ++i) total += red[i];
     if (!zok) atomicAdd(bad, 1u);
-    cwz[co] = 0;
-    tt[co] = total;
+    const int c = COLSCALE ? 0 : qmin + 128 - z;
+    cwz[co] = c;
+    tt[co] = total + (int)(Cig * RS) * c;
   }
 }
 
@@ -534,13 +387,6 @@ __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
   }
 }
 
-static int grange_ok(const char* what, int n_bits, int qmin) {
-  SSQ_REQUIRE(n_bits >= 1 && n_bits <= 8, SSQ_E_ARG, "%s: n_bits %d not in [1, 8]", what, n_bits);
-  SSQ_REQUIRE(qmin == 0 || qmin == -(1 << (n_bits - 1)), SSQ_E_ARG,
-              "%s: qmin %d is neither 0 nor -2^(n_bits-1)", what, qmin);
-  return SSQ_OK;
-}
-
 // C < 0: the caller has no C of its own (prepare); else C must be Cig * groups
 static int ggeo_ok(const char* what, const char* plain, int64_t C, int64_t Co, int64_t Cig,
                    int64_t R, int64_t S, int64_t groups) {
@@ -581,61 +427,33 @@ extern "C" size_t ssq_qweight_prepared_bytes_grouped(int64_t Co, int64_t Cig, in
   return glayout(Co, Cig, R, S, groups).bytes;
 }
 
-extern "C" int ssq_qweight_prepare_grouped(const void* packed, const float* zp, int64_t Co,
-                                           int64_t Cig, int64_t R, int64_t S, int64_t groups,
-                                           int n_bits, int qmin, void* prepared, uint32_t* bad,
-                                           ssq_stream_t stream) {
-  const char* me = "ssq_qweight_prepare_grouped";
-  SSQ_REQUIRE(packed && zp && prepared && bad, SSQ_E_ARG, "%s: null pointer", me);
-  int rc = grange_ok(me, n_bits, qmin);
+// kcol: the column factors of a column-scaled weight (the COLSCALE kernels), or null; `plain`:
+// the groups == 1 entry point an error message points to
+static int qweight_prepare_grouped_launch(const char* me, const char* plain, bool colscale,
+                                          const void* packed, const float* zp,
+                                          const int32_t* kcol, int64_t Co, int64_t Cig, int64_t R,
+                                          int64_t S, int64_t groups, int n_bits, int qmin,
+                                          void* prepared, uint32_t* bad, ssq_stream_t stream) {
+  SSQ_REQUIRE(packed && zp && (kcol || !colscale) && prepared && bad, SSQ_E_ARG,
+              "%s: null pointer", me);
+  int rc = qrange_ok(me, n_bits, qmin);
   if (rc) return rc;
-  rc = ggeo_ok(me, "ssq_qweight_prepare", -1, Co, Cig, R, S, groups);
-  if (rc) return rc;
-  const GLayout L = glayout(Co, Cig, R, S, groups);
-  int8_t* base = (int8_t*)prepared;
-  const int bs = n_bits <= 2 ? 2 : (n_bits <= 4 ? 4 : 8);
-  const uint32_t RS = (uint32_t)(R * S);
-  if (L.kind == 1) {
-    hipLaunchKernelGGL(qweight_prepare_dw_kernel, dim3(grid_for((int64_t)RS * L.Cp, kBlock)),
-                       dim3(kBlock), 0, (hipStream_t)stream, (const uint8_t*)packed, zp, bs, qmin,
-                       (uint32_t)L.C, RS, (uint32_t)L.Cp, make_fastdiv((uint32_t)L.Cp),
-                       (int32_t*)base, bad);
-  } else {
-    hipLaunchKernelGGL(qweight_prepare_grouped_kernel,
-                       dim3((uint32_t)(groups * L.Cogp + groups)), dim3(kBlock), 0,
-                       (hipStream_t)stream, (const uint8_t*)packed, zp, bs, qmin, (uint32_t)groups,
-                       (uint32_t)Cig, (uint32_t)L.Cog, (uint32_t)L.Cogp, RS, (uint32_t)L.Wc,
-                       (uint32_t)L.Kp, make_fastdiv((uint32_t)L.Wc),
-                       make_fastdiv((uint32_t)L.Cogp), base, base + L.off_mask,
-                       (int32_t*)(base + L.off_cwz), (int32_t*)(base + L.off_t), bad);
-  }
-  return check_launch(me);
-}
-
-extern "C" int ssq_qweight_prepare_grouped_colscale(const void* packed, const float* zp,
-                                                    const int32_t* kcol, int64_t Co, int64_t Cig,
-                                                    int64_t R, int64_t S, int64_t groups,
-                                                    int n_bits, int qmin, void* prepared,
-                                                    uint32_t* bad, ssq_stream_t stream) {
-  const char* me = "ssq_qweight_prepare_grouped_colscale";
-  SSQ_REQUIRE(packed && zp && kcol && prepared && bad, SSQ_E_ARG, "%s: null pointer", me);
-  int rc = grange_ok(me, n_bits, qmin);
-  if (rc) return rc;
-  rc = ggeo_ok(me, "ssq_qweight_prepare_colscale", -1, Co, Cig, R, S, groups);
+  rc = ggeo_ok(me, plain, -1, Co, Cig, R, S, groups);
   if (rc) return rc;
   const GLayout L = glayout(Co, Cig, R, S, groups);
   int8_t* base = (int8_t*)prepared;
-  const int bs = n_bits <= 2 ? 2 : (n_bits <= 4 ? 4 : 8);
+  const int bs = packed_bits(n_bits);
   const uint32_t RS = (uint32_t)(R * S);
   if (L.kind == 1) {
-    hipLaunchKernelGGL(qweight_prepare_dw_colscale_kernel,
-                       dim3(grid_for((int64_t)RS * L.Cp, kBlock)), dim3(kBlock), 0,
+    auto* kernel = colscale ? qweight_prepare_dw_kernel<true> : qweight_prepare_dw_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid_for((int64_t)RS * L.Cp, kBlock)), dim3(kBlock), 0,
                        (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, bs, qmin,
                        (uint32_t)L.C, RS, (uint32_t)L.Cp, make_fastdiv((uint32_t)L.Cp),
                        (int32_t*)base, bad);
   } else {
-    hipLaunchKernelGGL(qweight_prepare_grouped_colscale_kernel,
-                       dim3((uint32_t)(groups * L.Cogp + groups)), dim3(kBlock), 0,
+    auto* kernel =
+        colscale ? qweight_prepare_grouped_kernel<true> : qweight_prepare_grouped_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)(groups * L.Cogp + groups)), dim3(kBlock), 0,
                        (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, bs, qmin,
                        (uint32_t)groups, (uint32_t)Cig, (uint32_t)L.Cog, (uint32_t)L.Cogp, RS,
                        (uint32_t)L.Wc, (uint32_t)L.Kp, make_fastdiv((uint32_t)L.Wc),
@@ -643,6 +461,25 @@ extern "C" int ssq_qweight_prepare_grouped_colscale(const void* packed, const fl
                        (int32_t*)(base + L.off_cwz), (int32_t*)(base + L.off_t), bad);
   }
   return check_launch(me);
+}
+
+extern "C" int ssq_qweight_prepare_grouped(const void* packed, const float* zp, int64_t Co,
+                                           int64_t Cig, int64_t R, int64_t S, int64_t groups,
+                                           int n_bits, int qmin, void* prepared, uint32_t* bad,
+                                           ssq_stream_t stream) {
+  return qweight_prepare_grouped_launch("ssq_qweight_prepare_grouped", "ssq_qweight_prepare",
+                                        false, packed, zp, nullptr, Co, Cig, R, S, groups, n_bits,
+                                        qmin, prepared, bad, stream);
+}
+
+extern "C" int ssq_qweight_prepare_grouped_colscale(const void* packed, const float* zp,
+                                                    const int32_t* kcol, int64_t Co, int64_t Cig,
+                                                    int64_t R, int64_t S, int64_t groups,
+                                                    int n_bits, int qmin, void* prepared,
+                                                    uint32_t* bad, ssq_stream_t stream) {
+  return qweight_prepare_grouped_launch("ssq_qweight_prepare_grouped_colscale",
+                                        "ssq_qweight_prepare_colscale", true, packed, zp, kcol, Co,
+                                        Cig, R, S, groups, n_bits, qmin, prepared, bad, stream);
 }
 
 // y: the fp32 output (ssq_qconv_i8_grouped_fwd) or null with `epi` set (..._codes_fwd)
@@ -664,14 +501,8 @@ static int qconv_grouped_launch(const char* me, const int8_t* codes, const void*
   SSQ_REQUIRE(Nb >= 1 && H >= 1 && W >= 1 && stride >= 1 && pad >= 0 && H + 2 * pad >= R &&
                   W + 2 * pad >= S,
               SSQ_E_ARG, "%s: bad geometry", me);
-  SSQ_REQUIRE(act_qmin < act_qmax && act_qmax - act_qmin <= 255, SSQ_E_ARG,
-              "%s: activation code range [%d, %d] does not fit 8-bit codes", me, act_qmin,
-              act_qmax);
-  // a padded tap stores act_zero_point - (act_qmin + 128) as an int8
-  SSQ_REQUIRE(act_zero_point == rintf(act_zero_point) && act_zero_point >= (float)act_qmin &&
-                  act_zero_point <= (float)(act_qmin + 255),
-              SSQ_E_ARG, "%s: zero point %g is not an integer in [%d, %d]", me,
-              (double)act_zero_point, act_qmin, act_qmin + 255);
+  rc = qquant_ok(me, "activation ", nullptr, act_zero_point, act_qmin, act_qmax);
+  if (rc) return rc;
   const GLayout L = glayout(Co, Cig, R, S, groups);
   const int64_t OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
   SSQ_REQUIRE(Nb * H * W * L.Cp < (1ll << 31) && Nb * OH * OW * Co < (1ll << 31), SSQ_E_ARG,
@@ -779,11 +610,10 @@ extern "C" int ssq_qconv_i8_grouped_codes_fwd(
     const float* phi, int act, float out_delta, float out_zero_point, int out_qmin, int out_qmax,
     int8_t* out_codes, uint32_t* bad, ssq_stream_t stream) {
   const char* me = "ssq_qconv_i8_grouped_codes_fwd";
-  const int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
-                         out_codes, bad);
+  QEpi e;
+  const int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin,
+                           out_qmax, out_codes, bad, &e);
   if (rc) return rc;
-  QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax, act,
-            0u, out_codes, bad};
   return qconv_grouped_launch(me, codes, prepared, scale, Nb, C, H, W, Co, R, S, stride, pad,
                               groups, act_zero_point, act_qmin, act_qmax, nullptr, &e, stream);
 }

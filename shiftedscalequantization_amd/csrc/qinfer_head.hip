@@ -21,6 +21,7 @@
 // sp [N] int32; padded channels 0 in both planes, every output byte written by one thread.
 // K30 ssq_qlinear_pooled_fwd: hi, lo, sp and the fc's K22 blob -> y [N][Co] fp32.
 #include "ssq_common.h"
+#include "qinfer_check.h"
 #include "qinfer_layout.h"
 
 namespace ssq {
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(kBlock) void avgpool_i8_digits_kernel(
       *(i32x4*)(lo + (size_t)n * Cp + (size_t)chunk * 16) = ol.v;
     }
   }
+  // not wave_sum(uint32_t): through the helper one instruction of this kernel's stream moves
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) spacc += __shfl_xor(spacc, o, kWave);
   if ((tid & (kWave - 1)) == 0) wred[tid / kWave] = spacc;
@@ -266,13 +268,8 @@ extern "C" int ssq_qlinear_pooled_fwd(const int8_t* hi, const int8_t* lo, const 
               "%s: HW = %lld not in [1, %d] (the int8 digit range)", me, (long long)HW, kHeadMaxHW);
   SSQ_REQUIRE(Ci <= kQMaxK, SSQ_E_ARG, "%s: C = %lld exceeds 65536 (int32 accumulator range)", me,
               (long long)Ci);
-  SSQ_REQUIRE(act_qmin < act_qmax && act_qmax - act_qmin <= 255, SSQ_E_ARG,
-              "%s: activation code range [%d, %d] does not fit 8-bit codes", me, act_qmin,
-              act_qmax);
-  SSQ_REQUIRE(act_zero_point == rintf(act_zero_point) && act_zero_point >= (float)act_qmin &&
-                  act_zero_point <= (float)(act_qmin + 255),
-              SSQ_E_ARG, "%s: zero point %g is not an integer in [%d, %d]", me,
-              (double)act_zero_point, act_qmin, act_qmin + 255);
+  const int rc = qquant_ok(me, "activation ", nullptr, act_zero_point, act_qmin, act_qmax);
+  if (rc) return rc;
   const QLayout L = qlayout(Co, Ci, 1, 1);
   SSQ_REQUIRE(L.off_mask < (1ull << 31), SSQ_E_ARG, "%s: prepared weights exceed 2^31 bytes", me);
   SSQ_REQUIRE(Nb * L.Cp < (1ll << 31) && Nb * Co < (1ll << 31), SSQ_E_ARG,

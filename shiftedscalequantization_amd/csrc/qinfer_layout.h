@@ -1,7 +1,12 @@
-// K22's prepared-weight layout, shared by its readers (K23 in qinfer.hip, K30 in
-// qinfer_head.hip): [Cop = 64*ceil(Co/64)][Kp = 64*ceil(R*S*Cp/64)] int8 rows,
-// k = (r*S + s)*Cp + ci with Cp = 16*ceil(Ci/16), then the 0/1 row [Kp], then cwz[Cop] and
-// T[Cop] (int32).
+// The prepared-weight layouts of the integer route.
+//
+// QLayout, K22's blob, shared by its readers (K23 in qinfer.hip, K30 in qinfer_head.hip):
+// [Cop = 64*ceil(Co/64)][Kp = 64*ceil(R*S*Cp/64)] int8 rows, k = (r*S + s)*Cp + ci with
+// Cp = 16*ceil(Ci/16), then the 0/1 row [Kp], then cwz[Cop] and T[Cop] (int32).
+//
+// GLayout, K24's blob (qinfer_grouped.hip), by kind.  Depthwise (K25): int32 [R*S][Cp].
+// Grouped (K26): int8 [G*Cogp][Kp], Kp = 64*ceil(R*S*Wc/64), k = tap * Wc + (c - w0_g) inside
+// group g's 16-aligned channel window; then the 0/1 rows [G][Kp]; then cwz[Co], T[Co] (int32).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -28,6 +33,50 @@ static inline QLayout qlayout(int64_t Co, int64_t Ci, int64_t R, int64_t S) {
   L.off_cwz = L.off_mask + (size_t)L.Kp;
   L.off_t = L.off_cwz + (size_t)L.Cop * 4;
   L.bytes = L.off_t + (size_t)L.Cop * 4;
+  return L;
+}
+
+constexpr int kGT = 64;      // K26: pixels, channel rows (at most) and k per tile step
+constexpr int64_t kGMaxK = 65536;
+
+// 0 invalid, 1 depthwise direct, 2 grouped MFMA
+static inline int qg_kind(int64_t Co, int64_t Cig, int64_t groups) {
+  if (groups < 2 || Co < 1 || Cig < 1 || Co % groups != 0) return 0;
+  return (Cig == 1 && Co == groups) ? 1 : 2;
+}
+
+struct GLayout {
+  int kind;
+  int64_t C, Cp, Cog, Cogp, Wc, Kp, tiles;   // tiles: channel tiles per group
+  size_t off_mask, off_cwz, off_t, bytes;
+};
+
+static inline GLayout glayout(int64_t Co, int64_t Cig, int64_t R, int64_t S, int64_t groups) {
+  GLayout L = {};
+  L.kind = qg_kind(Co, Cig, groups);
+  if (!L.kind || R < 1 || S < 1) {
+    L.kind = 0;
+    return L;
+  }
+  L.C = Cig * groups;
+  L.Cp = rup(L.C, 16);
+  L.Cog = Co / groups;
+  if (L.kind == 1) {
+    L.bytes = (size_t)(R * S) * (size_t)L.Cp * 4;
+    return L;
+  }
+  L.Cogp = rup(L.Cog, 16);
+  L.tiles = (L.Cogp + kGT - 1) / kGT;
+  // the window width repeats with period 16 / gcd(Cig, 16) <= 16 groups
+  for (int64_t g = 0; g < groups && g < 16; ++g) {
+    const int64_t w = rup((g + 1) * Cig, 16) - g * Cig / 16 * 16;
+    if (w > L.Wc) L.Wc = w;
+  }
+  L.Kp = rup(R * S * L.Wc, kGT);
+  L.off_mask = (size_t)(groups * L.Cogp) * (size_t)L.Kp;
+  L.off_cwz = L.off_mask + (size_t)groups * (size_t)L.Kp;
+  L.off_t = L.off_cwz + (size_t)Co * 4;
+  L.bytes = L.off_t + (size_t)Co * 4;
   return L;
 }
 

@@ -16,14 +16,13 @@
 // Layouts: fp32 NCHW in (K27), NHWC int8 with C padded to Cp = 16*ceil(C/16) otherwise.
 #include "ssq_common.h"
 #include "qinfer_epi.h"
+#include "qinfer_layout.h"
 
 namespace ssq {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef short i16x8 __attribute__((ext_vector_type(8)));
-
-static inline int64_t rup16(int64_t v) { return (v + 15) / 16 * 16; }
 
 // ---------------------------------------------------------------- K27 epilogue to codes
 // One wave per (64 consecutive pixels, 16-channel chunk): lane = pixel, so each of the 16 channel
@@ -147,16 +146,16 @@ extern "C" int ssq_epilogue_codes_fwd(const float* y, const float* bias, const f
                                       ssq_stream_t stream) {
   const char* me = "ssq_epilogue_codes_fwd";
   SSQ_REQUIRE(y, SSQ_E_ARG, "%s: null pointer", me);
-  const int rc = qepi_ok(me, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
-                         out_codes, bad);
+  QEpi e;
+  const int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin,
+                           out_qmax, out_codes, bad, &e);
   if (rc) return rc;
   SSQ_REQUIRE(Nb >= 1 && C >= 1 && H >= 1 && W >= 1, SSQ_E_ARG, "%s: bad geometry", me);
-  const int64_t Cp = rup16(C);
+  const int64_t Cp = rup(C, 16);
   SSQ_REQUIRE(Nb * H * W * Cp < (1ll << 31), SSQ_E_ARG, "%s: tensor exceeds 2^31 elements", me);
   const uint32_t npix = (uint32_t)(Nb * H * W), nch = (uint32_t)(Cp / 16);
   const uint32_t nwork = (npix + kWave - 1) / kWave * nch;
-  const QEpi e = {bias, gamma, phi, out_delta, out_zero_point, (float)out_qmin, (float)out_qmax,
-                  act, (uint32_t)Cp, out_codes, bad};
+  e.Cpo = (uint32_t)Cp;
   const dim3 grid(grid_for((int64_t)nwork * kWave, kBlock, 8192));
   hipLaunchKernelGGL(epilogue_codes_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, y, npix,
                      (uint32_t)(H * W), (uint32_t)C, nch, nwork, make_fastdiv(nch),
@@ -175,7 +174,7 @@ extern "C" int ssq_maxpool_i8_fwd(const int8_t* codes, int64_t Nb, int64_t C, in
   const int64_t OH = (H + 2 * pad - K) / stride + 1, OW = (W + 2 * pad - K) / stride + 1;
   SSQ_REQUIRE(H + 2 * pad >= K && W + 2 * pad >= K && OH >= 1 && OW >= 1, SSQ_E_ARG,
               "%s: empty output", me);
-  const int64_t Cp = rup16(C);
+  const int64_t Cp = rup(C, 16);
   SSQ_REQUIRE(Nb * H * W * Cp < (1ll << 31) && Nb * OH * OW * Cp < (1ll << 31), SSQ_E_ARG,
               "%s: tensor exceeds 2^31 elements", me);
   const uint32_t nch = (uint32_t)(Cp / 16);

@@ -1972,6 +1972,15 @@ def colscale_grid(col_scale):
     return None
 
 
+# (grouped, column-scaled) -> (the blob's byte query, the prepare entry point)
+_QPREPARE_FNS = {
+    (False, False): ("ssq_qweight_prepared_bytes", "ssq_qweight_prepare"),
+    (False, True): ("ssq_qweight_prepared_bytes", "ssq_qweight_prepare_colscale"),
+    (True, False): ("ssq_qweight_prepared_bytes_grouped", "ssq_qweight_prepare_grouped"),
+    (True, True): ("ssq_qweight_prepared_bytes_grouped", "ssq_qweight_prepare_grouped_colscale"),
+}
+
+
 def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None):
     """Packed codes (pack_encode's layout) + zp[co] -> QPrepared.  `shape` is the weight's own
     (Co, Cig, R, S); `groups` > 1 prepares for the grouped kernels (K24).  `kcol`: the int32
@@ -1992,6 +2001,7 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None):
     z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
     if z.numel() != Co:
         raise A.SSQError("qweight_prepare: zero point must have one entry per output channel")
+    extra = ()
     if kcol is not None:
         kc = torch.as_tensor(kcol).detach().reshape(-1)
         if kc.dtype.is_floating_point or kc.numel() != Ci * R * S:
@@ -2000,26 +2010,12 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None):
             raise A.SSQError(f"qweight_prepare: kcol must lie in [1, {COLSCALE_MAX_L}]")
         kc = kc.to(device=packed.device, dtype=torch.int32).contiguous()
         prep.centred = True
-        nbytes = (query("ssq_qweight_prepared_bytes_grouped", Co, Ci, R, S, groups) if groups > 1
-                  else query("ssq_qweight_prepared_bytes", Co, Ci, R, S))
-        prep.blob = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=packed.device)
-        if groups > 1:
-            call("ssq_qweight_prepare_grouped_colscale", _vp(packed), zpp, _vp(kc), Co, Ci, R, S,
-                 groups, int(n_bits), int(qmin), _vp(prep.blob), _vp(prep.bad), stream_of(packed))
-        else:
-            call("ssq_qweight_prepare_colscale", _vp(packed), zpp, _vp(kc), Co, Ci, R, S,
-                 int(n_bits), int(qmin), _vp(prep.blob), _vp(prep.bad), stream_of(packed))
-        return prep
-    if groups > 1:
-        prep.blob = torch.empty(max(query("ssq_qweight_prepared_bytes_grouped", Co, Ci, R, S, groups), 1),
-                                dtype=torch.uint8, device=packed.device)
-        call("ssq_qweight_prepare_grouped", _vp(packed), zpp, Co, Ci, R, S, groups, int(n_bits),
-             int(qmin), _vp(prep.blob), _vp(prep.bad), stream_of(packed))
-        return prep
-    prep.blob = torch.empty(max(query("ssq_qweight_prepared_bytes", Co, Ci, R, S), 1),
-                            dtype=torch.uint8, device=packed.device)
-    call("ssq_qweight_prepare", _vp(packed), zpp, Co, Ci, R, S, int(n_bits), int(qmin),
-         _vp(prep.blob), _vp(prep.bad), stream_of(packed))
+        extra = (_vp(kc),)
+    geo = (Co, Ci, R, S) + ((groups,) if groups > 1 else ())
+    size_fn, prepare_fn = _QPREPARE_FNS[groups > 1, kcol is not None]
+    prep.blob = torch.empty(max(query(size_fn, *geo), 1), dtype=torch.uint8, device=packed.device)
+    call(prepare_fn, _vp(packed), zpp, *extra, *geo, int(n_bits), int(qmin), _vp(prep.blob),
+         _vp(prep.bad), stream_of(packed))
     return prep
 
 
@@ -2105,7 +2101,20 @@ def _qconv_args(name, codes_or_x, prepared, scale, stride, padding, groups, act_
     return args, (codes, s), (N, Co, max(OH, 0), max(OW, 0), codes.dim() == 4)
 
 
-class CarriedCodes:
+ActQuant = collections.namedtuple("ActQuant", "delta zp n_bits sym")   # a per-tensor act quantizer
+
+
+class _Quantized:
+    """A tagged tensor's act quantizer: `q`, an ActQuant (what quantizer() returns), with its
+    fields also as plain attributes.  Built in the subclass's __init__ by tuple.__new__: one is
+    made per emitting layer per forward, and the namedtuple's own constructor costs as much as
+    the rest of the object."""
+
+    def quantizer(self):
+        return self.q
+
+
+class CarriedCodes(_Quantized):
     """What an int8 code tensor carried between two integer layers stands for (the tensor's
     `_ssq_codes`): the logical (N, C, H, W) -- (N, C) for a Linear's -- and the act quantizer
     (delta, zp, n_bits, sym) whose output (q - zp) * delta the codes hold, q = code +
@@ -2113,14 +2122,35 @@ class CarriedCodes:
 
     def __init__(self, shape, delta, zp, n_bits, sym):
         self.shape = tuple(int(v) for v in shape)
-        self.delta, self.zp, self.n_bits, self.sym = float(delta), float(zp), int(n_bits), bool(sym)
-
-    def quantizer(self):
-        return self.delta, self.zp, self.n_bits, self.sym
+        self.q = q = tuple.__new__(ActQuant, (float(delta), float(zp), int(n_bits), bool(sym)))
+        self.delta, self.zp, self.n_bits, self.sym = q
 
     def decode(self, codes):
         x = act_decode(codes, self.shape[1], self.delta, self.zp, self.n_bits, self.sym)
         return x.view(self.shape)
+
+
+def _channel_vecs(name, C, bias, gamma, phi, per="output channel"):
+    """The epilogue's optional per-channel vectors -> (the contiguous tensors, which the caller
+    holds until its call is issued; their [bias, gamma, phi] device pointers)."""
+    keep, ptrs = [], []
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (phi, "phi")):
+        v, vp = (None, None) if t is None else fptr(t.detach().reshape(-1), nm)
+        if v is not None and v.numel() != C:
+            raise A.SSQError(f"{name}: {nm} must have one entry per {per}")
+        keep.append(v)
+        ptrs.append(vp)
+    return keep, ptrs
+
+
+def _nhwc_codes(name, codes):
+    """act_encode's 4-D int8 codes, contiguous on the device -> (codes, (N, H, W, Cpad))."""
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int8:
+        raise A.SSQError(f"{name}: expected int8 codes")
+    codes = _i8_dev(codes, name)
+    if codes.dim() != 4 or codes.shape[-1] % 16:
+        raise A.SSQError(f"{name}: codes {tuple(codes.shape)} are not (N, H, W, Cpad)")
+    return codes, tuple(int(v) for v in codes.shape)
 
 
 def carried(codes, shape, delta, zp, n_bits, sym):
@@ -2169,12 +2199,7 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
     args, keep, (N, Co, OH, OW, _) = _qconv_args(
         "qconv_codes", codes_or_x, prepared, scale, stride, padding, groups, act_zp, act_bits,
         act_sym, act_delta, bad)
-    vecs = []
-    for t, nm in ((bias, "bias"), (gamma, "gamma"), (phi, "phi")):
-        v, vp = (None, None) if t is None else fptr(t.detach().reshape(-1), nm)
-        if v is not None and v.numel() != Co:
-            raise A.SSQError(f"qconv_codes: {nm} must have one entry per output channel")
-        vecs.append((v, vp))
+    held, vecs = _channel_vecs("qconv_codes", Co, bias, gamma, phi)
     out = torch.empty((N, OH, OW, query("ssq_qinfer_cpad", Co)), dtype=torch.int8,
                       device=keep[0].device)
     olo, ohi = qrange(out_bits, out_sym)
@@ -2194,13 +2219,11 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
                                  f"codes, got {residual.dtype} {tuple(residual.shape)}")
             res, rp = fptr(residual.detach(), "residual")
             rargs = (rp, None, 0.0, 0.0, 0, 0)
-        call(_qconv_fn(prepared, 1, "codes_res_fwd"), *args, vecs[0][1], vecs[1][1], vecs[2][1],
-             int(relu),
-             float(out_delta), float(out_zp), olo, ohi, _vp(out), _vp(bad), *rargs, stream_of(out))
+        call(_qconv_fn(prepared, 1, "codes_res_fwd"), *args, *vecs, int(relu), float(out_delta),
+             float(out_zp), olo, ohi, _vp(out), _vp(bad), *rargs, stream_of(out))
         return out
-    call(_qconv_fn(prepared, groups, "codes_fwd"), *args, vecs[0][1], vecs[1][1], vecs[2][1],
-         int(relu), float(out_delta), float(out_zp),
-         olo, ohi, _vp(out), _vp(bad), stream_of(out))
+    call(_qconv_fn(prepared, groups, "codes_fwd"), *args, *vecs, int(relu), float(out_delta),
+         float(out_zp), olo, ohi, _vp(out), _vp(bad), stream_of(out))
     return out
 
 
@@ -2218,15 +2241,10 @@ def epilogue_codes(y, bias, gamma, phi, relu, out_delta, out_zp, out_bits, out_s
     if y.dim() != 4:
         raise A.SSQError(f"epilogue_codes: expected (N, C, H, W), got {tuple(y.shape)}")
     N, Cc, H, W = (int(v) for v in y.shape)
-    vecs = []
-    for t, nm in ((bias, "bias"), (gamma, "gamma"), (phi, "phi")):
-        v, vp = (None, None) if t is None else fptr(t.detach().reshape(-1), nm)
-        if v is not None and v.numel() != Cc:
-            raise A.SSQError(f"epilogue_codes: {nm} must have one entry per channel")
-        vecs.append((v, vp))
+    held, vecs = _channel_vecs("epilogue_codes", Cc, bias, gamma, phi, per="channel")
     out = torch.empty((N, H, W, query("ssq_qinfer_cpad", Cc)), dtype=torch.int8, device=y.device)
     olo, ohi = qrange(out_bits, out_sym)
-    call("ssq_epilogue_codes_fwd", yp, vecs[0][1], vecs[1][1], vecs[2][1], N, Cc, H, W, int(relu),
+    call("ssq_epilogue_codes_fwd", yp, *vecs, N, Cc, H, W, int(relu),
          float(out_delta), float(out_zp), olo, ohi, _vp(out), _vp(bad), stream_of(out))
     return out
 
@@ -2235,12 +2253,7 @@ def maxpool_codes(codes, k, stride, padding):
     """Max-pool (ssq_maxpool2d_fwd's geometry) on act_encode's int8 codes (N, H, W, Cpad) ->
     (N, OH, OW, Cpad) (ssq_maxpool_i8_fwd): the codes act_encode derives from the fp32 max-pool
     of the tensor the codes stand for."""
-    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int8:
-        raise A.SSQError("maxpool_codes: expected int8 codes")
-    codes = _i8_dev(codes, "maxpool_codes")
-    if codes.dim() != 4 or codes.shape[-1] % 16:
-        raise A.SSQError(f"maxpool_codes: codes {tuple(codes.shape)} are not (N, H, W, Cpad)")
-    N, H, W, Cp = (int(v) for v in codes.shape)
+    codes, (N, H, W, Cp) = _nhwc_codes("maxpool_codes", codes)
     k, stride, padding = int(k), int(stride), int(padding)
     OH = (H + 2 * padding - k) // max(stride, 1) + 1
     OW = (W + 2 * padding - k) // max(stride, 1) + 1
@@ -2259,12 +2272,7 @@ def avgpool_codes(codes):
     (ssq_avgpool_i8_digits_fwd): P_s[n, c] = sum_hw code as two int8 digits (N, Cpad),
     hi = (P_s + 64) >> 7 and lo = P_s - 128 * hi in [-64, 63], padded channels 0, and
     sp[n] = sum_c P_s[n, c] (int32) -> (hi, lo, sp)."""
-    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int8:
-        raise A.SSQError("avgpool_codes: expected int8 codes")
-    codes = _i8_dev(codes, "avgpool_codes")
-    if codes.dim() != 4 or codes.shape[-1] % 16:
-        raise A.SSQError(f"avgpool_codes: codes {tuple(codes.shape)} are not (N, H, W, Cpad)")
-    N, H, W, Cp = (int(v) for v in codes.shape)
+    codes, (N, H, W, Cp) = _nhwc_codes("avgpool_codes", codes)
     digits = torch.empty((2, N, Cp), dtype=torch.int8, device=codes.device)
     sp = torch.empty((N,), dtype=torch.int32, device=codes.device)
     call("ssq_avgpool_i8_digits_fwd", _vp(codes), N, Cp, H, W, _vp(digits[0]), _vp(digits[1]),
@@ -2319,7 +2327,7 @@ def qlinear_pooled_tile(tile=0):
     return query("ssq_qlinear_pooled_set_tile", int(tile))
 
 
-class PooledCodes:
+class PooledCodes(_Quantized):
     """What a pooled digit tensor stands for (the hi tensor's `_ssq_pooled`): the lo digits and
     the per-image sums that go with it, the logical (N, C), the HW pixels that were summed and
     the act quantizer (delta, zp, n_bits, sym) of the pooled codes.  Only the planned fc reads
@@ -2328,10 +2336,8 @@ class PooledCodes:
     def __init__(self, lo, sp, shape, HW, delta, zp, n_bits, sym):
         self.lo, self.sp = lo, sp
         self.shape, self.HW = tuple(int(v) for v in shape), int(HW)
-        self.delta, self.zp, self.n_bits, self.sym = float(delta), float(zp), int(n_bits), bool(sym)
-
-    def quantizer(self):
-        return self.delta, self.zp, self.n_bits, self.sym
+        self.q = q = tuple.__new__(ActQuant, (float(delta), float(zp), int(n_bits), bool(sym)))
+        self.delta, self.zp, self.n_bits, self.sym = q
 
 
 def pooled(hi, lo, sp, shape, HW, delta, zp, n_bits, sym):
