@@ -244,8 +244,9 @@ class SsqMaxPool2d(torch.nn.MaxPool2d):
     """nn.MaxPool2d whose forward runs on ssq_maxpool2d_fwd where it applies (a square
     window of <= 7, padding <= K // 2, no dilation / ceil mode / indices, a 4-D fp32 device
     input that needs no gradient); torch's pooling otherwise.  Same results either way.
-    A carried int8 code tensor (`carried`) is pooled as codes (ssq_maxpool_i8_fwd) when the
-    integer plan marks this pool, and decoded to the fp32 tensor it stands for otherwise."""
+    A carried int8 code tensor (`carried`) is pooled as codes (ssq_maxpool_i8_fwd) while the
+    integer plan's edge marks this pool and is live, and decoded to the fp32 tensor it stands for
+    otherwise."""
 
     @staticmethod
     def wrap(m):
@@ -266,7 +267,7 @@ class SsqMaxPool2d(torch.nn.MaxPool2d):
             return None
         return k, st, pad
 
-    _int_stem = None    # the StemCarry that marks a planned pool (quant/integer.py, carry_stem)
+    _int_stem = None    # the StemEdge that marks a planned pool (quant/integer.py, carry_stem)
 
     def forward(self, x):
         plan = self._plan()
@@ -274,8 +275,7 @@ class SsqMaxPool2d(torch.nn.MaxPool2d):
         if cc is not None:
             # a carried code tensor: pooled as codes (K28) by a planned pool, decoded otherwise
             stem = self._int_stem
-            if (stem is not None and plan is not None and not self._forward_hooks
-                    and not self._forward_pre_hooks):
+            if stem is not None and plan is not None and stem.live():
                 out = maxpool_codes(x, *plan)
                 stem.pooled[self] += 1
                 N, OH, OW, _ = (int(v) for v in out.shape)
@@ -292,8 +292,8 @@ class SsqGlobalAvgPool(torch.nn.AdaptiveAvgPool2d):
     ((N, C, 1, 1)), or with `flat` a GlobalMeanPool ((N, C)) -- whose forward is the wrapped
     module's on any untagged input.  A carried int8 code tensor (`carried`) is pooled as codes
     (ssq_avgpool_i8_digits_fwd, leaving as `pooled` digits for the planned fc) while the
-    integer plan's HeadCarry marks this pool and is live, and decoded to the fp32 tensor it
-    stands for otherwise."""
+    integer plan's edge marks this pool and is live, and decoded to the fp32 tensor it stands
+    for otherwise."""
 
     @staticmethod
     def wraps(m):
@@ -308,7 +308,7 @@ class SsqGlobalAvgPool(torch.nn.AdaptiveAvgPool2d):
         return s
 
     flat = False
-    _int_head = None    # the HeadCarry that marks a planned pool (quant/integer.py, carry_head)
+    _int_head = None    # the HeadEdge that marks a planned pool (quant/integer.py, carry_head)
 
     def forward(self, x):
         cc = getattr(x, "_ssq_codes", None)
@@ -317,7 +317,7 @@ class SsqGlobalAvgPool(torch.nn.AdaptiveAvgPool2d):
             if (head is not None and x.dim() == 4 and x.shape[1] * x.shape[2] <= HEAD_MAX_HW
                     and head.live()):
                 hi, lo, sp = avgpool_codes(x)
-                head.pooled += 1
+                head.pooled[self] += 1
                 return pooled(hi, lo, sp, (cc.shape[0], cc.shape[1]),
                               int(x.shape[1] * x.shape[2]), *cc.quantizer())
             x = materialize_epi(x)

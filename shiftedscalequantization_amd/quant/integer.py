@@ -1,196 +1,289 @@
-"""Integer inference of a calibrated model (K21-K23, csrc/qinfer.hip; grouped and depthwise
-convs on K24-K26, csrc/qinfer_grouped.hip, with `grouped=True`).
+"""Integer inference of a calibrated model (K21-K30, csrc/qinfer*.hip).
 
-A QuantModule whose input is the direct output of an act quantizer (scalar delta, integer
-zero point) and whose hard weight is (q - zero_point[co]) * scale[co] runs its conv / linear
-on the integer codes: the input is re-encoded to int8 (ssq_act_encode), multiplied with the
-layer's prepared int8 weight on the int8 MFMA (ssq_qconv_i8_fwd) and leaves as
-fp32(I) * fp32(delta_a * scale[co]).  The raw output then takes the module's unchanged bias /
-gamma^z, phi^z / activation / act-quant epilogue.  Every other layer keeps the decoded fp32
-path.  The switch is off until `enable_integer_inference` installs a plan; the plan holds the
-act quantizers' (delta, zero_point) as of that call, so re-enable after changing them.
+A QuantModule whose input is the direct output of a per-tensor act quantizer and whose hard
+weight is (q - zero_point[co]) * scale[co] runs its conv / linear on int8 codes and leaves as
+fp32(I) * fp32(delta_a * scale[co]); its bias / gamma^z, phi^z / activation / act-quant epilogue is
+unchanged.  Every other layer keeps the decoded fp32 path.  `enable_integer_inference` installs
+the plan (an IntPlan per layer); it holds the act quantizers' values as of that call, so
+re-enable after changing them.  `grouped=True` plans grouped and depthwise convs too (K24-K26);
+`colscale=True` plans column-scaled weights (ChannelQuantMSE) whose column scale lies on an
+integer grid k[j] / L, L <= 127 (K.colscale_grid), with the centred integer (q - z) * k[j] as the
+int8 operand.
 
-With `carry=True` the tensor between two integer layers of one block stays int8: the producer
-runs the code-emitting kernels (ssq_qconv_i8_codes_fwd / ssq_qconv_i8_grouped_codes_fwd:
-conv, bias, gamma^z / phi^z, activation and its act quantizer in one launch) and the consumer
-takes the codes as its operand, so the K13 epilogue pass and the K21 re-encode between them
-drop out.  Only the pairs a block declares (`BaseQuantBlock.interior_chain`) are carried: the
-planning trace sees module inputs, not residual adds or pooling, so the block's structure is
-what guarantees the producer's output has one reader.
-
-With `carry_blocks=True` the codes also cross a block's tail and its boundary: the block's last
-conv runs ssq_qconv_i8_codes_res_fwd (the residual add, the block's activation and the block's
-act quantizer in the conv kernel; the residual an fp32 tensor or the carried block input) and
-the next block's readers, its identity residual among them, take the codes.  Which boundaries
-qualify is structural again (`block_edges`: neighbours in an nn.Sequential, and the stages a
-model declares with `stage_chain`); the trace confirms the readers' input quantizer.  A tagged
-tensor that arrives where it is not the planned operand is decoded (K.materialize_epi), so a
-condition that fails at run time costs time, never correctness.
-
-With `carry_stem=True` the codes start at the model's front: the stem conv stays on the fp32
-route (its input is an unquantized image), but its K13 epilogue leaves as codes
-(ssq_epilogue_codes_fwd), a max-pool behind it pools the codes (ssq_maxpool_i8_fwd: a max-pool
-commutes with the decode, which is non-decreasing in the code) and the first block's readers
-take them.  The chain is structural once more (`stem_edges`, from the `stem_chain` a model
-declares); the planning trace follows an act quantizer's output through such a pool, so the
-layers behind it become eligible.
-
-With `carry_head=True` the codes run to the logits: the global average pool in front of the
-fc sums the carried codes of its input (ssq_avgpool_i8_digits_fwd: exact integers, stored as two
-int8 digits) and the fc multiplies the sums with its prepared int8 weight
-(ssq_qlinear_pooled_fwd), one int -> fp32 conversion and one multiply per logit.  The head has a
-numerics contract of its own: its logits are a function of the codes alone, not bit
-for bit those of an fp32 mean and an fp32 GEMM.  The chain is structural (`head_edges`, from
-the `head_chain` a model declares); the fc is planned for the pooled operand only, so whenever
-the pool does not pool codes the head is the fp32 one of the other routes.
-
-With `colscale=True` a column-scaled weight ((q - zero_point[co]) * scale[co]) * c[j]
-(ChannelQuantMSE, the form channelShift_wMSE puts on every conv) is planned too when its column
-scale lies on an integer grid c[j] = k[j] / L, L <= 127 (K.colscale_grid, host arithmetic on the
-J stored floats): the prepared int8 operand is the centred integer (q - zero_point[co]) * k[j]
-(ssq_qweight_prepare_colscale; every element must fit int8, counted on the device otherwise),
-the output scale fp32(fp32(delta * scale[co]) / fp32(L)), and the dense convs run the kernel
-instantiation without the window-sum MFMA.  Such a layer carries and consumes codes
-like any other; an all-ones column scale is a plain weight on the plain route.
+The carry flags keep a tensor between integer layers as int8 codes.  Each such tensor is one
+Edge: an emitting layer whose kernel applies the epilogue and the act quantizer and stores the
+codes, the readers whose planned operand the codes are, and the grid (K.ActQuant: delta, zp,
+n_bits, sym) they lie on.  Where the edges are is structural, because the planning trace sees
+module inputs, not residual adds or pooling:
+  carry         PairEdge  the pairs a block declares (`BaseQuantBlock.interior_chain`)
+  carry_blocks  TailEdge  a block's last conv with the residual add, the block's activation and
+                          act quantizer in its kernel, read by the next block (`block_edges`)
+  carry_stem    StemEdge  the stem conv's fp32 epilogue leaves as codes, max-pools behind it pool
+                          the codes, the first block reads them (`stem_edges`)
+  carry_head    HeadEdge  the global average pool sums the last producer's codes and the fc runs
+                          on the sums (`head_edges`); its logits are a function of the codes
+                          alone, not bit for bit those of an fp32 mean and GEMM
+Two rules decide whether an edge is installed: the emitter can emit onto the quantizer
+(`can_emit`) and the readers take the tensor (`readers_refuse`).  One rule decides at run time
+whether it still carries (`Edge.live`, over the modules of `Edge.watched`).  A tagged tensor
+that arrives where it is not the planned operand is decoded (K.materialize_epi), so a condition
+that fails at run time costs time, never correctness.  The installed edges are listed in
+`qnn._int_edges`; the marks the forwards read (`_int_plan.carry`, `_int_tail`, `_int_stem`,
+`_int_head`) are set and cleared through that list only.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import kernels as K
+from . import quant_layer as L
 from .export import PackedWeight, dequant_form
-from .quant_layer import QuantModule, UniformAffineQuantizer, fusable_act_quantizer
+from .fold_bn import StraightThrough as FoldedBN
+from .quant_block import BaseQuantBlock
+from .quant_layer import (QuantModule, StraightThrough, UniformAffineQuantizer, act_code,
+                          fusable_act_quantizer)
 
 INT8 = "int8"
 
 
 class IntPlan:
-    """One layer's installed integer route."""
+    """One layer's installed integer route; `grid`: the act quantizer of its input."""
 
-    def __init__(self, prepared, scale, delta, zp, n_bits, sym, stride, padding, counter):
-        self.prepared, self.scale = prepared, scale
+    def __init__(self, prepared, scale, grid, stride, padding, counter):
+        self.prepared, self.scale, self.grid = prepared, scale, grid
         self.groups = prepared.groups
         self.kind = K.qconv_kind(prepared)      # "dense" | "depthwise" | "grouped"
-        self.delta, self.zp, self.n_bits, self.sym = delta, zp, n_bits, sym
         self.stride, self.padding = stride, padding
         self.counter = counter
+        # the input operand's arguments of K.qconv / K.qconv_codes
+        self._operand = dict(groups=self.groups, act_zp=grid.zp, act_bits=grid.n_bits,
+                             act_sym=grid.sym, act_delta=grid.delta, bad=counter)
         self.calls = 0
-        self.carry = None                       # a Carry when this layer emits codes
-        self.head = None                        # a HeadCarry: the fc, on pooled digits only
+        self.carry = None                       # a PairEdge when this layer emits codes
+        self.head = None                        # a HeadEdge: the fc, on pooled digits only
+
+    # the input grid's fields under the plan's own names (views, not copies)
+    delta, zp, n_bits, sym = (property(lambda self, i=i: self.grid[i]) for i in range(4))
 
     def accepts(self, cc):
         """A carried tensor (K.CarriedCodes) holds this layer's planned operand."""
-        return cc.quantizer() == (self.delta, self.zp, self.n_bits, self.sym)
+        return cc.quantizer() == self.grid
 
-    def run_codes(self, x, bias, gamma, phi, relu, c=None, residual=None):
-        """The layer's whole forward as the consumer's int8 operand.  `c`: the output quantizer
-        and call counter (the layer's own Carry, or a block's TailCarry with the block's
-        activation as `relu` and the tail's `residual`)."""
-        c = self.carry if c is None else c
+    def takes(self, x):
+        """`x` is an operand of the code-emitting kernels: the planned codes or an fp32 tensor."""
+        cc = getattr(x, '_ssq_codes', None)
+        return self.accepts(cc) if cc is not None else x.dtype == torch.float32
+
+    def emit(self, x):
+        """QuantModule.forward's question: the forward as carried codes, or None."""
+        return None if self.carry is None else self.carry.emit(x)
+
+    def run_codes(self, x, bias, gamma, phi, relu, edge, residual=None):
+        """The layer's whole forward as `edge`'s int8 codes (`relu`: the activation's code)."""
+        o = edge.grid
         self.calls += 1
-        c.calls += 1
-        codes = K.qconv_codes(x, self.prepared, self.scale, self.stride, self.padding,
-                              groups=self.groups, act_zp=self.zp, act_bits=self.n_bits,
-                              act_sym=self.sym, act_delta=self.delta, bias=bias, gamma=gamma,
-                              phi=phi, relu=relu, out_delta=c.delta, out_zp=c.zp,
-                              out_bits=c.n_bits, out_sym=c.sym, bad=self.counter,
-                              residual=residual)
+        edge.calls += 1
+        codes = K.qconv_codes(x, self.prepared, self.scale, self.stride, self.padding, bias=bias,
+                              gamma=gamma, phi=phi, relu=relu, out_delta=o.delta, out_zp=o.zp,
+                              out_bits=o.n_bits, out_sym=o.sym, residual=residual, **self._operand)
         N, H, W, _ = codes.shape
-        return K.carried(codes, (N, self.prepared.shape[0], H, W), c.delta, c.zp, c.n_bits, c.sym)
+        return K.carried(codes, (N, self.prepared.shape[0], H, W), *o)
 
     def run(self, x):
         self.calls += 1
-        return K.qconv(x, self.prepared, self.scale, self.stride, self.padding,
-                       groups=self.groups, act_zp=self.zp,
-                       act_bits=self.n_bits, act_sym=self.sym, act_delta=self.delta,
-                       bad=self.counter)
+        return K.qconv(x, self.prepared, self.scale, self.stride, self.padding, **self._operand)
 
 
-class Carry:
-    """A producer's carried output: the consumer and the producer's act quantizer as the
-    consumer's plan holds it."""
+def _hooked(*mods):
+    return any(m._forward_hooks or m._forward_pre_hooks for m in mods)
 
-    def __init__(self, consumer):
-        p = consumer._int_plan
-        self.consumer = consumer
-        self.delta, self.zp, self.n_bits, self.sym = p.delta, p.zp, p.n_bits, p.sym
+
+def can_emit(m, q, own, x=None):
+    """Layer `m` can leave as codes of act quantizer `q`: its own (`own`; the layer then has
+    act quantization of its own), or its block's, whose tail `m` then is with neither activation
+    nor act quantizer of its own.  Its epilogue is one the kernels apply (a conv, no SE module, a
+    known activation: epilogue_fusable) and `q` one they apply (fusable_act_quantizer).  `x`: the
+    input at run time; None at plan time, where the weight stands in for it and `q`'s values
+    must be ones a plan can hold (_input_reason)."""
+    if own == m.disable_act_quant or not (own or isinstance(m.activation_function, StraightThrough)):
+        return False
+    if x is None and _input_reason(q)[0] is None:
+        return False
+    x = m.weight if x is None else x
+    return (isinstance(x, torch.Tensor) and m.epilogue_fusable(x)
+            and fusable_act_quantizer(q, True) is not None)
+
+
+def readers_refuse(q, readers, source, around, watched):
+    """Why `readers` do not take a tensor quantized by `q` as codes, None when they do:
+    "grouped", a grouped or depthwise conv of `around` left on the decoded path; "readers", none,
+    or one not planned or whose traced input (`source`) is not `q`'s output; "hook", a forward
+    hook on one of `watched` that would see the tensor."""
+    if any(isinstance(m, QuantModule) and m.fwd_kwargs.get("groups", 1) != 1 and m._int_plan is None
+           for a in around for m in a.modules()):
+        return "grouped"
+    if not readers or any(m._int_plan is None or source.get(m) is not q for m in readers):
+        return "readers"
+    return "hook" if _hooked(*watched) else None
+
+
+class Edge:
+    """One carried tensor of the installed plan: `readers`, the QuantModules whose planned
+    operand the codes are; `grid`, the act quantizer the codes lie on, as the readers' plans
+    hold it; `pools`, the marked pool modules the codes pass; `at`, the module the reports name
+    the edge by.  `marks`: the (object, attribute) pairs that hold the edge while it is
+    installed, where the forwards find it.  Counters: `calls`, the emitting forwards (a
+    HeadEdge's: the fc's), and `pooled`, per pool the forwards that pooled codes."""
+    emitter = None      # the edge a HeadEdge owns: its producer's TailEdge / PairEdge
+
+    def __init__(self, at, readers, watched, marks, pools=()):
+        self.at, self.readers, self.pools = at, list(readers), list(pools)
+        self.grid = self.readers[0]._int_plan.grid
+        self._watched, self._marks = list(dict.fromkeys(watched)), list(marks)
+        self.reset()
+
+    def watched(self):
+        """Exactly the modules whose run-time state `live` inspects."""
+        return self._watched
+
+    def live(self):
+        """The run-time state is still the planned one: no grad, no cached convs, no hook that
+        would see the tensor, no feature caching, weight and act quantization on, the readers
+        still planned and every mark still this edge."""
+        if torch.is_grad_enabled() or L._CONV_CACHE is not None:
+            return False
+        for m in self._watched:
+            if (m._forward_hooks or m._forward_pre_hooks
+                    or getattr(m, 'cache_features', 'none') != 'none'
+                    or not (getattr(m, 'use_weight_quant', True) and getattr(m, 'use_act_quant', True))):
+                return False
+        for m in self.readers:
+            if m._int_plan is None:
+                return False
+        for o, a in self._marks:
+            if getattr(o, a) is not self:
+                return False
+        return True
+
+    def reset(self):
         self.calls = 0
+        self.pooled = {m: 0 for m in self.pools}
+        if self.emitter is not None:
+            self.emitter.reset()
+
+    def install(self, on=True):
+        for o, a in self._marks:
+            setattr(o, a, self if on else None)
+        if self.emitter is not None:
+            self.emitter.install(on)
 
 
-class TailCarry:
-    """A block's carried output (carry_blocks): the block's last conv, the successor and its
-    module readers, and the block's act quantizer as the readers' plans hold it."""
+class PairEdge(Edge):
+    """A layer that emits with its own act quantizer for one reader: a block's interior pair
+    (carry), or the trailing layer in front of a carried head."""
 
-    def __init__(self, last, successor, entry, readers):
-        p = readers[0]._int_plan
-        self.last, self.successor, self.entry, self.readers = last, successor, entry, readers
-        self.delta, self.zp, self.n_bits, self.sym = p.delta, p.zp, p.n_bits, p.sym
-        self.calls = 0
-        self.residual = None        # the kind the last emitting forward added
+    def __init__(self, producer, consumer):
+        super().__init__(producer, [consumer], [producer, consumer], [(producer._int_plan, "carry")])
+
+    def emit(self, x):
+        """K.qconv_codes: conv, epilogue and act quantizer in one kernel."""
+        m = self.at
+        plan = m._int_plan
+        if not (self.live() and can_emit(m, m.act_quantizer, True, x) and plan.takes(x)):
+            return None
+        gamma, phi = m.affine()
+        return plan.run_codes(x, m.bias, gamma, phi, m.act_code(), self)
 
 
-class StemCarry:
-    """The stem's carried output (carry_stem): the producing conv, the pools its codes pass, the
-    successor with its entry and module readers, and the producer's act quantizer as the
-    readers' plans hold it."""
+class TailEdge(Edge):
+    """A block's carried output (carry_blocks): the block's last conv emits for the successor's
+    readers behind its `entry`; `residual`: the kind the last emitting forward added."""
+
+    def __init__(self, block, last, successor, entry, readers):
+        super().__init__(block, readers, [block, successor, last, entry, *readers],
+                         [(block, "_int_tail")])
+        self.last, self.successor, self.entry = last, successor, entry
+
+    def reset(self):
+        super().reset()
+        self.residual = None
+
+    def emit(self, last, x, residual):
+        """K.qconv_codes with the residual: conv, bias, gamma^z / phi^z, residual add, block
+        activation and block act quantizer in one kernel."""
+        blk, plan = self.at, last._int_plan
+        relu = act_code(blk.activation_function)
+        if (last is not self.last or plan is None or relu is None or not self.live()
+                or not can_emit(last, blk.act_quantizer, False, x) or not plan.takes(x)):
+            return None
+        if residual is None:
+            kind = "none"
+        elif not isinstance(residual, torch.Tensor):
+            return None
+        elif getattr(residual, '_ssq_codes', None) is not None:
+            kind = "codes"
+        elif residual.dtype == torch.float32 and residual.is_cuda:
+            kind = "fp32"
+        else:
+            return None
+        gamma, phi = last.affine()
+        out = plan.run_codes(x, last.bias, gamma, phi, relu, self, residual=residual)
+        self.residual = kind
+        return out
+
+
+class StemEdge(Edge):
+    """The stem's carried output (carry_stem): the producing conv stays on the fp32 route (its
+    input is an unquantized image), its epilogue emits, the pools pool the codes (a max-pool
+    commutes with the decode, which is non-decreasing in the code) and the successor's readers
+    behind its `entry` take them."""
 
     def __init__(self, producer, pools, successor, entry, readers):
-        p = readers[0]._int_plan
-        self.producer, self.pools, self.successor = producer, list(pools), successor
-        self.entry, self.readers = entry, readers
-        self.delta, self.zp, self.n_bits, self.sym = p.delta, p.zp, p.n_bits, p.sym
-        self.counter = p.counter
-        self.calls = 0
-        self.pooled = {m: 0 for m in self.pools}    # forwards in which a pool pooled codes
+        super().__init__(producer, readers, [producer, successor, *pools, entry, *readers],
+                         [(m, "_int_stem") for m in (producer, *pools)], pools)
+        self.successor, self.entry = successor, entry
+        self.counter = readers[0]._int_plan.counter
 
     def live(self):
-        """The run-time state behind the producer is still the planned one."""
-        mods = [self.entry] + self.readers
-        if _hooked(self.successor, *self.pools, *mods):
-            return False
-        if any(m._int_stem is not self or m._plan() is None for m in self.pools):
-            return False
-        if any(m.cache_features != 'none' for m in mods):
-            return False
-        return all(m._int_plan is not None and m.use_weight_quant and m.use_act_quant
-                   for m in self.readers)
+        return super().live() and all(m._plan() is not None for m in self.pools)
+
+    def emit(self, x):
+        """The conv on its fp32 route, then K.epilogue_codes."""
+        m = self.at
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 4
+                and self.live() and can_emit(m, m.act_quantizer, True, x)):
+            return None
+        out, bias = m.forward_raw(x)
+        gamma, phi = m.affine()
+        self.calls += 1
+        codes = K.epilogue_codes(out, bias, gamma, phi, m.act_code(), *self.grid, self.counter)
+        return K.carried(codes, tuple(out.shape), *self.grid)
 
 
-class HeadCarry:
-    """The carried head (carry_head): the producer (the last quant block, or a trailing
-    QuantModule) whose codes the marked pool sums and the fc that reads the sums; the fc's plan
-    holds the producer's act quantizer."""
+class HeadEdge(Edge):
+    """The carried head (carry_head): the pool sums the codes that `emitter`, the edge of the
+    producer (the last quant block, or a trailing QuantModule), emits for it, and the fc reads
+    the sums; named by the pool."""
 
-    def __init__(self, producer, pool, fc):
-        self.producer, self.pool, self.fc = producer, pool, fc
-        self.calls = 0          # fc forwards on ssq_qlinear_pooled_fwd
-        self.pooled = 0         # forwards in which the pool summed codes
+    def __init__(self, producer, pool, fc, emitter):
+        self.emitter = emitter
+        super().__init__(pool, [fc], [pool, fc], [(pool, "_int_head"), (fc._int_plan, "head")], [pool])
+        self.producer, self.fc = producer, fc
         self._scale_h = {}      # HW -> K.head_scale(plan.scale, HW)
-        self.emitter = None     # the producer's TailCarry / Carry: counts its emitting forwards
-
-    def live(self):
-        """The run-time state behind the pool is still the planned one."""
-        fc, p = self.fc, self.fc._int_plan
-        if torch.is_grad_enabled() or _hooked(self.pool, fc):
-            return False
-        if self.pool._int_head is not self or p is None or p.head is not self:
-            return False
-        return fc.cache_features == 'none' and fc.use_weight_quant and fc.use_act_quant
 
     def accepts(self, pc):
         """A pooled digit tensor (K.PooledCodes) holds the fc's planned operand."""
-        p = self.fc._int_plan
-        return (pc.quantizer() == (p.delta, p.zp, p.n_bits, p.sym)
-                and pc.shape[1] == p.prepared.shape[1] and 1 <= pc.HW <= K.HEAD_MAX_HW)
+        return (pc.quantizer() == self.grid and pc.shape[1] == self.fc._int_plan.prepared.shape[1]
+                and 1 <= pc.HW <= K.HEAD_MAX_HW)
 
     def run(self, hi, pc):
-        p = self.fc._int_plan
+        p, g = self.fc._int_plan, self.grid
         sh = self._scale_h.get(pc.HW)
         if sh is None:
             sh = self._scale_h[pc.HW] = K.head_scale(p.scale, pc.HW)
         self.calls += 1
         p.calls += 1
-        return K.qlinear_pooled(hi, pc.lo, pc.sp, p.prepared, sh, pc.HW, p.zp, p.n_bits, p.sym)
+        return K.qlinear_pooled(hi, pc.lo, pc.sp, p.prepared, sh, pc.HW, g.zp, g.n_bits, g.sym)
 
 
 def _layers(qnn):
@@ -289,7 +382,7 @@ def _input_reason(q):
         return None, f"input act quantizer's zero point {zp} is not an integer in [{lo}, {lo + 255}]"
     if q.n_bits < 2:
         return None, "activation bits below 2"
-    return (delta, zp, q.n_bits, q.sym), None
+    return K.ActQuant(delta, zp, q.n_bits, q.sym), None
 
 
 def _weight_codes(m, colscale=False):
@@ -335,6 +428,7 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     layers = _layers(qnn)
     if not layers:
         return {}
+    qnn._int_edges = []
     heads = head_edges(qnn) if carry_head else []
     source = _trace_inputs(qnn, sample, pools=carry_stem, heads=heads)
     head_fc = {fc: pool for _, pool, fc in heads}
@@ -410,14 +504,13 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
                             "scaled weight (q - z) * k leaves int8 (|m| > 127), or a zero point "
                             "is not an integer code")
             continue
-        delta, zp, n_bits, sym = act
         # s[co] = fp32(delta_a * d1[co]): one fp32 product of the two stored fp32 values
-        scale = (torch.full((1,), delta, dtype=torch.float32, device=dev)
+        scale = (torch.full((1,), act.delta, dtype=torch.float32, device=dev)
                  * f["scale"].detach().reshape(-1).float()).contiguous()
         if kcol is not None:
             # ... / fp32(L): the column grid's common denominator, one more rounding
             scale = (scale / torch.full((1,), float(L), dtype=torch.float32, device=dev)).contiguous()
-        m._int_plan = IntPlan(prep, scale, delta, zp, n_bits, sym, stride, padding, counter)
+        m._int_plan = IntPlan(prep, scale, act, stride, padding, counter)
         report[name] = INT8
     if carry:
         _plan_carry(qnn, source)
@@ -427,38 +520,34 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         _plan_stem_carry(qnn, source)
     if carry_head:
         _plan_head_carry(qnn, source, heads, report, sample)
+    order = {m: i for i, m in enumerate(qnn.modules())}
+    qnn._int_edges.sort(key=lambda e: order[e.at])      # the reports list them in module order
     return report
 
 
+def _install(qnn, edge):
+    edge.install()
+    qnn._int_edges.append(edge)
+    return edge
+
+
+def _edges(qnn, kind):
+    return [e for e in getattr(qnn, "_int_edges", ()) if type(e) is kind]
+
+
 def _plan_carry(qnn, source):
-    """Install a Carry on every producer of a block's interior chain whose pair can stay int8:
-    both planned, the consumer's traced input quantizer the producer's own act quantizer, the
-    producer's epilogue one the kernel applies (fusable quantizer and epilogue, no SE module),
-    and no hook that would see the tensor."""
-    from .quant_block import BaseQuantBlock
+    """A PairEdge on every producer of a block's interior chain whose pair can stay int8."""
     for blk in qnn.modules():
-        if not isinstance(blk, BaseQuantBlock):
-            continue
-        for prod, cons in blk.interior_chain():
-            if prod._int_plan is None or cons._int_plan is None:
-                continue
+        for prod, cons in blk.interior_chain() if isinstance(blk, BaseQuantBlock) else ():
             q = prod.act_quantizer
-            if source.get(cons) is not q or prod.disable_act_quant:
-                continue
-            if fusable_act_quantizer(q, True) is None or prod.se_module is not None:
-                continue
-            # (the weight stands in for the input: epilogue_fusable asks for its device only)
-            if not prod.epilogue_fusable(prod.weight) or prod.act_code() not in (0, 1, 2):
-                continue
-            if any(m._forward_hooks or m._forward_pre_hooks for m in (prod, cons)):
-                continue
-            prod._int_plan.carry = Carry(cons)
+            if (prod._int_plan is not None and can_emit(prod, q, True)
+                    and readers_refuse(q, [cons], source, (), (prod, cons)) is None):
+                _install(qnn, PairEdge(prod, cons))
 
 
 def _edge_entry(m):
     """The module a successor hands its input to and to nothing else: a quant block or a
     QuantModule itself, the first child (recursively) of an nn.Sequential; None otherwise."""
-    from .quant_block import BaseQuantBlock
     while not isinstance(m, (BaseQuantBlock, QuantModule)):
         if not isinstance(m, nn.Sequential) or len(m) == 0:
             return None
@@ -473,7 +562,6 @@ def block_edges(qnn):
     QuantModule or an nn.Sequential that starts with one; and, where the model declares the
     containers its forward applies back to back (`stage_chain()` on `qnn.model`), the last
     child of one stage and the first child of the next."""
-    from .quant_block import BaseQuantBlock
     edges = []
     for seq in qnn.modules():
         if isinstance(seq, nn.Sequential):
@@ -491,26 +579,9 @@ def block_edges(qnn):
     return edges
 
 
-def _hooked(*mods):
-    return any(m._forward_hooks or m._forward_pre_hooks for m in mods)
-
-
-def block_act_code(blk):
-    """The block activation as the kernels' code (0 identity, 1 ReLU, 2 ReLU6), None for any
-    other."""
-    from .quant_layer import StraightThrough
-    f = blk.activation_function
-    if isinstance(f, nn.ReLU6):
-        return 2
-    if isinstance(f, nn.ReLU):
-        return 1
-    return 0 if isinstance(f, StraightThrough) else None
-
-
 def edge_readers(successor):
     """(entry module, the QuantModules that read the successor's input, whether the input is
     also an identity residual); readers None when the input has a reader that is not known."""
-    from .quant_block import BaseQuantBlock
     entry = _edge_entry(successor)
     if isinstance(entry, QuantModule):
         return entry, [entry], False
@@ -524,52 +595,27 @@ def edge_readers(successor):
     return entry, None, False
 
 
-def _decoded_grouped(mod):
-    """`mod` holds a grouped or depthwise conv that is not planned."""
-    return any(isinstance(m, QuantModule) and m.fwd_kwargs.get("groups", 1) != 1
-               and m._int_plan is None for m in mod.modules())
-
-
 def _emitting_tail(blk):
-    """The block's last conv when its tail can emit codes (see _plan_block_carry), else None."""
-    from .quant_layer import StraightThrough
+    """The block's last conv when its tail can emit codes onto the block's act quantizer: a
+    planned dense conv under `can_emit`, the block's activation one the kernel applies."""
     last = blk.last_conv()
     plan = None if last is None else last._int_plan
-    if plan is None or plan.kind != "dense":
+    if plan is None or plan.kind != "dense" or act_code(blk.activation_function) is None:
         return None
-    if not isinstance(last.activation_function, StraightThrough) or last.se_module is not None:
-        return None
-    if not last.disable_act_quant or not last.epilogue_fusable(last.weight):
-        return None
-    q = blk.act_quantizer
-    if block_act_code(blk) is None or fusable_act_quantizer(q, True) is None:
-        return None
-    if _input_reason(q)[0] is None:
-        return None
-    return last
+    return last if can_emit(last, blk.act_quantizer, False) else None
 
 
 def _plan_block_carry(qnn, source):
-    """Install a TailCarry on every block of `block_edges` whose tail can emit codes: the last
-    conv a planned dense conv whose epilogue the kernel applies (no activation or act
-    quantizer of its own, no SE module), the block's activation and act quantizer ones the
-    kernel applies, every reader of the successor planned with the block's act quantizer as
-    its traced input, no grouped or depthwise conv of either side left on the decoded path
-    (without `grouped=True` a MobileNetV2 / RegNetX block has one in its middle: such a block
-    keeps its fp32 edges), and no hook that would see the tensor."""
+    """A TailEdge on every block of `block_edges` whose tail can emit and whose successor's
+    readers take the codes.  No grouped or depthwise conv of either side may be left on the
+    decoded path: without `grouped=True` a MobileNetV2 / RegNetX block has one in its middle,
+    and such a block keeps its fp32 edges."""
     for blk, succ in block_edges(qnn):
         last = _emitting_tail(blk)
-        if last is None:
-            continue
-        q = blk.act_quantizer
         entry, readers, _ = edge_readers(succ)
-        if not readers or any(m._int_plan is None or source.get(m) is not q for m in readers):
-            continue
-        if any(_decoded_grouped(m) for m in (blk, entry)):
-            continue
-        if _hooked(blk, last, succ, entry, *readers):
-            continue
-        blk._int_tail = TailCarry(last, succ, entry, readers)
+        if last is not None and readers_refuse(blk.act_quantizer, readers, source, (blk, entry),
+                                               (blk, last, succ, entry, *(readers or ()))) is None:
+            _install(qnn, TailEdge(blk, last, succ, entry, readers))
 
 
 def stem_edges(qnn):
@@ -579,9 +625,7 @@ def stem_edges(qnn):
     of one followed by StraightThrough only --, whose entries in between are StraightThrough or
     a max-pool the code kernel can run (SsqMaxPool2d with a plan), and whose last entry has an
     `_edge_entry`.  Empty for any other chain and for a model that declares none."""
-    from .fold_bn import StraightThrough as FoldedBN
-    from .quant_layer import StraightThrough as MovedAct
-    StraightThrough = (FoldedBN, MovedAct)      # a folded BN's and a moved activation's identity
+    ident = (FoldedBN, StraightThrough)     # a folded BN's and a moved activation's identity
     chain = getattr(getattr(qnn, "model", qnn), "stem_chain", None)
     mods = list(chain()) if callable(chain) else []
     if len(mods) < 2:
@@ -589,7 +633,7 @@ def stem_edges(qnn):
     prod = mods[0]
     if isinstance(prod, nn.Sequential):
         kids = list(prod)
-        if not kids or not all(isinstance(k, StraightThrough) for k in kids[1:]):
+        if not kids or not all(isinstance(k, ident) for k in kids[1:]):
             return []
         prod = kids[0]
     if not isinstance(prod, QuantModule):
@@ -598,7 +642,7 @@ def stem_edges(qnn):
     for m in mods[1:-1]:
         if isinstance(m, K.SsqMaxPool2d) and m._plan() is not None:
             pools.append(m)
-        elif not isinstance(m, StraightThrough):
+        elif not isinstance(m, ident):
             return []
     if _edge_entry(mods[-1]) is None:
         return []
@@ -606,31 +650,17 @@ def stem_edges(qnn):
 
 
 def _plan_stem_carry(qnn, source):
-    """Install a StemCarry on the producer of every `stem_edges` chain that can emit codes: a
-    conv on the fp32 route whose epilogue and act quantizer K27 applies (no SE module), every
-    reader of the successor planned with that act quantizer as its traced input (through the
-    pools), no grouped or depthwise conv of the entry left on the decoded path (the block-edge
-    rule), and no hook that would see the tensor.  The pools are marked with the same object."""
+    """A StemEdge on the producer of every `stem_edges` chain: a conv on the fp32 route that can
+    emit and whose successor's readers take the codes (their traced input is the producer's act
+    quantizer through the pools), with no grouped or depthwise conv of the entry left on the
+    decoded path."""
     for prod, pools, succ in stem_edges(qnn):
-        if prod._int_plan is not None or prod.fwd_func is not F.conv2d:
-            continue
-        if prod.se_module is not None or prod.disable_act_quant:
-            continue
-        if not prod.epilogue_fusable(prod.weight) or prod.act_code() not in (0, 1, 2):
-            continue
         q = prod.act_quantizer
-        if fusable_act_quantizer(q, True) is None or _input_reason(q)[0] is None:
-            continue
         entry, readers, _ = edge_readers(succ)
-        if not readers or any(m._int_plan is None or source.get(m) is not q for m in readers):
-            continue
-        if _decoded_grouped(entry):
-            continue
-        if _hooked(prod, succ, entry, *pools, *readers):
-            continue
-        prod._int_stem = StemCarry(prod, pools, succ, entry, readers)
-        for m in pools:
-            m._int_stem = prod._int_stem
+        if (prod._int_plan is None and can_emit(prod, q, True)
+                and readers_refuse(q, readers, source, (entry,),
+                                   (prod, succ, entry, *pools, *(readers or ()))) is None):
+            _install(qnn, StemEdge(prod, pools, succ, entry, readers))
 
 
 def head_edges(qnn):
@@ -641,10 +671,7 @@ def head_edges(qnn):
     `features.18`); the pool is a K.SsqGlobalAvgPool; the classifier a Linear QuantModule, or an
     nn.Sequential that ends in one behind nn.Dropout / nn.Flatten / identities only.  Empty for
     any other chain and for a model that declares none."""
-    from .fold_bn import StraightThrough as FoldedBN
-    from .quant_block import BaseQuantBlock
-    from .quant_layer import StraightThrough as MovedAct
-    ident = (FoldedBN, MovedAct, nn.Identity)
+    ident = (FoldedBN, StraightThrough, nn.Identity)
     chain = getattr(getattr(qnn, "model", qnn), "head_chain", None)
     mods = list(chain()) if callable(chain) else []
     if len(mods) != 3:
@@ -671,71 +698,53 @@ def head_edges(qnn):
     return [(prod, pool, fc)]
 
 
+def _plans(qnn):
+    return [(n, m._int_plan) for n, m in _layers(qnn) if getattr(m, "_int_plan", None) is not None]
+
+
 def _reset_calls(qnn):
     """Zero every forward counter of the installed plan (after the head's dry forward)."""
-    from .quant_block import BaseQuantBlock
-    for m in qnn.modules():
-        p = getattr(m, "_int_plan", None) if isinstance(m, QuantModule) else None
-        if p is not None:
-            p.calls = 0
-            if p.carry is not None:
-                p.carry.calls = 0
-        s = getattr(m, "_int_stem", None) if isinstance(m, QuantModule) else None
-        if s is not None:
-            s.calls = 0
-            s.pooled = {k: 0 for k in s.pooled}
-        t = getattr(m, "_int_tail", None) if isinstance(m, BaseQuantBlock) else None
-        if t is not None:
-            t.calls, t.residual = 0, None
-        h = getattr(m, "_int_head", None) if isinstance(m, K.SsqGlobalAvgPool) else None
-        if h is not None:
-            h.calls = h.pooled = 0
-    if getattr(qnn, "_int_counter", None) is not None:
-        qnn._int_counter.zero_()
+    for _, p in _plans(qnn):
+        p.calls = 0
+    for e in qnn._int_edges:
+        e.reset()
+    qnn._int_counter.zero_()
+
+
+HEAD_REFUSALS = {"grouped": "the last block holds a grouped conv on the decoded path",
+                 "readers": "the pool's input is not the last block's act quantizer output",
+                 "hook": "a forward hook on the last block, the pool or the fc"}
 
 
 def _plan_head_carry(qnn, source, heads, report, sample):
-    """Install a HeadCarry on every `head_edges` chain whose producer can emit codes for the
-    pool: a quant block whose tail emits under the block-edge rules with the fc as its reader
-    (ssq_qconv_i8_codes[_res]_fwd; a carried block input is then the RES = 2 residual), or a
-    trailing QuantModule under the interior-pair rules (ssq_qconv_i8_codes_fwd); the fc planned
-    with the producer's act quantizer as its traced input (through the pool); no hook that would
-    see the tensors; and a dry forward of `sample` under the installed plan that shows the
-    pooled digits arriving at the fc.  An fc whose edge is not installed loses its plan -- it
-    is planned for pooled digits only -- and is reported with the reason."""
-    from .quant_block import BaseQuantBlock
+    """A HeadEdge on every `head_edges` chain whose producer can emit codes for the pool -- a
+    quant block's tail (a carried block input is then the RES = 2 residual) or a trailing
+    QuantModule, not already emitting for another edge -- whose fc takes them through the pool,
+    and whose dry forward of `sample` under the installed plan shows the pooled digits arriving
+    at the fc.  An fc whose edge is not installed loses its plan -- it is planned for pooled
+    digits only -- and is reported with the reason."""
     names = {m: n for n, m in qnn.named_modules()}
     for prod, pool, fc in heads:
         if fc._int_plan is None:
             continue        # refused by the weight / input rules: the report says why
-        why = None
+        q, why = prod.act_quantizer, None
         if isinstance(prod, BaseQuantBlock):
-            q, last = prod.act_quantizer, _emitting_tail(prod)
+            last = _emitting_tail(prod)
             if last is None:
                 why = "the last block's tail cannot emit codes"
-            elif _decoded_grouped(prod):
-                why = "the last block holds a grouped conv on the decoded path"
-            elif getattr(prod, "_int_tail", None) is not None:
+            elif prod._int_tail is not None:
                 why = "the last block already emits codes for another edge"
+            watched = (prod, pool, fc, last)
         else:
-            q = prod.act_quantizer
-            if (prod._int_plan is None or prod.disable_act_quant or prod.se_module is not None
-                    or fusable_act_quantizer(q, True) is None
-                    or not prod.epilogue_fusable(prod.weight) or prod.act_code() not in (0, 1, 2)
-                    or prod._int_plan.carry is not None):
+            if prod._int_plan is None or not can_emit(prod, q, True) or prod._int_plan.carry is not None:
                 why = "the last layer cannot emit codes"
-        if why is None and source.get(fc) is not q:
-            why = "the pool's input is not the last block's act quantizer output"
-        if why is None and _hooked(prod, pool, fc, *([last] if isinstance(prod, BaseQuantBlock) else [])):
-            why = "a forward hook on the last block, the pool or the fc"
+            watched = (prod, pool, fc)
         if why is None:
-            head = HeadCarry(prod, pool, fc)
-            fc._int_plan.head = pool._int_head = head
-            if isinstance(prod, BaseQuantBlock):
-                head.emitter = prod._int_tail = TailCarry(last, pool, fc, [fc])
-            else:
-                head.emitter = prod._int_plan.carry = Carry(fc)
-            head.emitter.head = head
+            why = HEAD_REFUSALS.get(readers_refuse(q, [fc], source, (prod,), watched))
+        if why is None:
+            emitter = (TailEdge(prod, last, pool, fc, [fc]) if isinstance(prod, BaseQuantBlock)
+                       else PairEdge(prod, fc))
+            head = _install(qnn, HeadEdge(prod, pool, fc, emitter))
             try:
                 qnn(sample)
             except K.A.SSQError as e:
@@ -745,11 +754,8 @@ def _plan_head_carry(qnn, source, heads, report, sample):
                     why = "the dry forward did not bring pooled codes to the fc"
             _reset_calls(qnn)
             if why is not None:
-                pool._int_head = None
-                if isinstance(prod, BaseQuantBlock):
-                    prod._int_tail = None
-                else:
-                    prod._int_plan.carry = None
+                head.install(False)
+                qnn._int_edges.remove(head)
         if why is not None:
             fc._int_plan = None
             report[names[fc]] = f"no head edge: {why}"
@@ -757,18 +763,11 @@ def _plan_head_carry(qnn, source, heads, report, sample):
 
 def disable_integer_inference(qnn):
     """Every layer back on the decoded fp32 path."""
-    from .quant_block import BaseQuantBlock
+    for e in getattr(qnn, "_int_edges", ()):
+        e.install(False)
     for _, m in _layers(qnn):
         m._int_plan = None
-        m._int_stem = None
-    for m in qnn.modules():
-        if isinstance(m, BaseQuantBlock):
-            m._int_tail = None
-        elif isinstance(m, K.SsqMaxPool2d):
-            m._int_stem = None
-        elif isinstance(m, K.SsqGlobalAvgPool):
-            m._int_head = None
-    qnn._int_counter = None
+    qnn._int_edges, qnn._int_counter = [], None
 
 
 def integer_report(qnn):
@@ -777,21 +776,17 @@ def integer_report(qnn):
     rounding), "calls": {layer name: forwards taken on the integer route}}.  Reads one device
     word (the only sync of the integer path)."""
     counter = getattr(qnn, "_int_counter", None)
-    calls = {n: m._int_plan.calls for n, m in _layers(qnn) if getattr(m, "_int_plan", None) is not None}
-    return {"off_grid": int(counter.item()) if counter is not None else 0, "calls": calls}
+    return {"off_grid": int(counter.item()) if counter is not None else 0,
+            "calls": {n: p.calls for n, p in _plans(qnn)}}
 
 
 def carry_report(qnn):
     """{"pairs": [(producer name, consumer name), ...] the installed plan carries int8 codes
     between, "calls": {producer name: forwards that emitted codes}}; empty without a plan."""
-    names = {m: n for n, m in _layers(qnn)}
-    pairs, calls = [], {}
-    for n, m in _layers(qnn):
-        c = getattr(getattr(m, "_int_plan", None), "carry", None)
-        if c is not None and getattr(c, "head", None) is None:
-            pairs.append((n, names[c.consumer]))
-            calls[n] = c.calls
-    return {"pairs": pairs, "calls": calls}
+    names = {m: n for n, m in qnn.named_modules()}
+    pairs = _edges(qnn, PairEdge)
+    return {"pairs": [(names[e.at], names[e.readers[0]]) for e in pairs],
+            "calls": {names[e.at]: e.calls for e in pairs}}
 
 
 def block_carry_report(qnn):
@@ -799,25 +794,19 @@ def block_carry_report(qnn):
     emit int8 codes, "calls": {block name: forwards whose tail emitted codes}, "residual":
     {block name: "none" | "fp32" | "codes", the residual operand of the emitting tail: as the
     last emitting forward had it, before one as the plan expects it}}; empty without a plan."""
-    from .quant_block import BaseQuantBlock
     names = {m: n for n, m in qnn.named_modules()}
-    tails = [(n, m) for n, m in qnn.named_modules()
-             if isinstance(m, BaseQuantBlock) and getattr(m, "_int_tail", None) is not None
-             and getattr(m._int_tail, "head", None) is None]
-    fed = {m._int_tail.entry for _, m in tails}
-    fed |= {m._int_stem.entry for _, m in _layers(qnn) if getattr(m, "_int_stem", None) is not None}
-    edges, calls, residual = [], {}, {}
-    for n, blk in tails:
-        t = blk._int_tail
-        edges.append((n, names[t.successor]))
-        calls[n] = t.calls
-        kind = t.residual
+    tails = _edges(qnn, TailEdge)
+    fed = {e.entry for e in tails + _edges(qnn, StemEdge)}
+    residual = {}
+    for e in tails:
+        kind, blk = e.residual, e.at
         if kind is None and blk.identity_input_convs() is not None:
             kind = "codes" if blk in fed else "fp32"
         elif kind is None:
             kind = "none" if getattr(blk, "downsample", None) is None else "fp32"
-        residual[n] = kind
-    return {"edges": edges, "calls": calls, "residual": residual}
+        residual[names[blk]] = kind
+    return {"edges": [(names[e.at], names[e.successor]) for e in tails],
+            "calls": {names[e.at]: e.calls for e in tails}, "residual": residual}
 
 
 def stem_carry_report(qnn):
@@ -825,14 +814,10 @@ def stem_carry_report(qnn):
     installed plan lets emit int8 codes, "calls": {producer name: forwards that emitted codes},
     "pooled": {pool name: forwards that pooled codes}}; empty without a plan."""
     names = {m: n for n, m in qnn.named_modules()}
-    edges, calls, pooled = [], {}, {}
-    for n, m in _layers(qnn):
-        s = getattr(m, "_int_stem", None)
-        if s is not None:
-            edges.append((n, [names[p] for p in s.pools], names[s.successor]))
-            calls[n] = s.calls
-            pooled.update({names[p]: k for p, k in s.pooled.items()})
-    return {"edges": edges, "calls": calls, "pooled": pooled}
+    stems = _edges(qnn, StemEdge)
+    return {"edges": [(names[e.at], [names[p] for p in e.pools], names[e.successor]) for e in stems],
+            "calls": {names[e.at]: e.calls for e in stems},
+            "pooled": {names[p]: k for e in stems for p, k in e.pooled.items()}}
 
 
 def head_carry_report(qnn):
@@ -841,12 +826,8 @@ def head_carry_report(qnn):
     {pool name: forwards that summed codes (ssq_avgpool_i8_digits_fwd)}, "fc": {fc name: forwards
     on ssq_qlinear_pooled_fwd}}; empty without a plan."""
     names = {m: n for n, m in qnn.named_modules()}
-    out = {"edges": [], "calls": {}, "pooled": {}, "fc": {}}
-    for m in qnn.modules():
-        h = getattr(m, "_int_head", None) if isinstance(m, K.SsqGlobalAvgPool) else None
-        if h is not None:
-            out["edges"].append((names[h.producer], names[h.pool], names[h.fc]))
-            out["calls"][names[h.producer]] = h.emitter.calls
-            out["pooled"][names[h.pool]] = h.pooled
-            out["fc"][names[h.fc]] = h.calls
-    return out
+    heads = _edges(qnn, HeadEdge)
+    return {"edges": [(names[e.producer], names[e.at], names[e.fc]) for e in heads],
+            "calls": {names[e.producer]: e.emitter.calls for e in heads},
+            "pooled": {names[e.at]: e.pooled[e.at] for e in heads},
+            "fc": {names[e.fc]: e.calls for e in heads}}

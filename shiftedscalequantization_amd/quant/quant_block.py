@@ -104,48 +104,6 @@ class BaseQuantBlock(nn.Module):
             return K.materialize_epi(x)
         return x
 
-    def _tail_codes(self, last, inp, residual):
-        """The tail as carried int8 codes (K.qconv_codes with the residual: conv, bias,
-        gamma^z / phi^z, residual add, block activation and block act quantizer in one kernel)
-        when the block is a planned emitter (quant/integer.py, carry_blocks) and the run-time
-        state is still the planned one; None: take the usual route."""
-        from . import integer as I
-        from . import quant_layer as L
-        t = getattr(self, '_int_tail', None)
-        if t is None or t.last is not last or torch.is_grad_enabled():
-            return None
-        plan = last._int_plan
-        relu = I.block_act_code(self)
-        mods = [last, t.entry] + t.readers
-        if (plan is None or relu is None or L._CONV_CACHE is not None
-                or not (self.use_act_quant and self.cache_features == 'none')
-                or I._hooked(self, t.successor, *mods)
-                or any(m.cache_features != 'none' or not (m.use_weight_quant and m.use_act_quant)
-                       for m in mods)
-                or any(m._int_plan is None for m in t.readers)
-                or not last.disable_act_quant
-                or not isinstance(last.activation_function, StraightThrough)
-                or not isinstance(inp, torch.Tensor) or not last.epilogue_fusable(inp)
-                or fusable_act_quantizer(self.act_quantizer, True) is None):
-            return None
-        cc = getattr(inp, '_ssq_codes', None)
-        if not (plan.accepts(cc) if cc is not None else inp.dtype == torch.float32):
-            return None
-        if residual is None:
-            kind = "none"
-        elif not isinstance(residual, torch.Tensor):
-            return None
-        elif getattr(residual, '_ssq_codes', None) is not None:
-            kind = "codes"
-        elif residual.dtype == torch.float32 and residual.is_cuda:
-            kind = "fp32"
-        else:
-            return None
-        gamma, phi = last.affine()
-        out = plan.run_codes(inp, last.bias, gamma, phi, relu, c=t, residual=residual)
-        t.residual = kind
-        return out
-
     def _residual(self, ds, x):
         """ds(x), the downsample branch.  For the block the recon loop fuses (K.TAIL_LAZY)
         and a downsample whose forward ends in its K13 epilogue alone (bias, gamma^z/phi^z,
@@ -166,7 +124,7 @@ class BaseQuantBlock(nn.Module):
         no activation of its own and the block's is ReLU / identity, its bias add, the
         residual add and the activation run as one K13 epilogue pass (bit-identical)."""
         if getattr(self, '_int_tail', None) is not None:
-            out = self._tail_codes(last, inp, residual)
+            out = self._int_tail.emit(last, inp, residual)
             if out is not None:
                 return out
         # a carried block input as the identity residual of an fp32 tail: the tensor it stands for

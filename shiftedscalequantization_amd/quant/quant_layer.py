@@ -225,6 +225,16 @@ class UniformAffineQuantizer(nn.Module):
         return s.format(**self.__dict__)
 
 
+def act_code(f):
+    """An activation module as the fused epilogues' code: 0 identity, 1 ReLU, 2 ReLU6; None for
+    any other."""
+    if isinstance(f, nn.ReLU6):
+        return 2
+    if isinstance(f, nn.ReLU):
+        return 1
+    return 0 if isinstance(f, StraightThrough) else None
+
+
 def fusable_act_quantizer(q, active):
     """The act quantizer `q` if its per-tensor q/dq can run inside the K13 epilogue pass
     (an initialised plain UniformAffineQuantizer with scalar delta/zp and no hooks), else
@@ -360,10 +370,8 @@ class QuantModule(nn.Module):
         return weight, bias
 
     def act_code(self):
-        """The fused epilogues' activation code: 0 identity, 1 ReLU, 2 ReLU6."""
-        if isinstance(self.activation_function, nn.ReLU6):
-            return 2
-        return 1 if isinstance(self.activation_function, nn.ReLU) else 0
+        """The fused epilogues' activation code (act_code; identity for one they do not know)."""
+        return act_code(self.activation_function) or 0
 
     def epilogue_fusable(self, input):
         """The conv bias add, the gamma^z/phi^z affine and a ReLU / ReLU6 / identity
@@ -432,61 +440,16 @@ class QuantModule(nn.Module):
                 return hit[4], bias
         return self._conv(input, weight), bias
 
-    def _carry(self, input):
-        """The forward as carried int8 codes (K.qconv_codes: conv, epilogue and act quantizer
-        in one kernel) when this layer is a planned carrying producer (quant/integer.py) and
-        the run-time state is still the planned one; None: take the usual route."""
-        plan = self._int_plan
-        c = None if plan is None else plan.carry
-        if (c is None or torch.is_grad_enabled() or self.disable_act_quant
-                or not (self.use_weight_quant and self.use_act_quant)
-                or self.cache_features != 'none' or _CONV_CACHE is not None
-                or self._forward_hooks or self._forward_pre_hooks
-                or not isinstance(input, torch.Tensor) or not self.epilogue_fusable(input)
-                or fusable_act_quantizer(self.act_quantizer, True) is None):
-            return None
-        m = c.consumer
-        if (m._int_plan is None or m._forward_hooks or m._forward_pre_hooks
-                or m.cache_features != 'none' or not (m.use_weight_quant and m.use_act_quant)):
-            return None
-        cc = getattr(input, '_ssq_codes', None)
-        if not (plan.accepts(cc) if cc is not None else input.dtype == torch.float32):
-            return None
-        gamma, phi = self.affine()
-        return plan.run_codes(input, self.bias, gamma, phi, self.act_code())
-
-    def _stem_codes(self, input):
-        """The forward as carried int8 codes when this layer is the planned producer of a stem
-        edge (quant/integer.py, carry_stem): the conv on its fp32 route, then K.epilogue_codes
-        (bias, gamma^z / phi^z, activation and the act quantizer, leaving as the readers'
-        operand) when the run-time state is still the planned one; None: take the usual route."""
-        s = self._int_stem
-        if (torch.is_grad_enabled() or self.disable_act_quant
-                or not (self.use_weight_quant and self.use_act_quant)
-                or self.cache_features != 'none' or _CONV_CACHE is not None
-                or self._forward_hooks or self._forward_pre_hooks
-                or not isinstance(input, torch.Tensor) or input.dtype != torch.float32
-                or input.dim() != 4 or not self.epilogue_fusable(input)
-                or self.act_code() not in (0, 1, 2)
-                or fusable_act_quantizer(self.act_quantizer, True) is None or not s.live()):
-            return None
-        out, bias = self.forward_raw(input)
-        gamma, phi = self.affine()
-        s.calls += 1
-        codes = K.epilogue_codes(out, bias, gamma, phi, self.act_code(), s.delta, s.zp, s.n_bits,
-                                 s.sym, s.counter)
-        return K.carried(codes, tuple(out.shape), s.delta, s.zp, s.n_bits, s.sym)
-
     def forward(self, input: torch.Tensor):
         if self.cache_features == 'if':
             input = K.materialize_epi(input)
             self.cached_inp_features += [self._cache(input)]
         elif getattr(self, '_int_plan', None) is not None:
-            out = self._carry(input)
+            out = self._int_plan.emit(input)
             if out is not None:
                 return out
         elif getattr(self, '_int_stem', None) is not None:
-            out = self._stem_codes(input)
+            out = self._int_stem.emit(input)
             if out is not None:
                 return out
         act_q = self.use_act_quant and not self.disable_act_quant

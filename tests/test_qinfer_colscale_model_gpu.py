@@ -105,16 +105,9 @@ def logits_of(Q, qnn, x, **mode):
 
 def strip_carries(Q, qnn):
     """The installed plan with every layer on its own: no codes carried anywhere."""
-    from shiftedscalequantization_amd import kernels as K
-    for m in qnn.modules():
-        if isinstance(m, Q.QuantModule):
-            if m._int_plan is not None:
-                m._int_plan.carry = None
-            m._int_stem = None
-        elif isinstance(m, Q.BaseQuantBlock):
-            m._int_tail = None
-        elif isinstance(m, K.SsqMaxPool2d):
-            m._int_stem = None
+    for e in qnn._int_edges:
+        e.install(False)
+    del qnn._int_edges[:]
 
 
 @pytest.fixture(scope="module")

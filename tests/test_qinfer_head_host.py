@@ -254,3 +254,40 @@ def test_a_pooled_tensor_at_an_unplanned_layer_raises():
     t = K.pooled(d, d, torch.zeros(2, dtype=torch.int32), (2, 512), 49, 0.1, 0.0, 8, False)
     with torch.no_grad(), pytest.raises(SSQError, match="planned fc"):
         qnn.model.fc(t)
+
+
+def test_layer_and_block_modules_import_without_the_planner():
+    """quant_layer and quant_block ask the installed edges and import nothing from
+    quant.integer.  (A fresh child: this process has the whole package loaded; the stubbed
+    parent package keeps quant/__init__.py, which imports the planner for its API, out.)"""
+    import subprocess
+    import sys
+    code = ("import sys, types, importlib.util\n"
+            "import shiftedscalequantization_amd as pkg\n"
+            "q = types.ModuleType(pkg.__name__ + '.quant')\n"
+            "q.__path__ = [pkg.__path__[0] + '/quant']\n"
+            "sys.modules[q.__name__] = q\n"
+            "import shiftedscalequantization_amd.quant.quant_layer\n"
+            "import shiftedscalequantization_amd.quant.quant_block\n"
+            "assert q.__name__ + '.quant_block' in sys.modules\n"
+            "assert q.__name__ + '.integer' not in sys.modules, 'integer imported'\n")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True,
+                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert r.returncode == 0, r.stderr
+
+
+def test_the_grid_round_trips_through_the_tags():
+    """The one quantizer value (K.ActQuant) comes back from the tags it is unpacked into, and
+    is what a plan compares a tag with."""
+    from shiftedscalequantization_amd import kernels as K
+    from shiftedscalequantization_amd.quant import integer as I
+    grid = K.ActQuant(0.125, 3.0, 4, False)
+    t = K.carried(torch.zeros(1, 2, 2, 16, dtype=torch.int8), (1, 16, 2, 2), *grid)
+    assert t._ssq_codes.quantizer() == grid and type(t._ssq_codes.quantizer()) is K.ActQuant
+    d = torch.zeros(1, 16, dtype=torch.int8)
+    p = K.pooled(d, d, torch.zeros(1, dtype=torch.int32), (1, 16), 4, *grid)
+    assert p._ssq_pooled.quantizer() == grid and p._ssq_pooled.HW == 4
+    plan = I.IntPlan.__new__(I.IntPlan)
+    plan.grid = grid
+    assert plan.accepts(t._ssq_codes) and plan.takes(t) and plan.takes(torch.zeros(1))
+    assert not plan.accepts(K.CarriedCodes((1, 16, 2, 2), 0.125, 3.0, 8, False))

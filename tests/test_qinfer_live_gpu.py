@@ -1,15 +1,16 @@
-"""The run-time side of the carried routes (quant/integer.py with carry_head=True, so every
-kind of edge is installed): a condition that no longer holds at run time costs time, never
-correctness.  One condition at a time is applied AFTER planning -- a forward under
-torch.enable_grad(), act quantization switched off on one interior consumer and on one
-block-edge reader, quant_layer._CONV_CACHE set -- and the forward must give the logits of the
-same model in the same state planned with no carry flag, bit for bit, with nothing off the
+"""The single live rule of the carried routes (quant/integer.py, Edge.live, with
+carry_head=True, so every kind of edge is installed): a condition that no longer holds at run
+time costs time, never correctness.  One condition at a time is applied AFTER planning -- a
+forward under torch.enable_grad(), act quantization switched off on one interior consumer and on
+one block-edge reader, quant_layer._CONV_CACHE set, a no-op forward hook on an interior consumer,
+on the stem's max-pool and on the head's average pool -- and the forward must give the logits of
+the same model in the same state planned with no carry flag, bit for bit, with nothing off the
 grid, the counter of every edge the condition touches standing still and every other counter
 advancing.
 
-An edge is touched by a module when the module is one of those the edge's run-time check
-looks at: a pair's producer or consumer; a tail's last conv, the successor's entry or a reader;
-a stem's producer, entry or a reader.  Grad mode and a set _CONV_CACHE are looked at by every
+An edge is touched by a module when the module is in the edge's own watched(): the modules its
+live() inspects.  A head's pool and fc see codes only when its emitter edge emitted, so they are
+touched by the emitter's watched() too.  Grad mode and a set _CONV_CACHE are looked at by every
 emitter, and with no emitter no pool sees codes, so they touch everything."""
 import numpy as np
 import pytest
@@ -47,21 +48,25 @@ def counters(Q, qnn):
 
 
 def touched_by(Q, qnn, mod):
-    """The counters of the edges whose run-time check looks at `mod`."""
+    """The counters of the edges whose watched() holds `mod`."""
+    from shiftedscalequantization_amd.quant import integer as I
     names = {m: n for n, m in qnn.named_modules()}
     keys = set()
-    for m, n in names.items():
-        plan = getattr(m, "_int_plan", None)
-        c = getattr(plan, "carry", None)
-        if c is not None and getattr(c, "head", None) is None and mod in (m, c.consumer):
-            keys.add(("pair", n))
-        t = getattr(m, "_int_tail", None) if isinstance(m, Q.BaseQuantBlock) else None
-        if t is not None and mod in [t.last, t.entry] + list(t.readers):
-            keys.add(("tail" if getattr(t, "head", None) is None else "head_emit", n))
-        s = getattr(m, "_int_stem", None) if isinstance(m, Q.QuantModule) else None
-        if s is not None and mod in [s.producer, s.entry] + list(s.readers):
-            keys.add(("stem", n))
-            keys.update(("stem_pool", names[p]) for p in s.pools)
+    for e in qnn._int_edges:
+        mine = mod in e.watched()
+        if isinstance(e, I.PairEdge) and mine:
+            keys.add(("pair", names[e.at]))
+        elif isinstance(e, I.TailEdge) and mine:
+            keys.add(("tail", names[e.at]))
+        elif isinstance(e, I.StemEdge) and mine:
+            keys.add(("stem", names[e.at]))
+            keys.update(("stem_pool", names[p]) for p in e.pools)
+        elif isinstance(e, I.HeadEdge):
+            emits = mod in e.emitter.watched()
+            if emits:
+                keys.add(("head_emit", names[e.producer]))
+            if emits or mine:
+                keys.update({("head_pool", names[e.at]), ("head_fc", names[e.fc])})
     return keys
 
 
@@ -77,7 +82,7 @@ def block_edge_reader(Q, qnn):
     switching its act quantization off takes nothing off the grid."""
     mods = dict(qnn.named_modules())
     for blk, _ in Q.block_carry_report(qnn)["edges"]:
-        for r in mods[blk]._int_tail.readers:
+        for r in mods[blk]._int_tail.readers:       # the block's TailEdge
             if r.disable_act_quant:
                 return r
     raise AssertionError("no block-edge reader without an act quantizer of its own")
@@ -86,8 +91,8 @@ def block_edge_reader(Q, qnn):
 class Condition:
     """pick(Q, qnn) -> the module the condition is applied to (None: the whole forward)."""
 
-    def __init__(self, pick=None, grad=False, conv_cache=False):
-        self.pick, self.grad, self.conv_cache = pick, grad, conv_cache
+    def __init__(self, pick=None, grad=False, conv_cache=False, hook=False):
+        self.pick, self.grad, self.conv_cache, self.hook = pick, grad, conv_cache, hook
 
     def forward(self, Q, qnn, x, monkeypatch):
         """(logits, the module) of one forward of the planned model under the condition."""
@@ -96,20 +101,28 @@ class Condition:
         with monkeypatch.context() as mp:
             if self.conv_cache:
                 mp.setattr(quant_layer, "_CONV_CACHE", {})
-            if mod is not None:
+            handle = None
+            if self.hook:
+                handle = mod.register_forward_hook(lambda m, args, out: None)
+            elif mod is not None:
                 mod.set_quant_state(True, False)
             try:
                 with torch.enable_grad() if self.grad else torch.no_grad():
                     return qnn(x).detach().clone(), mod
             finally:
-                if mod is not None:
+                if handle is not None:
+                    handle.remove()
+                elif mod is not None:
                     mod.set_quant_state(True, True)
 
 
 CONDITIONS = {"enable_grad": Condition(grad=True),
               "interior_consumer_act_off": Condition(pick=interior_consumer),
               "block_edge_reader_act_off": Condition(pick=block_edge_reader),
-              "conv_cache_set": Condition(conv_cache=True)}
+              "conv_cache_set": Condition(conv_cache=True),
+              "interior_consumer_hooked": Condition(pick=interior_consumer, hook=True),
+              "stem_maxpool_hooked": Condition(pick=lambda Q, qnn: qnn.model.maxpool, hook=True),
+              "head_avgpool_hooked": Condition(pick=lambda Q, qnn: qnn.model.avgpool, hook=True)}
 
 
 @pytest.mark.parametrize("name", list(CONDITIONS))
@@ -123,7 +136,8 @@ def test_condition_costs_time_not_correctness(Q, r18, monkeypatch, name):
         Q.enable_integer_inference(qnn, x)
         assert counters(Q, qnn) == {}
         want, _ = Condition(pick=(lambda Q, q: picked) if picked is not None else None,
-                            grad=cond.grad, conv_cache=cond.conv_cache).forward(Q, qnn, x, monkeypatch)
+                            grad=cond.grad, conv_cache=cond.conv_cache,
+                            hook=cond.hook).forward(Q, qnn, x, monkeypatch)
         assert Q.integer_report(qnn)["off_grid"] == 0
 
         Q.enable_integer_inference(qnn, x, carry_head=True)
@@ -147,3 +161,20 @@ def test_condition_costs_time_not_correctness(Q, r18, monkeypatch, name):
         assert all(again[k] > after[k] for k in before)
     finally:
         Q.disable_integer_inference(qnn)
+
+
+def test_disable_leaves_no_edge_and_no_mark(Q, r18):
+    """enable(carry_head=True) then disable: the registry is empty, the four carry reports are
+    their empty forms and no module holds a mark."""
+    qnn, x = r18
+    Q.enable_integer_inference(qnn, x, carry_head=True)
+    assert {type(e).__name__ for e in qnn._int_edges} == {"PairEdge", "TailEdge", "StemEdge", "HeadEdge"}
+    Q.disable_integer_inference(qnn)
+    assert qnn._int_edges == [] and qnn._int_counter is None
+    assert Q.carry_report(qnn) == {"pairs": [], "calls": {}}
+    assert Q.block_carry_report(qnn) == {"edges": [], "calls": {}, "residual": {}}
+    assert Q.stem_carry_report(qnn) == {"edges": [], "calls": {}, "pooled": {}}
+    assert Q.head_carry_report(qnn) == {"edges": [], "calls": {}, "pooled": {}, "fc": {}}
+    marks = ("_int_plan", "_int_tail", "_int_stem", "_int_head")
+    assert not [(n, a) for n, m in qnn.named_modules() for a in marks
+                if getattr(m, a, None) is not None]

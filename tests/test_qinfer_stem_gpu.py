@@ -255,7 +255,9 @@ def test_planned_pool_pools_codes_and_an_unplanned_one_decodes(K):
     out = pool(tag())
     assert out.dtype == torch.float32 and not hasattr(out, "_ssq_codes")
     assert np.array_equal(host(out).view(np.int32), host(want).view(np.int32))
-    pool._int_stem = types.SimpleNamespace(pooled={pool: 0})
+    # (the pool asks its mark whether the edge is live: Edge.live's hook rule, for this pool)
+    pool._int_stem = types.SimpleNamespace(
+        pooled={pool: 0}, live=lambda: not (pool._forward_hooks or pool._forward_pre_hooks))
     out = pool(tag())
     assert out.dtype == torch.int8 and out._ssq_codes.shape == (2, 20, 5, 4)
     assert out._ssq_codes.quantizer() == (0.3, 2.0, 4, False) and pool._int_stem.pooled[pool] == 1
