@@ -878,6 +878,74 @@ int ssq_qconv_i8_centred_codes_res_fwd(const int8_t* codes, const void* prepared
                                        float res_delta, float res_zero_point, int res_qmin,
                                        int res_qmax, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- K23 split along K
+ * The six dense conv entry points with the k walk divided among `splits` = Z workgroups per
+ * output tile, for planes whose (ceil(M/64), ceil(Co/64)) grid does not fill the device
+ * (M = Nb*OH*OW).  Two kernels, no atomics: the partial kernel (grid z = Z) walks the k steps
+ * [floor(z*nk/Z), floor((z+1)*nk/Z)) of the nk = Kp/64 and stores its raw int32 accumulators to
+ * the caller's workspace, D[Z][Co][M] then (plain blobs only) SA[Z][M]; the finish kernel adds
+ * the slices and runs the parent's epilogue functions.  The integer sum is exact and
+ * associative, so every result equals the parent entry point's bit for bit, `*bad` included.
+ * Every workspace element is written once by one thread before it is read: the workspace needs
+ * no initialisation and holds nothing between calls.
+ *
+ * Each takes its parent's argument list plus (splits, ws, ws_bytes) before the stream.
+ * SSQ_E_ARG before any launch: splits < 2, splits > 16, splits > nk, groups != 1, ws null or
+ * ws_bytes below ssq_qconv_i8_splitk_workspace_size, and everything the parent refuses.
+ * ssq_qconv_i8_splitk_workspace_size: bytes for the geometry (Cp = qinfer_cpad(Ci)); 0 when
+ * the split would be refused.  No allocation, no sync, capturable. */
+size_t ssq_qconv_i8_splitk_workspace_size(int64_t Nb, int64_t H, int64_t W, int64_t Co, int64_t R,
+                                          int64_t S, int64_t stride, int64_t pad, int64_t Cp,
+                                          int splits, int centred);
+int ssq_qconv_i8_splitk_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                            int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R,
+                            int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                            float act_zero_point, int act_qmin, int act_qmax, float* y, int splits,
+                            void* ws, size_t ws_bytes, ssq_stream_t stream);
+int ssq_qconv_i8_centred_splitk_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                    int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                    int64_t R, int64_t S, int64_t stride, int64_t pad,
+                                    int64_t groups, float act_zero_point, int act_qmin,
+                                    int act_qmax, float* y, int splits, void* ws, size_t ws_bytes,
+                                    ssq_stream_t stream);
+int ssq_qconv_i8_splitk_codes_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                  int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                  int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                                  float act_zero_point, int act_qmin, int act_qmax,
+                                  const float* bias, const float* gamma, const float* phi, int act,
+                                  float out_delta, float out_zero_point, int out_qmin, int out_qmax,
+                                  int8_t* out_codes, uint32_t* bad, int splits, void* ws,
+                                  size_t ws_bytes, ssq_stream_t stream);
+int ssq_qconv_i8_centred_splitk_codes_fwd(const int8_t* codes, const void* prepared,
+                                          const float* scale, int64_t Nb, int64_t Ci, int64_t H,
+                                          int64_t W, int64_t Co, int64_t R, int64_t S,
+                                          int64_t stride, int64_t pad, int64_t groups,
+                                          float act_zero_point, int act_qmin, int act_qmax,
+                                          const float* bias, const float* gamma, const float* phi,
+                                          int act, float out_delta, float out_zero_point,
+                                          int out_qmin, int out_qmax, int8_t* out_codes,
+                                          uint32_t* bad, int splits, void* ws, size_t ws_bytes,
+                                          ssq_stream_t stream);
+int ssq_qconv_i8_splitk_codes_res_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                      int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                      int64_t R, int64_t S, int64_t stride, int64_t pad,
+                                      int64_t groups, float act_zero_point, int act_qmin,
+                                      int act_qmax, const float* bias, const float* gamma,
+                                      const float* phi, int act, float out_delta,
+                                      float out_zero_point, int out_qmin, int out_qmax,
+                                      int8_t* out_codes, uint32_t* bad, const float* res_f32,
+                                      const int8_t* res_codes, float res_delta,
+                                      float res_zero_point, int res_qmin, int res_qmax, int splits,
+                                      void* ws, size_t ws_bytes, ssq_stream_t stream);
+int ssq_qconv_i8_centred_splitk_codes_res_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t Ci,
+    int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+    int64_t groups, float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+    const float* gamma, const float* phi, int act, float out_delta, float out_zero_point,
+    int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad, const float* res_f32,
+    const int8_t* res_codes, float res_delta, float res_zero_point, int res_qmin, int res_qmax,
+    int splits, void* ws, size_t ws_bytes, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- pooling head on codes (K29, K30)
  * The global average pool and the fc behind it on stored codes, with a numerics contract of
  * their own (the fc has no input quantizer, so the pooled value is never re-quantized):

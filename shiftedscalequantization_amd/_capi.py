@@ -161,6 +161,12 @@ SIGNATURES["ssq_qweight_prepare_grouped_colscale"] = (_i, [_p, _p, _p, _i64, _i6
                                                            _p, _p, _p])
 for _n in ("fwd", "codes_fwd", "codes_res_fwd"):
     SIGNATURES[f"ssq_qconv_i8_centred_{_n}"] = SIGNATURES[f"ssq_qconv_i8_{_n}"]
+# the split-K convs take their parents' arguments with (splits, ws, ws_bytes) before the stream
+for _n in ("fwd", "codes_fwd", "codes_res_fwd"):
+    _res, _args = SIGNATURES[f"ssq_qconv_i8_{_n}"]
+    for _c in ("", "centred_"):
+        SIGNATURES[f"ssq_qconv_i8_{_c}splitk_{_n}"] = (_res, _args[:-1] + [_i, _p, _sz, _p])
+SIGNATURES["ssq_qconv_i8_splitk_workspace_size"] = (_sz, [_i64] * 9 + [_i, _i])
 
 _lib = None
 

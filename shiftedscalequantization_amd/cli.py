@@ -97,6 +97,13 @@ def build_parser():
                         'on integer codes too: the column scale as integers k / L, L <= 127, folded '
                         'into the int8 weight operand; with --test the act quantizers are '
                         'initialised and the route runs after channelShift_wMSE; implies --int_infer')
+    p.add_argument('--int_infer_splitk', action='store_true',
+                   help='--int_infer with the dense int8 convs of small planes split along K '
+                        'where the host rule asks for it (two kernels, bit-identical); implies '
+                        '--int_infer')
+    p.add_argument('--int_infer_graph', action='store_true',
+                   help='--int_infer with the integer forward captured once per batch shape and '
+                        'replayed as one HIP graph; implies --int_infer')
     p.add_argument('--deterministic', default=1, type=int,
                    help='1 (reference): deterministic MIOpen conv solvers; 0: fastest solvers')
     # data parallel: one process per GPU, spawned by main_imagenet.py itself with --gpus N
@@ -120,7 +127,8 @@ def parse_args(argv=None):
         a.int_infer_carry_blocks = True
     if a.int_infer_carry_blocks:
         a.int_infer_carry = True
-    if a.int_infer_grouped or a.int_infer_carry or a.int_infer_colscale:
+    if (a.int_infer_grouped or a.int_infer_carry or a.int_infer_colscale or a.int_infer_splitk
+            or a.int_infer_graph):
         a.int_infer = True
     return a
 
@@ -172,20 +180,26 @@ def get_train_samples(train_loader, num_samples):
 
 
 @torch.no_grad()
-def validate_model(val_loader, model, device=None, print_result=False):
+def validate_model(val_loader, model, device=None, print_result=False, graph=False):
     """common.py:152-221: top-1 over (images, target) batches.  With several ranks each
     validates its own shard of the validation set and the (correct, total) sums are
     all-reduced (Brecq/main_imagenet_dist.py:114-124), so every rank returns the
-    whole-set top-1."""
+    whole-set top-1.  `graph`: every batch goes through a quant.IntegerGraph of `model`
+    (an installed integer plan, one capture per batch shape); each batch's static logits are
+    reduced before the next replay, the all-reduce stays outside."""
     from .parallel_dp import all_sum_
     from .quant.quant_layer import frozen_weight_cache
     device = next(model.parameters()).device if device is None else device
     model.eval()
+    forward = model
+    if graph:
+        from .quant.integer import IntegerGraph
+        forward = IntegerGraph(model)
     sums = torch.zeros(2, dtype=torch.float64, device=device)
     # every layer's W_hat is quantized once per pass, not once per batch (bit-identical)
     with frozen_weight_cache():
         for images, target in val_loader:
-            out = model(images.to(device))
+            out = forward(images.to(device))
             sums[0] += (out.argmax(1) == target.to(device)).sum()
             sums[1] += target.numel()
     all_sum_(sums)

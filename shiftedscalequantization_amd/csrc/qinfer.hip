@@ -176,14 +176,27 @@ __device__ __forceinline__ long long qconv_sum(int d, const int32_t* __restrict_
 // CENTRED: the blob holds a centred operand (ssq_qweight_prepare_colscale: cwz = 0), so SA is
 // not needed: no 0/1 row load, LDS store or fragment read, no SA MFMA (four per k step, not
 // five) and I = D + az * T[co].  `mask` and `cwz` are not read.
-template <bool CODES, int RES = 0, bool CENTRED = false>
+// PARTIAL (qconv_i8_partial_kernel<CENTRED>, the split-K form's first kernel): a third grid
+// dimension of Z slices; slice z walks the k steps [z nk / Z, (z + 1) nk / Z) with the staging,
+// LDS layout, fragment map and MFMAs of the whole walk, and instead of an epilogue stores its raw
+// int32 accumulators to the QPartial `y`.  Every element of D[Z][Co][M] and (not CENTRED)
+// SA[Z][M] is written exactly once, by one thread, and nothing else: no memset, no counter.
+struct QPartial {
+  int32_t* D;    // [Z][Co][M]: slice z's sum of a_s w_s, the fp32 form's store pattern
+  int32_t* SA;   // [Z][M]: slice z's window sum (not CENTRED)
+};
+
+template <bool CODES, int RES = 0, bool CENTRED = false, bool PARTIAL = false>
 __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
     const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ mask,
     const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
     const float* __restrict__ scale, QConvGeo g,
-    typename std::conditional<CODES, typename std::conditional<RES != 0, QEpiRes, QEpi>::type,
-                              float* __restrict__>::type y) {
+    typename std::conditional<
+        PARTIAL, QPartial,
+        typename std::conditional<CODES, typename std::conditional<RES != 0, QEpiRes, QEpi>::type,
+                                  float* __restrict__>::type>::type y) {
   static_assert(CODES || RES == 0, "a residual goes with the code-emitting epilogue");
+  static_assert(!PARTIAL || (!CODES && RES == 0), "a partial walk has no epilogue");
   __shared__ __attribute__((aligned(16))) int8_t lA[kQT * kQRow];
   __shared__ __attribute__((aligned(16))) int8_t lB[(kQT + 1) * kQRow];
   const uint32_t tid = threadIdx.x;
@@ -217,11 +230,18 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
     return padfill;
   };
 
-  i32x4 ra = load_a(0);
-  i32x4 rb = *(const i32x4*)wrow;
+  const uint32_t nk = g.Kp / kQT;
+  uint32_t kt0 = 0, kt1 = nk;   // this workgroup's k steps: all of them, or slice blockIdx.z's
+  if constexpr (PARTIAL) {
+    kt0 = blockIdx.z * nk / gridDim.z;
+    kt1 = (blockIdx.z + 1) * nk / gridDim.z;
+  }
+
+  i32x4 ra = load_a(kt0);
+  i32x4 rb = *(const i32x4*)(wrow + (size_t)kt0 * kQT);
   i32x4 rm = {0, 0, 0, 0};
   if constexpr (!CENTRED) {
-    if (tid < 4) rm = *(const i32x4*)(mask + tid * 16);
+    if (tid < 4) rm = *(const i32x4*)(mask + (size_t)kt0 * kQT + tid * 16);
   }
 
   i32x4 acc[4];
@@ -229,8 +249,7 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
   for (int j = 0; j < 4; ++j) acc[j] = i32x4{0, 0, 0, 0};
   i32x4 accs = {0, 0, 0, 0};
 
-  const uint32_t nk = g.Kp / kQT;
-  for (uint32_t kt = 0; kt < nk; ++kt) {
+  for (uint32_t kt = kt0; kt < kt1; ++kt) {
     __syncthreads();   // the previous step's fragment reads are done
     *(i32x4*)(lA + srow * kQRow + sc * 16) = ra;
     *(i32x4*)(lB + srow * kQRow + sc * 16) = rb;
@@ -238,7 +257,7 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
       if (tid < 4) *(i32x4*)(lB + kQT * kQRow + tid * 16) = rm;
     }
     __syncthreads();
-    if (kt + 1 < nk) {
+    if (kt + 1 < kt1) {
       ra = load_a(kt + 1);
       rb = *(const i32x4*)(wrow + (size_t)(kt + 1) * kQT);
       if constexpr (!CENTRED) {
@@ -260,7 +279,23 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
   // C/D map: column (pixel) = lane & 15, row (channel) = 4 * (lane >> 4) + reg
   const uint32_t pixel = blockIdx.x * kQT + wave * 16 + fr;
   const long long sa = (long long)accs[0];
-  if constexpr (CODES) {
+  if constexpr (PARTIAL) {
+    if (pixel >= g.M) return;
+    int32_t* dz = y.D + (size_t)blockIdx.z * g.Co * g.M + pixel;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
+        if (co < g.Co) dz[(size_t)co * g.M] = acc[j][r];
+      }
+    }
+    if constexpr (!CENTRED) {
+      // every C row of the 0/1-row product holds the window sum: row 0 (register 0 of the
+      // fq == 0 lanes) of the first channel tile's workgroup writes it
+      if (blockIdx.y == 0 && fq == 0) y.SA[(size_t)blockIdx.z * g.M + pixel] = accs[0];
+    }
+  } else if constexpr (CODES) {
     const QEpi& e = qepi_of(y);
     const bool pval = pixel < g.M;
     uint32_t nbad = 0;
@@ -334,6 +369,132 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
         }
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------- K23 split along K
+// The integer sum is exact and associative, so Z workgroups may each walk a slice of the k steps
+// and a second kernel add the slices: bit-identical to the whole walk, and with each element of
+// the workspace written once by one thread, identical from run to run.  No atomics.
+template <bool CENTRED>
+constexpr auto qconv_i8_partial_kernel = qconv_i8_kernel<false, 0, CENTRED, true>;
+
+// slices summed: D in int32 (|whole-K sum| <= 65536 * 128 * 128 = 2^30, as in one walk), SA in int64
+template <bool CENTRED>
+__device__ __forceinline__ long long qsplit_sa(const int32_t* __restrict__ SA, uint32_t Z,
+                                               uint32_t M, uint32_t pixel) {
+  long long sa = 0;
+  if constexpr (!CENTRED) {
+    for (uint32_t z = 0; z < Z; ++z) sa += (long long)SA[(size_t)z * M + pixel];
+  }
+  return sa;
+}
+__device__ __forceinline__ int qsplit_d(const int32_t* __restrict__ D, uint32_t Z, size_t slice,
+                                        size_t at) {
+  int d = 0;
+  for (uint32_t z = 0; z < Z; ++z) d += D[(size_t)z * slice + at];
+  return d;
+}
+
+// The finish: K23's own epilogue functions on the summed slices, so the bits are K23's.
+// fp32 form: one thread per (co, pixel), coalesced along pixels, NCHW store.  Code forms: one
+// thread per (pixel, 16-channel chunk), K25's pattern: a wave reads 64 consecutive pixels of a
+// channel row per load and each thread stores its pixel's chunk as one 16-B word; channels at or
+// past Co inside a chunk are 0.  RES as in K23: 1 loads fp32 NCHW along pixels, 2 one 16-B word
+// at the output's own address.  Threads past the end are predicated, not returned: qepi_count is
+// a wave reduction.
+template <bool CODES, int RES = 0, bool CENTRED = false>
+__global__ __launch_bounds__(kBlock) void qconv_i8_finish_kernel(
+    const int32_t* __restrict__ D, const int32_t* __restrict__ SA, uint32_t Z,
+    const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
+    const float* __restrict__ scale, QConvGeo g, FastDiv div_m,
+    typename std::conditional<CODES, typename std::conditional<RES != 0, QEpiRes, QEpi>::type,
+                              float* __restrict__>::type y) {
+  static_assert(CODES || RES == 0, "a residual goes with the code-emitting epilogue");
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const size_t slice = (size_t)g.Co * g.M;
+  if constexpr (CODES) {
+    const QEpi& e = qepi_of(y);
+    const bool live = i < g.M * (e.Cpo / 16);
+    const uint32_t ic = live ? i : 0u;
+    const uint32_t chunk = fdiv(ic, div_m);
+    const uint32_t pixel = ic - chunk * g.M;
+    uint32_t nbad = 0;
+    union {
+      i32x4 v;
+      int8_t b[16];
+    } o, rc;
+    const float* rp = nullptr;
+    if constexpr (RES == 1) {
+      const uint32_t n = fdiv(pixel, g.div_p);
+      rp = y.r.f32 + (size_t)n * g.Co * g.P + (pixel - n * g.P);
+    } else if constexpr (RES == 2) {
+      rc.v = *(const i32x4*)(y.r.codes + (size_t)pixel * e.Cpo + chunk * 16);
+    }
+    const long long sa = qsplit_sa<CENTRED>(SA, Z, g.M, pixel);
+    // Straight-line code: a channel at or past Co (and every channel of a thread past the end)
+    // computes on its chunk's first channel, which is a real one, and is discarded by a select,
+    // so the 16 rows of a slice are 16 independent loads in flight and so are the per-channel
+    // vectors; with the work under a branch per channel every load is waited for on its own.
+    const uint32_t co0 = chunk * 16;
+    const uint32_t real = !live ? 0u : (g.Co - co0 < 16u ? g.Co - co0 : 16u);
+    const int32_t* dp = D + (size_t)co0 * g.M + pixel;
+    int d[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) d[j] = 0;
+    for (uint32_t z = 0; z < Z; ++z) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        d[j] += dp[(size_t)z * slice + (size_t)((uint32_t)j < real ? j : 0) * g.M];
+    }
+    // `el`: the epilogue with its optional vectors known present or absent (the launch-wide
+    // tests of qepi_code_y hoisted out of the 16 channels), so their loads are issued together
+    auto emit = [&](const QEpi& el) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const bool on = (uint32_t)j < real;
+        const uint32_t co = on ? co0 + j : co0;
+        const long long I = qconv_sum<CENTRED>(d[j], cwz, sa, g.az, tt, co);
+        uint32_t nb = 0;
+        int c;
+        if constexpr (RES == 1) {
+          c = qepi_code<true>((float)I, co, scale, el, nb, rp[(size_t)co * g.P]);
+        } else if constexpr (RES == 2) {
+          c = qepi_code<true>((float)I, co, scale, el, nb, qres_decode((int)rc.b[j], y.r));
+        } else {
+          c = qepi_code((float)I, co, scale, el, nb);
+        }
+        nbad += on ? nb : 0u;
+        o.b[j] = (int8_t)(on ? c : 0);
+      }
+    };
+    QEpi el = e;
+    if (e.bias && e.gamma) {
+      __builtin_assume(el.bias != nullptr && el.gamma != nullptr);
+      emit(el);
+    } else if (e.bias) {
+      __builtin_assume(el.bias != nullptr);
+      el.gamma = el.phi = nullptr;
+      emit(el);
+    } else if (e.gamma) {
+      __builtin_assume(el.gamma != nullptr);
+      el.bias = nullptr;
+      emit(el);
+    } else {
+      el.bias = el.gamma = el.phi = nullptr;
+      emit(el);
+    }
+    if (live) *(i32x4*)(e.out + (size_t)pixel * e.Cpo + chunk * 16) = o.v;
+    qepi_count(nbad, e.bad);
+  } else {
+    if (i >= g.Co * g.M) return;
+    const uint32_t co = fdiv(i, div_m);
+    const uint32_t pixel = i - co * g.M;
+    const uint32_t n = fdiv(pixel, g.div_p);
+    const uint32_t p = pixel - n * g.P;
+    const long long sa = qsplit_sa<CENTRED>(SA, Z, g.M, pixel);
+    const long long I = qconv_sum<CENTRED>(qsplit_d(D, Z, slice, i), cwz, sa, g.az, tt, co);
+    y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
   }
 }
 
@@ -447,15 +608,48 @@ extern "C" int ssq_qweight_prepare_colscale(const void* packed, const float* zp,
 
 // One form of K23 on a blob: CENTRED for a centred one (ssq_qweight_prepare_colscale), which is
 // bit-identical to the plain instantiation there, one MFMA per k step less.
+// `sp`: the split-K form (the ssq_qconv_i8_*splitk_* entry points): the partial kernel over
+// sp->splits slices into the caller's workspace, then the finish kernel of the same form.
+struct QSplit {
+  int splits;
+  void* ws;
+  size_t ws_bytes;
+};
+constexpr int kQMaxSplits = 16;
+
+// D[Z][Co][M] then, unless centred, SA[Z][M], int32
+static size_t qsplit_ws_bytes(int64_t M, int64_t Co, int64_t Z, bool centred) {
+  return (size_t)Z * (size_t)(Co + (centred ? 0 : 1)) * (size_t)M * 4;
+}
+
 template <bool CENTRED>
 static void qconv_i8_run(dim3 grid, ssq_stream_t stream, const int8_t* codes, const int8_t* base,
                          const QLayout& L, const float* scale, const QConvGeo& g, float* y,
-                         const QEpi* epi, const QRes* res) {
+                         const QEpi* epi, const QRes* res, const QSplit* sp) {
+  const int8_t* mask = base + L.off_mask;
+  const int32_t* cwz = (const int32_t*)(base + L.off_cwz);
+  const int32_t* tt = (const int32_t*)(base + L.off_t);
   auto run = [&](auto* kernel, auto out) {
-    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base,
-                       base + L.off_mask, (const int32_t*)(base + L.off_cwz),
-                       (const int32_t*)(base + L.off_t), scale, g, out);
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base, mask, cwz,
+                       tt, scale, g, out);
   };
+  if (sp) {
+    const uint32_t Z = (uint32_t)sp->splits;
+    const QPartial part = {(int32_t*)sp->ws, (int32_t*)sp->ws + (size_t)Z * g.Co * g.M};
+    grid.z = Z;
+    run(qconv_i8_partial_kernel<CENTRED>, part);
+    const uint32_t items = epi ? g.M * (epi->Cpo / 16) : g.Co * g.M;
+    auto finish = [&](auto* kernel, auto out) {
+      hipLaunchKernelGGL(kernel, dim3((items + kBlock - 1) / kBlock), dim3(kBlock), 0,
+                         (hipStream_t)stream, (const int32_t*)part.D, (const int32_t*)part.SA, Z,
+                         cwz, tt, scale, g, make_fastdiv(g.M), out);
+    };
+    if (!epi) finish(qconv_i8_finish_kernel<false, 0, CENTRED>, y);
+    else if (!res) finish(qconv_i8_finish_kernel<true, 0, CENTRED>, *epi);
+    else if (res->f32) finish(qconv_i8_finish_kernel<true, 1, CENTRED>, QEpiRes{*epi, *res});
+    else finish(qconv_i8_finish_kernel<true, 2, CENTRED>, QEpiRes{*epi, *res});
+    return;
+  }
   if (!epi) run(qconv_i8_kernel<false, 0, CENTRED>, y);
   else if (!res) run(qconv_i8_kernel<true, 0, CENTRED>, *epi);
   else if (res->f32) run(qconv_i8_kernel<true, 1, CENTRED>, QEpiRes{*epi, *res});
@@ -473,9 +667,10 @@ struct QConvIn {
 };
 
 // y: the fp32 output (ssq_qconv_i8_fwd) or null with `epi` set (ssq_qconv_i8_codes_fwd); `res`
-// with `epi`: the tail's residual (ssq_qconv_i8_codes_res_fwd); centred: the *_centred_* forms
+// with `epi`: the tail's residual (ssq_qconv_i8_codes_res_fwd); centred: the *_centred_* forms;
+// `sp`: the split-K forms
 static int qconv_i8_launch(const char* me, bool centred, const QConvIn& a, float* y, QEpi* epi,
-                           const QRes* res, ssq_stream_t stream) {
+                           const QRes* res, ssq_stream_t stream, const QSplit* sp = nullptr) {
   SSQ_REQUIRE(a.codes && a.prepared && a.scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
   SSQ_REQUIRE(a.groups == 1, SSQ_E_ARG, "%s: groups = %lld (only groups == 1)", me,
               (long long)a.groups);
@@ -516,10 +711,18 @@ static int qconv_i8_launch(const char* me, bool centred, const QConvIn& a, float
     SSQ_REQUIRE(Nb * OH * OW * (int64_t)epi->Cpo < (1ll << 31), SSQ_E_ARG,
                 "%s: tensor exceeds 2^31 elements", me);
   }
+  if (sp) {
+    SSQ_REQUIRE(sp->splits >= 2 && sp->splits <= kQMaxSplits && sp->splits <= L.Kp / kQT,
+                SSQ_E_ARG, "%s: splits = %d not in [2, min(%d, the %lld k steps)]", me, sp->splits,
+                kQMaxSplits, (long long)(L.Kp / kQT));
+    SSQ_REQUIRE(sp->ws && sp->ws_bytes >= qsplit_ws_bytes(g.M, Co, sp->splits, centred),
+                SSQ_E_ARG, "%s: workspace null or smaller than %zu bytes", me,
+                qsplit_ws_bytes(g.M, Co, sp->splits, centred));
+  }
   const dim3 grid((g.M + kQT - 1) / kQT, (uint32_t)(L.Cop / kQT));
   const int8_t* base = (const int8_t*)a.prepared;
-  if (centred) qconv_i8_run<true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res);
-  else qconv_i8_run<false>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res);
+  if (centred) qconv_i8_run<true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, sp);
+  else qconv_i8_run<false>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, sp);
   return check_launch(me);
 }
 
@@ -653,3 +856,130 @@ extern "C" int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_
                      zero_point, (float)qmin, x);
   return check_launch("ssq_act_decode");
 }
+
+// ---------------------------------------------------------------- K23 split along K: the ABI
+extern "C" size_t ssq_qconv_i8_splitk_workspace_size(int64_t Nb, int64_t H, int64_t W, int64_t Co,
+                                                     int64_t R, int64_t S, int64_t stride,
+                                                     int64_t pad, int64_t Cp, int splits,
+                                                     int centred) {
+  if (Nb < 1 || H < 1 || W < 1 || Co < 1 || R < 1 || S < 1 || R > 7 || S > 7 || stride < 1 ||
+      pad < 0 || H + 2 * pad < R || W + 2 * pad < S || Cp < 16 || Cp % 16 != 0)
+    return 0;
+  const int64_t nk = rup(R * S * Cp, kQT) / kQT;
+  if (splits < 2 || splits > kQMaxSplits || splits > nk) return 0;
+  const int64_t OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
+  if (Nb * OH * OW * Co >= (1ll << 31)) return 0;
+  return qsplit_ws_bytes(Nb * OH * OW, Co, splits, centred != 0);
+}
+
+// The six dense entry points again, each with (splits, ws, ws_bytes) before the stream: the
+// parent's checks, then the split's, then the partial and the finish kernel on `stream`.
+#define SSQ_QCONV_IN                                                                       \
+  {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups, act_zero_point,    \
+   act_qmin, act_qmax}
+
+static int qsplitk_fwd(const char* me, bool centred, const QConvIn& a, float* y, const QSplit& sp,
+                       ssq_stream_t stream) {
+  SSQ_REQUIRE(y, SSQ_E_ARG, "%s: null pointer", me);
+  return qconv_i8_launch(me, centred, a, y, nullptr, nullptr, stream, &sp);
+}
+
+extern "C" int ssq_qconv_i8_splitk_fwd(const int8_t* codes, const void* prepared,
+                                       const float* scale, int64_t Nb, int64_t Ci, int64_t H,
+                                       int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
+                                       int64_t pad, int64_t groups, float act_zero_point,
+                                       int act_qmin, int act_qmax, float* y, int splits, void* ws,
+                                       size_t ws_bytes, ssq_stream_t stream) {
+  return qsplitk_fwd("ssq_qconv_i8_splitk_fwd", false, SSQ_QCONV_IN, y, {splits, ws, ws_bytes},
+                     stream);
+}
+
+extern "C" int ssq_qconv_i8_centred_splitk_fwd(const int8_t* codes, const void* prepared,
+                                               const float* scale, int64_t Nb, int64_t Ci,
+                                               int64_t H, int64_t W, int64_t Co, int64_t R,
+                                               int64_t S, int64_t stride, int64_t pad,
+                                               int64_t groups, float act_zero_point, int act_qmin,
+                                               int act_qmax, float* y, int splits, void* ws,
+                                               size_t ws_bytes, ssq_stream_t stream) {
+  return qsplitk_fwd("ssq_qconv_i8_centred_splitk_fwd", true, SSQ_QCONV_IN, y,
+                     {splits, ws, ws_bytes}, stream);
+}
+
+static int qsplitk_codes(const char* me, bool centred, const QConvIn& a, const float* bias,
+                         const float* gamma, const float* phi, int act, float out_delta,
+                         float out_zero_point, int out_qmin, int out_qmax, int8_t* out_codes,
+                         uint32_t* bad, const QSplit& sp, ssq_stream_t stream) {
+  QEpi e;
+  const int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin,
+                           out_qmax, out_codes, bad, &e);
+  if (rc) return rc;
+  return qconv_i8_launch(me, centred, a, nullptr, &e, nullptr, stream, &sp);
+}
+
+extern "C" int ssq_qconv_i8_splitk_codes_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t Ci,
+    int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+    int64_t groups, float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+    const float* gamma, const float* phi, int act, float out_delta, float out_zero_point,
+    int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad, int splits, void* ws,
+    size_t ws_bytes, ssq_stream_t stream) {
+  return qsplitk_codes("ssq_qconv_i8_splitk_codes_fwd", false, SSQ_QCONV_IN, bias, gamma, phi, act,
+                       out_delta, out_zero_point, out_qmin, out_qmax, out_codes, bad,
+                       {splits, ws, ws_bytes}, stream);
+}
+
+extern "C" int ssq_qconv_i8_centred_splitk_codes_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t Ci,
+    int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+    int64_t groups, float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+    const float* gamma, const float* phi, int act, float out_delta, float out_zero_point,
+    int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad, int splits, void* ws,
+    size_t ws_bytes, ssq_stream_t stream) {
+  return qsplitk_codes("ssq_qconv_i8_centred_splitk_codes_fwd", true, SSQ_QCONV_IN, bias, gamma,
+                       phi, act, out_delta, out_zero_point, out_qmin, out_qmax, out_codes, bad,
+                       {splits, ws, ws_bytes}, stream);
+}
+
+static int qsplitk_codes_res(const char* me, bool centred, const QConvIn& a, const float* bias,
+                             const float* gamma, const float* phi, int act, float out_delta,
+                             float out_zero_point, int out_qmin, int out_qmax, int8_t* out_codes,
+                             uint32_t* bad, const float* res_f32, const int8_t* res_codes,
+                             float res_delta, float res_zero_point, int res_qmin, int res_qmax,
+                             const QSplit& sp, ssq_stream_t stream) {
+  QEpi e;
+  QRes r;
+  int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
+                     out_codes, bad, &e);
+  if (!rc) rc = qres_init(me, res_f32, res_codes, res_delta, res_zero_point, res_qmin, res_qmax, &r);
+  if (rc) return rc;
+  return qconv_i8_launch(me, centred, a, nullptr, &e, &r, stream, &sp);
+}
+
+extern "C" int ssq_qconv_i8_splitk_codes_res_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t Ci,
+    int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+    int64_t groups, float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+    const float* gamma, const float* phi, int act, float out_delta, float out_zero_point,
+    int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad, const float* res_f32,
+    const int8_t* res_codes, float res_delta, float res_zero_point, int res_qmin, int res_qmax,
+    int splits, void* ws, size_t ws_bytes, ssq_stream_t stream) {
+  return qsplitk_codes_res("ssq_qconv_i8_splitk_codes_res_fwd", false, SSQ_QCONV_IN, bias, gamma,
+                           phi, act, out_delta, out_zero_point, out_qmin, out_qmax, out_codes, bad,
+                           res_f32, res_codes, res_delta, res_zero_point, res_qmin, res_qmax,
+                           {splits, ws, ws_bytes}, stream);
+}
+
+extern "C" int ssq_qconv_i8_centred_splitk_codes_res_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t Ci,
+    int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+    int64_t groups, float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+    const float* gamma, const float* phi, int act, float out_delta, float out_zero_point,
+    int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad, const float* res_f32,
+    const int8_t* res_codes, float res_delta, float res_zero_point, int res_qmin, int res_qmax,
+    int splits, void* ws, size_t ws_bytes, ssq_stream_t stream) {
+  return qsplitk_codes_res("ssq_qconv_i8_centred_splitk_codes_res_fwd", true, SSQ_QCONV_IN, bias,
+                           gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
+                           out_codes, bad, res_f32, res_codes, res_delta, res_zero_point, res_qmin,
+                           res_qmax, {splits, ws, ws_bytes}, stream);
+}
+#undef SSQ_QCONV_IN

@@ -2036,6 +2036,87 @@ def _qconv_fn(prepared, groups, form):
     return f"ssq_qconv_i8_{form}"
 
 
+# K23 split along K (csrc/qinfer.hip, "K23 split along K"): Z workgroups per output tile each walk
+# a slice of the k steps, a finish kernel adds the slices and runs K23's epilogue; bit-identical
+# to the one-kernel form.  qconv_splits is the host rule.  A/B knob: SSQ_QCONV_SPLITK=auto|0|<Z>.
+QCONV_SPLITK = os.environ.get("SSQ_QCONV_SPLITK", "auto")
+if QCONV_SPLITK != "auto" and not QCONV_SPLITK.isdigit():
+    raise ValueError(f"SSQ_QCONV_SPLITK={QCONV_SPLITK!r}: expected auto, 0 or a number of slices")
+QSPLIT_MAX = 16          # the ABI's bound on Z
+# The rule's two thresholds, from profiles/int_infer_smallplane_rate.txt ("keep rule" there, which
+# the tool derives from its in-graph medians; a Z is kept where it saves more than the unsplit
+# form's spread in BOTH the fp32 and the code-emitting form, the rule not knowing which will
+# run): a shape is split, doubling Z up to 8, only while its grid, ceil(M/64) * ceil(Co/64) * Z
+# workgroups, stays at or below QSPLIT_WORKGROUPS and each slice keeps at least QSPLIT_STEPS k
+# steps.  QSPLIT_STEPS is the fewest steps per slice of a kept (class, Z); QSPLIT_WORKGROUPS the
+# largest split grid of one.  The file's rows (saved us, fp32 / code-emitting form):
+#   56 wgs, nk 72 (512 3x3 @7, batch 8):   Z=4 saves 18.4 / 12.1 of 32.7 / 37.9   (224 wgs, 18 steps)
+#   100 wgs, nk 36 (256 3x3 @14, batch 8): Z=2 saves 5.2 / 2.0; Z=4 loses on codes   (200 wgs, 18 steps)
+#   56 wgs, nk 32 (1x1 2048->512, batch 8): Z=2 saves 5.6 / 1.7; Z=4 loses on codes  (112 wgs, 16 steps)
+#   784 wgs, nk 36 and 392 wgs, nk 32 (batch 64): no Z clears
+#   392 wgs, nk 72 (512 3x3 @7, batch 64): Z=2 saves 3.6 / 1.8 and is given up: two thresholds
+#   cannot admit its 784-workgroup split and refuse the 1x1's at batch 64, which loses
+# so QSPLIT_WORKGROUPS = 224 and QSPLIT_STEPS = 16: no class is split that was not measured to clear.
+QSPLIT_WORKGROUPS = 224
+QSPLIT_STEPS = 16
+
+
+def qconv_splits(M, Co, Kp):
+    """The number of K slices Z in {1, 2, 4, 8} for a dense integer conv of M output pixels, Co
+    channels and Kp padded taps (a pure function of the three and of SSQ_QCONV_SPLITK): 1 unless
+    the split grid stays within QSPLIT_WORKGROUPS workgroups and nk / Z, nk = Kp / 64, at or above
+    QSPLIT_STEPS.  Never above nk.  SSQ_QCONV_SPLITK=0: always 1; =<Z>: the largest of 1, 2, 4, 8
+    that is <= min(Z, nk) whatever the grid."""
+    nk = max(int(Kp) // 64, 1)
+    if QCONV_SPLITK == "0":
+        return 1
+    if QCONV_SPLITK != "auto":
+        if not QCONV_SPLITK.isdigit():
+            raise A.SSQError(f"qconv_splits: SSQ_QCONV_SPLITK={QCONV_SPLITK!r} is not auto, 0 or a "
+                             f"number of slices")
+        want, Z = min(int(QCONV_SPLITK), nk, 8), 1
+        while 2 * Z <= want:
+            Z *= 2
+        return Z
+    wg = -(-int(M) // 64) * -(-int(Co) // 64)
+    Z = 1
+    while Z < 8 and 2 * Z <= nk and wg * 2 * Z <= QSPLIT_WORKGROUPS and nk // (2 * Z) >= QSPLIT_STEPS:
+        Z *= 2
+    return Z
+
+
+def qconv_split_workspace_bytes(prepared, N, H, W, stride, padding, splits):
+    """Bytes of the split-K workspace for a dense prepared weight on an (N, H, W) code plane
+    (ssq_qconv_i8_splitk_workspace_size); 0 where the entry points refuse the split."""
+    Co, Ci, R, S = prepared.geometry()
+    return query("ssq_qconv_i8_splitk_workspace_size", int(N), int(H), int(W), Co, R, S,
+                 int(stride), int(padding), query("ssq_qinfer_cpad", Ci), int(splits),
+                 int(QCONV_CENTRED and getattr(prepared, "centred", False)))
+
+
+def _qconv_split(name, prepared, groups, form, splits, workspace, codes, stride, padding):
+    """A split-K call of `form`: (the entry point; the workspace tensor, which the caller holds
+    until its call is issued; the (splits, ws, ws_bytes) arguments that follow the parent's).
+    The workspace is the caller's, or a torch.empty per call like the output (every element is
+    written before it is read).  A grouped weight has no split form.  A split the ABI refuses
+    reaches it with no workspace, so the refusal and its message are the entry point's."""
+    if int(groups) > 1:
+        raise A.SSQError(f"{name}: splits need a dense weight (groups == 1), got groups = {groups}")
+    centred = QCONV_CENTRED and getattr(prepared, "centred", False)
+    fn = f"ssq_qconv_i8_{'centred_' if centred else ''}splitk_{form}"
+    if workspace is None:
+        N = int(codes.shape[0])
+        H, W = (int(codes.shape[1]), int(codes.shape[2])) if codes.dim() == 4 else (1, 1)
+        nbytes = qconv_split_workspace_bytes(prepared, N=N, H=H, W=W, stride=_pair(stride)[0],
+                                             padding=_pair(padding)[0], splits=splits)
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=codes.device) if nbytes else None
+    elif (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8
+          or workspace.device != codes.device or not workspace.is_contiguous()):
+        raise A.SSQError(f"{name}: workspace must be a contiguous uint8 tensor on the output's device")
+    nb = 0 if workspace is None else workspace.numel()
+    return fn, workspace, (int(splits), None if workspace is None else _vp(workspace), nb)
+
+
 def qconv_kind(prepared):
     """The kernel `qconv` runs for a prepared weight: "dense" (K23), "depthwise" (K25) or
     "grouped" (K26)."""
@@ -2049,16 +2130,24 @@ def qconv_kind(prepared):
 
 
 def qconv(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0, act_bits=8,
-          act_sym=False, act_delta=None, bad=None):
+          act_sym=False, act_delta=None, bad=None, splits=None, workspace=None):
     """y = fp32(I) * scale[co] (fp32 NCHW / (N, Co)), I the exact integer conv of the centred
     codes.  `codes_or_x`: act_encode's int8 codes, or the fp32 activation itself, which is then
     encoded with (act_delta, act_zp, act_bits, act_sym), off-grid elements ADDED to `bad`.
-    (act_zp, act_bits, act_sym) are the act quantizer's either way."""
+    (act_zp, act_bits, act_sym) are the act quantizer's either way.
+    `splits` (dense weights only): None or 1 the one-kernel form; Z in 2..16 (at most the weight's
+    k steps) the split-K form, the same bits; `workspace`: a caller-owned uint8 device tensor of
+    qconv_split_workspace_bytes for it instead of one allocated per call."""
     args, keep, (N, Co, OH, OW, conv) = _qconv_args(
         "qconv", codes_or_x, prepared, scale, stride, padding, groups, act_zp, act_bits, act_sym,
         act_delta, bad)
     y = torch.empty((N, Co, OH, OW) if conv else (N, Co), dtype=torch.float32,
                     device=keep[0].device)
+    if splits is not None and int(splits) != 1:
+        fn, ws, tail = _qconv_split("qconv", prepared, groups, "fwd", splits, workspace, keep[0],
+                                    stride, padding)
+        call(fn, *args, _vp(y), *tail, stream_of(y))
+        return y
     call(_qconv_fn(prepared, groups, "fwd"), *args, _vp(y), stream_of(y))
     return y
 
@@ -2179,7 +2268,8 @@ def act_decode(codes, C, delta, zp, n_bits, sym=False):
 
 def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_zp=0.0, act_bits=8,
                 act_sym=False, act_delta=None, bias=None, gamma=None, phi=None, relu=0,
-                out_delta=None, out_zp=0.0, out_bits=8, out_sym=False, bad=None, residual=None):
+                out_delta=None, out_zp=0.0, out_bits=8, out_sym=False, bad=None, residual=None,
+                splits=None, workspace=None):
     """qconv with the layer's epilogue and output act quantizer applied in the kernel
     (csrc/qinfer_epi.h): returns the int8 codes of clamp(round(act((I * scale + bias) * gamma +
     phi) / out_delta) + out_zp) in act_encode's layout (N, OH, OW, Cpad) -- what act_encode
@@ -2189,7 +2279,8 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
     `residual` (dense convs only, ssq_qconv_i8_codes_res_fwd): a block tail's residual, added
     between the affine and the activation as the K13 epilogue adds it -- an fp32 tensor of the
     output's (N, Co, OH, OW), or a carried code tensor (`carried`) of that logical shape, which
-    enters as the fp32 value act_decode gives it."""
+    enters as the fp32 value act_decode gives it.
+    `splits`, `workspace`: as qconv's."""
     if out_delta is None or bad is None:
         raise A.SSQError("qconv_codes: out_delta and bad are required")
     if len(prepared.shape) != 4:
@@ -2203,7 +2294,9 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
     out = torch.empty((N, OH, OW, query("ssq_qinfer_cpad", Co)), dtype=torch.int8,
                       device=keep[0].device)
     olo, ohi = qrange(out_bits, out_sym)
+    form, rargs, fn_groups = "codes_fwd", (), groups
     if residual is not None:
+        form, fn_groups = "codes_res_fwd", 1
         cc = getattr(residual, "_ssq_codes", None)
         if cc is not None:
             if (residual.dtype != torch.int8 or cc.shape != (N, Co, OH, OW)
@@ -2219,11 +2312,13 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
                                  f"codes, got {residual.dtype} {tuple(residual.shape)}")
             res, rp = fptr(residual.detach(), "residual")
             rargs = (rp, None, 0.0, 0.0, 0, 0)
-        call(_qconv_fn(prepared, 1, "codes_res_fwd"), *args, *vecs, int(relu), float(out_delta),
-             float(out_zp), olo, ohi, _vp(out), _vp(bad), *rargs, stream_of(out))
+    epi = (*vecs, int(relu), float(out_delta), float(out_zp), olo, ohi, _vp(out), _vp(bad), *rargs)
+    if splits is not None and int(splits) != 1:
+        fn, ws, tail = _qconv_split("qconv_codes", prepared, groups, form, splits, workspace,
+                                    keep[0], stride, padding)
+        call(fn, *args, *epi, *tail, stream_of(out))
         return out
-    call(_qconv_fn(prepared, groups, "codes_fwd"), *args, *vecs, int(relu), float(out_delta),
-         float(out_zp), olo, ohi, _vp(out), _vp(bad), stream_of(out))
+    call(_qconv_fn(prepared, fn_groups, form), *args, *epi, stream_of(out))
     return out
 
 

@@ -18,6 +18,6 @@ from .layer_recon_shiftedScale import (LinearTempDecayShift, ScaleLossBlockFunct
                                        layer_recon_shiftedScale)
 from .data_utils import save_inp_oup_data, save_grad_data
 from .export import PackedWeight, dequant_form, export_quantized, load_quantized
-from .integer import (block_carry_report, block_edges, carry_report, disable_integer_inference,
-                      enable_integer_inference, head_carry_report, head_edges, integer_report,
-                      stem_carry_report, stem_edges)
+from .integer import (IntegerGraph, block_carry_report, block_edges, carry_report,
+                      disable_integer_inference, enable_integer_inference, head_carry_report,
+                      head_edges, integer_report, split_report, stem_carry_report, stem_edges)

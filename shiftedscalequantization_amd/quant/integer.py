@@ -30,7 +30,14 @@ that arrives where it is not the planned operand is decoded (K.materialize_epi),
 that fails at run time costs time, never correctness.  The installed edges are listed in
 `qnn._int_edges`; the marks the forwards read (`_int_plan.carry`, `_int_tail`, `_int_stem`,
 `_int_head`) are set and cleared through that list only.
+
+Two opt-in forms for the small planes, where launches and a starved grid cost more than bytes:
+`enable_integer_inference(..., splitk=True)` lets a dense layer take K23's split-K form where the
+host rule K.qconv_splits asks for it (the same bits; `split_report`), and `IntegerGraph` replays
+the whole forward as one captured HIP graph.
 """
+import collections
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -61,6 +68,23 @@ class IntPlan:
         self.calls = 0
         self.carry = None                       # a PairEdge when this layer emits codes
         self.head = None                        # a HeadEdge: the fc, on pooled digits only
+        self.splitk = False                     # dense only: ask K.qconv_splits per call
+        self.splits = None                      # the Z of the last run / run_codes
+        Co, Ci, R, S = prepared.geometry()
+        self._Kp = -(-R * S * (-(-Ci // 16) * 16) // 64) * 64     # the blob's padded taps (QLayout)
+
+    def _splits(self, x):
+        """{"splits": K.qconv_splits for this call's M = N * OH * OW} (M depends on the batch), the
+        Z kept for `split_report`; only a plan with `splitk` comes here."""
+        cc = getattr(x, '_ssq_codes', None)
+        shape = x.shape if cc is None else cc.shape
+        Co, _, R, S = self.prepared.geometry()
+        M = int(shape[0])
+        if len(shape) == 4:
+            M *= (((int(shape[2]) + 2 * self.padding - R) // self.stride + 1)
+                  * ((int(shape[3]) + 2 * self.padding - S) // self.stride + 1))
+        self.splits = K.qconv_splits(M, Co, self._Kp)
+        return {"splits": self.splits}
 
     # the input grid's fields under the plan's own names (views, not copies)
     delta, zp, n_bits, sym = (property(lambda self, i=i: self.grid[i]) for i in range(4))
@@ -85,12 +109,16 @@ class IntPlan:
         edge.calls += 1
         codes = K.qconv_codes(x, self.prepared, self.scale, self.stride, self.padding, bias=bias,
                               gamma=gamma, phi=phi, relu=relu, out_delta=o.delta, out_zp=o.zp,
-                              out_bits=o.n_bits, out_sym=o.sym, residual=residual, **self._operand)
+                              out_bits=o.n_bits, out_sym=o.sym, residual=residual, **self._operand,
+                              **(self._splits(x) if self.splitk else {}))
         N, H, W, _ = codes.shape
         return K.carried(codes, (N, self.prepared.shape[0], H, W), *o)
 
     def run(self, x):
         self.calls += 1
+        if self.splitk:
+            return K.qconv(x, self.prepared, self.scale, self.stride, self.padding, **self._operand,
+                           **self._splits(x))
         return K.qconv(x, self.prepared, self.scale, self.stride, self.padding, **self._operand)
 
 
@@ -405,7 +433,7 @@ def _weight_codes(m, colscale=False):
 
 @torch.no_grad()
 def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
-                             carry_stem=False, carry_head=False, colscale=False):
+                             carry_stem=False, carry_head=False, colscale=False, splitk=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
@@ -420,7 +448,9 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     `colscale`: also plan column-scaled weights (ChannelQuantMSE) whose column scale lies on an
     integer grid k[j] / L, L <= 127 (K.colscale_grid), with the centred integer (q - z) * k[j] as
     the int8 operand; off, they are reported as refused.  An all-ones column scale is
-    a plain weight and takes the plain route."""
+    a plain weight and takes the plain route.  `splitk`: a dense layer asks the host rule
+    K.qconv_splits on every forward and takes K23's split-K form where it returns Z > 1
+    (bit-identical; `split_report`); off, no layer does."""
     carry_stem = carry_stem or carry_head
     carry_blocks = carry_blocks or carry_stem
     carry = carry or carry_blocks
@@ -511,6 +541,7 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
             # ... / fp32(L): the column grid's common denominator, one more rounding
             scale = (scale / torch.full((1,), float(L), dtype=torch.float32, device=dev)).contiguous()
         m._int_plan = IntPlan(prep, scale, act, stride, padding, counter)
+        m._int_plan.splitk = bool(splitk) and m._int_plan.kind == "dense"
         report[name] = INT8
     if carry:
         _plan_carry(qnn, source)
@@ -768,6 +799,8 @@ def disable_integer_inference(qnn):
     for _, m in _layers(qnn):
         m._int_plan = None
     qnn._int_edges, qnn._int_counter = [], None
+    # every enable passes here: a captured forward (IntegerGraph) of the previous plan is stale
+    qnn._int_epoch = getattr(qnn, "_int_epoch", 0) + 1
 
 
 def integer_report(qnn):
@@ -778,6 +811,12 @@ def integer_report(qnn):
     counter = getattr(qnn, "_int_counter", None)
     return {"off_grid": int(counter.item()) if counter is not None else 0,
             "calls": {n: p.calls for n, p in _plans(qnn)}}
+
+
+def split_report(qnn):
+    """{layer name: the Z of its last forward} for the dense layers planned with `splitk` that
+    have run (1: the one-kernel form); empty without `splitk`."""
+    return {n: p.splits for n, p in _plans(qnn) if p.splitk and p.splits is not None}
 
 
 def carry_report(qnn):
@@ -831,3 +870,114 @@ def head_carry_report(qnn):
             "calls": {names[e.producer]: e.emitter.calls for e in heads},
             "pooled": {names[e.at]: e.pooled[e.at] for e in heads},
             "fc": {names[e.fc]: e.calls for e in heads}}
+
+
+class IntegerGraph:
+    """The integer forward of `qnn` as one replayed HIP graph: `graph(x)` copies `x` into a static
+    input, replays the capture for `x.shape` and returns the static logits tensor, which is valid
+    until the next call.  Every kernel of the route is capturable (no allocation, no sync, no
+    float atomics); what replay removes is the per-launch host cost, which bounds the small planes.
+
+    The first call for a shape warms up with two eager forwards on a side stream (MIOpen's solver
+    choice for the decoded layers, every once-per-tensor check) and captures `qnn(static_in)` under
+    no_grad, eval mode and frozen_weight_cache in one torch.cuda.graph: one stream, no parallel
+    branches.  At most `MAX_SHAPES` shapes are kept, the least recently used evicted (a validation
+    pass's last batch is partial).
+
+    Ownership: the object holds what the captured kernels read and the graph's pool does not own:
+    the static input, the decoded layers' frozen W_hat (the frozen-weight dictionary is dropped
+    when its context exits), the split-K and kernel workspaces.  Counters: the off-grid device word
+    is written by the replayed kernels and keeps accumulating; the Python-side `calls` of plans and
+    edges advance only at capture, so their increments during capture are recorded and added on
+    every replay, and the five reports mean what they mean eagerly.
+
+    Staleness: enable_integer_inference / disable_integer_inference bump an epoch on `qnn`; a call
+    under another epoch than the construction's raises SSQError.  Beyond that the contract is
+    frozen_weight_cache's: nothing -- no weight, quantizer, flag, hook or module -- may change
+    between capture and replay; the modules are not walked on a replay.
+
+    Raises ValueError without an installed plan, and, naming it, for a module of `qnn` with a
+    forward hook or pre-hook (it would run once, at capture)."""
+    MAX_SHAPES = 4
+
+    def __init__(self, qnn):
+        if not _plans(qnn) and not getattr(qnn, "_int_edges", None):
+            raise ValueError("IntegerGraph: no integer plan installed (enable_integer_inference)")
+        for name, m in qnn.named_modules():
+            if _hooked(m):
+                raise ValueError(f"IntegerGraph: module {name or type(m).__name__!r} carries a forward "
+                                 "hook, which would run once, at capture")
+        self.qnn, self.epoch = qnn, qnn._int_epoch
+        self._shapes = collections.OrderedDict()     # (shape, dtype) -> the captured entry
+
+    def shapes(self):
+        """The captured input shapes, least recently used first."""
+        return [k[0] for k in self._shapes]
+
+    def _cells(self):
+        """The Python-side forward counters: (object, attribute) and (edge, pool) cells."""
+        qnn = self.qnn
+        edges = list(qnn._int_edges) + [e.emitter for e in qnn._int_edges if e.emitter is not None]
+        cells = [(p, None) for _, p in _plans(qnn)] + [(e, None) for e in edges]
+        return cells + [(e, m) for e in edges for m in e.pools]
+
+    @staticmethod
+    def _read(cells):
+        return [o.calls if m is None else o.pooled[m] for o, m in cells]
+
+    @staticmethod
+    def _add(cells, by):
+        for (o, m), d in zip(cells, by):
+            if m is None:
+                o.calls += d
+            else:
+                o.pooled[m] += d
+
+    @torch.no_grad()
+    def _capture(self, x):
+        qnn = self.qnn
+        qnn.eval()
+        cells = self._cells()
+        before, word = self._read(cells), qnn._int_counter.clone()
+        e = {"in": x.clone(), "ws": {}}
+        with L.frozen_weight_cache(), K.A.workspace_scope(e["ws"]):
+            side = torch.cuda.Stream(device=x.device)
+            side.wait_stream(torch.cuda.current_stream(x.device))
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    qnn(e["in"])
+            torch.cuda.current_stream(x.device).wait_stream(side)
+            mid = self._read(cells)
+            e["graph"] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(e["graph"]):
+                e["out"] = qnn(e["in"])
+            e["frozen"] = dict(L._FROZEN_W)
+        after = self._read(cells)
+        e["cells"], e["by"] = cells, [a - b for a, b in zip(after, mid)]
+        e["residual"] = [(t, t.residual) for t in {c[0] for c in cells} if isinstance(t, TailEdge)]
+        # the warm-up and the capture count as no forward: the first replay is the first
+        self._add(cells, [b - a for a, b in zip(after, before)])
+        qnn._int_counter.copy_(word)
+        return e
+
+    def __call__(self, x):
+        qnn = self.qnn
+        if getattr(qnn, "_int_epoch", 0) != self.epoch:
+            raise K.A.SSQError("IntegerGraph: the integer plan was re-installed or removed since "
+                               "this graph was built (enable / disable_integer_inference)")
+        if not (isinstance(x, torch.Tensor) and x.is_cuda):
+            raise K.A.SSQError("IntegerGraph: the input must be a tensor on the HIP device")
+        key = (tuple(x.shape), x.dtype)
+        e = self._shapes.get(key)
+        if e is None:
+            e = self._shapes[key] = self._capture(x)
+            while len(self._shapes) > self.MAX_SHAPES:
+                self._shapes.popitem(last=False)
+        else:
+            self._shapes.move_to_end(key)
+            e["in"].copy_(x)
+        e["graph"].replay()
+        self._add(e["cells"], e["by"])
+        for t, kind in e["residual"]:
+            t.residual = kind
+        return e["out"]
