@@ -878,6 +878,65 @@ int ssq_qconv_i8_centred_codes_res_fwd(const int8_t* codes, const void* prepared
                                        float res_delta, float res_zero_point, int res_qmin,
                                        int res_qmax, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- per-(co, ci) scales, the wide operand
+ * A weight whose scale is per (co, ci) on a common grid (ChannelQuant's shifted scale),
+ *     W_hat[co, ci, r, s] = (q_w - z_w[co]) * fp32(base[co] * fp32(kfac[co, ci] / L)),
+ * runs like a column-scaled one with the centred integer m = (q_w - z_w[co]) * kfac[co, ci] as
+ * the operand, T[co] = sum m and the caller's scale[co] = fp32(fp32(delta_a * base[co]) / fp32(L)).
+ *
+ * ssq_qweight_prepare_perci / ssq_qweight_prepare_grouped_perci: the *_colscale prepares with
+ * kfac (device int32 [Co*Ci], [Co*Cig] grouped) in kcol's place: same blob, same *bad rules
+ * (kfac outside [1, 127], |m| > 127).  A Linear's scale is per element (R = S = 1).  A depthwise
+ * weight has no such form (SSQ_E_ARG).
+ *
+ * The wide blob holds a centred operand of up to |m| <= 16319 as two int8 digits,
+ *     m = 128 h + l,  l = ((m + 64) mod 128) - 64 in [-64, 63],  h = (m - l) / 128 in [-127, 127]:
+ * [Cop][Kp] int8 rows of h, [Cop][Kp] rows of l, the 0/1 row [Kp], cwz[Cop] = 0, T[Cop] = sum m
+ * (ssq_qweight_prepared_bytes_wide bytes).  ssq_qweight_prepare_wide writes it from kfac, column
+ * factors [Ci*R*S] (per_ci = 0) or per-(co, ci) factors [Co*Ci] (per_ci = 1), in [1, 16319];
+ * *bad counts a factor outside that range, an |m| > 16319 and a zero point that is no code.
+ *
+ * ssq_qconv_i8_wide_fwd / _codes_fwd / _codes_res_fwd: the centred forms' arguments, checks and
+ * epilogue on a wide blob: D_h = sum a_s h and D_l = sum a_s l are exact int32 sums (eight MFMAs per
+ * k step), I = 128 D_h + D_l + az * T[co] in int64, then one conversion and one multiply (or the
+ * code-emitting epilogue): a function of the codes alone, equal bit for bit to the centred form
+ * wherever |m| <= 127.  Dense only, no split-K form; a blob of any other prepare gives wrong
+ * results.  No allocation, no sync, capturable. */
+int ssq_qweight_prepare_perci(const void* packed, const float* zp, const int32_t* kfac,
+                              int64_t Co, int64_t Ci, int64_t R, int64_t S, int n_bits, int qmin,
+                              void* prepared, uint32_t* bad, ssq_stream_t stream);
+int ssq_qweight_prepare_grouped_perci(const void* packed, const float* zp, const int32_t* kfac,
+                                      int64_t Co, int64_t Cig, int64_t R, int64_t S,
+                                      int64_t groups, int n_bits, int qmin, void* prepared,
+                                      uint32_t* bad, ssq_stream_t stream);
+size_t ssq_qweight_prepared_bytes_wide(int64_t Co, int64_t Ci, int64_t R, int64_t S);
+int ssq_qweight_prepare_wide(const void* packed, const float* zp, const int32_t* kfac, int per_ci,
+                             int64_t Co, int64_t Ci, int64_t R, int64_t S, int n_bits, int qmin,
+                             void* prepared, uint32_t* bad, ssq_stream_t stream);
+int ssq_qconv_i8_wide_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                          int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R,
+                          int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                          float act_zero_point, int act_qmin, int act_qmax, float* y,
+                          ssq_stream_t stream);
+int ssq_qconv_i8_wide_codes_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                                float act_zero_point, int act_qmin, int act_qmax,
+                                const float* bias, const float* gamma, const float* phi, int act,
+                                float out_delta, float out_zero_point, int out_qmin, int out_qmax,
+                                int8_t* out_codes, uint32_t* bad, ssq_stream_t stream);
+int ssq_qconv_i8_wide_codes_res_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                    int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                    int64_t R, int64_t S, int64_t stride, int64_t pad,
+                                    int64_t groups, float act_zero_point, int act_qmin,
+                                    int act_qmax, const float* bias, const float* gamma,
+                                    const float* phi, int act, float out_delta,
+                                    float out_zero_point, int out_qmin, int out_qmax,
+                                    int8_t* out_codes, uint32_t* bad, const float* res_f32,
+                                    const int8_t* res_codes, float res_delta,
+                                    float res_zero_point, int res_qmin, int res_qmax,
+                                    ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- K23 split along K
  * The six dense conv entry points with the k walk divided among `splits` = Z workgroups per
  * output tile, for planes whose (ceil(M/64), ceil(Co/64)) grid does not fill the device

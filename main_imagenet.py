@@ -78,7 +78,8 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
                                     carry_stem=args.int_infer_carry_stem,
                                     carry_head=args.int_infer_carry_head,
                                     colscale=args.int_infer_colscale,
-                                    splitk=args.int_infer_splitk)
+                                    splitk=args.int_infer_splitk,
+                                    per_ci=args.int_infer_per_ci, wide=args.int_infer_wide)
     n_int = sum(v == 'int8' for v in plan.values())
     print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
     if args.int_infer_carry:

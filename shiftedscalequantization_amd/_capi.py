@@ -161,6 +161,15 @@ SIGNATURES["ssq_qweight_prepare_grouped_colscale"] = (_i, [_p, _p, _p, _i64, _i6
                                                            _p, _p, _p])
 for _n in ("fwd", "codes_fwd", "codes_res_fwd"):
     SIGNATURES[f"ssq_qconv_i8_centred_{_n}"] = SIGNATURES[f"ssq_qconv_i8_{_n}"]
+# the per-(co, ci) prepares are the column-scaled ones with kfac[Co * Ci] for kcol; the wide blob has
+# its own byte query and one prepare (kfac, then per_ci: 0 column factors, 1 per-(co, ci) factors);
+# the wide convs take their plain twins' arguments
+SIGNATURES["ssq_qweight_prepare_perci"] = SIGNATURES["ssq_qweight_prepare_colscale"]
+SIGNATURES["ssq_qweight_prepare_grouped_perci"] = SIGNATURES["ssq_qweight_prepare_grouped_colscale"]
+SIGNATURES["ssq_qweight_prepared_bytes_wide"] = SIGNATURES["ssq_qweight_prepared_bytes"]
+SIGNATURES["ssq_qweight_prepare_wide"] = (_i, [_p, _p, _p, _i, _i64, _i64, _i64, _i64, _i, _i, _p, _p, _p])
+for _n in ("fwd", "codes_fwd", "codes_res_fwd"):
+    SIGNATURES[f"ssq_qconv_i8_wide_{_n}"] = SIGNATURES[f"ssq_qconv_i8_{_n}"]
 # the split-K convs take their parents' arguments with (splits, ws, ws_bytes) before the stream
 for _n in ("fwd", "codes_fwd", "codes_res_fwd"):
     _res, _args = SIGNATURES[f"ssq_qconv_i8_{_n}"]

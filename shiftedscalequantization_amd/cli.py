@@ -97,6 +97,15 @@ def build_parser():
                         'on integer codes too: the column scale as integers k / L, L <= 127, folded '
                         'into the int8 weight operand; with --test the act quantizers are '
                         'initialised and the route runs after channelShift_wMSE; implies --int_infer')
+    p.add_argument('--int_infer_per_ci', action='store_true',
+                   help='--int_infer with weights scaled per (co, ci) (ChannelQuant shifted scales: '
+                        'the layer / block shiftedScale reconstructions) on integer codes too: the '
+                        'scale as base[co] * k / L, the integer k folded into the int8 weight '
+                        'operand; implies --int_infer')
+    p.add_argument('--int_infer_wide', action='store_true',
+                   help='--int_infer with a scaled weight operand (q - z) * k that leaves int8 run '
+                        'as two int8 digits (|m| <= 16319, L <= 1024) instead of being refused; '
+                        'goes with --int_infer_per_ci / --int_infer_colscale; implies --int_infer')
     p.add_argument('--int_infer_splitk', action='store_true',
                    help='--int_infer with the dense int8 convs of small planes split along K '
                         'where the host rule asks for it (two kernels, bit-identical); implies '
@@ -128,7 +137,7 @@ def parse_args(argv=None):
     if a.int_infer_carry_blocks:
         a.int_infer_carry = True
     if (a.int_infer_grouped or a.int_infer_carry or a.int_infer_colscale or a.int_infer_splitk
-            or a.int_infer_graph):
+            or a.int_infer_graph or a.int_infer_per_ci or a.int_infer_wide):
         a.int_infer = True
     return a
 

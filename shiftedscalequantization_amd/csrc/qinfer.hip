@@ -36,6 +36,11 @@
 // prepared operand is the centred integer m = (q_w - z_w[co]) * kcol[j] itself (|m| <= 127), so
 // cwz = 0, I = D + az * T[co] with T[co] = sum m, and the CENTRED instantiation of K23 drops the
 // 0/1 row and the SA MFMA; the caller's s[co] = fp32(fp32(delta_a * d1[co]) / fp32(L)).
+//
+// Per-(co, ci) scaled weights, W_hat = (q_w - z_w[co]) * fp32(base[co] * fp32(k[co, ci] / L)), are the
+// same centred operand with the factor read per (co, ci) (QFactor, qinfer_prepare.h).  Where
+// |m| leaves int8 the wide blob holds m = 128 h + l as two int8 planes (|m| <= 16319) and the WIDE
+// instantiation of K23 sums D_h and D_l separately: I = 128 D_h + D_l + az * T[co].
 #include <type_traits>
 
 #include "ssq_common.h"
@@ -93,18 +98,20 @@ __global__ __launch_bounds__(kBlock) void act_encode_kernel(const float* __restr
 // ---------------------------------------------------------------- K22 weight prepare
 // One workgroup per padded output channel, one more (blockIdx.x == Cop) for the 0/1 row.
 // Plain: the operand is q - cw, cwz[co] = cw - z_w[co], T[co] = sum + K * cwz[co].
-// COLSCALE, a column-scaled weight W_hat = ((q - z_w[co]) * d1[co]) * (kcol[j] / L), j = (ci, r, s):
-// the operand is the centred integer m = (q - z_w[co]) * kcol[j] itself (qinfer_prepare.h), so
-// cwz = 0 and T[co] = sum m; the 0/1 row is written all the same, so every reader of the layout
-// runs the blob as it stands.  *bad counts the real channels whose zero point breaks zp_is_code
-// and, COLSCALE, the real elements colscaled() counts.
-template <bool COLSCALE>
+// SCALED, a weight W_hat = ((q - z_w[co]) * d[co]) * (k / L) with k the QFactor's entry of the
+// element (a column scale or a per-(co, ci) scale, qinfer_prepare.h): the operand is the centred
+// integer m = (q - z_w[co]) * k itself, so cwz = 0 and T[co] = sum m; the 0/1 row is written all
+// the same, so every reader of the layout runs the blob as it stands.  WIDE (with SCALED): m leaves
+// as its two digits, h into the first plane and l into the second (qinfer_layout.h).  *bad counts
+// the real channels whose zero point breaks zp_is_code and, SCALED, the real elements qscaled()
+// counts.
+template <bool SCALED, bool WIDE = false>
 __global__ __launch_bounds__(kBlock) void qweight_prepare_kernel(
-    const uint8_t* __restrict__ packed, const float* __restrict__ zp,
-    const int32_t* __restrict__ kcol, int bs, int qmin, uint32_t Co, uint32_t Ci, uint32_t RS,
-    uint32_t Cp, uint32_t Kp, uint32_t Cop, FastDiv div_cp, int8_t* __restrict__ wp,
-    int8_t* __restrict__ mask, int32_t* __restrict__ cwz, int32_t* __restrict__ tt,
-    uint32_t* __restrict__ bad) {
+    const uint8_t* __restrict__ packed, const float* __restrict__ zp, QFactor f, int bs, int qmin,
+    uint32_t Co, uint32_t Ci, uint32_t RS, uint32_t Cp, uint32_t Kp, uint32_t Cop, FastDiv div_cp,
+    int8_t* __restrict__ wp, int8_t* __restrict__ mask, int32_t* __restrict__ cwz,
+    int32_t* __restrict__ tt, uint32_t* __restrict__ bad) {
+  static_assert(SCALED || !WIDE, "the wide blob holds a centred operand");
   __shared__ int red[kBlock / kWave];
   const uint32_t co = blockIdx.x;
   if (co == Cop) {
@@ -126,11 +133,16 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_kernel(
     if (real && tap < RS && ci < Ci) {
       const size_t j = (size_t)ci * RS + tap;
       const int u = (int)packed_code(packed, (size_t)co * Ci * RS + j, bs);   // q - qmin
-      if constexpr (COLSCALE) v = colscaled(u + qmin - z, kcol[j], nbad);
+      if constexpr (SCALED) v = qscaled(u + qmin - z, qfactor_at(f, co, ci, tap), f.lim, nbad);
       else v = u - 128;   // q - cw, cw = qmin + 128
-      sum += v;
+      sum += v;   // WIDE: |sum| <= 65536 * 16319 < 2^31
     }
-    wp[(size_t)co * Kp + k] = (int8_t)v;
+    if constexpr (WIDE) {
+      wp[(size_t)co * Kp + k] = (int8_t)qdigit_hi(v);
+      wp[((size_t)Cop + co) * Kp + k] = (int8_t)qdigit_lo(v);
+    } else {
+      wp[(size_t)co * Kp + k] = (int8_t)v;
+    }
   }
   sum = (int)wave_sum((uint32_t)sum);
   nbad = wave_sum(nbad);
@@ -143,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_kernel(
     int total = 0;
     for (int i = 0; i < kBlock / kWave; ++i) total += red[i];
     if (!zok) atomicAdd(bad, 1u);
-    const int c = (COLSCALE || !real) ? 0 : qmin + 128 - z;
+    const int c = (SCALED || !real) ? 0 : qmin + 128 - z;
     cwz[co] = c;
     tt[co] = total + (int)(Ci * RS) * c;   // a padded channel: 0
   }
@@ -165,6 +177,21 @@ __device__ __forceinline__ long long qconv_sum(int d, const int32_t* __restrict_
   else return (long long)d + (long long)cwz[co] * sa + (long long)az * (long long)tt[co];
 }
 
+// the wide operand's sum: I = 128 D_h + D_l + az * T[co], each D an exact int32 digit sum
+__device__ __forceinline__ long long qconv_sum_wide(int dh, int dl, int az,
+                                                    const int32_t* __restrict__ tt, uint32_t co) {
+  return 128ll * (long long)dh + (long long)dl + (long long)az * (long long)tt[co];
+}
+
+// K23's choice between the two: `d` is D, or, WIDE, D_h with `dl` = D_l
+template <bool CENTRED, bool WIDE>
+__device__ __forceinline__ long long qconv_sum_of(int d, int dl, const int32_t* __restrict__ cwz,
+                                                  long long sa, int az,
+                                                  const int32_t* __restrict__ tt, uint32_t co) {
+  if constexpr (WIDE) return qconv_sum_wide(d, dl, az, tt, co);
+  else return qconv_sum<CENTRED>(d, cwz, sa, az, tt, co);
+}
+
 // CODES: the code-emitting epilogue (qinfer_epi.h) instead of the fp32 NCHW store; `y` is then
 // the QEpi.  The 64 px x 64 ch code tile is transposed through the (then free) activation
 // tile and leaves as one 16-B chunk of a pixel's channels per thread.
@@ -181,12 +208,19 @@ __device__ __forceinline__ long long qconv_sum(int d, const int32_t* __restrict_
 // LDS layout, fragment map and MFMAs of the whole walk, and instead of an epilogue stores its raw
 // int32 accumulators to the QPartial `y`.  Every element of D[Z][Co][M] and (not CENTRED)
 // SA[Z][M] is written exactly once, by one thread, and nothing else: no memset, no counter.
+// WIDE (implies CENTRED; not with PARTIAL): the blob holds a centred operand m = 128 h + l in two
+// int8 digit planes (qinfer_layout.h).  The tile and lane maps stay; per k step a thread stages
+// one activation chunk and one chunk of each plane (lB holds two 64-row tiles, h then l), a wave
+// reads one activation fragment and eight weight fragments and issues eight MFMAs into two sets
+// of accumulators, D_h = sum a_s h and D_l = sum a_s l (|D| <= 65536 * 128 * 127 < 2^30 each), and
+// the epilogue takes I = 128 D_h + D_l + az * T[co] in int64 (qconv_sum_wide) and is otherwise
+// the one above.
 struct QPartial {
   int32_t* D;    // [Z][Co][M]: slice z's sum of a_s w_s, the fp32 form's store pattern
   int32_t* SA;   // [Z][M]: slice z's window sum (not CENTRED)
 };
 
-template <bool CODES, int RES = 0, bool CENTRED = false, bool PARTIAL = false>
+template <bool CODES, int RES = 0, bool CENTRED = false, bool PARTIAL = false, bool WIDE = false>
 __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
     const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ mask,
     const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
@@ -197,8 +231,9 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
                                   float* __restrict__>::type>::type y) {
   static_assert(CODES || RES == 0, "a residual goes with the code-emitting epilogue");
   static_assert(!PARTIAL || (!CODES && RES == 0), "a partial walk has no epilogue");
+  static_assert(!WIDE || (CENTRED && !PARTIAL), "the wide operand is centred and has no split form");
   __shared__ __attribute__((aligned(16))) int8_t lA[kQT * kQRow];
-  __shared__ __attribute__((aligned(16))) int8_t lB[(kQT + 1) * kQRow];
+  __shared__ __attribute__((aligned(16))) int8_t lB[(WIDE ? 2 * kQT : kQT + 1) * kQRow];
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & (kWave - 1), wave = tid / kWave;
   const uint32_t fr = lane & 15, fq = lane >> 4;
@@ -239,6 +274,10 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
 
   i32x4 ra = load_a(kt0);
   i32x4 rb = *(const i32x4*)(wrow + (size_t)kt0 * kQT);
+  // WIDE: the l plane lies Cop * Kp bytes behind the h plane, Cop = 64 gridDim.y
+  const size_t plane = WIDE ? (size_t)gridDim.y * kQT * g.Kp : 0;
+  i32x4 rl = {0, 0, 0, 0};
+  if constexpr (WIDE) rl = *(const i32x4*)(wrow + plane + (size_t)kt0 * kQT);
   i32x4 rm = {0, 0, 0, 0};
   if constexpr (!CENTRED) {
     if (tid < 4) rm = *(const i32x4*)(mask + (size_t)kt0 * kQT + tid * 16);
@@ -248,11 +287,15 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j] = i32x4{0, 0, 0, 0};
   i32x4 accs = {0, 0, 0, 0};
+  i32x4 accl[WIDE ? 4 : 1];   // WIDE: acc is D_h, accl D_l
+#pragma unroll
+  for (int j = 0; j < (WIDE ? 4 : 1); ++j) accl[j] = i32x4{0, 0, 0, 0};
 
   for (uint32_t kt = kt0; kt < kt1; ++kt) {
     __syncthreads();   // the previous step's fragment reads are done
     *(i32x4*)(lA + srow * kQRow + sc * 16) = ra;
     *(i32x4*)(lB + srow * kQRow + sc * 16) = rb;
+    if constexpr (WIDE) *(i32x4*)(lB + (kQT + srow) * kQRow + sc * 16) = rl;
     if constexpr (!CENTRED) {
       if (tid < 4) *(i32x4*)(lB + kQT * kQRow + tid * 16) = rm;
     }
@@ -260,6 +303,7 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
     if (kt + 1 < kt1) {
       ra = load_a(kt + 1);
       rb = *(const i32x4*)(wrow + (size_t)(kt + 1) * kQT);
+      if constexpr (WIDE) rl = *(const i32x4*)(wrow + plane + (size_t)(kt + 1) * kQT);
       if constexpr (!CENTRED) {
         if (tid < 4) rm = *(const i32x4*)(mask + (size_t)(kt + 1) * kQT + tid * 16);
       }
@@ -273,6 +317,13 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
     for (int j = 0; j < 4; ++j) {
       const i32x4 wf = *(const i32x4*)(lB + (j * 16 + fr) * kQRow + fq * 16);
       acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, af, acc[j], 0, 0, 0);
+    }
+    if constexpr (WIDE) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const i32x4 wf = *(const i32x4*)(lB + (kQT + j * 16 + fr) * kQRow + fq * 16);
+        accl[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, af, accl[j], 0, 0, 0);
+      }
     }
   }
 
@@ -330,7 +381,8 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
         const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
         c[r] = 0;
         if (pval && co < g.Co) {
-          const long long I = qconv_sum<CENTRED>(acc[j][r], cwz, sa, g.az, tt, co);
+          const long long I = qconv_sum_of<CENTRED, WIDE>(acc[j][r], accl[WIDE ? j : 0][r], cwz, sa,
+                                                          g.az, tt, co);
           if constexpr (RES == 1) {
             c[r] = qepi_code<true>((float)I, co, scale, e, nbad, rf[j * 4 + r]);
           } else if constexpr (RES == 2) {
@@ -364,7 +416,8 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
       for (int r = 0; r < 4; ++r) {
         const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
         if (co < g.Co) {
-          const long long I = qconv_sum<CENTRED>(acc[j][r], cwz, sa, g.az, tt, co);
+          const long long I = qconv_sum_of<CENTRED, WIDE>(acc[j][r], accl[WIDE ? j : 0][r], cwz, sa,
+                                                          g.az, tt, co);
           y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
         }
       }
@@ -529,13 +582,14 @@ __global__ __launch_bounds__(kBlock) void act_decode_kernel(const int8_t* __rest
   }
 }
 
-static int qgeo_ok(const char* what, int64_t Co, int64_t Ci, int64_t R, int64_t S) {
+static int qgeo_ok(const char* what, int64_t Co, int64_t Ci, int64_t R, int64_t S,
+                   int planes = 1) {
   SSQ_REQUIRE(Co >= 1 && Ci >= 1 && R >= 1 && S >= 1 && R <= 7 && S <= 7, SSQ_E_ARG,
               "%s: bad geometry (Co, Ci >= 1; R, S in [1, 7])", what);
   SSQ_REQUIRE(Ci * R * S <= kQMaxK, SSQ_E_ARG,
               "%s: K = Ci*R*S = %lld exceeds 65536 (int32 accumulator range)", what,
               (long long)(Ci * R * S));
-  const QLayout L = qlayout(Co, Ci, R, S);
+  const QLayout L = qlayout(Co, Ci, R, S, planes);
   SSQ_REQUIRE(L.off_mask < (1ull << 31), SSQ_E_ARG, "%s: prepared weights exceed 2^31 bytes", what);
   return SSQ_OK;
 }
@@ -569,22 +623,25 @@ extern "C" int ssq_act_encode(const float* x, int64_t Nb, int64_t C, int64_t H, 
   return check_launch("ssq_act_encode");
 }
 
-// kcol: the column factors of a column-scaled weight (the COLSCALE kernel), or null
-static int qweight_prepare_launch(const char* me, bool colscale, const void* packed,
-                                  const float* zp, const int32_t* kcol, int64_t Co, int64_t Ci,
-                                  int64_t R, int64_t S, int n_bits, int qmin, void* prepared,
-                                  uint32_t* bad, ssq_stream_t stream) {
-  SSQ_REQUIRE(packed && zp && (kcol || !colscale) && prepared && bad, SSQ_E_ARG,
+// kfac: the integer factors of a scaled weight (the SCALED kernels), or null: one per (ci, r, s)
+// column, or, per_ci, one per (co, ci); wide: the two-digit blob, factors and |m| up to kQWideMax
+static int qweight_prepare_launch(const char* me, bool scaled, bool per_ci, bool wide,
+                                  const void* packed, const float* zp, const int32_t* kfac,
+                                  int64_t Co, int64_t Ci, int64_t R, int64_t S, int n_bits,
+                                  int qmin, void* prepared, uint32_t* bad, ssq_stream_t stream) {
+  SSQ_REQUIRE(packed && zp && (kfac || !scaled) && prepared && bad, SSQ_E_ARG,
               "%s: null pointer", me);
   int rc = qrange_ok(me, n_bits, qmin);
   if (rc) return rc;
-  rc = qgeo_ok(me, Co, Ci, R, S);
+  rc = qgeo_ok(me, Co, Ci, R, S, wide ? 2 : 1);
   if (rc) return rc;
-  const QLayout L = qlayout(Co, Ci, R, S);
+  const QLayout L = qlayout(Co, Ci, R, S, wide ? 2 : 1);
   int8_t* base = (int8_t*)prepared;
-  auto* kernel = colscale ? qweight_prepare_kernel<true> : qweight_prepare_kernel<false>;
+  const QFactor f = qfactor(kfac, per_ci, (uint32_t)Ci, (uint32_t)(R * S), wide ? kQWideMax : 127);
+  auto* kernel = wide ? qweight_prepare_kernel<true, true>
+                      : (scaled ? qweight_prepare_kernel<true> : qweight_prepare_kernel<false>);
   hipLaunchKernelGGL(kernel, dim3((uint32_t)L.Cop + 1), dim3(kBlock), 0, (hipStream_t)stream,
-                     (const uint8_t*)packed, zp, kcol, packed_bits(n_bits), qmin, (uint32_t)Co,
+                     (const uint8_t*)packed, zp, f, packed_bits(n_bits), qmin, (uint32_t)Co,
                      (uint32_t)Ci, (uint32_t)(R * S), (uint32_t)L.Cp, (uint32_t)L.Kp,
                      (uint32_t)L.Cop, make_fastdiv((uint32_t)L.Cp), base, base + L.off_mask,
                      (int32_t*)(base + L.off_cwz), (int32_t*)(base + L.off_t), bad);
@@ -594,16 +651,37 @@ static int qweight_prepare_launch(const char* me, bool colscale, const void* pac
 extern "C" int ssq_qweight_prepare(const void* packed, const float* zp, int64_t Co, int64_t Ci,
                                    int64_t R, int64_t S, int n_bits, int qmin, void* prepared,
                                    uint32_t* bad, ssq_stream_t stream) {
-  return qweight_prepare_launch("ssq_qweight_prepare", false, packed, zp, nullptr, Co, Ci, R, S,
-                                n_bits, qmin, prepared, bad, stream);
+  return qweight_prepare_launch("ssq_qweight_prepare", false, false, false, packed, zp, nullptr, Co,
+                                Ci, R, S, n_bits, qmin, prepared, bad, stream);
 }
 
 extern "C" int ssq_qweight_prepare_colscale(const void* packed, const float* zp,
                                             const int32_t* kcol, int64_t Co, int64_t Ci, int64_t R,
                                             int64_t S, int n_bits, int qmin, void* prepared,
                                             uint32_t* bad, ssq_stream_t stream) {
-  return qweight_prepare_launch("ssq_qweight_prepare_colscale", true, packed, zp, kcol, Co, Ci, R,
-                                S, n_bits, qmin, prepared, bad, stream);
+  return qweight_prepare_launch("ssq_qweight_prepare_colscale", true, false, false, packed, zp,
+                                kcol, Co, Ci, R, S, n_bits, qmin, prepared, bad, stream);
+}
+
+extern "C" int ssq_qweight_prepare_perci(const void* packed, const float* zp, const int32_t* kfac,
+                                         int64_t Co, int64_t Ci, int64_t R, int64_t S, int n_bits,
+                                         int qmin, void* prepared, uint32_t* bad,
+                                         ssq_stream_t stream) {
+  return qweight_prepare_launch("ssq_qweight_prepare_perci", true, true, false, packed, zp, kfac,
+                                Co, Ci, R, S, n_bits, qmin, prepared, bad, stream);
+}
+
+extern "C" size_t ssq_qweight_prepared_bytes_wide(int64_t Co, int64_t Ci, int64_t R, int64_t S) {
+  if (Co < 1 || Ci < 1 || R < 1 || S < 1) return 0;
+  return qlayout(Co, Ci, R, S, 2).bytes;
+}
+
+extern "C" int ssq_qweight_prepare_wide(const void* packed, const float* zp, const int32_t* kfac,
+                                        int per_ci, int64_t Co, int64_t Ci, int64_t R, int64_t S,
+                                        int n_bits, int qmin, void* prepared, uint32_t* bad,
+                                        ssq_stream_t stream) {
+  return qweight_prepare_launch("ssq_qweight_prepare_wide", true, per_ci != 0, true, packed, zp,
+                                kfac, Co, Ci, R, S, n_bits, qmin, prepared, bad, stream);
 }
 
 // One form of K23 on a blob: CENTRED for a centred one (ssq_qweight_prepare_colscale), which is
@@ -622,7 +700,7 @@ static size_t qsplit_ws_bytes(int64_t M, int64_t Co, int64_t Z, bool centred) {
   return (size_t)Z * (size_t)(Co + (centred ? 0 : 1)) * (size_t)M * 4;
 }
 
-template <bool CENTRED>
+template <bool CENTRED, bool WIDE = false>
 static void qconv_i8_run(dim3 grid, ssq_stream_t stream, const int8_t* codes, const int8_t* base,
                          const QLayout& L, const float* scale, const QConvGeo& g, float* y,
                          const QEpi* epi, const QRes* res, const QSplit* sp) {
@@ -633,6 +711,13 @@ static void qconv_i8_run(dim3 grid, ssq_stream_t stream, const int8_t* codes, co
     hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base, mask, cwz,
                        tt, scale, g, out);
   };
+  if constexpr (WIDE) {
+    if (!epi) run(qconv_i8_kernel<false, 0, true, false, true>, y);
+    else if (!res) run(qconv_i8_kernel<true, 0, true, false, true>, *epi);
+    else if (res->f32) run(qconv_i8_kernel<true, 1, true, false, true>, QEpiRes{*epi, *res});
+    else run(qconv_i8_kernel<true, 2, true, false, true>, QEpiRes{*epi, *res});
+    return;
+  }
   if (sp) {
     const uint32_t Z = (uint32_t)sp->splits;
     const QPartial part = {(int32_t*)sp->ws, (int32_t*)sp->ws + (size_t)Z * g.Co * g.M};
@@ -668,21 +753,23 @@ struct QConvIn {
 
 // y: the fp32 output (ssq_qconv_i8_fwd) or null with `epi` set (ssq_qconv_i8_codes_fwd); `res`
 // with `epi`: the tail's residual (ssq_qconv_i8_codes_res_fwd); centred: the *_centred_* forms;
-// `sp`: the split-K forms
+// `sp`: the split-K forms; wide: the *_wide_* forms on the two-digit blob (centred, never split)
 static int qconv_i8_launch(const char* me, bool centred, const QConvIn& a, float* y, QEpi* epi,
-                           const QRes* res, ssq_stream_t stream, const QSplit* sp = nullptr) {
+                           const QRes* res, ssq_stream_t stream, const QSplit* sp = nullptr,
+                           bool wide = false) {
   SSQ_REQUIRE(a.codes && a.prepared && a.scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
   SSQ_REQUIRE(a.groups == 1, SSQ_E_ARG, "%s: groups = %lld (only groups == 1)", me,
               (long long)a.groups);
   const int64_t Nb = a.Nb, H = a.H, W = a.W, Co = a.Co, R = a.R, S = a.S, pad = a.pad;
-  int rc = qgeo_ok(me, Co, a.Ci, R, S);
+  SSQ_REQUIRE(!wide || (centred && !sp), SSQ_E_ARG, "%s: the wide blob has no split-K form", me);
+  int rc = qgeo_ok(me, Co, a.Ci, R, S, wide ? 2 : 1);
   if (rc) return rc;
   SSQ_REQUIRE(Nb >= 1 && H >= 1 && W >= 1 && a.stride >= 1 && pad >= 0 &&
                   H + 2 * pad >= R && W + 2 * pad >= S,
               SSQ_E_ARG, "%s: bad geometry", me);
   rc = qquant_ok(me, "activation ", nullptr, a.act_zero_point, a.act_qmin, a.act_qmax);
   if (rc) return rc;
-  const QLayout L = qlayout(Co, a.Ci, R, S);
+  const QLayout L = qlayout(Co, a.Ci, R, S, wide ? 2 : 1);
   const int64_t OH = (H + 2 * pad - R) / a.stride + 1, OW = (W + 2 * pad - S) / a.stride + 1;
   SSQ_REQUIRE(Nb * H * W * L.Cp < (1ll << 31) && Nb * OH * OW * Co < (1ll << 31), SSQ_E_ARG,
               "%s: tensor exceeds 2^31 elements", me);
@@ -721,7 +808,8 @@ static int qconv_i8_launch(const char* me, bool centred, const QConvIn& a, float
   }
   const dim3 grid((g.M + kQT - 1) / kQT, (uint32_t)(L.Cop / kQT));
   const int8_t* base = (const int8_t*)a.prepared;
-  if (centred) qconv_i8_run<true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, sp);
+  if (wide) qconv_i8_run<true, true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, nullptr);
+  else if (centred) qconv_i8_run<true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, sp);
   else qconv_i8_run<false>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, sp);
   return check_launch(me);
 }
@@ -834,6 +922,61 @@ extern "C" int ssq_qconv_i8_centred_codes_res_fwd(
                          {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
                           act_zero_point, act_qmin, act_qmax},
                          nullptr, &e, &r, stream);
+}
+
+// The wide forms: the centred forms' arguments, checks and epilogues on a blob of
+// ssq_qweight_prepare_wide (two int8 digit planes, eight MFMAs per k step).
+extern "C" int ssq_qconv_i8_wide_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                     int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                     int64_t R, int64_t S, int64_t stride, int64_t pad,
+                                     int64_t groups, float act_zero_point, int act_qmin,
+                                     int act_qmax, float* y, ssq_stream_t stream) {
+  SSQ_REQUIRE(y, SSQ_E_ARG, "ssq_qconv_i8_wide_fwd: null pointer");
+  return qconv_i8_launch("ssq_qconv_i8_wide_fwd", true,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         y, nullptr, nullptr, stream, nullptr, true);
+}
+
+extern "C" int ssq_qconv_i8_wide_codes_fwd(const int8_t* codes, const void* prepared,
+                                           const float* scale, int64_t Nb, int64_t Ci, int64_t H,
+                                           int64_t W, int64_t Co, int64_t R, int64_t S,
+                                           int64_t stride, int64_t pad, int64_t groups,
+                                           float act_zero_point, int act_qmin, int act_qmax,
+                                           const float* bias, const float* gamma, const float* phi,
+                                           int act, float out_delta, float out_zero_point,
+                                           int out_qmin, int out_qmax, int8_t* out_codes,
+                                           uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_wide_codes_fwd";
+  QEpi e;
+  const int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin,
+                           out_qmax, out_codes, bad, &e);
+  if (rc) return rc;
+  return qconv_i8_launch(me, true,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         nullptr, &e, nullptr, stream, nullptr, true);
+}
+
+extern "C" int ssq_qconv_i8_wide_codes_res_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t Ci,
+    int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+    int64_t groups, float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+    const float* gamma, const float* phi, int act, float out_delta, float out_zero_point,
+    int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad, const float* res_f32,
+    const int8_t* res_codes, float res_delta, float res_zero_point, int res_qmin, int res_qmax,
+    ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_wide_codes_res_fwd";
+  QEpi e;
+  QRes r;
+  int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin, out_qmax,
+                     out_codes, bad, &e);
+  if (!rc) rc = qres_init(me, res_f32, res_codes, res_delta, res_zero_point, res_qmin, res_qmax, &r);
+  if (rc) return rc;
+  return qconv_i8_launch(me, true,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         nullptr, &e, &r, stream, nullptr, true);
 }
 
 extern "C" int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W,

@@ -44,8 +44,9 @@ constexpr uint32_t kDwBlocks = 2048;   // workgroups K25 aims for: 8 per CU
 
 // ---------------------------------------------------------------- K24 weight prepare
 // Plain and COLSCALE as K22 (qinfer.hip): COLSCALE stores the centred integer
-// m = (q - z_w[co]) * kcol[j], j = (ci, r, s) within the group (J = Cig*R*S, shared by all groups),
-// and *bad also counts what colscaled() counts (qinfer_prepare.h).
+// m = (q - z_w[co]) * k, k the QFactor's entry of the element (qinfer_prepare.h): a column scale's
+// k[j], j = (ci, r, s) within the group (J = Cig*R*S, shared by all groups), or a per-(co, ci)
+// scale's k[co * Cig + ci]; *bad also counts what qscaled() counts.
 //
 // depthwise: one thread per (tap, padded channel) of K25's centred int32 blob [R*S][Cp],
 // wc = q - z_w[c]; COLSCALE multiplies it by kcol[tap]
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_dw_kernel(
       const int z = ok ? (int)zf : qmin;
       if (!ok && tap == 0) ++nbad;   // counted once per channel
       v = (int)packed_code(packed, (size_t)c * RS + tap, bs) + qmin - z;
-      if constexpr (COLSCALE) v = colscaled(v, kcol[tap], nbad);
+      if constexpr (COLSCALE) v = qscaled(v, kcol[tap], 127, nbad);
     }
     wc[i] = v;
   }
@@ -77,8 +78,8 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_dw_kernel(
 // COLSCALE: m as the int8 operand, cwz = 0, T[co] = sum m, the 0/1 rows all the same
 template <bool COLSCALE>
 __global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_kernel(
-    const uint8_t* __restrict__ packed, const float* __restrict__ zp,
-    const int32_t* __restrict__ kcol, int bs, int qmin, uint32_t groups, uint32_t Cig,
+    const uint8_t* __restrict__ packed, const float* __restrict__ zp, QFactor f, int bs, int qmin,
+    uint32_t groups, uint32_t Cig,
     uint32_t Cog, uint32_t Cogp, uint32_t RS, uint32_t Wc, uint32_t Kp, FastDiv div_wc,
     FastDiv div_cogp, int8_t* __restrict__ wp, int8_t* __restrict__ mask,
     int32_t* __restrict__ cwz, int32_t* __restrict__ tt, uint32_t* __restrict__ bad) {
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_kernel(
     if (real && tap < RS && cw >= lo && cw < lo + Cig) {
       const size_t j = (size_t)(cw - lo) * RS + tap;
       const int u = (int)packed_code(packed, (size_t)co * Cig * RS + j, bs);   // q - qmin
-      if constexpr (COLSCALE) v = colscaled(u + qmin - z, kcol[j], nbad);
+      if constexpr (COLSCALE) v = qscaled(u + qmin - z, qfactor_at(f, co, cw - lo, tap), f.lim, nbad);
       else v = u - 128;   // q - cw, cw = qmin + 128
       sum += v;
     }
@@ -427,10 +428,11 @@ extern "C" size_t ssq_qweight_prepared_bytes_grouped(int64_t Co, int64_t Cig, in
   return glayout(Co, Cig, R, S, groups).bytes;
 }
 
-// kcol: the column factors of a column-scaled weight (the COLSCALE kernels), or null; `plain`:
-// the groups == 1 entry point an error message points to
+// kcol: the factors of a scaled weight (the COLSCALE kernels), or null: one per column, or,
+// per_ci, one per (co, ci) (grouped only: a depthwise weight has no such form); `plain`: the
+// groups == 1 entry point an error message points to
 static int qweight_prepare_grouped_launch(const char* me, const char* plain, bool colscale,
-                                          const void* packed, const float* zp,
+                                          bool per_ci, const void* packed, const float* zp,
                                           const int32_t* kcol, int64_t Co, int64_t Cig, int64_t R,
                                           int64_t S, int64_t groups, int n_bits, int qmin,
                                           void* prepared, uint32_t* bad, ssq_stream_t stream) {
@@ -444,6 +446,8 @@ static int qweight_prepare_grouped_launch(const char* me, const char* plain, boo
   int8_t* base = (int8_t*)prepared;
   const int bs = packed_bits(n_bits);
   const uint32_t RS = (uint32_t)(R * S);
+  SSQ_REQUIRE(!per_ci || L.kind == 2, SSQ_E_ARG,
+              "%s: a depthwise weight has one input channel per row: no per-(co, ci) scale", me);
   if (L.kind == 1) {
     auto* kernel = colscale ? qweight_prepare_dw_kernel<true> : qweight_prepare_dw_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(grid_for((int64_t)RS * L.Cp, kBlock)), dim3(kBlock), 0,
@@ -454,7 +458,8 @@ static int qweight_prepare_grouped_launch(const char* me, const char* plain, boo
     auto* kernel =
         colscale ? qweight_prepare_grouped_kernel<true> : qweight_prepare_grouped_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3((uint32_t)(groups * L.Cogp + groups)), dim3(kBlock), 0,
-                       (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, bs, qmin,
+                       (hipStream_t)stream, (const uint8_t*)packed, zp,
+                       qfactor(kcol, per_ci, (uint32_t)Cig, RS, 127), bs, qmin,
                        (uint32_t)groups, (uint32_t)Cig, (uint32_t)L.Cog, (uint32_t)L.Cogp, RS,
                        (uint32_t)L.Wc, (uint32_t)L.Kp, make_fastdiv((uint32_t)L.Wc),
                        make_fastdiv((uint32_t)L.Cogp), base, base + L.off_mask,
@@ -468,8 +473,8 @@ extern "C" int ssq_qweight_prepare_grouped(const void* packed, const float* zp, 
                                            int n_bits, int qmin, void* prepared, uint32_t* bad,
                                            ssq_stream_t stream) {
   return qweight_prepare_grouped_launch("ssq_qweight_prepare_grouped", "ssq_qweight_prepare",
-                                        false, packed, zp, nullptr, Co, Cig, R, S, groups, n_bits,
-                                        qmin, prepared, bad, stream);
+                                        false, false, packed, zp, nullptr, Co, Cig, R, S, groups,
+                                        n_bits, qmin, prepared, bad, stream);
 }
 
 extern "C" int ssq_qweight_prepare_grouped_colscale(const void* packed, const float* zp,
@@ -478,8 +483,19 @@ extern "C" int ssq_qweight_prepare_grouped_colscale(const void* packed, const fl
                                                     int n_bits, int qmin, void* prepared,
                                                     uint32_t* bad, ssq_stream_t stream) {
   return qweight_prepare_grouped_launch("ssq_qweight_prepare_grouped_colscale",
-                                        "ssq_qweight_prepare_colscale", true, packed, zp, kcol, Co,
-                                        Cig, R, S, groups, n_bits, qmin, prepared, bad, stream);
+                                        "ssq_qweight_prepare_colscale", true, false, packed, zp,
+                                        kcol, Co, Cig, R, S, groups, n_bits, qmin, prepared, bad,
+                                        stream);
+}
+
+extern "C" int ssq_qweight_prepare_grouped_perci(const void* packed, const float* zp,
+                                                 const int32_t* kfac, int64_t Co, int64_t Cig,
+                                                 int64_t R, int64_t S, int64_t groups, int n_bits,
+                                                 int qmin, void* prepared, uint32_t* bad,
+                                                 ssq_stream_t stream) {
+  return qweight_prepare_grouped_launch("ssq_qweight_prepare_grouped_perci",
+                                        "ssq_qweight_prepare_perci", true, true, packed, zp, kfac,
+                                        Co, Cig, R, S, groups, n_bits, qmin, prepared, bad, stream);
 }
 
 // y: the fp32 output (ssq_qconv_i8_grouped_fwd) or null with `epi` set (..._codes_fwd)

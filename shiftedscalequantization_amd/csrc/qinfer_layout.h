@@ -4,6 +4,11 @@
 // [Cop = 64*ceil(Co/64)][Kp = 64*ceil(R*S*Cp/64)] int8 rows, k = (r*S + s)*Cp + ci with
 // Cp = 16*ceil(Ci/16), then the 0/1 row [Kp], then cwz[Cop] and T[Cop] (int32).
 //
+// The wide blob (qlayout(..., 2), ssq_qweight_prepare_wide; read by K23's WIDE instantiations
+// only): a centred operand m = 128 h + l in two int8 digit planes of the rows above, first h
+// in [-127, 127], then l in [-64, 63], at a distance of Cop * Kp bytes; then the 0/1 row [Kp] (written,
+// not read), cwz[Cop] = 0 and T[Cop] = sum m (int32).
+//
 // GLayout, K24's blob (qinfer_grouped.hip), by kind.  Depthwise (K25): int32 [R*S][Cp].
 // Grouped (K26): int8 [G*Cogp][Kp], Kp = 64*ceil(R*S*Wc/64), k = tap * Wc + (c - w0_g) inside
 // group g's 16-aligned channel window; then the 0/1 rows [G][Kp]; then cwz[Co], T[Co] (int32).
@@ -24,12 +29,15 @@ struct QLayout {
   size_t off_mask, off_cwz, off_t, bytes;
 };
 
-static inline QLayout qlayout(int64_t Co, int64_t Ci, int64_t R, int64_t S) {
+constexpr int kQWideMax = 16319;   // |m| of the wide operand: 128 * 127 + 63
+
+// planes: 1, K22's blob; 2, the wide blob
+static inline QLayout qlayout(int64_t Co, int64_t Ci, int64_t R, int64_t S, int planes = 1) {
   QLayout L;
   L.Cp = rup(Ci, 16);
   L.Kp = rup(R * S * L.Cp, kQT);
   L.Cop = rup(Co, kQT);
-  L.off_mask = (size_t)L.Cop * (size_t)L.Kp;
+  L.off_mask = (size_t)planes * (size_t)L.Cop * (size_t)L.Kp;
   L.off_cwz = L.off_mask + (size_t)L.Kp;
   L.off_t = L.off_cwz + (size_t)L.Cop * 4;
   L.bytes = L.off_t + (size_t)L.Cop * 4;

@@ -1936,12 +1936,15 @@ class QPrepared:
     group; `bad` counts the channels whose zero point is not an integer code (device int32).
     `centred`: the blob holds a column-scaled weight's centred operand m = (q - z) * kcol[j]
     (qweight_prepare(..., kcol=...)), cwz = 0: the dense convs run it without the window sum,
-    and `bad` also counts the elements whose |m| exceeds 127."""
+    and `bad` also counts the elements whose |m| exceeds 127.  `wide` (with `centred`, dense
+    only): the blob holds m as two int8 digits (qweight_prepare(..., wide=True)), |m| up to
+    QWIDE_MAX; only K23's wide forms read it."""
 
-    def __init__(self, blob, shape, bad, groups=1, centred=False):
+    def __init__(self, blob, shape, bad, groups=1, centred=False, wide=False):
         self.blob, self.shape, self.bad = blob, tuple(int(s) for s in shape), bad
         self.groups = int(groups)
         self.centred = bool(centred)
+        self.wide = bool(wide)
 
     def geometry(self):
         Co, Ci = self.shape[:2]
@@ -1950,42 +1953,151 @@ class QPrepared:
 
 
 COLSCALE_MAX_L = 127
+QWIDE_MAX = 16319        # |m| and the factors of the wide operand: 128 * 127 + 63
+QWIDE_MAX_L = 1024
 
 
-def colscale_grid(col_scale):
+def colscale_grid(col_scale, max_l=COLSCALE_MAX_L, kmax=COLSCALE_MAX_L):
     """The common integer grid of a column scale (ChannelQuantMSE's c[j] = k[j] / level): the
-    smallest L in 1..127 with, for every j, k[j] = rint(c[j] * L) an integer >= 1 and
+    smallest L in 1..max_l with, for every j, k[j] = rint(c[j] * L) an integer >= 1 and
     fp32(k[j] / L) == c[j] bit for bit -> (L, k as an int32 CPU tensor); None when there is no
-    such L with every k[j] <= 127 (a zero, negative or non-finite entry included).  Host
+    such L with every k[j] <= kmax (a zero, negative or non-finite entry included).  Host
     arithmetic on a CPU copy of the J floats; L may be smaller than the level the search ran
-    with."""
+    with.  The defaults are the int8 operand's limits; the wide operand's are QWIDE_MAX_L and
+    QWIDE_MAX."""
     import numpy as np
     c = np.ascontiguousarray(col_scale.detach().reshape(-1).float().cpu().numpy(), dtype=np.float32)
     if c.size == 0 or not np.all(np.isfinite(c)) or not np.all(c > 0):
         return None
-    for L in range(1, COLSCALE_MAX_L + 1):
-        k = np.rint(c.astype(np.float64) * L)      # exact product: 24 + 7 bits
-        if k.min() < 1 or k.max() > COLSCALE_MAX_L:
+    for L in range(1, int(max_l) + 1):
+        k = np.rint(c.astype(np.float64) * L)      # exact product: 24 + 10 bits
+        if k.min() < 1 or k.max() > kmax:
             continue
         if np.array_equal((k.astype(np.float32) / np.float32(L)).view(np.int32), c.view(np.int32)):
             return L, torch.from_numpy(k.astype(np.int32))
     return None
 
 
-# (grouped, column-scaled) -> (the blob's byte query, the prepare entry point)
+def _perci_try(v, pad, L, kmax):
+    """One L of perci_grid on rows of distinct values `v` [R, U] (fp32; `pad` marks the filler
+    entries, which hold the row's maximum): per row the first (kr, base) in ascending order that
+    satisfies the predicate -> (found[R], base[R] fp32, k[R, U] int64)."""
+    import numpy as np
+    R, U = v.shape
+    kr = np.arange(1, min(int(kmax), 2 * L) + 1, dtype=np.float64)
+    vmax = v.max(axis=1).astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        b0 = (vmax[:, None] * L / kr[None, :]).astype(np.float32)                   # [R, Kr]
+        bases = np.stack([np.nextafter(b0, np.float32(0)), b0,
+                          np.nextafter(b0, np.float32(np.inf))], axis=2)             # [R, Kr, 3]
+        k = np.rint(v[:, None, None, :].astype(np.float64) / bases[..., None].astype(np.float64) * L)
+        inside = (k >= 1) & (k <= kmax)
+        prod = bases[..., None] * (np.where(inside, k, 1).astype(np.float32) / np.float32(L))
+        hit = inside & (prod.view(np.int32) == v[:, None, None, :].view(np.int32))
+        ok = (hit | pad[:, None, None, :]).all(axis=3) & (bases > 0) & np.isfinite(bases)
+    flat = ok.reshape(R, -1)
+    first = flat.argmax(axis=1)
+    found = flat[np.arange(R), first]
+    ik, ib = first // 3, first % 3
+    return found, bases[np.arange(R), ik, ib], k[np.arange(R), ik, ib].astype(np.int64)
+
+
+def perci_grid(scale, Co, Ci, kmax=COLSCALE_MAX_L, max_l=None):
+    """The integer grid of a per-(co, ci) weight scale (ChannelQuant's shifted scale, delta[co]
+    times a shift target per input channel), from the stored floats alone: one integer L for the
+    layer, per row an fp32 base[co] > 0 and per element an integer 1 <= k <= kmax with
+        fp32(base[co] * fp32(k / L)) == scale[co, ci]   bit for bit
+    -> (L, base as an fp32 CPU tensor [Co], k as an int32 CPU tensor [Co * Ci]); None when there
+    is none (a zero, negative or non-finite entry included).  L <= max_l, by default 127 for
+    kmax <= 127 and QWIDE_MAX_L beyond.  Among the solutions: the smallest L; then per row the
+    smallest k at the row's largest scale; then the smaller base.  A shifted scale stays below
+    twice its base, so the search takes k <= 2 L (without that bound every grid with exact k / L
+    would be found at L = 1 with the k of its true L, e.g. 31, 32, 33).  Per (L, k at the row's
+    maximum) the base is one of the three fp32 neighbours of max * L / k.
+
+    Host arithmetic on a CPU copy, on each row's distinct values, vectorised over rows and the
+    candidate (k, base); an L is first tried on the row with the most distinct values (eight of
+    them), which rejects nearly every L that fails."""
+    import numpy as np
+    Co, Ci = int(Co), int(Ci)
+    c = np.ascontiguousarray(scale.detach().reshape(-1).float().cpu().numpy(), dtype=np.float32)
+    if c.size == 0 or c.size != Co * Ci or not np.all(np.isfinite(c)) or not np.all(c > 0):
+        return None
+    if max_l is None:
+        max_l = COLSCALE_MAX_L if kmax <= COLSCALE_MAX_L else QWIDE_MAX_L
+    c = c.reshape(Co, Ci)
+    srt = np.sort(c, axis=1)
+    new = np.concatenate([np.ones((Co, 1), bool), srt[:, 1:] != srt[:, :-1]], axis=1)
+    U = int(new.sum(axis=1).max())
+    # v[co]: the row's distinct values, ascending, filled up with its maximum (pad)
+    slot = np.cumsum(new, axis=1) - 1
+    v = np.repeat(srt[:, -1:], U, axis=1)
+    v[np.arange(Co)[:, None], slot] = srt
+    pad = np.arange(U)[None, :] >= new.sum(axis=1)[:, None]
+    probe = int(new.sum(axis=1).argmax())
+    pv = v[probe:probe + 1, np.unique(np.linspace(0, U - 1, min(U, 8)).astype(int))]
+    ppad = np.zeros(pv.shape, bool)
+    for L in range(1, int(max_l) + 1):
+        if not _perci_try(pv, ppad, L, kmax)[0][0]:
+            continue
+        per = max(1, (1 << 21) // (min(int(kmax), 2 * L) * 3 * U))
+        base, kk, good = np.empty(Co, np.float32), np.empty((Co, U), np.int64), True
+        for r0 in range(0, Co, per):
+            found, b, k = _perci_try(v[r0:r0 + per], pad[r0:r0 + per], L, kmax)
+            if not found.all():
+                good = False
+                break
+            base[r0:r0 + per], kk[r0:r0 + per] = b, k
+        if not good:
+            continue
+        # back from the distinct values to the elements
+        idx = (c[:, :, None] == v[:, None, :]).argmax(axis=2) if U <= 16 else np.stack(
+            [np.searchsorted(v[i, :int(new[i].sum())], c[i]) for i in range(Co)])
+        k = np.take_along_axis(kk, idx, axis=1)
+        return L, torch.from_numpy(base), torch.from_numpy(k.reshape(-1).astype(np.int32))
+    return None
+
+
+def perci_plain(grid):
+    """A perci_grid result whose every k equals L: a plain per-co weight with scale = base."""
+    return grid is not None and bool((grid[2] == grid[0]).all())
+
+
+def wide_digits(m):
+    """The wide operand's two int8 digits of an integer array |m| <= QWIDE_MAX: (h, l) with
+    m = 128 h + l, l = ((m + 64) mod 128) - 64 in [-64, 63] (floor mod), h in [-127, 127]."""
+    import numpy as np
+    m = np.asarray(m, dtype=np.int64)
+    lo = np.mod(m + 64, 128) - 64
+    return (m - lo) // 128, lo
+
+
+# (grouped, factors: None | "col" | "perci") -> (the blob's byte query, the prepare entry point)
 _QPREPARE_FNS = {
-    (False, False): ("ssq_qweight_prepared_bytes", "ssq_qweight_prepare"),
-    (False, True): ("ssq_qweight_prepared_bytes", "ssq_qweight_prepare_colscale"),
-    (True, False): ("ssq_qweight_prepared_bytes_grouped", "ssq_qweight_prepare_grouped"),
-    (True, True): ("ssq_qweight_prepared_bytes_grouped", "ssq_qweight_prepare_grouped_colscale"),
+    (False, None): ("ssq_qweight_prepared_bytes", "ssq_qweight_prepare"),
+    (False, "col"): ("ssq_qweight_prepared_bytes", "ssq_qweight_prepare_colscale"),
+    (False, "perci"): ("ssq_qweight_prepared_bytes", "ssq_qweight_prepare_perci"),
+    (True, None): ("ssq_qweight_prepared_bytes_grouped", "ssq_qweight_prepare_grouped"),
+    (True, "col"): ("ssq_qweight_prepared_bytes_grouped", "ssq_qweight_prepare_grouped_colscale"),
+    (True, "perci"): ("ssq_qweight_prepared_bytes_grouped", "ssq_qweight_prepare_grouped_perci"),
 }
 
+# SSQ_QCONV_WIDE=auto|1 (qweight_prepare_scaled): auto, the wide blob only where the int8 one
+# does not hold the scaled weight; 1, every dense centred blob on it (the A/B run,
+# profiles/int_infer_wide_rate.txt, and the bit-identity test).
+QCONV_WIDE = os.environ.get("SSQ_QCONV_WIDE", "auto")
+if QCONV_WIDE not in ("auto", "1"):
+    raise ValueError(f"SSQ_QCONV_WIDE={QCONV_WIDE!r}: expected auto or 1")
 
-def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None):
+
+def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=None, wide=False):
     """Packed codes (pack_encode's layout) + zp[co] -> QPrepared.  `shape` is the weight's own
     (Co, Cig, R, S); `groups` > 1 prepares for the grouped kernels (K24).  `kcol`: the int32
     column factors k[j], j = (ci, r, s) (colscale_grid), of a column-scaled weight: the blob then
-    holds the centred operand (q - zp[co]) * k[j] (`centred`)."""
+    holds the centred operand (q - zp[co]) * k[j] (`centred`).  `kfac`: the int32 factors
+    k[co, ci] (perci_grid) of a per-(co, ci) scaled weight instead, the operand
+    (q - zp[co]) * k[co, ci].  `wide` (with either, dense only): the two-digit blob, factors and
+    |m| up to QWIDE_MAX instead of 127."""
     if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
         raise A.SSQError("qweight_prepare: packed codes must be a uint8 tensor")
     packed = _i8_dev(packed, "qweight_prepare")
@@ -1994,6 +2106,13 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None):
     groups = int(groups)
     if groups < 1 or (groups > 1 and len(shape) != 4):
         raise A.SSQError(f"qweight_prepare: groups = {groups} needs a Conv2d weight and groups >= 1")
+    if kcol is not None and kfac is not None:
+        raise A.SSQError("qweight_prepare: a column scale and a per-(co, ci) scale do not go together")
+    if wide and kcol is None and kfac is None:
+        raise A.SSQError("qweight_prepare: the wide blob holds a scaled weight (kcol or kfac)")
+    if wide and groups > 1:
+        raise A.SSQError("qweight_prepare: the wide blob is dense only: the grouped kernels (K26) "
+                         "read int8 operands")
     prep = QPrepared(None, shape, torch.zeros(1, dtype=torch.int32, device=packed.device), groups)
     Co, Ci, R, S = prep.geometry()
     if packed.numel() < query("ssq_pack_bytes", Co * Ci * R * S, n_bits):
@@ -2001,22 +2120,48 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None):
     z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
     if z.numel() != Co:
         raise A.SSQError("qweight_prepare: zero point must have one entry per output channel")
-    extra = ()
-    if kcol is not None:
-        kc = torch.as_tensor(kcol).detach().reshape(-1)
-        if kc.dtype.is_floating_point or kc.numel() != Ci * R * S:
-            raise A.SSQError("qweight_prepare: kcol must hold one integer per (ci, r, s) column")
-        if int(kc.min()) < 1 or int(kc.max()) > COLSCALE_MAX_L:
-            raise A.SSQError(f"qweight_prepare: kcol must lie in [1, {COLSCALE_MAX_L}]")
+    extra, factors = (), None
+    if kcol is not None or kfac is not None:
+        factors, name, want = (("col", "kcol", Ci * R * S) if kfac is None else ("perci", "kfac", Co * Ci))
+        kc = torch.as_tensor(kcol if kfac is None else kfac).detach().reshape(-1)
+        lim = QWIDE_MAX if wide else COLSCALE_MAX_L
+        if kc.dtype.is_floating_point or kc.numel() != want:
+            raise A.SSQError(f"qweight_prepare: {name} must hold one integer per " +
+                             ("(ci, r, s) column" if kfac is None else "(co, ci)"))
+        if int(kc.min()) < 1 or int(kc.max()) > lim:
+            raise A.SSQError(f"qweight_prepare: {name} must lie in [1, {lim}]")
         kc = kc.to(device=packed.device, dtype=torch.int32).contiguous()
-        prep.centred = True
+        prep.centred, prep.wide = True, bool(wide)
         extra = (_vp(kc),)
     geo = (Co, Ci, R, S) + ((groups,) if groups > 1 else ())
-    size_fn, prepare_fn = _QPREPARE_FNS[groups > 1, kcol is not None]
+    if wide:
+        size_fn, prepare_fn = "ssq_qweight_prepared_bytes_wide", "ssq_qweight_prepare_wide"
+        extra += (int(kfac is not None),)
+    else:
+        size_fn, prepare_fn = _QPREPARE_FNS[groups > 1, factors]
     prep.blob = torch.empty(max(query(size_fn, *geo), 1), dtype=torch.uint8, device=packed.device)
     call(prepare_fn, _vp(packed), zpp, *extra, *geo, int(n_bits), int(qmin), _vp(prep.blob),
          _vp(prep.bad), stream_of(packed))
     return prep
+
+
+def qweight_prepare_scaled(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=None,
+                           wide=False):
+    """qweight_prepare for a scaled weight whose operand may leave int8: the int8 blob where it
+    holds the weight (every factor <= 127 and `bad` zero, one device word read), else, with
+    `wide` and a dense weight, the wide blob; elsewhere the int8 blob with its `bad` set (no
+    factor above 127 reaches it: None then).  SSQ_QCONV_WIDE=1: with `wide`, every dense scaled
+    weight takes the wide blob."""
+    k = torch.as_tensor(kcol if kfac is None else kfac)
+    dense = int(groups) == 1
+    fits = int(k.max()) <= COLSCALE_MAX_L
+    if not (wide and dense and (QCONV_WIDE == "1" or not fits)):
+        if not fits:
+            return None
+        prep = qweight_prepare(packed, shape, zp, n_bits, qmin, groups, kcol, kfac)
+        if not (wide and dense and int(prep.bad.item())):
+            return prep
+    return qweight_prepare(packed, shape, zp, n_bits, qmin, groups, kcol, kfac, wide=True)
 
 
 QCONV_KINDS = {1: "depthwise", 2: "grouped"}
@@ -2029,6 +2174,11 @@ QCONV_CENTRED = os.environ.get("SSQ_QCONV_CENTRED", "1") != "0"
 
 def _qconv_fn(prepared, groups, form):
     """The entry point of `form` ("fwd" | "codes_fwd" | "codes_res_fwd") for a prepared weight."""
+    if getattr(prepared, "wide", False):
+        if int(groups) > 1:
+            raise A.SSQError("qconv: a wide blob is dense only: the grouped kernels (K26) read int8 "
+                             "operands")
+        return f"ssq_qconv_i8_wide_{form}"
     if int(groups) > 1:
         return f"ssq_qconv_i8_grouped_{form}"
     if QCONV_CENTRED and getattr(prepared, "centred", False):
@@ -2102,6 +2252,9 @@ def _qconv_split(name, prepared, groups, form, splits, workspace, codes, stride,
     reaches it with no workspace, so the refusal and its message are the entry point's."""
     if int(groups) > 1:
         raise A.SSQError(f"{name}: splits need a dense weight (groups == 1), got groups = {groups}")
+    if getattr(prepared, "wide", False):
+        raise A.SSQError(f"{name}: a wide blob has no split-K form (the partial kernel holds one "
+                         "int32 accumulator set)")
     centred = QCONV_CENTRED and getattr(prepared, "centred", False)
     fn = f"ssq_qconv_i8_{'centred_' if centred else ''}splitk_{form}"
     if workspace is None:
@@ -2398,6 +2551,9 @@ def qlinear_pooled(hi, lo, sp, prepared, scale_h, HW, act_zp=0.0, act_bits=8, ac
     hi, lo, sp = (_i8_dev(t, "qlinear_pooled") for t in (hi, lo, sp))
     if len(prepared.shape) != 2 or getattr(prepared, "groups", 1) != 1:
         raise A.SSQError("qlinear_pooled: the weight must be a prepared Linear")
+    if getattr(prepared, "wide", False):
+        raise A.SSQError("qlinear_pooled: a wide blob is not K30's operand (the pooled-operand fc "
+                         "reads one int8 weight plane)")
     Co, Ci, _, _ = prepared.geometry()
     Cp = query("ssq_qinfer_cpad", Ci)
     if hi.dim() != 2 or hi.shape[1] != Cp or tuple(lo.shape) != tuple(hi.shape):

@@ -8,7 +8,10 @@ the plan (an IntPlan per layer); it holds the act quantizers' values as of that 
 re-enable after changing them.  `grouped=True` plans grouped and depthwise convs too (K24-K26);
 `colscale=True` plans column-scaled weights (ChannelQuantMSE) whose column scale lies on an
 integer grid k[j] / L, L <= 127 (K.colscale_grid), with the centred integer (q - z) * k[j] as the
-int8 operand.
+int8 operand.  `per_ci=True` plans weights whose scale is per (co, ci) on a grid base[co] * k / L
+(ChannelQuant's shifted scale; K.perci_grid) the same way, with (q - z) * k[co, ci] as the operand,
+and `wide=True` lets either kind of scaled weight whose operand leaves int8 run as two int8
+digits (|m| <= 16319) on K23's wide forms.
 
 The carry flags keep a tensor between integer layers as int8 codes.  Each such tensor is one
 Edge: an emitting layer whose kernel applies the epilogue and the act quantizer and stores the
@@ -413,15 +416,16 @@ def _input_reason(q):
     return K.ActQuant(delta, zp, q.n_bits, q.sym), None
 
 
-def _weight_codes(m, colscale=False):
+def _weight_codes(m, colscale=False, per_ci=False):
     """(packed codes, fields) of the module's hard weight: a restored model's PackedWeight as
     stored, a live quantizer through dequant_form + pack_encode (soft state is refused there).
-    A column-scaled weight is encoded only with `colscale` (its caller refuses it otherwise)."""
+    A column-scaled weight is encoded only with `colscale`, one scaled per (co, ci) only with
+    `per_ci` (the caller refuses them otherwise)."""
     q = m.weight_quantizer
     if isinstance(q, PackedWeight):
         return q.packed, q.fields()
     what, f = dequant_form(m)
-    if f["per_ci"] or (f["col_scale"] is not None and not colscale):
+    if (f["per_ci"] and not per_ci) or (f["col_scale"] is not None and not colscale):
         return None, f
     packed, bad = K.pack_encode(what, f["zero_point"], f["scale"], f["per_ci"], f["col_scale"],
                                 f["n_bits"], f["qmin"], f["qmax"])
@@ -433,7 +437,8 @@ def _weight_codes(m, colscale=False):
 
 @torch.no_grad()
 def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
-                             carry_stem=False, carry_head=False, colscale=False, splitk=False):
+                             carry_stem=False, carry_head=False, colscale=False, splitk=False,
+                             per_ci=False, wide=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
@@ -450,7 +455,15 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     the int8 operand; off, they are reported as refused.  An all-ones column scale is
     a plain weight and takes the plain route.  `splitk`: a dense layer asks the host rule
     K.qconv_splits on every forward and takes K23's split-K form where it returns Z > 1
-    (bit-identical; `split_report`); off, no layer does."""
+    (bit-identical; `split_report`); off, no layer does.  `per_ci`: also plan weights whose scale
+    is per (co, ci) (ChannelQuant's shifted scale) and lies on a grid base[co] * k / L
+    (K.perci_grid), with (q - z) * k[co, ci] as the operand and
+    scale[co] = fp32(fp32(delta_a * base[co]) / fp32(L)); off, they are reported as refused.  Every
+    k equal to L is a plain weight.  `wide`: a scaled weight of either kind whose operand leaves
+    int8 (|m| > 127, or a grid beyond 127) runs as two int8 digits, |m| <= 16319, L <= 1024, on
+    K23's wide forms (dense layers only: never split along K, not the grouped kernels, not the
+    pooled-operand fc); off, it is refused as leaving int8.  A weight with both a column scale and
+    a per-(co, ci) scale is refused."""
     carry_stem = carry_stem or carry_head
     carry_blocks = carry_blocks or carry_stem
     carry = carry or carry_blocks
@@ -506,42 +519,78 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
             report[name] = "weight is not on the HIP device"
             continue
         try:
-            packed, f = _weight_codes(m, colscale)
+            packed, f = _weight_codes(m, colscale, per_ci)
         except TypeError as e:
             report[name] = str(e)
             continue
-        if f["per_ci"]:
+        if f["per_ci"] and not per_ci:
             report[name] = f"weight scale is per (co, ci) ({f['kind']})"
             continue
-        kcol, L = None, 1
-        if f["col_scale"] is not None:
+        if f["per_ci"] and f["col_scale"] is not None:
+            report[name] = f"weight has both a column scale and a per-(co, ci) scale ({f['kind']})"
+            continue
+        kcol, kfac, L, d1 = None, None, 1, f["scale"]
+        max_l = K.QWIDE_MAX_L if wide else K.COLSCALE_MAX_L
+        if f["per_ci"]:
+            Co, Cig = int(m.weight.shape[0]), int(m.weight.shape[1])
+            grid = K.perci_grid(f["scale"], Co, Cig)
+            if grid is None and wide:
+                grid = K.perci_grid(f["scale"], Co, Cig, K.QWIDE_MAX)
+            if grid is None:
+                report[name] = (f"weight scale is per (co, ci) ({f['kind']}) and not on an integer "
+                                f"grid base[co] * k / L, L <= {max_l}")
+                continue
+            L, d1, kfac = grid
+            d1 = d1.to(dev)
+            if K.perci_plain(grid):
+                kfac, L = None, 1               # every k = L: a plain weight with scale = base
+        elif f["col_scale"] is not None:
             grid = K.colscale_grid(f["col_scale"]) if colscale else None
+            if grid is None and colscale and wide:
+                grid = K.colscale_grid(f["col_scale"], K.QWIDE_MAX_L, K.QWIDE_MAX)
             if grid is None:
                 report[name] = f"weight has a column scale ({f['kind']})" + (
-                    f" that is not on an integer grid k / L, L <= {K.COLSCALE_MAX_L}" if colscale else "")
+                    f" that is not on an integer grid k / L, L <= {max_l}" if colscale else "")
                 continue
             L, kcol = grid
             if L == 1 and int(kcol.max()) == 1:
                 kcol = None                     # all ones: a plain weight, the plain K22 blob
-            elif m in head_fc:
-                report[name] = (f"weight has a column scale ({f['kind']}): the pooled-operand fc "
-                                "takes plain weights only")
-                continue
-        prep = K.qweight_prepare(packed, tuple(m.weight.shape), f["zero_point"], f["n_bits"],
-                                 f["qmin"], groups=groups, kcol=kcol)
+        scaled = kcol is not None or kfac is not None
+        if scaled and m in head_fc:
+            report[name] = ((f"weight has a column scale ({f['kind']})" if kcol is not None else
+                             f"weight scale is per (co, ci) ({f['kind']})")
+                            + ": the pooled-operand fc takes plain weights only")
+            continue
+        if not scaled:
+            prep = K.qweight_prepare(packed, tuple(m.weight.shape), f["zero_point"], f["n_bits"],
+                                     f["qmin"], groups=groups)
+        else:
+            prep = K.qweight_prepare_scaled(packed, tuple(m.weight.shape), f["zero_point"],
+                                            f["n_bits"], f["qmin"], groups=groups, kcol=kcol,
+                                            kfac=kfac, wide=wide)
+        if prep is None:
+            report[name] = ("scaled weight's grid leaves int8 (k > 127): the wide operand is dense "
+                            "only, the grouped kernels (K26) read int8")
+            continue
         if int(prep.bad.item()):
-            report[name] = ("weight zero point is not an integer code" if kcol is None else
+            report[name] = ("weight zero point is not an integer code" if not scaled else
+                            "scaled weight (q - z) * k leaves the wide operand (|m| > 16319), or a "
+                            "zero point is not an integer code" if prep.wide else
                             "scaled weight (q - z) * k leaves int8 (|m| > 127), or a zero point "
                             "is not an integer code")
+            if scaled and wide and groups != 1:
+                report[name] += "; the wide operand is dense only, the grouped kernels (K26) read int8"
             continue
-        # s[co] = fp32(delta_a * d1[co]): one fp32 product of the two stored fp32 values
+        # s[co] = fp32(delta_a * d1[co]): one fp32 product of the two stored fp32 values (per
+        # (co, ci): of delta_a and the grid's base[co])
         scale = (torch.full((1,), act.delta, dtype=torch.float32, device=dev)
-                 * f["scale"].detach().reshape(-1).float()).contiguous()
-        if kcol is not None:
-            # ... / fp32(L): the column grid's common denominator, one more rounding
+                 * d1.detach().reshape(-1).float()).contiguous()
+        if scaled:
+            # ... / fp32(L): the grid's common denominator, one more rounding
             scale = (scale / torch.full((1,), float(L), dtype=torch.float32, device=dev)).contiguous()
         m._int_plan = IntPlan(prep, scale, act, stride, padding, counter)
-        m._int_plan.splitk = bool(splitk) and m._int_plan.kind == "dense"
+        # a wide layer is never asked to split: K23's split form holds one accumulator set
+        m._int_plan.splitk = bool(splitk) and m._int_plan.kind == "dense" and not prep.wide
         report[name] = INT8
     if carry:
         _plan_carry(qnn, source)
