@@ -465,6 +465,15 @@ int ssq_epilogue_fwd(const float* y, const float* bias, const float* gamma, cons
  * per-channel / quantizer sums are produced).  Per-(n, c) partials in ws
  * (ssq_epilogue_bwd_workspace_size(N*C)), reduced in a fixed order.                     */
 size_t ssq_epilogue_bwd_workspace_size(int64_t rows);
+/* The form the K13 forward runs for n elements in planes of hw (aligned: every tensor pointer
+ * is 16-B aligned; rows: y or res is read through a row map): 0 scalar, 1 float4s with a
+ * channel lookup per element, 2 float4s that never straddle a plane (hw % 4 == 0).        */
+int ssq_epilogue_fwd_form(int64_t n, int64_t hw, int aligned, int rows);
+/* The form the K13 backward (and its fused tail: loss) runs for rows of hw elements: returns
+ * 16 (4 rows per wave, 16 lanes per row), 4 (4 rows per wave, a lane per element: the A/B
+ * form) or 1 (a row per wave), and in *vec (may be NULL) whether the rows are read as
+ * float4s.  quant: an act quantizer; res2: the residual's own epilogue is folded in.      */
+int ssq_epilogue_bwd_form(int64_t hw, int aligned, int quant, int res2, int loss, int* vec);
 int ssq_epilogue_bwd(const float* g, const float* y, const float* bias, const float* gamma,
                      const float* phi, const float* res, int64_t N, int64_t C, int64_t hw,
                      int relu, const float* delta, const float* zp, int qmin, int qmax, float* gy,

@@ -428,13 +428,14 @@ def inpscale_fwd(w, inp, delta, raw_zp, n_bits):
 
 
 # ----------------------------------------------------------------- K11 / K12  losses
-def lp_loss(pred, tgt, p=2.0, reduction="none"):
-    """quant_layer.py:25-32 (+ its autograd wrt pred).  Returns (loss float64, grad fp32)."""
+def lp_loss(pred, tgt, p=2.0, reduction="none", M=None):
+    """quant_layer.py:25-32 (+ its autograd wrt pred).  Returns (loss float64, grad fp32).
+    M: the 'none' reduction's divisor when the caller states it (the fused tail's argument)."""
     pred, tgt = _f(pred), _f(tgt)
     d = (pred - tgt).astype(F32)
     a = np.abs(d).astype(np.float64)
     if reduction == "none":
-        M = d.size // d.shape[1]
+        M = d.size // d.shape[1] if M is None else int(M)
         loss = (a ** p).sum() / M
     else:
         M = d.size
@@ -492,6 +493,157 @@ def linear_temp_decay(t, t_max, rel_start_decay=0.2, start_b=20, end_b=2, guard_
     else:
         rel_t = (t - start_decay) / (t_max - start_decay)
     return end_b + (start_b - end_b) * max(0.0, (1 - rel_t))
+
+
+# ----------------------------------------------------------------- K13 epilogue
+# QuantModule.forward after the conv (quant_layer.py:250-272): the conv's bias add (:250), the
+# --bias_cal affine out * alpha_out + beta_out (:259), the activation (:267), the act
+# quantizer (:271); a block's tail adds the residual before the activation and quantizes
+# after it (quant_block.py:105-109, 161-165, 197-201, 234-238).
+def _chan(v):
+    return _f(v).reshape(1, -1, 1, 1)
+
+
+def _act(t, relu):
+    """Activation code 0 / 1 (ReLU) / 2 (ReLU6) as torch.clamp: -0.0 and NaN are kept."""
+    if relu >= 1:
+        t = np.where(t < 0, F32(0), t)
+    if relu == 2:
+        t = np.where(t > 6, F32(6), t)
+    return t.astype(F32)
+
+
+def _act_blocks(t, relu):
+    """Where the activation's backward passes nothing: threshold_backward (out <= 0) for ReLU,
+    hardtanh_backward (out <= 0 or out >= 6) for ReLU6; a NaN output passes its gradient."""
+    if relu == 1:
+        return t <= 0
+    if relu == 2:
+        return (t <= 0) | (t >= 6)
+    return np.zeros(t.shape, bool)
+
+
+def _epi_affine(y, bias, gamma, phi):
+    """(y + bias[c], (y + bias[c]) * gamma[c] + phi[c]): one fp32 rounding per operation."""
+    pre = (y + _chan(bias)).astype(F32) if bias is not None else y
+    t = ((pre * _chan(gamma)).astype(F32) + _chan(phi)).astype(F32) if gamma is not None else pre
+    return pre, t
+
+
+def _res_epi(res, res_epi):
+    """The residual branch's own epilogue (bias, gamma / phi, no activation): (its
+    pre-affine value, its output)."""
+    if res_epi is None:
+        return res, res
+    rb, rg, rp = res_epi
+    return _epi_affine(res, rb, rg, rp)
+
+
+def epilogue_fwd(y, bias, gamma, phi, res, relu, delta=None, zp=None, n_bits=8, sym=False,
+                 res_epi=None):
+    """The K13 epilogue: act(((y + bias[c]) * gamma[c] + phi[c]) + res) then the per-tensor
+    act fake-quant (delta None: none).  y, res: [N, C, H, W]; bias / gamma / phi: [C] or None.
+    Returns (pre_quant, out)."""
+    y = _f(y)
+    with np.errstate(all="ignore"):
+        _, t = _epi_affine(y, bias, gamma, phi)
+        if res is not None:
+            t = (t + _res_epi(_f(res), res_epi)[1]).astype(F32)
+        t = _act(t, int(relu))
+        out = t if delta is None else fake_quant(t, delta, zp, n_bits, sym)[0]
+    return t, out
+
+
+def _fsum(a):
+    """The correctly rounded float64 sum of a (its own value when something is not finite)."""
+    import math
+    a = np.asarray(a, np.float64).reshape(-1)
+    return math.fsum(a) if np.all(np.isfinite(a)) else float(np.sum(a))
+
+
+def _chan_sums(terms):
+    """Per-channel sums of [N, C, H, W] float64 terms and of their absolute values."""
+    C = terms.shape[1]
+    rows = terms.transpose(1, 0, 2, 3).reshape(C, -1)
+    return (np.array([_fsum(r) for r in rows]), np.array([_fsum(np.abs(r)) for r in rows]))
+
+
+def _epilogue_bwd(g, t, pre, gamma, relu, delta, zp, n_bits, sym, prer=None, rgamma=None):
+    """The backward from g = dL/d(output) given the forward's values (t: the activation's
+    output, pre: y + bias[c], prer: the residual epilogue's pre-affine value or None)."""
+    f64 = np.float64
+    r = {"n_chan": g.size // g.shape[1], "n_all": g.size}
+    with np.errstate(all="ignore"):
+        if delta is not None:
+            d, z = F32(delta), F32(zp)
+            lo, hi = qrange(n_bits, sym)
+            gx = fake_quant_bwd(t, d, z, n_bits, sym, g)[0]        # the STE gradient
+            # the four sums of fake_quant_bwd's gdelta / gzp, term by term
+            tq = (t / d).astype(F32)
+            x_int = round_ste_fwd(tq) + z
+            m = (x_int >= lo) & (x_int <= hi)
+            xq = np.clip(x_int, F32(lo), F32(hi))
+            gq = (g * d).astype(F32)
+            gi = np.where(m, gq, F32(0))
+            a0 = g.astype(f64) * (xq - z).astype(F32).astype(f64)
+            a1 = gi.astype(f64) * (tq / d).astype(F32).astype(f64)
+            r["gdelta"] = _fsum(np.concatenate([a0.reshape(-1), -a1.reshape(-1)]))
+            r["gdelta_abs"] = _fsum(np.abs(a0)) + _fsum(np.abs(a1))
+            r["gzp"] = _fsum(np.concatenate([gi.astype(f64).reshape(-1), -gq.astype(f64).reshape(-1)]))
+            r["gzp_abs"] = _fsum(np.abs(gi.astype(f64))) + _fsum(np.abs(gq.astype(f64)))
+            r["in_range"] = m
+        else:
+            gx = g
+        g_t = np.where(_act_blocks(t, int(relu)), F32(0), gx).astype(F32)
+        r["g_t"] = g_t
+        r["gy"] = (g_t * _chan(gamma)).astype(F32) if gamma is not None else g_t
+        r["gres"] = (g_t * _chan(rgamma)).astype(F32) if rgamma is not None else g_t
+        r["ggamma"], r["ggamma_abs"] = _chan_sums(g_t.astype(f64) * pre.astype(f64))
+        r["gphi"], r["gphi_abs"] = _chan_sums(g_t.astype(f64))
+        if prer is not None:
+            r["gres_gamma"], r["gres_gamma_abs"] = _chan_sums(g_t.astype(f64) * prer.astype(f64))
+            r["gres_phi"], r["gres_phi_abs"] = r["gphi"], r["gphi_abs"]
+    return r
+
+
+def epilogue_bwd(g, y, bias, gamma, phi, res, relu, delta=None, zp=None, n_bits=8, sym=False):
+    """Autograd of epilogue_fwd from g = dL/d(out).  g_t = dL/d(pre-activation): the act
+    quantizer's STE (fake_quant_bwd), then the activation's mask on its output.  Returns a
+    dict: gy = g_t * gamma[c], gres = g_t (fp32, elementwise); ggamma[c] = sum g_t * (y +
+    bias[c]), gphi[c] = sum g_t, gdelta, gzp (correctly rounded float64 sums of exact
+    products of fp32 values), for each sum NAME also NAME_abs, the sum of its absolute terms
+    (gdelta / gzp: of both sums they subtract), and n_chan / n_all, the term counts of a
+    channel sum and of a whole-tensor sum."""
+    y, g = _f(y), _f(g)
+    with np.errstate(all="ignore"):
+        pre, _ = _epi_affine(y, bias, gamma, phi)
+    t, _ = epilogue_fwd(y, bias, gamma, phi, res, relu)
+    return _epilogue_bwd(g, t, pre, gamma, relu, delta, zp, n_bits, sym)
+
+
+def epilogue_loss_bwd(tgt_rows, p, M, y, bias, gamma, phi, res, relu, delta=None, zp=None,
+                      n_bits=8, sym=False, res_epi=None, g=None):
+    """The block tail with its loss: out = epilogue_fwd(...), loss = lp_loss(out, tgt_rows, p)
+    over M, and epilogue_bwd of the loss gradient.  res_epi = (bias, gamma, phi) (each [C] or
+    None; gamma and phi together): res is a downsample conv's raw output and its epilogue
+    (no activation, no quantizer) is applied first; gres is then the gradient of that raw
+    output and gres_gamma / gres_phi its gamma / phi sums.  g (fp32, out's shape): the loss
+    gradient taken as given instead of lp_loss's -- a general power p goes through pow, whose
+    fp32 evaluations differ in their last bits, and everything after the loss gradient is
+    exact again once the gradient itself is fixed.  Returns epilogue_bwd's dict plus loss
+    (float64), out and g (the loss gradient used)."""
+    y = _f(y)
+    res = None if res is None else _f(res)
+    with np.errstate(all="ignore"):
+        pre, _ = _epi_affine(y, bias, gamma, phi)
+        prer = None if res_epi is None else _res_epi(res, res_epi)[0]
+    t, out = epilogue_fwd(y, bias, gamma, phi, res, relu, delta, zp, n_bits, sym, res_epi)
+    loss, g_lp = lp_loss(out, tgt_rows, p, "none", M)
+    g = g_lp if g is None else _f(g).reshape(out.shape)
+    r = _epilogue_bwd(g, t, pre, gamma, relu, delta, zp, n_bits, sym, prer,
+                      None if res_epi is None else res_epi[1])
+    r.update(loss=loss, out=out, g=g)
+    return r
 
 
 # ----------------------------------------------------------------- K14 gather

@@ -95,6 +95,8 @@ SIGNATURES = {
     "ssq_epilogue_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _p, _p, _i, _i,
                               _p]),
     "ssq_epilogue_bwd_workspace_size": (_sz, [_i64]),
+    "ssq_epilogue_fwd_form": (_i, [_i64, _i64, _i, _i]),
+    "ssq_epilogue_bwd_form": (_i, [_i64, _i, _i, _i, _i, _p]),
     "ssq_epilogue_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i, _p, _p, _i, _i, _p,
                               _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ssq_epilogue_loss_bwd": (_i, [_p, _p, _i64, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64,

@@ -997,6 +997,48 @@ static int epi_multi_row() {
   return mode;
 }
 
+// The K13 forward's form for n elements in planes of hw (aligned: every tensor pointer is
+// 16-B aligned; rows: y or res is read through a row map).  0: scalar; 1: float4s that may
+// straddle (n, c) planes, a channel lookup per element; 2: float4s that never straddle a
+// plane (hw % 4 == 0), one lookup per float4 (SSQ_K13_PLANE4=0: form 1 instead, for A/B).
+static int epilogue_fwd_form(int64_t n, int64_t hw, bool aligned, bool rows) {
+  static const bool kPlane4 = !getenv("SSQ_K13_PLANE4") || atoi(getenv("SSQ_K13_PLANE4")) != 0;
+  const int vec = n % 4 == 0 && aligned && (!rows || hw % 4 == 0);
+  return (vec && hw % 4 == 0 && kPlane4) ? 2 : vec;
+}
+
+extern "C" int ssq_epilogue_fwd_form(int64_t n, int64_t hw, int aligned, int rows) {
+  return epilogue_fwd_form(n, hw, aligned != 0, rows != 0);
+}
+
+// The K13 backward's form for rows of hw elements (aligned: hw % 4 == 0 is not enough for
+// float4 rows, every tensor pointer must be 16-B aligned too; quant: the act quantizer's four
+// extra sums; res2: the residual's own epilogue folded in; loss: the fused tail).
+//   rpw kG16: rows of <= 64 elements or float4s, 4 rows per wave, 16 lanes each (every
+//             variant, the same form for the plain backward and the fused tail);
+//   rpw 4:    SSQ_EPI_G16=0 for A/B: 4 rows per wave with a lane per element, where the
+//             registers allow (no act quantizer, no residual epilogue; the fused tail only
+//             with SSQ_EPI_MULTI_ROW=2, never with SSQ_EPI_MULTI_ROW=0);
+//   rpw 1:    a row per wave, any length.
+struct EpiBwdForm {
+  bool vec;
+  int rpw;
+};
+static EpiBwdForm epilogue_bwd_form(int64_t hw, bool aligned, bool quant, bool res2, bool loss) {
+  const bool vec = hw % 4 == 0 && aligned;
+  const bool small = (vec ? hw / 4 : hw) <= kWave;
+  if (small && epi_g16()) return {vec, kG16};
+  const bool multi = small && !quant && !res2 && epi_multi_row() >= (loss ? 2 : 1);
+  return {vec, multi ? 4 : 1};
+}
+
+extern "C" int ssq_epilogue_bwd_form(int64_t hw, int aligned, int quant, int res2, int loss,
+                                     int* vec) {
+  const EpiBwdForm f = epilogue_bwd_form(hw, aligned != 0, quant != 0, res2 != 0, loss != 0);
+  if (vec) *vec = f.vec;
+  return f.rpw;
+}
+
 static int bias_act(const char* what, const float* y, const float* bias, const float* res,
                     float* out, float* yq, int64_t n, int64_t hw, int64_t C, int relu,
                     const float* qdelta, const float* qzp, int qmin, int qmax, hipStream_t s,
@@ -1017,12 +1059,8 @@ static int bias_act(const char* what, const float* y, const float* bias, const f
   SSQ_REQUIRE(!rrows || res, SSQ_E_ARG, "%s: res_rows without res", what);
   SSQ_REQUIRE(!stage_dst || (stage_src && stage_n > 0 && stage_n <= 4096), SSQ_E_ARG,
               "%s: staging needs a source and 1..4096 words", what);
-  // vec 2: float4s that never straddle an (n, c) plane (SSQ_K13_PLANE4=0: the per-element
-  // channel form, for A/B)
-  static const bool kPlane4 = !getenv("SSQ_K13_PLANE4") || atoi(getenv("SSQ_K13_PLANE4")) != 0;
-  int vec = n % 4 == 0 && al(y) && (!out || al(out)) && (!res || al(res)) &&
-            (!yq || al(yq)) && ((!yrows && !rrows) || hw % 4 == 0);
-  if (vec && hw % 4 == 0 && kPlane4) vec = 2;
+  const int vec = epilogue_fwd_form(
+      n, hw, al(y) && (!out || al(out)) && (!res || al(res)) && (!yq || al(yq)), yrows || rrows);
   const FastDiv dh = make_fastdiv((uint32_t)hw), dc = make_fastdiv((uint32_t)C);
   const dim3 grid(grid_for(vec ? n / 4 : n, kBlock, 2048));
   const float lo = (float)qmin, hi = (float)qmax;
@@ -1122,19 +1160,12 @@ static int epilogue_bwd(const char* what, const float* g, const float* y, const 
   SSQ_REQUIRE(ws && ws_bytes >= ssq_epilogue_bwd_workspace_size(rows), SSQ_E_WS,
               "%s: workspace too small", what);
   auto al = [](const void* q) { return ((uintptr_t)q & 15u) == 0; };
-  const bool vec = hw % 4 == 0 && al(g) && al(y) && (!gy || al(gy)) && (!res || al(res)) &&
-                   (!gres || al(gres));
   SSQ_REQUIRE(relu >= 0 && relu <= 2, SSQ_E_ARG, "%s: activation code %d", what, relu);
-  // small planes (<= 64 elements or float4s per row): 4 rows per wave (same bits); not with
-  // the act quantizer's four extra sums per row (3-4 waves per SIMD instead of 7-8)
-  // rows of <= 64 elements or float4s: 4 rows per wave, 16 lanes each (kG16; every variant,
-  // the same form for the plain backward and the fused tail); SSQ_EPI_G16=0 for A/B: the r4
-  // forms (4 rows per wave with a lane per element where the registers allow, else a row
-  // per wave)
-  const bool small = (vec ? hw / 4 : hw) <= kWave;
-  const bool g16 = small && epi_g16();
-  const bool multi = !g16 && small && !delta && !res2 && epi_multi_row() >= (loss ? 2 : 1);
-  const int64_t rpw = (g16 || multi) ? 4 : 1;
+  const EpiBwdForm form = epilogue_bwd_form(
+      hw, al(g) && al(y) && (!gy || al(gy)) && (!res || al(res)) && (!gres || al(gres)),
+      delta != nullptr, res2, loss);
+  const bool vec = form.vec, g16 = form.rpw == kG16, multi = form.rpw == 4;
+  const int64_t rpw = (g16 || multi) ? 4 : 1;     // rows per wave (kG16: 4 rows of 16 lanes)
   const int64_t waves = (rows + rpw - 1) / rpw;
   const uint32_t nmain = (uint32_t)((waves + kBlock / kWave - 1) / (kBlock / kWave));
   int frc = SSQ_OK;

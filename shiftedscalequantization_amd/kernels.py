@@ -1645,6 +1645,21 @@ def epilogue(y, bias, gamma, phi, res, relu, q=None, lazy=False):
                             q.sym)
 
 
+def epilogue_fwd_form(n, hw, aligned=True, rows=False):
+    """The K13 forward's form for n elements in planes of hw (ssq_epilogue_fwd_form): 0 scalar,
+    1 float4s with a channel lookup per element, 2 float4s inside one plane."""
+    return int(query("ssq_epilogue_fwd_form", int(n), int(hw), int(bool(aligned)), int(bool(rows))))
+
+
+def epilogue_bwd_form(hw, aligned=True, quant=False, res2=False, loss=False):
+    """The K13 backward's form for rows of hw elements (ssq_epilogue_bwd_form): (rows per wave
+    -- 16: 4 rows of 16 lanes, 4: the A/B register form, 1: a row per wave --, float4 rows)."""
+    vec = C.c_int(0)
+    rpw = query("ssq_epilogue_bwd_form", int(hw), int(bool(aligned)), int(bool(quant)),
+                int(bool(res2)), int(bool(loss)), C.byref(vec))
+    return int(rpw), bool(vec.value)
+
+
 def epilogue_loss_bwd(tail, tgt, M, p=2.0):
     """The fused tail (ssq_epilogue_loss_bwd): for a lazy epilogue placeholder's inputs and a
     Rows target, the lp_loss value at power p (1-element device tensor, mean over M) and the
