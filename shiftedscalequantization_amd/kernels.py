@@ -1143,14 +1143,7 @@ class BiasActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, bias, res, relu):
-        y, yp, bp, rp, C, hw, _, (yi, ri), stg = _epilogue_layout(y, bias, res, rows=True,
-                                                                 stage=True)
-        out = torch.empty_like(y)
-        if yi is not None or ri is not None:
-            call("ssq_epilogue_fwd_rows", yp, yi, bp, None, None, rp, ri, _vp(out), None,
-                 y.numel(), hw, C, int(relu), None, None, 0, 1, *stg, stream_of(y))
-        else:
-            call("ssq_bias_act", yp, bp, rp, _vp(out), y.numel(), hw, C, int(relu), stream_of(y))
+        _, out, _, _ = _k13_forward("bias_act", y, bias, None, None, res, relu)
         ctx.relu = int(relu)
         if relu:
             ctx.save_for_backward(out)
@@ -1169,22 +1162,65 @@ class BiasActFn(torch.autograd.Function):
         return gin, None, (gin if ctx.needs_input_grad[2] else None), None
 
 
-class LazyRes:
-    """A block's downsample branch whose epilogue is deferred to the block's fused tail: the
-    downsample conv's raw output y and its epilogue's inputs (bias, gamma^z / phi^z, no
-    activation, no act quantizer).  The tail's pass applies that epilogue itself
-    (ssq_epilogue_loss_bwd's res_* arguments) and returns dL/dy; anywhere else the residual is
-    materialised with exactly the ops QuantModule.forward runs for it."""
+def k13(y, bias, gamma, phi, res, relu, q, nonaffine_q, lazy):
+    """act(((y + bias) * gamma + phi) + res) [-> q], the K13 epilogue: the one place that picks
+    the wrapper that runs it.  q is a fusable act quantizer (quant_layer.fusable_act_quantizer)
+    or None -- one that is on but not fusable runs as a module after this, at the caller.
 
-    def __init__(self, y, bias, gamma, phi):
-        self.y, self.bias, self.gamma, self.phi = y, bias, gamma, phi
+        gamma   q     nonaffine_q   bias / relu / res    runs
+        set     any   any           any                  epilogue
+        None    set   on            any                  epilogue (gamma = phi = None)
+        None    set   off           any                  bias_act_quant
+        None    None  any           one of them set      bias_act
+        None    None  any           none                 materialize(y): y as it is, a row
+                                                         view gathered into the batch
+
+    lazy (the block tail the recon loop fuses, TAIL_LAZY) goes to epilogue / bias_act, which
+    hand back the placeholder (_lazy_tail) where the fused tail takes the case and run
+    otherwise; bias_act_quant has no lazy form, so a lazy caller passes nonaffine_q=True.
+
+    Forward: one kernel body (csrc/recon.hip bias_act) whichever wrapper runs, so bias_act =
+    epilogue(gamma = q = None) and bias_act_quant = epilogue(gamma = None, q) bit for bit.
+    Backward: a kernel per wrapper.  The first pair is element-wise on both sides
+    (ssq_relu_bwd masks with the saved output, ssq_epilogue_bwd with the recomputed one).  The
+    second pair sums the act delta / zero-point gradient in different orders -- bias_act_quant
+    over the whole tensor, finalised in a launch of its own (ssq_fq_relu_bwd); epilogue per
+    (n, c) row, finalised in the next launch's task list, as the fused tail does -- so there
+    the two agree to rounding only, and the fused tail is bit-identical to the epilogue form
+    and no other.  Hence nonaffine_q: quant_layer.EPI_NONAFFINE_Q at a QuantModule (an A/B
+    knob), always on at a block tail."""
+    if gamma is not None or (q is not None and nonaffine_q):
+        return epilogue(y, bias, gamma, phi, res, relu, q, lazy=lazy)
+    if q is not None:
+        return bias_act_quant(y, bias, res, relu, q.delta, q.zero_point, q.n_bits, q.sym)
+    if bias is not None or relu or res is not None:
+        return bias_act(y, bias, res, relu, lazy=lazy)
+    return materialize(y)
+
+
+class LazyK13(collections.namedtuple("LazyK13", "y bias gamma phi res relu q",
+                                     defaults=(None, None, None, None, 0, None))):
+    """A K13 epilogue whose inputs exist but which has not run (the conv's raw output y and
+    k13's inputs): the lazy block tail (out._ssq_tail, _lazy_tail), which the recon loop runs
+    fused with the loss and its own backward (epilogue_loss_bwd); a downsample branch deferred
+    into that tail (LazyRes(y, bias, gamma, phi)), which the tail's pass applies itself
+    (ssq_epilogue_loss_bwd's res_* arguments), returning dL/dy; conv1's epilogue folded into
+    conv2's im2col GEMM (x._ssq_epi, lazy_epilogue).  Anywhere else materialize() runs exactly
+    the ops the eager site would have."""
+    __slots__ = ()
 
     def materialize(self):
-        if self.gamma is not None:
-            return epilogue(self.y, self.bias, self.gamma, self.phi, None, 0, None)
-        if self.bias is not None:
-            return bias_act(self.y, self.bias, None, 0)
-        return self.y
+        return k13(*self, nonaffine_q=True, lazy=False)
+
+    def grad_inputs(self):
+        """The tensors (or None) of which one must require a gradient for the pass to have any
+        to return -- whether a loop iteration steps."""
+        q, res = self.q, self.res
+        return ([self.y, self.gamma, self.phi] + ([q.delta, q.zero_point] if q is not None else [])
+                + (res.grad_inputs() if isinstance(res, LazyK13) else [res]))
+
+
+LazyRes = LazyEpi = LazyK13
 
 
 def materialize(res):
@@ -1226,12 +1262,21 @@ def _tail_ok(y, res):
             and (res is None or res.data_ptr() % 16 == 0))
 
 
+def _lazy_tail(y, bias, gamma, phi, res, relu, q):
+    """The lazy tail's placeholder (TAIL_LAZY): an uninitialised tensor like y carrying the
+    epilogue's inputs as _ssq_tail; None where the fused tail does not take the case."""
+    if int(relu) not in (0, 1) or not _tail_ok(y, res):
+        return None
+    out = torch.empty_like(y)
+    out._ssq_tail = LazyK13(y, bias, gamma, phi, res, int(relu), q)
+    return out
+
+
 def bias_act(y, bias=None, res=None, relu=True, lazy=False):
     """relu: activation code (False/0 identity, True/1 ReLU, 2 ReLU6).  lazy: see
     TAIL_LAZY (the block's final epilogue, fused with the loss and its backward)."""
-    if lazy and int(relu) in (0, 1) and _tail_ok(y, res):
-        out = torch.empty_like(y)
-        out._ssq_tail = (y, bias, None, None, res, int(relu), None)
+    out = _lazy_tail(y, bias, None, None, res, relu, None) if lazy else None
+    if out is not None:
         return out
     res = _unlazy(res)
     out = BiasActFn.apply(y, bias, res, int(relu))
@@ -1242,21 +1287,33 @@ def bias_act(y, bias=None, res=None, relu=True, lazy=False):
     return out
 
 
-def _epilogue_layout(y, bias, res, rows=False, stage=False):
-    """Pointers and (C, hw) of an epilogue's operands.  rows: y / res may stay row views --
-    their pointers are then their caches' and the result ends with their row maps' pointers
-    (None for an operand that is the batch itself); otherwise a row view is gathered (fptr).
-    stage (the K13 forward): a pending stage of the iteration's device words (_capi.ROW_STAGE)
-    is taken over by the caller's launch -- the maps then point into the ring row it copies
-    from -- and the result ends with (src, dst, n) pointers for ssq_epilogue_fwd_rows, or
+def _chan(t, C_, what):
+    """(tensor, pointer) of a per-channel operand, flattened; (None, None) without one."""
+    if t is None:
+        return None, None
+    t, p = fptr(t.detach().reshape(-1), what)
+    if t.numel() != C_:
+        raise A.SSQError(f"K13 epilogue: {what} must have one value per channel")
+    return t, p
+
+
+_K13Layout = collections.namedtuple("_K13Layout", "y yp yi bp rp ri C hw stage hold")
+
+
+def _epilogue_layout(y, bias, res, stage=False):
+    """A K13 launch's operands: y as launched, the pointers of y / bias / res, (C, hw), and
+    hold (what the pointers point into).  y / res may be row views: their pointers (yp / rp)
+    are then their caches' and yi / ri their row maps' (None for an operand that is the batch
+    itself).  stage (the K13 forward): a pending stage of the iteration's device words
+    (_capi.ROW_STAGE) is taken over by the caller's launch -- the maps then point into the
+    ring row it copies from -- and `stage` is (src, dst, n) for ssq_epilogue_fwd_rows, or
     (None, None, 0); without a row map the stage is performed here as a copy."""
     st = None
-    if rows and stage:
+    if stage:
         st = A.take_row_stage()
     elif A.ROW_STAGE:
         A.flush_row_stage()
-    yr = rows_of(y) if rows else None
-    rr = rows_of(res) if rows else None
+    yr, rr = rows_of(y), rows_of(res)
     if yr is not None:
         A.check(y, "conv output")
         yp = _vp(yr[0])
@@ -1264,11 +1321,8 @@ def _epilogue_layout(y, bias, res, rows=False, stage=False):
         y, yp = fptr(y.detach(), "conv output")
     C = y.shape[1] if y.dim() > 1 else 1
     hw = y[0, 0].numel() if y.dim() > 2 else 1
-    bp = rp = None
-    if bias is not None:
-        bias, bp = fptr(bias.detach().reshape(-1), "bias")
-        if bias.numel() != C:
-            raise A.SSQError("bias_act: bias must have one value per channel")
+    bias, bp = _chan(bias, C, "bias")
+    rp = None
     if res is not None:
         if rr is not None:
             A.check(res, "residual")
@@ -1277,21 +1331,40 @@ def _epilogue_layout(y, bias, res, rows=False, stage=False):
             res, rp = fptr(res.detach(), "residual")
         if res.shape != y.shape:
             raise A.SSQError("bias_act: residual shape mismatch")
-    if rows:
-        def rmap(t):
-            # the static slot's indices are read from the ring row this launch copies
-            if st is not None and t.data_ptr() == st[1].data_ptr():
-                return _vp(st[0])
-            return _vp(t)
-        maps = (None if yr is None else rmap(yr[1]), None if rr is None else rmap(rr[1]))
-        if st is not None and maps == (None, None):
-            st[1].copy_(st[0])
-            st = None
-        if stage:
-            stg = (None, None, 0) if st is None else (_vp(st[0]), _vp(st[1]), st[0].numel())
-            return y, yp, bp, rp, C, hw, (bias, res), maps, stg
-        return y, yp, bp, rp, C, hw, (bias, res), maps
-    return y, yp, bp, rp, C, hw, (bias, res)
+
+    def rmap(t):
+        # the static slot's indices are read from the ring row this launch copies
+        if st is not None and t.data_ptr() == st[1].data_ptr():
+            return _vp(st[0])
+        return _vp(t)
+    yi, ri = None if yr is None else rmap(yr[1]), None if rr is None else rmap(rr[1])
+    if st is not None and yi is None and ri is None:
+        st[1].copy_(st[0])
+        st = None
+    stg = (None, None, 0) if st is None else (_vp(st[0]), _vp(st[1]), st[0].numel())
+    return _K13Layout(y, yp, yi, bp, rp, ri, C, hw, stg, (bias, res))
+
+
+def _k13_forward(what, y, bias, gamma, phi, res, relu, delta=None, zp=None, n_bits=8, sym=False,
+                 keep=True):
+    """The K13 forward launch of BiasActFn, BiasActQuantFn and EpilogueFn: layout, quantizer
+    operands, ssq_epilogue_fwd_rows (null row maps for an operand that is the batch itself, a
+    null stage when none is pending).  keep: the activation before the quantizer is written
+    too.  Returns (layout, that activation or None, the quantized output or None, (lo, hi))."""
+    L = _epilogue_layout(y, bias, res, stage=True)
+    gm, gmp = _chan(gamma, L.C, "gamma")
+    ph, php = _chan(phi, L.C, "phi")
+    quant = delta is not None
+    if quant and (delta.numel() != 1 or zp.numel() != 1):
+        raise A.SSQError(f"{what}: per-tensor activation quantizer only")
+    d, dp = fptr(delta.detach().reshape(-1), "delta") if quant else (None, None)
+    z, zpp = fptr(zp.detach().reshape(-1), "zero_point") if quant else (None, None)
+    lo, hi = qrange(n_bits, sym) if quant else (0, 1)
+    out = torch.empty_like(L.y) if (keep or not quant) else None
+    yq = torch.empty_like(L.y) if quant else None
+    call("ssq_epilogue_fwd_rows", L.yp, L.yi, L.bp, gmp, php, L.rp, L.ri, _vp(out), _vp(yq),
+         L.y.numel(), L.hw, L.C, int(relu), dp, zpp, lo, hi, *L.stage, stream_of(L.y))
+    return L, out, yq, (lo, hi)
 
 
 class BiasActQuantFn(torch.autograd.Function):
@@ -1303,22 +1376,9 @@ class BiasActQuantFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, bias, res, delta, zp, relu, n_bits, sym, keep):
-        y, yp, bp, rp, C_, hw, hold, (yi, ri), stg = _epilogue_layout(y, bias, res, rows=True,
-                                                                     stage=True)
-        d, dp = fptr(delta.detach().reshape(-1), "delta")
-        z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
-        if d.numel() != 1 or z.numel() != 1:
-            raise A.SSQError("bias_act_fq: per-tensor activation quantizer only")
-        lo, hi = qrange(n_bits, sym)
-        out = torch.empty_like(y) if keep else None
-        yq = torch.empty_like(y)
-        if yi is not None or ri is not None:
-            call("ssq_epilogue_fwd_rows", yp, yi, bp, None, None, rp, ri, _vp(out), _vp(yq),
-                 y.numel(), hw, C_, int(relu), dp, zpp, lo, hi, *stg, stream_of(y))
-        else:
-            call("ssq_bias_act_fq", yp, bp, rp, _vp(out), _vp(yq), y.numel(), hw, C_, int(relu),
-                 dp, zpp, lo, hi, stream_of(y))
-        ctx.relu, ctx.q = int(relu), (lo, hi)
+        _, out, yq, ctx.q = _k13_forward("bias_act_fq", y, bias, None, None, res, relu, delta, zp,
+                                         n_bits, sym, keep)
+        ctx.relu = int(relu)
         if keep:
             ctx.save_for_backward(out, delta, zp)
         return yq
@@ -1364,34 +1424,12 @@ class EpilogueFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, bias, gamma, phi, res, delta, zp, relu, n_bits, sym):
-        y, yp, bp, rp, C_, hw, _, (yi, ri), stg = _epilogue_layout(y, bias, res, rows=True,
-                                                                  stage=True)
-        gm, gmp = fptr(gamma.detach().reshape(-1), "gamma") if gamma is not None else (None, None)
-        ph, php = fptr(phi.detach().reshape(-1), "phi") if phi is not None else (None, None)
-        if gm is not None and (gm.numel() != C_ or ph.numel() != C_):
-            raise A.SSQError("epilogue: gamma / phi must have one value per channel")
         quant = delta is not None
-        if quant:
-            d, dp = fptr(delta.detach().reshape(-1), "delta")
-            z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
-            if d.numel() != 1 or z.numel() != 1:
-                raise A.SSQError("epilogue: per-tensor activation quantizer only")
-            lo, hi = qrange(n_bits, sym)
-        else:
-            dp = zpp = None
-            lo, hi = 0, 1
-        out = torch.empty_like(y)
-        if yi is not None or ri is not None:
-            call("ssq_epilogue_fwd_rows", yp, yi, bp, gmp, php, rp, ri, None if quant else _vp(out),
-                 _vp(out) if quant else None, y.numel(), hw, C_, int(relu), dp, zpp, lo, hi,
-                 *stg, stream_of(y))
-        else:
-            call("ssq_epilogue_fwd", yp, bp, gmp, php, rp, None if quant else _vp(out),
-                 _vp(out) if quant else None, y.numel(), hw, C_, int(relu), dp, zpp, lo, hi,
-                 stream_of(y))
-        ctx.cfg = (int(relu), lo, hi, quant, C_, hw)
-        ctx.save_for_backward(y, bias, gamma, phi, res, delta, zp)
-        return out
+        L, out, yq, (lo, hi) = _k13_forward("epilogue", y, bias, gamma, phi, res, relu, delta, zp,
+                                            n_bits, sym, keep=False)
+        ctx.cfg = (int(relu), lo, hi, quant, L.C, L.hw)
+        ctx.save_for_backward(L.y, bias, gamma, phi, res, delta, zp)
+        return yq if quant else out
 
     @staticmethod
     def backward(ctx, g):
@@ -1401,37 +1439,39 @@ class EpilogueFn(torch.autograd.Function):
                                   C_, hw, ctx.needs_input_grad)
 
 
+def _k13_bwd_operands(gamma, phi, delta, zp, need, N, C_, dev_):
+    """What the K13 backward and the fused tail hand their kernel besides y / res: gamma / phi /
+    delta / zero point flattened; their gradients' destinations where need asks for one
+    (_grad_dest; the flags: written into a GRAD_INTO slice, not handed back); the workspace for
+    N * C rows, in two alternating slots (a queued finalize of the previous call reads its own)."""
+    flat = (lambda t: None if t is None else t.detach().reshape(-1).contiguous())
+    ggm, gm_into = _grad_dest(gamma, C_, dev_, need[0])
+    gph, ph_into = _grad_dest(phi, C_, dev_, need[1])
+    gd = torch.empty(1, device=dev_) if need[2] else None
+    gz = torch.empty(1, device=dev_) if need[3] else None
+    ws = workspace(query("ssq_epilogue_bwd_workspace_size", N * C_), dev_, _epi_slot())
+    return ((flat(gamma), flat(phi), flat(delta), flat(zp)), (ggm, gph, gd, gz),
+            (gm_into, ph_into), ws)
+
+
 def _epilogue_backward(g, y, bias, gamma, phi, res, delta, zp, relu, lo, hi, quant, C_, hw, need):
-    """ssq_epilogue_bwd for EpilogueFn (need = its needs_input_grad) and EpiConvGemmFn:
+    """ssq_epilogue_bwd_rows for EpilogueFn (need = its needs_input_grad) and EpiConvGemmFn:
     EpilogueFn.backward's return tuple."""
     g, gp = fptr(g.contiguous(), "grad")
-    dev_ = g.device
-
-    def flat(t):
-        return None if t is None else t.detach().reshape(-1).contiguous()
-    b, gm, ph, r = flat(bias), flat(gamma), flat(phi), res
-    d, z = flat(delta), flat(zp)
-    yr, rr = rows_of(y), rows_of(r)
+    b = None if bias is None else bias.detach().reshape(-1).contiguous()
+    yr, rr = rows_of(y), rows_of(res)
+    # (a residual that is the batch itself: contiguous, and alive until the launch)
+    r = None if res is None else (res.contiguous() if rr is None else rr[0])
     gy = torch.empty_like(g) if need[0] else None
     gres = torch.empty_like(g) if (res is not None and need[4]) else None
-    ggm, gm_into = _grad_dest(gamma, C_, dev_, need[2])
-    gph, ph_into = _grad_dest(phi, C_, dev_, need[3])
-    gd = torch.empty(1, device=dev_) if (quant and need[5]) else None
-    gz = torch.empty(1, device=dev_) if (quant and need[6]) else None
     N = g.numel() // (C_ * hw)
-    # two alternating slots: a queued finalize of the previous call still reads its own
-    ws, wsn = workspace(query("ssq_epilogue_bwd_workspace_size", N * C_), dev_, _epi_slot())
-    if yr is not None or rr is not None:
-        call("ssq_epilogue_bwd_rows", gp, _vp(y if yr is None else yr[0]),
-             None if yr is None else _vp(yr[1]), _vp(b), _vp(gm), _vp(ph),
-             _vp(r.contiguous() if (r is not None and rr is None) else (rr[0] if rr else None)),
-             None if rr is None else _vp(rr[1]), N, C_, hw, int(relu), _vp(d), _vp(z), lo, hi,
-             _vp(gy), _vp(gres), _vp(ggm), _vp(gph), _vp(gd), _vp(gz), ws, wsn, stream_of(g))
-    else:
-        call("ssq_epilogue_bwd", gp, _vp(y), _vp(b), _vp(gm), _vp(ph),
-             _vp(r.contiguous() if r is not None else None), N, C_, hw, int(relu), _vp(d),
-             _vp(z), lo, hi, _vp(gy), _vp(gres), _vp(ggm), _vp(gph), _vp(gd), _vp(gz), ws, wsn,
-             stream_of(g))
+    (gm, ph, d, z), (ggm, gph, gd, gz), (gm_into, ph_into), ws = _k13_bwd_operands(
+        gamma, phi, delta, zp, (need[2], need[3], quant and need[5], quant and need[6]), N, C_,
+        g.device)
+    call("ssq_epilogue_bwd_rows", gp, _vp(y if yr is None else yr[0]),
+         None if yr is None else _vp(yr[1]), _vp(b), _vp(gm), _vp(ph), _vp(r),
+         None if rr is None else _vp(rr[1]), N, C_, hw, int(relu), _vp(d), _vp(z), lo, hi,
+         _vp(gy), _vp(gres), _vp(ggm), _vp(gph), _vp(gd), _vp(gz), *ws, stream_of(g))
     shape = (lambda t, o: None if o is None else o.view(t.shape))
     return (gy if need[0] else None, None, None if gm_into else shape(gamma, ggm),
             None if ph_into else shape(phi, gph), gres, shape(delta, gd), shape(zp, gz), None,
@@ -1529,27 +1569,12 @@ EPI_INTO_GEMM = os.environ.get("SSQ_EPI_GEMM", "0") == "1"
 EPI_CONSUMER = [None]
 
 
-class LazyEpi:
-    """conv1's raw output y and its K13 epilogue's inputs (QuantModule.forward's fused
-    branch: bias, gamma^z / phi^z, activation code, per-tensor act quantizer)."""
-
-    def __init__(self, y, bias, gamma, phi, relu, q):
-        self.y, self.bias, self.gamma, self.phi, self.relu, self.q = y, bias, gamma, phi, relu, q
-
-    def materialize(self):
-        y, bias, gamma, phi, relu, q = self.y, self.bias, self.gamma, self.phi, self.relu, self.q
-        if gamma is not None:
-            return epilogue(y, bias, gamma, phi, None, relu, q)
-        if q is not None:
-            return bias_act_quant(y, bias, None, relu, q.delta, q.zero_point, q.n_bits, q.sym)
-        if bias is not None or relu:
-            return bias_act(y, bias, None, relu)
-        return y
-
-
 def lazy_epilogue(y, bias, gamma, phi, relu, q):
+    """conv1's raw output y and its K13 epilogue's inputs (QuantModule.forward's fused branch:
+    bias, gamma^z / phi^z, activation code, per-tensor act quantizer -- the last only together
+    with gamma^z / phi^z) as a placeholder for the consumer conv (x._ssq_epi)."""
     out = torch.empty_like(y)
-    out._ssq_epi = LazyEpi(y, bias, gamma, phi, int(relu), q)
+    out._ssq_epi = LazyEpi(y, bias, gamma, phi, None, int(relu), q)
     return out
 
 
@@ -1577,16 +1602,11 @@ class EpiConvGemmFn(torch.autograd.Function):
         Nb, C_, H, W, Co, _, R, S, st, pad, _, _, OH, OW, _ = conv_geometry(
             y.shape, weight.shape, stride, padding)
         y, yp = fptr(y.detach(), "conv output")
-        flat = (lambda t, nm: (None, None) if t is None else fptr(t.detach().reshape(-1), nm))
-        b, bp = flat(bias, "bias")
-        gm, gmp = flat(gamma, "gamma")
-        ph, php = flat(phi, "phi")
-        d, dp = flat(delta, "delta")
-        z, zpp = flat(zp, "zero_point")
-        for t, nm in ((b, "bias"), (gm, "gamma"), (ph, "phi")):
-            if t is not None and t.numel() != C_:
-                raise A.SSQError(f"epilogue into GEMM: {nm} must have one value per channel")
-        quant = d is not None
+        (b, bp), (gm, gmp), (ph, php) = (_chan(bias, C_, "bias"), _chan(gamma, C_, "gamma"),
+                                         _chan(phi, C_, "phi"))
+        quant = delta is not None
+        d, dp = fptr(delta.detach().reshape(-1), "delta") if quant else (None, None)
+        z, zpp = fptr(zp.detach().reshape(-1), "zero_point") if quant else (None, None)
         lo, hi = qrange(n_bits, sym) if quant else (0, 1)
         NP, CRS = Nb * OH * OW, C_ * R * S
         col = torch.empty(NP, CRS, dtype=torch.float32, device=y.device)
@@ -1624,25 +1644,24 @@ class EpiConvGemmFn(torch.autograd.Function):
 def epi_conv_gemm(x, weight, stride, padding):
     """conv2d of a LazyEpi placeholder x through EpiConvGemmFn."""
     e = x._ssq_epi
-    q = e.q
-    cfg = (e.relu, q.n_bits if q is not None else 8, q.sym if q is not None else False,
-           stride, padding)
-    return EpiConvGemmFn.apply(e.y, e.bias, e.gamma, e.phi, None if q is None else q.delta,
-                               None if q is None else q.zero_point, weight, cfg)
+    delta, zp, n_bits, sym = _q_operands(e.q)
+    return EpiConvGemmFn.apply(e.y, e.bias, e.gamma, e.phi, delta, zp, weight,
+                               (e.relu, n_bits, sym, stride, padding))
+
+
+def _q_operands(q):
+    """(delta, zero point, n_bits, sym) of a fusable act quantizer, or of none."""
+    return (None, None, 8, False) if q is None else (q.delta, q.zero_point, q.n_bits, q.sym)
 
 
 def epilogue(y, bias, gamma, phi, res, relu, q=None, lazy=False):
     """EpilogueFn with q an (initialised, per-tensor) act quantizer or None.  lazy: see
     TAIL_LAZY (the placeholder must only reach epilogue_loss_bwd)."""
-    if lazy and int(relu) in (0, 1) and _tail_ok(y, res):
-        out = torch.empty_like(y)
-        out._ssq_tail = (y, bias, gamma, phi, res, int(relu), q)
+    out = _lazy_tail(y, bias, gamma, phi, res, relu, q) if lazy else None
+    if out is not None:
         return out
-    res = _unlazy(res)
-    if q is None:
-        return EpilogueFn.apply(y, bias, gamma, phi, res, None, None, int(relu), 8, False)
-    return EpilogueFn.apply(y, bias, gamma, phi, res, q.delta, q.zero_point, int(relu), q.n_bits,
-                            q.sym)
+    delta, zp, n_bits, sym = _q_operands(q)
+    return EpilogueFn.apply(y, bias, gamma, phi, _unlazy(res), delta, zp, int(relu), n_bits, sym)
 
 
 def epilogue_fwd_form(n, hw, aligned=True, rows=False):
@@ -1668,59 +1687,39 @@ def epilogue_loss_bwd(tail, tgt, M, p=2.0):
     lp_loss_and_grad -> backward.  A LazyRes residual (the downsample's deferred epilogue) is
     applied in the same pass: gres is then dL/d(its raw conv output) and gres_gamma /
     gres_phi its gamma^z / phi^z gradients."""
-    y, bias, gamma, phi, res, relu, q = tail
+    if not isinstance(tail, LazyK13):
+        tail = LazyK13(*tail)           # (the seven fields in order)
     if not isinstance(tgt, Rows):
         raise A.SSQError("epilogue_loss_bwd: the target must be a Rows view of the cache")
-    lres = res if isinstance(res, LazyRes) else None
-    if lres is not None:
-        res = lres.y
-    y, yp, bp, rp, C_, hw, _, (yi, ri) = _epilogue_layout(y, bias, res, rows=True)
+    gamma, phi, q = tail.gamma, tail.phi, tail.q
+    lres = tail.res if isinstance(tail.res, LazyRes) else None
+    res = tail.res if lres is None else lres.y
+    L = _epilogue_layout(tail.y, tail.bias, res)
+    y, C_, N = L.y, L.C, L.y.shape[0]
     dev_ = y.device
     cache, cp = fptr(tgt.cache.detach(), "tgt cache")
     idx = tgt.idx
-    N = y.shape[0]
     if idx.dtype != torch.int64 or idx.numel() != N or tuple(cache.shape[1:]) != tuple(y.shape[1:]):
         raise A.SSQError("epilogue_loss_bwd: Rows target does not match the output")
-    flat = (lambda t: None if t is None else t.detach().reshape(-1).contiguous())
-    gm, ph = flat(gamma), flat(phi)
-    if q is not None:
-        d, z = flat(q.delta), flat(q.zero_point)
-        lo, hi = qrange(q.n_bits, q.sym)
-    else:
-        d = z = None
-        lo, hi = 0, 1
+    delta, zp, n_bits, sym = _q_operands(q)
+    lo, hi = qrange(n_bits, sym) if q is not None else (0, 1)
     loss = torch.empty(1, dtype=torch.float32, device=dev_)
     gy = torch.empty_like(y)
     gres = torch.empty_like(y) if (res is not None and res.requires_grad) else None
-    ggm, gm_into = _grad_dest(gamma, C_, dev_, gamma is not None and gamma.requires_grad)
-    gph, ph_into = _grad_dest(phi, C_, dev_, phi is not None and phi.requires_grad)
-    rbp = rgp = rphp = None
-    grg, grph, rg_into, rph_into = None, None, False, False
-    if lres is not None:
-        if lres.bias is not None:
-            rb, rbp = fptr(lres.bias.detach().reshape(-1), "residual bias")
-            if rb.numel() != C_:
-                raise A.SSQError("epilogue_loss_bwd: residual bias must have one value per channel")
-        if lres.gamma is not None:
-            rg, rgp = fptr(lres.gamma.detach().reshape(-1), "residual gamma")
-            rph_, rphp = fptr(lres.phi.detach().reshape(-1), "residual phi")
-            if rg.numel() != C_ or rph_.numel() != C_:
-                raise A.SSQError("epilogue_loss_bwd: residual gamma / phi must have one value per channel")
-            grg, rg_into = _grad_dest(lres.gamma, C_, dev_, lres.gamma.requires_grad)
-            grph, rph_into = _grad_dest(lres.phi, C_, dev_, lres.phi.requires_grad)
-    gd = torch.empty(1, device=dev_) if (q is not None and q.delta.requires_grad) else None
-    gz = torch.empty(1, device=dev_) if (q is not None and q.zero_point.requires_grad) else None
-    ws, wsn = workspace(query("ssq_epilogue_bwd_workspace_size", N * C_), dev_, _epi_slot())
-    if yi is not None or ri is not None:
-        call("ssq_epilogue_loss_bwd_rows", cp, _vp(idx), int(M), float(p), _vp(loss), yp, yi, bp,
-             _vp(gm), _vp(ph), rp, ri, rbp, rgp, rphp, N, C_, hw, int(relu), _vp(d), _vp(z), lo,
-             hi, _vp(gy), _vp(gres), _vp(ggm), _vp(gph), _vp(grg), _vp(grph), _vp(gd), _vp(gz),
-             ws, wsn, stream_of(y))
-    else:
-        call("ssq_epilogue_loss_bwd", cp, _vp(idx), int(M), float(p), _vp(loss), yp, bp, _vp(gm),
-             _vp(ph), rp, rbp, rgp, rphp, N, C_, hw, int(relu), _vp(d), _vp(z), lo, hi, _vp(gy),
-             _vp(gres), _vp(ggm), _vp(gph), _vp(grg), _vp(grph), _vp(gd), _vp(gz), ws, wsn,
-             stream_of(y))
+    wants = (lambda t: t is not None and t.requires_grad)
+    (gm, ph, d, z), (ggm, gph, gd, gz), (gm_into, ph_into), ws = _k13_bwd_operands(
+        gamma, phi, delta, zp, (wants(gamma), wants(phi), wants(delta), wants(zp)), N, C_, dev_)
+    # the residual's own epilogue (none: null operands, no gradient slots)
+    rbias, rgamma, rphi = (None,) * 3 if lres is None else (lres.bias, lres.gamma, lres.phi)
+    (rb, rbp), (rg, rgp), (rph_, rphp) = (_chan(rbias, C_, "residual bias"),
+                                          _chan(rgamma, C_, "residual gamma"),
+                                          _chan(rphi, C_, "residual phi"))
+    grg, rg_into = _grad_dest(rgamma, C_, dev_, wants(rgamma))
+    grph, rph_into = _grad_dest(rphi, C_, dev_, wants(rphi))
+    call("ssq_epilogue_loss_bwd_rows", cp, _vp(idx), int(M), float(p), _vp(loss), L.yp, L.yi,
+         L.bp, _vp(gm), _vp(ph), L.rp, L.ri, rbp, rgp, rphp, N, C_, L.hw, int(tail.relu), _vp(d),
+         _vp(z), lo, hi, _vp(gy), _vp(gres), _vp(ggm), _vp(gph), _vp(grg), _vp(grph), _vp(gd),
+         _vp(gz), *ws, stream_of(y))
     # a gradient written into its GRAD_INTO slice is not handed back (already in place)
     return (loss, gy, gres, None if gm_into else ggm, None if ph_into else gph, gd, gz,
             None if rg_into else grg, None if rph_into else grph)

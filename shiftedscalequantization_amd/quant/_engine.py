@@ -199,10 +199,10 @@ def backward_tail(tail, grads):
     """Resume autograd at a fused tail's inputs: the conv output y and the residual through
     their graphs; gamma^z / phi^z / the act quantizer's delta and zero point are leaves here
     (or views of leaves), accumulated as autograd would."""
-    y, bias, gamma, phi, res, relu, q = tail
+    res, q = tail.res, tail.q
     _, gy, gres, ggm, gph, gd, gz, grg, grph = grads
-    roots, grs = [y], [gy]
-    leaves = [(gamma, ggm), (phi, gph)]
+    roots, grs = [tail.y], [gy]
+    leaves = [(tail.gamma, ggm), (tail.phi, gph)]
     if isinstance(res, K.LazyRes):
         # the downsample's deferred epilogue: gres is dL/d(its conv output); its gamma^z /
         # phi^z are leaves like the block's own
@@ -229,6 +229,50 @@ def backward_tail(tail, grads):
             roots.append(t)
             grs.append(g)
     run_backward(roots, grs)
+
+
+class lazy_tail:
+    """Context around a loop's block forward: K.TAIL_LAZY[0] = block inside (None: the block
+    runs its last epilogue itself), cleared on exit."""
+
+    def __init__(self, block):
+        self.block = block
+
+    def __enter__(self):
+        K.TAIL_LAZY[0] = self.block
+
+    def __exit__(self, *exc):
+        K.TAIL_LAZY[0] = None
+
+
+def loss_backward(out, tgt, loss_and_grad, p=2.0):
+    """The loss of a block output against the target rows and the backward from it, by what
+    the output carries.  A lazy tail (out._ssq_tail): the block's last epilogue, the lp loss at
+    power p and that epilogue's backward in one pass (K.epilogue_loss_bwd), autograd resuming
+    at the epilogue's inputs.  The output of a fused epilogue's ReLU (out._ssq_relu_inputs):
+    loss_and_grad(out, tgt, relu_mask=True) writes the gradient at the ReLU's input and
+    backward starts from the epilogue's inputs.  Anything else: loss_and_grad(out, tgt) and
+    backward from out.  Returns (the loss value on the device, stepped); stepped is False --
+    only the loss value is computed, nothing back-propagated -- where no optimised parameter
+    reaches the output (e.g. the act delta of a layer whose act quantizer is disabled): the
+    reference's backward yields no gradient then and its Adam step skips the parameter."""
+    tail = getattr(out, '_ssq_tail', None)
+    if tail is not None:
+        grads = K.epilogue_loss_bwd(tail, tgt, K._lp_M(out, "none"), p)
+        stepped = any(t is not None and t.requires_grad for t in tail.grad_inputs())
+        if stepped:
+            backward_tail(tail, grads)
+        return grads[0], stepped
+    if not out.requires_grad:
+        return loss_and_grad(out, tgt, want_grad=False)[0], False
+    relu_in = getattr(out, '_ssq_relu_inputs', None)
+    if relu_in:
+        rec, g = loss_and_grad(out, tgt, relu_mask=True)
+        run_backward(list(relu_in), [g] * len(relu_in))
+    else:
+        rec, g = loss_and_grad(out, tgt)
+        run_backward([out], [g])
+    return rec, True
 
 
 def stash_block_weights(quantizers):

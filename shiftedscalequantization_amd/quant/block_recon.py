@@ -16,8 +16,8 @@ import torch
 from .. import kernels as K
 from ..parallel_dp import GradBucket, world
 from ._engine import (GRAPH_REPLAYS, ITER_PROBE, BatchFeeder, IterationGraph, LazyValue,
-                      CosineLR, SsqAdam, as_float, backward_tail, clear_stash, frozen_except,
-                      probe, run_backward, stash_adaround)
+                      CosineLR, SsqAdam, as_float, clear_stash, frozen_except, lazy_tail,
+                      loss_backward, probe, stash_adaround)
 from .adaptive_rounding import AdaRoundQuantizer
 from .data_utils import save_grad_data, save_inp_oup_data
 from .quant_block import BaseQuantBlock
@@ -377,42 +377,13 @@ def _fast_loop(block, qmodules, opt_params, loss_func, feeder, bucket, iters, ac
             cur_inp, cur_out = feeder.gather_lazy(input_needed=need_input[0])
         if stash_ada:
             stash_adaround(qmodules)
-        K.TAIL_LAZY[0] = block if fuse_tail else None
         try:
-            out = block(cur_inp)
+            with lazy_tail(block if fuse_tail else None):
+                out = block(cur_inp)
         finally:
-            K.TAIL_LAZY[0] = None
             if stash_ada:
                 clear_stash([m.weight_quantizer for m in qmodules])
-        tail = getattr(out, '_ssq_tail', None)
-        if tail is not None:
-            # the block's final epilogue, the loss and the epilogue's backward in one pass;
-            # autograd resumes at the epilogue's inputs
-            grads = K.epilogue_loss_bwd(tail, cur_out, K._lp_M(out, "none"), p)
-            y, _, gamma, phi, res, _, q = tail
-            live = [y, gamma, phi] + ([q.delta, q.zero_point] if q is not None else [])
-            live += [res.y, res.gamma, res.phi] if isinstance(res, K.LazyRes) else [res]
-            last['rec'] = grads[0]
-            last['step'] = any(t is not None and t.requires_grad for t in live)
-            if last['step']:
-                backward_tail(tail, grads)
-            return
-        relu_in = getattr(out, '_ssq_relu_inputs', None)
-        if not out.requires_grad:
-            # no optimised parameter reaches the output (e.g. the act delta of a layer whose
-            # act quantizer is disabled): the reference's backward yields no gradient for it
-            # and its Adam step skips it -- only the loss value remains
-            last['rec'], _ = loss_and_grad(out, cur_out, want_grad=False)
-            last['step'] = False
-            return
-        if relu_in:
-            rec, g = loss_and_grad(out, cur_out, relu_mask=True)
-            run_backward(list(relu_in), [g] * len(relu_in))
-        else:
-            rec, g = loss_and_grad(out, cur_out)
-            run_backward([out], [g])
-        last['rec'] = rec
-        last['step'] = True
+        last['rec'], last['step'] = loss_backward(out, cur_out, loss_and_grad, p)
 
     def _step():
         if last['step']:

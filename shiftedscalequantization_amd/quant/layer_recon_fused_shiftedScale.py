@@ -19,8 +19,8 @@ from tqdm import tqdm
 
 from .. import kernels as K
 from ..parallel_dp import GradBucket, world
-from ._engine import (BatchFeeder, IterationGraph, LazyValue, SsqAdam, as_float, backward_tail,
-                      clear_stash, probe, run_backward, stash_block_weights)
+from ._engine import (BatchFeeder, IterationGraph, LazyValue, SsqAdam, as_float, clear_stash,
+                      lazy_tail, loss_backward, probe, stash_block_weights)
 from .quant_block import BaseQuantBlock
 from .quant_layer import QuantModule
 
@@ -134,28 +134,12 @@ def _fused_loop(block, modules, iters, lmda, model, p, lr, bias_cal, batch_size,
             if on_gpu:
                 stash_block_weights(quantizers)
             cur_inp, cur_out = feeder.gather_lazy()
-        K.TAIL_LAZY[0] = block if fuse_tail else None
-        try:
+        with lazy_tail(block if fuse_tail else None):
             quant_out = block(cur_inp)
-        finally:
-            K.TAIL_LAZY[0] = None
         clear_stash(quantizers)
-        tail = getattr(quant_out, '_ssq_tail', None)
-        relu_in = getattr(quant_out, '_ssq_relu_inputs', None)
-        if tail is not None:
-            # the block's final epilogue, the loss and the epilogue's backward in one pass;
-            # autograd resumes at the epilogue's inputs
-            rec, grads = loss_func.fused_tail(tail, quant_out, cur_out)
-            backward_tail(tail, grads)
-        elif relu_in:
-            # the block ends in the fused epilogue's ReLU: the loss pass writes the gradient
-            # at the ReLU's input and backward starts from the epilogue's inputs
-            rec, g_pre = loss_func.loss_and_grad(quant_out, cur_out, relu_mask=True)
-            run_backward(list(relu_in), [g_pre] * len(relu_in))
-        else:
-            rec, g_out = loss_func.loss_and_grad(quant_out, cur_out)
-            run_backward([quant_out], [g_out])
-        last['rec'] = rec
+        # (every iteration of this loop steps: alpha always reaches the output)
+        rec, _ = loss_backward(quant_out, cur_out, loss_func.loss_and_grad, p)
+        last['rec'] = rec.view(())
 
     def body_post():
         """After the (RCCL) bucket all-reduce: the fused Adam step."""
@@ -367,19 +351,13 @@ class FusedScaleLossFunction:
         for qt in self.quantizer:
             qt._fused_reg = None
 
-    def fused_tail(self, tail, pred, tgt):
-        """loss_and_grad + the final epilogue's backward in one pass (K.epilogue_loss_bwd);
-        returns (rec_loss, the epilogue's input gradients)."""
-        grads = K.epilogue_loss_bwd(tail, tgt, K._lp_M(pred, "none"))
-        return grads[0][0], grads
-
-    def loss_and_grad(self, pred, tgt, relu_mask=False):
+    def loss_and_grad(self, pred, tgt, **kw):
         """One ssq_lp_loss pass: the loss value AND d loss / d pred (device only) -- or,
         with relu_mask, d loss / d (ReLU input) when pred is a ReLU output.  The caller
         back-propagates it -- exactly what total_loss.backward() delivers there; the
         regulariser terms reach alpha through the armed adaShift backward, and beta is
         never optimised by this loop."""
-        rec_loss, grad = K.lp_loss_and_grad(pred, tgt, self.p, relu_mask=relu_mask)
+        rec_loss, grad = K.lp_loss_and_grad(pred, tgt, self.p, **kw)
         return rec_loss[0], grad
 
     def fused(self, pred, tgt):

@@ -139,25 +139,17 @@ class BaseQuantBlock(nn.Module):
             relu = isinstance(self.activation_function, nn.ReLU)
             q = fusable_act_quantizer(self.act_quantizer, self.use_act_quant)
             gamma, phi = last.affine()
-            # lazy only for the block the loop targets, and only when no hook can see the
-            # placeholder output (K.TAIL_LAZY)
-            lazy_ok = K.TAIL_LAZY[0] is self and not self._forward_hooks
-            if gamma is not None:   # last's gamma^z/phi^z, residual, act (+ act quant)
-                lazy = lazy_ok and (q is not None or not self.use_act_quant)
-                out = K.epilogue(raw, bias, gamma, phi, residual, relu, q, lazy=lazy)
-                if q is None and self.use_act_quant:
-                    out = self.act_quantizer(out)
-                return out
-            if q is not None:
-                # + the block's act quant in the same pass: the general epilogue with no
-                # gamma^z / phi^z, whose backward sums the act delta per (n, c) row as the
-                # fused tail does -- so the recon loop (BRECQ's act phase without --bias_cal)
-                # takes the block's last epilogue, the loss and its backward as one pass
-                # (lazy), bit-identical to this unfused form
-                return K.epilogue(raw, bias, None, None, residual, relu, q, lazy=lazy_ok)
-            lazy = lazy_ok and not self.use_act_quant
-            out = K.bias_act(raw, bias, residual, relu, lazy=lazy)
-            if self.use_act_quant:
+            # lazy only for the block the loop targets, only when no hook can see the
+            # placeholder output (K.TAIL_LAZY), and only when the epilogue is the block's last
+            # op (an act quantizer that is on but not fusable runs after it)
+            lazy = (K.TAIL_LAZY[0] is self and not self._forward_hooks
+                    and (q is not None or not self.use_act_quant))
+            # nonaffine_q: a tail with the block's act quantizer and no gamma^z / phi^z always
+            # takes the general epilogue, whatever quant_layer.EPI_NONAFFINE_Q says -- the
+            # form the recon loop's fused tail (BRECQ's act phase without --bias_cal) is
+            # bit-identical to (K.k13)
+            out = K.k13(raw, bias, gamma, phi, residual, relu, q, nonaffine_q=True, lazy=lazy)
+            if q is None and self.use_act_quant:
                 out = self.act_quantizer(out)
             return out
         residual = K.materialize(residual)

@@ -23,7 +23,8 @@ from .. import kernels as K
 _FROZEN_W = None
 
 # A QuantModule's epilogue with an act quantizer and no gamma^z / phi^z (BRECQ's act phase
-# without --bias_cal) through the general epilogue (K.epilogue) rather than bias_act_quant.
+# without --bias_cal) through the general epilogue rather than bias_act_quant: K.k13's
+# nonaffine_q at QuantModule.forward (a block tail always passes it on).
 # A/B knob: SSQ_EPI_NONAFFINE_Q=0.
 EPI_NONAFFINE_Q = os.environ.get("SSQ_EPI_NONAFFINE_Q", "1") != "0"
 
@@ -392,8 +393,9 @@ class QuantModule(nn.Module):
 
     def _conv(self, input, weight, bias=None):
         """The layer's conv / linear; a conv whose weight needs a gradient goes through
-        K.conv2d (deterministic K17 weight gradient, see kernels.WGRAD_POLICY; a LazyEpi
-        input folded into its im2col GEMM there)."""
+        K.conv2d (deterministic K17 weight gradient, see kernels.WGRAD_POLICY; an input that
+        is a K13 placeholder -- x._ssq_epi, a K.LazyK13 -- folded into its im2col GEMM there),
+        any other consumer materialises such an input first (K.materialize_epi)."""
         plan = getattr(self, '_int_plan', None)
         integer = (plan is not None and not torch.is_grad_enabled() and self.use_weight_quant
                    and self.use_act_quant and self.cache_features == 'none')
@@ -458,29 +460,17 @@ class QuantModule(nn.Module):
             relu = self.act_code()
             q = fusable_act_quantizer(self.act_quantizer, act_q)
             gamma, phi = self.affine()
-            # (with an act quantizer only in the affine epilogue's form: the plain bias+act+q
-            # pass has its own backward kernel, whose delta sums are not the affine one's)
+            # (with an act quantizer only in the epilogue's form, i.e. with gamma^z / phi^z:
+            # the consumer's backward is ssq_epilogue_bwd, see K.k13)
             if (K.EPI_CONSUMER[0] is not None and (q is not None or not act_q)
                     and (q is None or gamma is not None)
                     and self.cache_features == 'none' and not self._forward_hooks):
                 # the parent block's next conv folds this epilogue into its im2col GEMM
                 # (kernels.EPI_CONSUMER); anything else materialises it
                 return K.lazy_epilogue(out, bias, gamma, phi, relu, q)
-            if gamma is not None or (q is not None and EPI_NONAFFINE_Q):
-                # (no gamma^z / phi^z with an act quantizer: the general epilogue too, whose
-                # backward sums the act delta per (n, c) row and hands its finalisation to
-                # the next launch's task list -- bias_act_quant's backward finalises in a
-                # launch of its own)
-                out = K.epilogue(out, bias, gamma, phi, None, relu, q)
-                act_q = act_q and q is None
-            elif q is not None:
-                out = K.bias_act_quant(out, bias, None, relu, q.delta, q.zero_point, q.n_bits,
-                                       q.sym)
-                act_q = False
-            elif bias is not None or relu:
-                out = K.bias_act(out, bias, None, relu)
-            else:
-                out = K.materialize(out)     # a row view leaves as the batch it stands for
+            out = K.k13(out, bias, gamma, phi, None, relu, q, nonaffine_q=EPI_NONAFFINE_Q,
+                        lazy=False)
+            act_q = act_q and q is None      # (on but not fusable: as a module, below)
         else:
             weight, bias = self._weight_bias()
             out = self._conv(input, weight, bias)

@@ -200,6 +200,23 @@ WORKER_ENVS = {
 }
 
 
+# The plain ABI entries (ssq_bias_act, ssq_bias_act_fq, ssq_epilogue_fwd, ssq_epilogue_bwd,
+# ssq_epilogue_loss_bwd) against their _rows twins with null maps (tests/test_k13_glue_gpu.py;
+# no Python wrapper calls the plain ones): every forward form with and without residual,
+# activation 0 / 1 / 2, with and without a 4-bit quantizer, with gamma / phi (ssq_epilogue_fwd)
+# and without; the backward on WORKER's four plane classes; the tail on the same four.
+ENTRY_SEEDS = {"fwd-2x4x4x4-b1a0r1t0-q4z0": 2}     # (see _c's seed)
+ENTRY_FWD = [
+    _c(shape, "entry: forward form %d" % f, "fwd", fwd=f, affine=a, res=r, act=t, q=q)
+    for shape, f in (((2, 3, 5, 5), 0), ((4, 3, 7, 7), 1), ((2, 4, 4, 4), 2))
+    for a in (False, True) for r in (None, "tensor") for t in (0, 1, 2) for q in (None, Q4Z0)]
+ENTRY_BWD = [c for c in WORKER if c.kind == "bwd"]
+ENTRY_TAIL = [c for c in WORKER if c.kind == "tail"] + [
+    _c((3, 5, 13, 20), "entry: tail, long float4 plane", "tail", form=R1V, res="tensor", q=Q4Z0),
+    _c((3, 5, 5, 13), "entry: tail, long scalar plane", "tail", form=R1S, res=LAZY_BIAS, q=Q4Z0),
+]
+
+
 def case_id(c):
     s = f"{c.kind}-" + "x".join(str(v) for v in c.shape)
     s += f"-b{int(c.bias)}a{int(c.affine)}r{ {None: 0, 'tensor': 1, LAZY_BIAS: 2, LAZY_AFFINE: 3}[c.res] }t{c.act}"
@@ -407,3 +424,7 @@ def sums_of(c):
 
 
 BY_ID = {case_id(c): c for c in CASES + WORKER}
+for _cases in (ENTRY_FWD, ENTRY_TAIL):
+    for _k, _case in enumerate(_cases):
+        _case.seed = ENTRY_SEEDS.get(case_id(_case), _case.seed)
+        _cases[_k] = BY_ID.setdefault(case_id(_case), _case)     # (a case above: that one)

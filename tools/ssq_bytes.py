@@ -92,7 +92,8 @@ def bytes_of(name, a):
         cnt = a[5] if name == "ssq_adam" else a[4]
         return 28 * sum(int(cnt[s]) for s in range(int(a[0])))
     if name in ("ssq_bias_act", "ssq_bias_act_fq"):
-        # (y, bias, res, out, [yq,] n, ...)
+        # (y, bias, res, out, [yq,] n, ...): the same bytes as ssq_epilogue_fwd_rows prices for
+        # these operands, which is what the Python wrappers launch (kernels._k13_forward)
         if name == "ssq_bias_act":
             return 4 * int(a[4]) * (2 + (not _null(a[2])))
         return 4 * int(a[5]) * (1 + (not _null(a[2])) + (not _null(a[3])) + (not _null(a[4])))
