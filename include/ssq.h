@@ -834,6 +834,39 @@ int ssq_epilogue_codes_fwd(const float* y, const float* bias, const float* gamma
 int ssq_maxpool_i8_fwd(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W, int64_t K,
                        int64_t stride, int64_t pad, int8_t* out, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- fused stem (K31)
+ * The stem conv itself, on the fp32 MFMA, with a stated summation order.  For an fp32 NCHW image
+ * x [Nb, Ci, H, W] and an fp32 OIHW weight w [Co, Ci, R, S], stride (stride_h, stride_w), padding
+ * (pad_h, pad_w), dilation 1, groups 1, no bias,
+ *     y[n, co, oh, ow] = acc_K,  acc_0 = +0.0f,  acc_{k+1} = fmaf(x_k, w[co, k], acc_k),
+ * k over (ci, r, s) in the memory order of w[co], K = Ci*R*S, x_k the pixel under tap k or +0.0f
+ * outside the image; one rounding per tap and no other, so a host fmaf loop gives the same bits.
+ *
+ * ssq_stem_weight_prepare (once per layer): w -> ssq_stem_weight_prepared_bytes(Co, Ci, R, S)
+ * bytes in the conv's operand order (csrc/qinfer_layout.h, SLayout); 0 bytes for a geometry
+ * outside 1 <= Ci <= 4, 1 <= R, S <= 7, Co >= 1.
+ * ssq_stem_conv_fwd: y as fp32 NCHW [Nb, Co, OH, OW].
+ * ssq_stem_conv_codes_fwd: qepi_code_y on each accumulator, i.e. ssq_epilogue_codes_fwd's
+ * arguments, checks and bytes for that y (NHWC int8 [Nb*OH*OW][qinfer_cpad(Co)], padded channels
+ * 0, every byte written, a NaN q stored as out_qmin and ADDED to *bad) without the fp32 tensor.
+ *
+ * Refused with SSQ_E_ARG before any launch: a null pointer, the geometry above, strides < 1,
+ * pad_h >= R or pad_w >= S or negative, an empty output, prepared_bytes below the blob's size, a
+ * tensor of 2^31 elements or more.  No allocation, no sync, no float atomics, capturable.      */
+size_t ssq_stem_weight_prepared_bytes(int64_t Co, int64_t Ci, int64_t R, int64_t S);
+int ssq_stem_weight_prepare(const float* w, int64_t Co, int64_t Ci, int64_t R, int64_t S,
+                            void* prepared, ssq_stream_t stream);
+int ssq_stem_conv_fwd(const float* x, const void* prepared, size_t prepared_bytes, int64_t Nb,
+                      int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S,
+                      int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, float* y,
+                      ssq_stream_t stream);
+int ssq_stem_conv_codes_fwd(const float* x, const void* prepared, size_t prepared_bytes,
+                            int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R,
+                            int64_t S, int64_t stride_h, int64_t stride_w, int64_t pad_h,
+                            int64_t pad_w, const float* bias, const float* gamma, const float* phi,
+                            int act, float out_delta, float out_zero_point, int out_qmin,
+                            int out_qmax, int8_t* out_codes, uint32_t* bad, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- column-scaled weights
  * A weight with a per-column input scale on a common integer grid,
  *     W_hat[co, j] = ((q_w - z_w[co]) * d1[co]) * c[j],  c[j] = fp32(kcol[j] / L),  j = (ci, r, s)

@@ -72,6 +72,7 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
                                                      enable_integer_inference,
                                                      head_carry_report, integer_report,
                                                      split_report, stem_carry_report)
+    fused = {'fused_stem': True} if getattr(args, 'int_infer_fused_stem', False) else {}
     plan = enable_integer_inference(qnn, cali[:8], grouped=args.int_infer_grouped,
                                     carry=args.int_infer_carry,
                                     carry_blocks=args.int_infer_carry_blocks,
@@ -79,7 +80,8 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
                                     carry_head=args.int_infer_carry_head,
                                     colscale=args.int_infer_colscale,
                                     splitk=args.int_infer_splitk,
-                                    per_ci=args.int_infer_per_ci, wide=args.int_infer_wide)
+                                    per_ci=args.int_infer_per_ci, wide=args.int_infer_wide,
+                                    **fused)
     n_int = sum(v == 'int8' for v in plan.values())
     print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
     if args.int_infer_carry:
@@ -94,6 +96,10 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
         edges = stem_carry_report(qnn)['edges']
         print(f'integer inference: int8 codes carried from {len(edges)} stem edges: '
               + ', '.join(' -> '.join([a] + pools + [b]) for a, pools, b in edges))
+    if fused:
+        why = stem_carry_report(qnn)['unfused']
+        print('integer inference: stem conv emitting its own codes (K31): '
+              + ', '.join(f'{n}: {"yes" if not w else w}' for n, w in why.items()))
     if args.int_infer_carry_head:
         edges = head_carry_report(qnn)['edges']
         print(f'integer inference: int8 codes carried to the logits along {len(edges)} head '

@@ -92,6 +92,10 @@ def build_parser():
                    help='--int_infer_carry_stem with the codes running to the logits: the global '
                         'average pool sums the int8 codes and the fc runs on the sums (a numerics '
                         'contract of its own, DESIGN 4); implies --int_infer_carry_stem')
+    p.add_argument('--int_infer_fused_stem', action='store_true',
+                   help='--int_infer_carry_stem with the stem conv itself emitting the int8 codes '
+                        '(fp32-MFMA conv with a stated summation order, no fp32 tensor and no '
+                        'library conv; DESIGN 4 "Fused stem (K31)"); implies --int_infer_carry_stem')
     p.add_argument('--int_infer_colscale', action='store_true',
                    help='--int_infer with column-scaled weights (ChannelQuantMSE, the --test path) '
                         'on integer codes too: the column scale as integers k / L, L <= 127, folded '
@@ -130,7 +134,7 @@ def parse_args(argv=None):
     a = build_parser().parse_args(argv)
     if a.run_device:
         a.device_gpu = a.run_device
-    if a.int_infer_carry_head:
+    if a.int_infer_carry_head or a.int_infer_fused_stem:
         a.int_infer_carry_stem = True
     if a.int_infer_carry_stem:
         a.int_infer_carry_blocks = True

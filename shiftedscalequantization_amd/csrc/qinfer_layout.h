@@ -12,11 +12,37 @@
 // GLayout, K24's blob (qinfer_grouped.hip), by kind.  Depthwise (K25): int32 [R*S][Cp].
 // Grouped (K26): int8 [G*Cogp][Kp], Kp = 64*ceil(R*S*Wc/64), k = tap * Wc + (c - w0_g) inside
 // group g's 16-aligned channel window; then the 0/1 rows [G][Kp]; then cwz[Co], T[Co] (int32).
+//
+// SLayout, K31's blob (qinfer_stemconv.hip): the fp32 weight in the order the 16x16x4 fp32 MFMA
+// takes its A operand, float [Kp / 4][Cop / 16][4][16] with Kp = 4*ceil(K/4), K = Ci*R*S,
+// k = (ci*R + r)*S + s (the weight's own memory order) and Cop = 16*ceil(Co/16): entry
+// [t][c][kk][j] is W[co = 16 c + j][k = 4 t + kk], so lane l of a wave reads word l of the 64
+// of (step t, chunk c).  A padded channel is +0; a padded k is -0 in every channel (the pixel
+// operand there is +0, the product -0, and acc + (-0) is acc for every acc, a signed zero too).
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 namespace ssq {
+
+constexpr int64_t kStemMaxCi = 4, kStemMaxRS = 7;
+
+struct SLayout {
+  int64_t K, Kp, Cop;
+  size_t bytes;   // 0: outside K31's geometry
+};
+
+static inline SLayout slayout(int64_t Co, int64_t Ci, int64_t R, int64_t S) {
+  SLayout L = {};
+  if (Co < 1 || Co >= (1ll << 24) || Ci < 1 || Ci > kStemMaxCi || R < 1 || R > kStemMaxRS ||
+      S < 1 || S > kStemMaxRS)
+    return L;
+  L.K = Ci * R * S;
+  L.Kp = (L.K + 3) / 4 * 4;
+  L.Cop = (Co + 15) / 16 * 16;
+  L.bytes = (size_t)L.Kp * (size_t)L.Cop * 4;
+  return L;
+}
 
 constexpr int kQT = 64;     // pixels, channels and k per tile step
 constexpr int kQRow = 80;   // LDS row stride in bytes (64 + 16)

@@ -2511,6 +2511,95 @@ def epilogue_codes(y, bias, gamma, phi, relu, out_delta, out_zp, out_bits, out_s
     return out
 
 
+# ------------------------------------------------------------------ K31 fused stem conv
+STEM_MAX_CI, STEM_MAX_RS = 4, 7
+
+
+class StemWeight:
+    """A stem weight prepared for K31 (stem_weight_prepare): `blob`, the device bytes;
+    `shape`, the weight's (Co, Ci, R, S)."""
+
+    def __init__(self, blob, shape):
+        self.blob, self.shape = blob, tuple(int(v) for v in shape)
+
+
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def stem_geometry_reason(Co, Ci, R, S, stride, padding, dilation=1, groups=1):
+    """Why K31 does not take this conv, None when it does (ssq_stem_conv_fwd's geometry)."""
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    if groups != 1:
+        return "grouped conv"
+    if (dh, dw) != (1, 1) or not (1 <= Ci <= STEM_MAX_CI and 1 <= R <= STEM_MAX_RS
+                                  and 1 <= S <= STEM_MAX_RS and Co >= 1 and sh >= 1 and sw >= 1
+                                  and 0 <= ph < R and 0 <= pw < S):
+        return (f"geometry (Ci {Ci}, kernel {R}x{S}, stride {(sh, sw)}, padding {(ph, pw)}, "
+                f"dilation {(dh, dw)}: K31 takes Ci <= {STEM_MAX_CI}, R, S <= {STEM_MAX_RS}, "
+                "padding below the kernel, dilation 1)")
+    return None
+
+
+def stem_weight_prepare(weight):
+    """fp32 OIHW weight (Co, Ci <= 4, R <= 7, S <= 7) -> StemWeight, the operand of stem_conv /
+    stem_conv_codes (ssq_stem_weight_prepare; layout: csrc/qinfer_layout.h, SLayout)."""
+    w, wp = fptr(weight.detach(), "weight")
+    if w.dim() != 4:
+        raise A.SSQError(f"stem_weight_prepare: expected (Co, Ci, R, S), got {tuple(w.shape)}")
+    Co, Ci, R, S = (int(v) for v in w.shape)
+    nbytes = query("ssq_stem_weight_prepared_bytes", Co, Ci, R, S)
+    if nbytes == 0:
+        raise A.SSQError(f"stem_weight_prepare: weight {tuple(w.shape)} is outside K31's geometry "
+                         f"(Ci <= {STEM_MAX_CI}, R, S <= {STEM_MAX_RS})")
+    blob = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    call("ssq_stem_weight_prepare", wp, Co, Ci, R, S, _vp(blob), stream_of(blob))
+    return StemWeight(blob, w.shape)
+
+
+def _stem_args(name, x, prepared, stride, padding):
+    if not isinstance(prepared, StemWeight):
+        raise A.SSQError(f"{name}: prepared must come from stem_weight_prepare")
+    x, xp = fptr(x, "x")
+    Co, Ci, R, S = prepared.shape
+    if x.dim() != 4 or int(x.shape[1]) != Ci:
+        raise A.SSQError(f"{name}: expected (N, {Ci}, H, W), got {tuple(x.shape)}")
+    N, _, H, W = (int(v) for v in x.shape)
+    (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
+    OH = (H + 2 * ph - R) // max(sh, 1) + 1
+    OW = (W + 2 * pw - S) // max(sw, 1) + 1
+    args = (xp, _vp(prepared.blob), prepared.blob.numel(), N, Ci, H, W, Co, R, S, sh, sw, ph, pw)
+    return x, args, (N, Co, max(OH, 0), max(OW, 0))
+
+
+def stem_conv(x, prepared, stride=1, padding=0):
+    """K31's fp32 form (ssq_stem_conv_fwd): the conv of an fp32 image x (N, Ci, H, W) with a
+    prepared weight as fp32 (N, Co, OH, OW), each output the k-ordered fp32 fma chain over
+    (ci, r, s) from +0 (include/ssq.h).  `stride`, `padding`: an int or (h, w)."""
+    x, args, (N, Co, OH, OW) = _stem_args("stem_conv", x, prepared, stride, padding)
+    y = torch.empty((N, Co, OH, OW), dtype=torch.float32, device=x.device)
+    call("ssq_stem_conv_fwd", *args, _vp(y), stream_of(y))
+    return y
+
+
+def stem_conv_codes(x, prepared, bias, gamma, phi, relu, out_delta, out_zp, out_bits, out_sym, bad,
+                    stride=1, padding=0):
+    """K31's code form (ssq_stem_conv_codes_fwd): epilogue_codes(stem_conv(x, prepared), ...)
+    byte for byte in one kernel, without the fp32 tensor.  The epilogue's arguments are
+    epilogue_codes'."""
+    if bad is None:
+        raise A.SSQError("stem_conv_codes: bad is required")
+    if (gamma is None) != (phi is None):
+        raise A.SSQError("stem_conv_codes: gamma and phi go together")
+    x, args, (N, Co, OH, OW) = _stem_args("stem_conv_codes", x, prepared, stride, padding)
+    held, vecs = _channel_vecs("stem_conv_codes", Co, bias, gamma, phi)
+    out = torch.empty((N, OH, OW, query("ssq_qinfer_cpad", Co)), dtype=torch.int8, device=x.device)
+    olo, ohi = qrange(out_bits, out_sym)
+    call("ssq_stem_conv_codes_fwd", *args, *vecs, int(relu), float(out_delta), float(out_zp), olo,
+         ohi, _vp(out), _vp(bad), stream_of(out))
+    return out
+
+
 def maxpool_codes(codes, k, stride, padding):
     """Max-pool (ssq_maxpool2d_fwd's geometry) on act_encode's int8 codes (N, H, W, Cpad) ->
     (N, OH, OW, Cpad) (ssq_maxpool_i8_fwd): the codes act_encode derives from the fp32 max-pool

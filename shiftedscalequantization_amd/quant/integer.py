@@ -22,7 +22,8 @@ module inputs, not residual adds or pooling:
   carry_blocks  TailEdge  a block's last conv with the residual add, the block's activation and
                           act quantizer in its kernel, read by the next block (`block_edges`)
   carry_stem    StemEdge  the stem conv's fp32 epilogue leaves as codes, max-pools behind it pool
-                          the codes, the first block reads them (`stem_edges`)
+                          the codes, the first block reads them (`stem_edges`); with
+                          `fused_stem` the conv itself emits them (K31, fp32 MFMA)
   carry_head    HeadEdge  the global average pool sums the last producer's codes and the fc runs
                           on the sums (`head_edges`); its logits are a function of the codes
                           alone, not bit for bit those of an fp32 mean and GEMM
@@ -40,6 +41,7 @@ host rule K.qconv_splits asks for it (the same bits; `split_report`), and `Integ
 the whole forward as one captured HIP graph.
 """
 import collections
+import os
 
 import torch
 import torch.nn as nn
@@ -290,6 +292,67 @@ class StemEdge(Edge):
         codes = K.epilogue_codes(out, bias, gamma, phi, m.act_code(), *self.grid, self.counter)
         return K.carried(codes, tuple(out.shape), *self.grid)
 
+    # fused_stem: `fuse` replaces `emit` on this instance; an edge planned without it has neither
+    # attribute below and runs the method above
+    def fuse(self, blob, stride, padding):
+        """From now on the conv itself emits (K31) wherever `stem_fused_takes` lets it."""
+        self.blob, self.stride, self.padding = blob, stride, padding
+        self.fused, self.unfused = 0, {}
+        self.emit = self.emit_fused
+
+    def emit_fused(self, x):
+        """K.stem_conv_codes: conv, epilogue and act quantizer in one kernel; an input or a
+        shape K31 is not to take goes the K27 way, counted by reason."""
+        m = self.at
+        why = None
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_cuda):
+            why = "input is not a 4-D device tensor"
+        elif x.dtype != torch.float32 or not x.is_contiguous():
+            why = "non-contiguous / non-fp32 input"
+        elif not stem_fused_takes(self.blob.shape, x.shape, self.stride, self.padding):
+            why = "shape rule: K27 is faster here (SSQ_STEM_FUSED=1 overrides)"
+        if why is None and not (self.live() and can_emit(m, m.act_quantizer, True, x)):
+            return None
+        if why is not None:
+            self.unfused[why] = self.unfused.get(why, 0) + 1
+            return StemEdge.emit(self, x)
+        gamma, phi = m.affine()
+        self.calls += 1
+        self.fused += 1
+        codes = K.stem_conv_codes(x, self.blob, m.bias, gamma, phi, m.act_code(), *self.grid,
+                                  self.counter, stride=self.stride, padding=self.padding)
+        N, H, W, _ = codes.shape
+        return K.carried(codes, (N, self.blob.shape[0], H, W), *self.grid)
+
+    def reset(self):
+        super().reset()
+        if "emit" in self.__dict__:
+            self.fused, self.unfused = 0, {}
+
+
+def fused_stem_reason(m):
+    """Why K31 cannot run QuantModule `m`'s conv, None when it can: an ungrouped F.conv2d inside
+    ssq_stem_conv_fwd's geometry (K.stem_geometry_reason)."""
+    if m.fwd_func is not F.conv2d:
+        return "not a conv"
+    kw = m.fwd_kwargs
+    if isinstance(kw.get("padding", 0), str):
+        return "geometry (padding given as a string)"
+    Co, Ci, R, S = (int(v) for v in m.weight.shape)
+    return K.stem_geometry_reason(Co, Ci, R, S, kw.get("stride", 1), kw.get("padding", 0),
+                                  kw.get("dilation", 1), int(kw.get("groups", 1)))
+
+
+def stem_fused_takes(wshape, xshape, stride, padding):
+    """The host shape rule of a fused stem edge ("Fused stem (K31)"): K31 takes every
+    shape class whose measured median saving over MIOpen + K27 exceeded that baseline's min-max
+    spread (profiles/int_infer_fused_stem_rate.txt).  SSQ_STEM_FUSED=1 / 0 forces K31 / K27 for
+    an A/B run; auto (the default) asks the rule."""
+    knob = os.environ.get("SSQ_STEM_FUSED", "auto")
+    if knob in ("0", "1"):
+        return knob == "1"
+    return True
+
 
 class HeadEdge(Edge):
     """The carried head (carry_head): the pool sums the codes that `emitter`, the edge of the
@@ -438,7 +501,7 @@ def _weight_codes(m, colscale=False, per_ci=False):
 @torch.no_grad()
 def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
                              carry_stem=False, carry_head=False, colscale=False, splitk=False,
-                             per_ci=False, wide=False):
+                             per_ci=False, wide=False, fused_stem=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
@@ -463,7 +526,13 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     int8 (|m| > 127, or a grid beyond 127) runs as two int8 digits, |m| <= 16319, L <= 1024, on
     K23's wide forms (dense layers only: never split along K, not the grouped kernels, not the
     pooled-operand fc); off, it is refused as leaving int8.  A weight with both a column scale and
-    a per-(co, ci) scale is refused."""
+    a per-(co, ci) scale is refused.  `fused_stem`: on every stem edge that `carry_stem` (or
+    `carry_head`) installs and whose producer is an ungrouped conv inside K31's geometry
+    (`fused_stem_reason`), the conv itself emits the codes (K.stem_conv_codes, a weight blob
+    prepared here from the producer's hard weight) instead of the fp32 conv + K27; it plans no
+    edge of its own, and `stem_carry_report` then also counts the fused forwards and names what
+    kept an edge or a forward on K27.  The stem's fp32 values are K31's fma chain, not the
+    library conv's: the logits are those of the `carry_stem` route up to that summation order."""
     carry_stem = carry_stem or carry_head
     carry_blocks = carry_blocks or carry_stem
     carry = carry or carry_blocks
@@ -598,6 +667,8 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         _plan_block_carry(qnn, source)
     if carry_stem:
         _plan_stem_carry(qnn, source)
+    if fused_stem:
+        _fuse_stems(qnn)
     if carry_head:
         _plan_head_carry(qnn, source, heads, report, sample)
     order = {m: i for i, m in enumerate(qnn.modules())}
@@ -743,6 +814,21 @@ def _plan_stem_carry(qnn, source):
             _install(qnn, StemEdge(prod, pools, succ, entry, readers))
 
 
+def _fuse_stems(qnn):
+    """fused_stem: every installed StemEdge whose producer K31 can run gets its weight blob and
+    emits through K.stem_conv_codes; `qnn._int_fused_stem`: {producer name: why not, or None}."""
+    names = {m: n for n, m in qnn.named_modules()}
+    qnn._int_fused_stem = {}
+    for e in _edges(qnn, StemEdge):
+        m = e.at
+        why = fused_stem_reason(m)
+        if why is None:
+            kw = m.fwd_kwargs
+            e.fuse(K.stem_weight_prepare(m._weight_bias()[0]), tuple(kw["stride"]),
+                   tuple(kw["padding"]))
+        qnn._int_fused_stem[names[m]] = why
+
+
 def head_edges(qnn):
     """The (producer, pool, fc) chains of the pooling head, from the structure alone (no device,
     no forward): the `head_chain()` the model declares on `qnn.model`, [last stage, pool,
@@ -848,6 +934,7 @@ def disable_integer_inference(qnn):
     for _, m in _layers(qnn):
         m._int_plan = None
     qnn._int_edges, qnn._int_counter = [], None
+    qnn._int_fused_stem = None
     # every enable passes here: a captured forward (IntegerGraph) of the previous plan is stale
     qnn._int_epoch = getattr(qnn, "_int_epoch", 0) + 1
 
@@ -900,12 +987,21 @@ def block_carry_report(qnn):
 def stem_carry_report(qnn):
     """{"edges": [(producer name, [pool names], successor name), ...] whose producer the
     installed plan lets emit int8 codes, "calls": {producer name: forwards that emitted codes},
-    "pooled": {pool name: forwards that pooled codes}}; empty without a plan."""
+    "pooled": {pool name: forwards that pooled codes}}; empty without a plan.  Under a plan
+    installed with `fused_stem`, also "fused": {producer name: forwards whose conv emitted the
+    codes itself (K31)} and "unfused": {producer name: why the edge stays on K27 (geometry,
+    grouped conv), or {reason: forwards of a fused edge that took K27 (non-contiguous / non-fp32
+    input, the shape rule)}}."""
     names = {m: n for n, m in qnn.named_modules()}
     stems = _edges(qnn, StemEdge)
-    return {"edges": [(names[e.at], [names[p] for p in e.pools], names[e.successor]) for e in stems],
-            "calls": {names[e.at]: e.calls for e in stems},
-            "pooled": {names[p]: k for e in stems for p, k in e.pooled.items()}}
+    rep = {"edges": [(names[e.at], [names[p] for p in e.pools], names[e.successor]) for e in stems],
+           "calls": {names[e.at]: e.calls for e in stems},
+           "pooled": {names[p]: k for e in stems for p, k in e.pooled.items()}}
+    why = getattr(qnn, "_int_fused_stem", None)
+    if why is not None:
+        rep["fused"] = {names[e.at]: getattr(e, "fused", 0) for e in stems}
+        rep["unfused"] = {names[e.at]: why[names[e.at]] or dict(e.unfused) for e in stems}
+    return rep
 
 
 def head_carry_report(qnn):
@@ -964,21 +1060,26 @@ class IntegerGraph:
         return [k[0] for k in self._shapes]
 
     def _cells(self):
-        """The Python-side forward counters: (object, attribute) and (edge, pool) cells."""
+        """The Python-side forward counters: (object, None) for `calls`, (edge, name) for a named
+        counter, (edge, pool) for `pooled[pool]`."""
         qnn = self.qnn
         edges = list(qnn._int_edges) + [e.emitter for e in qnn._int_edges if e.emitter is not None]
         cells = [(p, None) for _, p in _plans(qnn)] + [(e, None) for e in edges]
+        cells += [(e, "fused") for e in edges if "emit" in e.__dict__]    # a fused StemEdge
         return cells + [(e, m) for e in edges for m in e.pools]
 
     @staticmethod
     def _read(cells):
-        return [o.calls if m is None else o.pooled[m] for o, m in cells]
+        return [o.calls if m is None else getattr(o, m) if isinstance(m, str) else o.pooled[m]
+                for o, m in cells]
 
     @staticmethod
     def _add(cells, by):
         for (o, m), d in zip(cells, by):
             if m is None:
                 o.calls += d
+            elif isinstance(m, str):
+                setattr(o, m, getattr(o, m) + d)
             else:
                 o.pooled[m] += d
 
