@@ -867,6 +867,58 @@ int ssq_stem_conv_codes_fwd(const float* x, const void* prepared, size_t prepare
                             int act, float out_delta, float out_zero_point, int out_qmin,
                             int out_qmax, int8_t* out_codes, uint32_t* bad, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- uint8 stem (K32)
+ * The stem conv of a uint8 image on the int8 MFMA.  The image is x = (u/255 - mean[c]) / std[c]
+ * with u [Nb, Ci, H, W] uint8 NCHW, the weight W_hat = (q_w - z_w[co]) * d[co, c] (packed codes as
+ * ssq_qweight_prepare takes them; d per co or per (co, ci)).  With the caller's two fp32 tables
+ *     M[c] = fp32(255 * mean[c])        s[co, c] = fp32(fp32(1 / fp32(255 * std[c])) * d[co, c])
+ * (s as [Co][Ci]) and, per (pixel, co, c) over the taps of the window inside the image, the exact
+ * integers B_c = sum (q_w - z_w[co]) and A_c = sum (q_w - z_w[co]) * u (a padded tap is x = 0 and
+ * enters neither; |A_c| <= 49 * 767 * 255 < 2^24),
+ *     t_c = fp32(A_c) - M[c] * fp32(B_c)
+ *     y   = t_0 * s[co, 0];  y = y + t_c * s[co, c],  c = 1 .. Ci - 1 ascending
+ * every product, difference and sum rounded once, no FMA: a host float32 loop gives the same bits.
+ *
+ * ssq_stem_u8_weight_prepare (once per layer): packed codes + zp[co] -> the operand,
+ * ssq_stem_u8_weight_prepared_bytes(Co, Ci, R, S) bytes (csrc/qinfer_layout.h, ULayout; 0 bytes
+ * outside 1 <= Ci <= 4, 1 <= R, S <= 7, Co >= 1): int8 q_w - (qmin + 128) as [Ci][Cop][64], the
+ * vector cwz[co] = qmin + 128 - z_w[co] and the full-window sums T[c][co].  ADDS to *bad the number
+ * of channels whose zp is not an integer in [qmin-256, qmin+511] (taken as qmin), as K22 does.
+ * ssq_stem_conv_u8_fwd: y as fp32 NCHW [Nb, Co, OH, OW].
+ * ssq_stem_conv_u8_codes_fwd: qepi_code_y on each y, i.e. ssq_epilogue_codes_fwd's arguments,
+ * checks and bytes for the fp32 form's y (NHWC int8 [Nb*OH*OW][qinfer_cpad(Co)], padded channels 0,
+ * every byte written, a NaN q stored as out_qmin and ADDED to *bad) without the fp32 tensor.
+ * A workgroup whose tile has every tap inside the image reads B_c from T and skips the validity
+ * sums; every_tile_border != 0 makes every workgroup compute them (the same bits: an A/B and test
+ * knob).  ssq_stem_u8_tiles: the workgroups of a launch of this geometry (codes: the code form's)
+ * that take the interior and the border path.
+ *
+ * Refused with SSQ_E_ARG before any launch: a null pointer, the geometry above, strides < 1,
+ * pad_h >= R or pad_w >= S or negative, an empty output, prepared_bytes below the blob's size, a
+ * prepared pointer that is not 16-byte aligned (the kernel reads the weight rows as 16-byte
+ * vectors), a tensor of 2^31 elements or more.  No allocation, no sync, no float atomics,
+ * capturable.                                                                                  */
+size_t ssq_stem_u8_weight_prepared_bytes(int64_t Co, int64_t Ci, int64_t R, int64_t S);
+int ssq_stem_u8_weight_prepare(const void* packed, const float* zp, int64_t Co, int64_t Ci,
+                               int64_t R, int64_t S, int n_bits, int qmin, void* prepared,
+                               uint32_t* bad, ssq_stream_t stream);
+int ssq_stem_u8_tiles(int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R,
+                      int64_t S, int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                      int codes, int64_t* interior, int64_t* border);
+int ssq_stem_conv_u8_fwd(const uint8_t* u, const void* prepared, size_t prepared_bytes,
+                         const float* M, const float* s, int64_t Nb, int64_t Ci, int64_t H,
+                         int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride_h,
+                         int64_t stride_w, int64_t pad_h, int64_t pad_w, int every_tile_border,
+                         float* y, ssq_stream_t stream);
+int ssq_stem_conv_u8_codes_fwd(const uint8_t* u, const void* prepared, size_t prepared_bytes,
+                               const float* M, const float* s, int64_t Nb, int64_t Ci, int64_t H,
+                               int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride_h,
+                               int64_t stride_w, int64_t pad_h, int64_t pad_w,
+                               int every_tile_border, const float* bias, const float* gamma,
+                               const float* phi, int act, float out_delta, float out_zero_point,
+                               int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad,
+                               ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- column-scaled weights
  * A weight with a per-column input scale on a common integer grid,
  *     W_hat[co, j] = ((q_w - z_w[co]) * d1[co]) * c[j],  c[j] = fp32(kcol[j] / L),  j = (ci, r, s)

@@ -73,6 +73,8 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
                                                      head_carry_report, integer_report,
                                                      split_report, stem_carry_report)
     fused = {'fused_stem': True} if getattr(args, 'int_infer_fused_stem', False) else {}
+    u8 = getattr(args, 'int_infer_u8_images', False)
+    image_u8 = {'image_u8': (IMAGENET_MEAN, IMAGENET_STD)} if u8 else {}
     plan = enable_integer_inference(qnn, cali[:8], grouped=args.int_infer_grouped,
                                     carry=args.int_infer_carry,
                                     carry_blocks=args.int_infer_carry_blocks,
@@ -81,7 +83,7 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
                                     colscale=args.int_infer_colscale,
                                     splitk=args.int_infer_splitk,
                                     per_ci=args.int_infer_per_ci, wide=args.int_infer_wide,
-                                    **fused)
+                                    **fused, **image_u8)
     n_int = sum(v == 'int8' for v in plan.values())
     print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')
     if args.int_infer_carry:
@@ -100,13 +102,18 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
         why = stem_carry_report(qnn)['unfused']
         print('integer inference: stem conv emitting its own codes (K31): '
               + ', '.join(f'{n}: {"yes" if not w else w}' for n, w in why.items()))
+    if u8:
+        print('integer inference: uint8 images, stem conv on the int8 MFMA (K32): '
+              + ', '.join(f'{n}: {"yes" if not w else w}' for n, w in qnn._int_u8.items()))
     if args.int_infer_carry_head:
         edges = head_carry_report(qnn)['edges']
         print(f'integer inference: int8 codes carried to the logits along {len(edges)} head '
               'edges: ' + ', '.join(' -> '.join(e) for e in edges))
     for name, why in plan.items():
         print(f'  {name}: {why}')
-    if loader is not None:
+    if u8:
+        run_u8_images(qnn, args, cali, loader, bs)
+    elif loader is not None:
         acc = validate_model(loader, qnn, graph=args.int_infer_graph)
         print('Integer inference (W{}A{}) accuracy: {}'.format(args.n_bits_w, args.n_bits_a, acc))
     elif args.int_infer_graph:
@@ -119,6 +126,53 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
         print(f'integer inference: {len(split)} layers split along K: '
               + ', '.join(f'{n} x{z}' for n, z in split.items()))
     print(f'integer inference: {integer_report(qnn)["off_grid"]} off-grid activations')
+
+
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def to_u8(images):
+    """A float image batch back on the loader's uint8 grid; a uint8 batch passes as it is.  A float
+    batch is taken to be normalised with IMAGENET_MEAN / IMAGENET_STD, the values `image_u8` gets:
+    a validation set normalised otherwise has to be stored as uint8."""
+    if images.dtype == torch.uint8:
+        return images
+    mean = torch.tensor(IMAGENET_MEAN, device=images.device).reshape(1, 3, 1, 1)
+    std = torch.tensor(IMAGENET_STD, device=images.device).reshape(1, 3, 1, 1)
+    return ((images * std + mean) * 255).round().clamp(0, 255).to(torch.uint8)
+
+
+def run_u8_images(qnn, args, cali, loader, bs):
+    """--int_infer_u8_images: validation (or one synthetic batch drawn as uint8) on uint8 images,
+    then the same batches normalised to fp32 through the same plan, and the stem report."""
+    from shiftedscalequantization_amd.quant import IntegerGraph, stem_carry_report
+    from shiftedscalequantization_amd.quant.integer import normalise_u8
+    dev = cali.device
+    mean = torch.tensor(IMAGENET_MEAN, device=dev).reshape(1, 3, 1, 1)
+    std = torch.tensor(IMAGENET_STD, device=dev).reshape(1, 3, 1, 1)
+    if loader is not None:
+        # one batch at a time in each pass: no second copy of the validation set
+        acc = validate_model(((to_u8(x), t) for x, t in loader), qnn, graph=args.int_infer_graph)
+        print('Integer inference on uint8 images (W{}A{}) accuracy: {}'.format(
+            args.n_bits_w, args.n_bits_a, acc))
+        acc = validate_model(((normalise_u8(to_u8(x), mean.cpu(), std.cpu()), t) for x, t in loader),
+                             qnn, graph=args.int_infer_graph)
+        print('Integer inference on the same images normalised to fp32 (W{}A{}) accuracy: {}'.format(
+            args.n_bits_w, args.n_bits_a, acc))
+    else:
+        g = torch.Generator().manual_seed(args.seed)
+        u = torch.randint(0, 256, (bs,) + tuple(cali.shape[1:]), generator=g, dtype=torch.uint8).to(dev)
+        forward = IntegerGraph(qnn) if args.int_infer_graph else qnn
+        with torch.no_grad():
+            out_u8 = forward(u).clone()
+            out_f32 = forward(normalise_u8(u, mean, std)).clone()
+        diff = (out_u8 - out_f32).abs().max().item()
+        same = (out_u8.argmax(1) == out_f32.argmax(1)).float().mean().item()
+        print(f'integer inference: one uint8 batch of {bs}: max |logit difference| to the same batch '
+              f'normalised to fp32 {diff:.4g}, same top-1 on {100 * same:.1f}%')
+    rep = stem_carry_report(qnn)
+    print(f'integer inference: uint8 stem forwards on K32: {rep["u8"]}; normalised on the device '
+          f'instead, by reason: {rep["un_u8"]}')
 
 
 def main(argv=None):

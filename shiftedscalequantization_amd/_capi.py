@@ -156,6 +156,12 @@ SIGNATURES = {
     "ssq_stem_conv_fwd": (_i, [_p, _p, _sz] + [_i64] * 11 + [_p, _p]),
     "ssq_stem_conv_codes_fwd": (_i, [_p, _p, _sz] + [_i64] * 11 + [_p, _p, _p, _i, _f, _f, _i, _i,
                                                                   _p, _p, _p]),
+    "ssq_stem_u8_weight_prepared_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "ssq_stem_u8_weight_prepare": (_i, [_p, _p, _i64, _i64, _i64, _i64, _i, _i, _p, _p, _p]),
+    "ssq_stem_u8_tiles": (_i, [_i64] * 11 + [_i, _p, _p]),
+    "ssq_stem_conv_u8_fwd": (_i, [_p, _p, _sz, _p, _p] + [_i64] * 11 + [_i, _p, _p]),
+    "ssq_stem_conv_u8_codes_fwd": (_i, [_p, _p, _sz, _p, _p] + [_i64] * 11 + [_i, _p, _p, _p, _i, _f,
+                                                                           _f, _i, _i, _p, _p, _p]),
     "ssq_avgpool_i8_digits_fwd": (_i, [_p] + [_i64] * 4 + [_p, _p, _p, _p]),
     "ssq_qlinear_pooled_fwd": (_i, [_p] * 5 + [_i64] * 4 + [_f, _i, _i, _p, _p]),
     "ssq_qlinear_pooled_set_tile": (_i, [_i]),

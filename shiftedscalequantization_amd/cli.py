@@ -96,6 +96,11 @@ def build_parser():
                    help='--int_infer_carry_stem with the stem conv itself emitting the int8 codes '
                         '(fp32-MFMA conv with a stated summation order, no fp32 tensor and no '
                         'library conv; DESIGN 4 "Fused stem (K31)"); implies --int_infer_carry_stem')
+    p.add_argument('--int_infer_u8_images', action='store_true',
+                   help='with --int_infer_carry_stem or --int_infer_carry_head: the integer route is '
+                        'fed uint8 images (x = (u/255 - mean)/std, the ImageNet mean / std) and the '
+                        'stem conv runs on the int8 MFMA (K32; DESIGN 4 "uint8 stem (K32)"); it '
+                        'implies none of them and is an error without a stem edge')
     p.add_argument('--int_infer_colscale', action='store_true',
                    help='--int_infer with column-scaled weights (ChannelQuantMSE, the --test path) '
                         'on integer codes too: the column scale as integers k / L, L <= 127, folded '
@@ -131,11 +136,15 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    a = build_parser().parse_args(argv)
+    parser = build_parser()
+    a = parser.parse_args(argv)
     if a.run_device:
         a.device_gpu = a.run_device
     if a.int_infer_carry_head or a.int_infer_fused_stem:
         a.int_infer_carry_stem = True
+    if a.int_infer_u8_images and not a.int_infer_carry_stem:
+        parser.error('--int_infer_u8_images needs a stem edge: --int_infer_carry_stem, '
+                     '--int_infer_carry_head or --int_infer_fused_stem')
     if a.int_infer_carry_stem:
         a.int_infer_carry_blocks = True
     if a.int_infer_carry_blocks:

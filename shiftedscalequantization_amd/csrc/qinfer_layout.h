@@ -44,6 +44,26 @@ static inline SLayout slayout(int64_t Co, int64_t Ci, int64_t R, int64_t S) {
   return L;
 }
 
+// ULayout, K32's blob (qinfer_stemu8.hip): per input channel c the int8 rows w_s = q - (qmin + 128)
+// as [Ci][Cop][64], k = r*S + s (R*S <= 49 taps, zero from R*S on, a padded channel all zero), the
+// order the 16x16x64 int8 MFMA takes its A operand (row = channel, 16 k per lane); then
+// cwz[Cop] = qmin + 128 - z_w[co] and T[Ci][Cop] = sum over every tap of (q - z_w[co]) (int32).
+struct ULayout {
+  int64_t RS, Cop;
+  size_t off_cwz, off_t, bytes;   // bytes 0: outside K32's geometry (K31's)
+};
+
+static inline ULayout ulayout(int64_t Co, int64_t Ci, int64_t R, int64_t S) {
+  ULayout L = {};
+  if (!slayout(Co, Ci, R, S).bytes) return L;
+  L.RS = R * S;
+  L.Cop = (Co + 15) / 16 * 16;
+  L.off_cwz = (size_t)(Ci * L.Cop) * 64;
+  L.off_t = L.off_cwz + (size_t)L.Cop * 4;
+  L.bytes = L.off_t + (size_t)(Ci * L.Cop) * 4;
+  return L;
+}
+
 constexpr int kQT = 64;     // pixels, channels and k per tile step
 constexpr int kQRow = 80;   // LDS row stride in bytes (64 + 16)
 constexpr int64_t kQMaxK = 65536;

@@ -2600,6 +2600,155 @@ def stem_conv_codes(x, prepared, bias, gamma, phi, relu, out_delta, out_zp, out_
     return out
 
 
+# ------------------------------------------------------------------ K32 uint8 stem conv
+class StemU8Weight:
+    """A stem weight prepared for K32 (stem_u8_weight_prepare): `blob`, the device bytes;
+    `shape`, the weight's (Co, Ci, R, S); `bad`, the device word of the zero points that are not
+    integer codes."""
+
+    def __init__(self, blob, shape, bad):
+        self.blob, self.shape, self.bad = blob, tuple(int(v) for v in shape), bad
+
+
+def stem_u8_geometry_reason(Co, Ci, R, S, stride, padding, dilation=1, groups=1):
+    """Why K32 does not take this conv, None when it does: K31's geometry
+    (ssq_stem_conv_u8_fwd's), by its refusals' names -- a grouped stem, Ci > 4, R or S > 7,
+    dilation != 1, padding not below the kernel."""
+    (sh, sw), (ph, pw), (dh, dw) = _pair(stride), _pair(padding), _pair(dilation)
+    if groups != 1:
+        return "grouped conv"
+    if not 1 <= Ci <= STEM_MAX_CI:
+        return f"Ci = {Ci} exceeds {STEM_MAX_CI}"
+    if not (1 <= R <= STEM_MAX_RS and 1 <= S <= STEM_MAX_RS):
+        return f"kernel {R}x{S} exceeds {STEM_MAX_RS}x{STEM_MAX_RS}"
+    if (dh, dw) != (1, 1):
+        return f"dilation {(dh, dw)} != 1"
+    if not (0 <= ph < R and 0 <= pw < S):
+        return f"padding {(ph, pw)} not below the kernel {R}x{S}"
+    if Co < 1 or sh < 1 or sw < 1:
+        return f"geometry (Co {Co}, stride {(sh, sw)})"
+    return None
+
+
+def stem_u8_weight_prepare(packed, shape, zp, n_bits, qmin):
+    """Packed codes (pack_encode's layout) + zp[co] of a stem weight `shape` = (Co, Ci <= 4,
+    R <= 7, S <= 7) -> StemU8Weight, the operand of stem_conv_u8 / stem_conv_u8_codes
+    (ssq_stem_u8_weight_prepare; layout: csrc/qinfer_layout.h, ULayout).  Its `bad` counts the
+    channels whose zero point is not an integer code, as qweight_prepare's."""
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
+        raise A.SSQError("stem_u8_weight_prepare: packed codes must be a uint8 tensor")
+    packed = _i8_dev(packed, "stem_u8_weight_prepare")
+    if len(shape) != 4:
+        raise A.SSQError(f"stem_u8_weight_prepare: expected (Co, Ci, R, S), got {tuple(shape)}")
+    Co, Ci, R, S = (int(v) for v in shape)
+    nbytes = query("ssq_stem_u8_weight_prepared_bytes", Co, Ci, R, S)
+    if nbytes == 0:
+        raise A.SSQError(f"stem_u8_weight_prepare: weight {tuple(shape)} is outside K32's geometry "
+                         f"(Ci <= {STEM_MAX_CI}, R, S <= {STEM_MAX_RS})")
+    if packed.numel() < query("ssq_pack_bytes", Co * Ci * R * S, n_bits):
+        raise A.SSQError("stem_u8_weight_prepare: packed buffer too small for the shape")
+    z, zpp = fptr(zp.detach().reshape(-1), "zero_point")
+    if z.numel() != Co:
+        raise A.SSQError("stem_u8_weight_prepare: zero point must have one entry per output channel")
+    blob = torch.empty(nbytes, dtype=torch.uint8, device=packed.device)
+    bad = torch.zeros(1, dtype=torch.int32, device=packed.device)
+    call("ssq_stem_u8_weight_prepare", _vp(packed), zpp, Co, Ci, R, S, int(n_bits), int(qmin),
+         _vp(blob), _vp(bad), stream_of(packed))
+    return StemU8Weight(blob, shape, bad)
+
+
+def stem_u8_tables(mean, std, scale, Co, Ci):
+    """The two fp32 tables of K32 in their stated operation order ("uint8 stem (K32)"):
+    M[c] = fp32(255 * mean[c]) and s[co, c] = fp32(fp32(1 / fp32(255 * std[c])) * d[co, c]), from
+    the caller's fp32 per-channel `mean`, `std` (Ci entries each) and the weight's scale d, `scale`:
+    Co entries (per co) or Co * Ci (per (co, ci)).  Each operation is one fp32 torch operation on
+    the scale's device; returns (M [Ci], s [Co, Ci]), contiguous."""
+    d = torch.as_tensor(scale).detach().float()
+    dev = d.device
+    mean = torch.as_tensor(mean, dtype=torch.float32).detach().reshape(-1).to(dev)
+    std = torch.as_tensor(std, dtype=torch.float32).detach().reshape(-1).to(dev)
+    if mean.numel() != Ci or std.numel() != Ci:
+        raise A.SSQError(f"stem_u8_tables: mean and std must have {Ci} entries")
+    if d.numel() == Co:
+        d = d.reshape(Co, 1).expand(Co, Ci)
+    elif d.numel() == Co * Ci:
+        d = d.reshape(Co, Ci)
+    else:
+        raise A.SSQError(f"stem_u8_tables: scale must have {Co} or {Co * Ci} entries")
+    c255 = torch.full((1,), 255.0, dtype=torch.float32, device=dev)
+    M = (c255 * mean).contiguous()
+    inv = torch.ones(1, dtype=torch.float32, device=dev) / (c255 * std)
+    return M, (inv.reshape(1, Ci) * d).contiguous()
+
+
+def _stem_u8_args(name, u, prepared, M, s, stride, padding, every_tile_border):
+    if not isinstance(prepared, StemU8Weight):
+        raise A.SSQError(f"{name}: prepared must come from stem_u8_weight_prepare")
+    if not isinstance(u, torch.Tensor) or u.dtype != torch.uint8:
+        raise A.SSQError(f"{name}: the image must be a uint8 tensor")
+    u = _i8_dev(u, name)
+    Co, Ci, R, S = prepared.shape
+    if u.dim() != 4 or int(u.shape[1]) != Ci:
+        raise A.SSQError(f"{name}: expected (N, {Ci}, H, W), got {tuple(u.shape)}")
+    M, Mp = fptr(M.detach().reshape(-1), "M")
+    s, sp = fptr(s.detach().reshape(-1), "s")
+    if M.numel() != Ci or s.numel() != Co * Ci:
+        raise A.SSQError(f"{name}: M must have {Ci} entries and s {Co} x {Ci} (stem_u8_tables)")
+    N, _, H, W = (int(v) for v in u.shape)
+    (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
+    OH = (H + 2 * ph - R) // max(sh, 1) + 1
+    OW = (W + 2 * pw - S) // max(sw, 1) + 1
+    args = (_vp(u), _vp(prepared.blob), prepared.blob.numel(), Mp, sp, N, Ci, H, W, Co, R, S, sh,
+            sw, ph, pw, int(bool(every_tile_border)))
+    return (u, M, s), args, (N, Co, max(OH, 0), max(OW, 0))
+
+
+def stem_u8_tiles(prepared, ushape, stride=1, padding=0, codes=True):
+    """(interior, border): the workgroups of stem_conv_u8_codes (`codes`; else stem_conv_u8) on an
+    image of `ushape` that read B_c from the blob's full-window sums, and those that sum the valid
+    taps (ssq_stem_u8_tiles; host only)."""
+    Co, Ci, R, S = prepared.shape
+    N, _, H, W = (int(v) for v in ushape)
+    (sh, sw), (ph, pw) = _pair(stride), _pair(padding)
+    inner, border = C.c_int64(0), C.c_int64(0)
+    call("ssq_stem_u8_tiles", N, Ci, H, W, Co, R, S, sh, sw, ph, pw, int(bool(codes)),
+         C.byref(inner), C.byref(border))
+    return int(inner.value), int(border.value)
+
+
+def stem_conv_u8(u, prepared, M, s, stride=1, padding=0, every_tile_border=False):
+    """K32's fp32 form (ssq_stem_conv_u8_fwd): the stem conv of the uint8 image u (N, Ci, H, W),
+    standing for x = (u/255 - mean)/std, with a prepared weight and the tables of stem_u8_tables,
+    as fp32 (N, Co, OH, OW) in the stated operation order (include/ssq.h).  `stride`, `padding`:
+    an int or (h, w).  `every_tile_border`: no workgroup takes the interior shortcut (the same
+    bits)."""
+    keep, args, (N, Co, OH, OW) = _stem_u8_args("stem_conv_u8", u, prepared, M, s, stride, padding,
+                                                every_tile_border)
+    y = torch.empty((N, Co, OH, OW), dtype=torch.float32, device=keep[0].device)
+    call("ssq_stem_conv_u8_fwd", *args, _vp(y), stream_of(y))
+    return y
+
+
+def stem_conv_u8_codes(u, prepared, M, s, bias, gamma, phi, relu, out_delta, out_zp, out_bits,
+                       out_sym, bad, stride=1, padding=0, every_tile_border=False):
+    """K32's code form (ssq_stem_conv_u8_codes_fwd): epilogue_codes(stem_conv_u8(u, ...), ...) byte
+    for byte in one kernel, without the fp32 tensor.  The epilogue's arguments are
+    stem_conv_codes'."""
+    if bad is None:
+        raise A.SSQError("stem_conv_u8_codes: bad is required")
+    if (gamma is None) != (phi is None):
+        raise A.SSQError("stem_conv_u8_codes: gamma and phi go together")
+    keep, args, (N, Co, OH, OW) = _stem_u8_args("stem_conv_u8_codes", u, prepared, M, s, stride,
+                                                padding, every_tile_border)
+    held, vecs = _channel_vecs("stem_conv_u8_codes", Co, bias, gamma, phi)
+    out = torch.empty((N, OH, OW, query("ssq_qinfer_cpad", Co)), dtype=torch.int8,
+                      device=keep[0].device)
+    olo, ohi = qrange(out_bits, out_sym)
+    call("ssq_stem_conv_u8_codes_fwd", *args, *vecs, int(relu), float(out_delta), float(out_zp),
+         olo, ohi, _vp(out), _vp(bad), stream_of(out))
+    return out
+
+
 def maxpool_codes(codes, k, stride, padding):
     """Max-pool (ssq_maxpool2d_fwd's geometry) on act_encode's int8 codes (N, H, W, Cpad) ->
     (N, OH, OW, Cpad) (ssq_maxpool_i8_fwd): the codes act_encode derives from the fp32 max-pool

@@ -324,10 +324,127 @@ class StemEdge(Edge):
         N, H, W, _ = codes.shape
         return K.carried(codes, (N, self.blob.shape[0], H, W), *self.grid)
 
+    # image_u8: `take_u8` puts `emit_u8` in front of whichever emit the edge has; an edge planned
+    # without it has none of the attributes below
+    def take_u8(self, norm, why, prepared=None, tables=None, stride=None, padding=None):
+        """From now on a uint8 image goes to K32 wherever `stem_u8_takes` lets it; `why`: what
+        keeps this edge's conv off K32 altogether (`u8_stem_reason`), its uint8 batches are then
+        normalised (`norm`: mean, std as (1, Ci, 1, 1) device tensors) for the fp32 emit."""
+        self.u8_norm, self.u8_why = norm, why
+        self.u8_blob, self.u8_tables, self.u8_geo = prepared, tables, (stride, padding)
+        self.u8, self.un_u8 = 0, ({} if why is None else {why: 0})
+        self._emit_f32, self._u8_declined = self.emit, False
+        self.emit = self.emit_u8
+
+    def emit_u8(self, x):
+        """K.stem_conv_u8_codes on a uint8 image: conv, epilogue and act quantizer in one kernel on
+        the int8 MFMA; an fp32 input takes the edge's fp32 emit untouched, a uint8 input K32 is
+        not to take is normalised on the device and takes it too, counted by reason."""
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.uint8):
+            # the normalised batch of the branch below, back through the module's forward: its
+            # fp32 emit has already declined it
+            return None if self._u8_declined else self._emit_f32(x)
+        m = self.at
+        why = self.u8_why
+        if why is None:
+            if not (x.dim() == 4 and x.is_cuda):
+                why = U8_NOT_4D
+            elif not x.is_contiguous():
+                why = (U8_NHWC if x.is_contiguous(memory_format=torch.channels_last)
+                       else U8_STRIDED)
+            elif not stem_u8_takes(self.u8_blob.shape, x.shape, *self.u8_geo):
+                why = U8_SHAPE_RULE
+            elif not (self.live() and can_emit(m, m.act_quantizer, True, x)):
+                why = U8_NOT_LIVE
+        if why is not None:
+            self.un_u8[why] = self.un_u8.get(why, 0) + 1
+            # contiguous first (a quarter of the fp32 copy's bytes): the fp32 emit's own rules then
+            # see the layout K31 takes
+            xf = normalise_u8(x.contiguous(), *self.u8_norm)
+            out = self._emit_f32(xf)
+            if out is not None:
+                return out
+            self._u8_declined = True        # the fp32 emit is asked once per forward
+            try:
+                return m.forward(xf)
+            finally:
+                self._u8_declined = False
+        gamma, phi = m.affine()
+        self.calls += 1
+        self.u8 += 1
+        stride, padding = self.u8_geo
+        codes = K.stem_conv_u8_codes(x, self.u8_blob, *self.u8_tables, m.bias, gamma, phi,
+                                     m.act_code(), *self.grid, self.counter, stride=stride,
+                                     padding=padding)
+        N, H, W, _ = codes.shape
+        return K.carried(codes, (N, self.u8_blob.shape[0], H, W), *self.grid)
+
     def reset(self):
         super().reset()
-        if "emit" in self.__dict__:
+        if "fused" in self.__dict__:
             self.fused, self.unfused = 0, {}
+        if "u8" in self.__dict__:
+            self.u8, self.un_u8 = 0, ({} if self.u8_why is None else {self.u8_why: 0})
+
+
+# what keeps one uint8 forward of an edge that takes K32 off it (`un_u8`'s per-forward reasons)
+U8_NOT_4D = "input is not a 4-D device tensor"
+U8_NHWC, U8_STRIDED = "channels-last input", "non-contiguous input"
+U8_SHAPE_RULE = "shape rule: K31 is faster here (SSQ_STEM_U8=1 overrides)"
+U8_NOT_LIVE = "the stem edge does not carry in this state"
+U8_FORWARD_REASONS = (U8_NOT_4D, U8_NHWC, U8_STRIDED, U8_SHAPE_RULE, U8_NOT_LIVE)
+
+
+def normalise_u8(u, mean, std):
+    """The loader's normalisation of a uint8 image batch as three torch operations:
+    (u.float() / 255 - mean) / std."""
+    return (u.float() / 255 - mean) / std
+
+
+def u8_stem_reason(m, fields=None):
+    """Why K32 cannot run QuantModule `m`'s conv on a uint8 image, None when it can: an ungrouped
+    F.conv2d inside ssq_stem_conv_u8_fwd's geometry (K.stem_u8_geometry_reason), no forward hook
+    on it, and -- `fields`, the hard weight's dequant fields -- a weight without a column scale
+    whose zero points are integer codes."""
+    if m.fwd_func is not F.conv2d:
+        return "not a conv"
+    kw = m.fwd_kwargs
+    if isinstance(kw.get("padding", 0), str):
+        return "padding given as a string"
+    Co, Ci, R, S = (int(v) for v in m.weight.shape)
+    why = K.stem_u8_geometry_reason(Co, Ci, R, S, kw.get("stride", 1), kw.get("padding", 0),
+                                    kw.get("dilation", 1), int(kw.get("groups", 1)))
+    if why is not None:
+        return why
+    if _hooked(m):
+        return "a forward hook on the producer"
+    if fields is not None:
+        if fields["col_scale"] is not None:
+            return (f"weight has a column scale ({fields['kind']}): (q - z) * k leaves int8 at 8 "
+                    "bits and would need the two-digit operand")
+        zp, qmin = fields["zero_point"].detach().float().reshape(-1), int(fields["qmin"])
+        if not bool(((zp == zp.round()) & (zp >= qmin - 256) & (zp <= qmin + 511)).all()):
+            return "weight zero point is not an integer code"
+    return None
+
+
+def stem_u8_takes(wshape, xshape, stride, padding):
+    """The host shape rule of a uint8 stem edge ("uint8 stem (K32)"): K32 takes a shape
+    class only where its measured median saving over K31 fed the normalised image exceeded that
+    baseline's min-max spread (profiles/int_infer_u8_stem_rate.txt); elsewhere the batch is
+    normalised on the device and takes K31.  Measured at batch 64: the 7x7/2 stem on a 32 x 32
+    image clears it (36.8 -> 34.3 us, spread 0.1), on a 224 x 224 image it does not (280.4 ->
+    283.3), nor does the 3x3/2 stem there (62.3 -> 129.0: nine of the k step's 64 taps are
+    real).  So auto takes K32 for the measured class, a 7x7 kernel at stride 2 on at most
+    64 x 16 x 16 output pixels, and nothing else; a smaller batch of that class is taken by
+    extrapolation (fewer pixels are more launch-bound, not measured).  SSQ_STEM_U8=1 / 0 forces
+    K32 / the normalised route for an A/B run; auto (the default) asks the rule."""
+    knob = os.environ.get("SSQ_STEM_U8", "auto")
+    if knob in ("0", "1"):
+        return knob == "1"
+    (_, _, R, S), (N, _, H, W), (sh, sw), (ph, pw) = wshape, xshape, stride, padding
+    pixels = int(N) * ((int(H) + 2 * ph - R) // sh + 1) * ((int(W) + 2 * pw - S) // sw + 1)
+    return (R, S, sh, sw) == (7, 7, 2, 2) and pixels <= 64 * 16 * 16
 
 
 def fused_stem_reason(m):
@@ -501,7 +618,7 @@ def _weight_codes(m, colscale=False, per_ci=False):
 @torch.no_grad()
 def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
                              carry_stem=False, carry_head=False, colscale=False, splitk=False,
-                             per_ci=False, wide=False, fused_stem=False):
+                             per_ci=False, wide=False, fused_stem=False, image_u8=None):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
@@ -532,8 +649,23 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     prepared here from the producer's hard weight) instead of the fp32 conv + K27; it plans no
     edge of its own, and `stem_carry_report` then also counts the fused forwards and names what
     kept an edge or a forward on K27.  The stem's fp32 values are K31's fma chain, not the
-    library conv's: the logits are those of the `carry_stem` route up to that summation order."""
+    library conv's: the logits are those of the `carry_stem` route up to that summation order.
+    `image_u8` = (mean, std), the loader's per-channel normalisation: a forward whose input is a
+    uint8 image batch (N, Ci, H, W; x = (u/255 - mean)/std) runs the stem conv on the int8 MFMA
+    (K32, K.stem_conv_u8_codes; DESIGN 4 "uint8 stem (K32)") on every stem edge whose producer
+    passes `u8_stem_reason`, its blob and tables prepared here.  It plans no edge of its own and
+    needs `carry_stem` and an installed stem edge (ValueError without either, the plan removed); it is independent of `fused_stem`.  An fp32 input
+    takes exactly the path it takes without the keyword; a uint8 input K32 does not take is
+    normalised on the device and takes that path too.  `stem_carry_report` then also counts the
+    K32 forwards ("u8") and the normalised ones by reason ("un_u8").  The stem codes of a uint8
+    forward are K32's own contract's, not pinned to the fp32 routes'; `sample` may be uint8."""
     carry_stem = carry_stem or carry_head
+    if image_u8 is not None:
+        if not carry_stem:
+            raise ValueError("enable_integer_inference: image_u8 needs a stem edge (carry_stem or "
+                             "carry_head)")
+        if isinstance(sample, torch.Tensor) and sample.dtype == torch.uint8:
+            sample = normalise_u8(sample, *_u8_norm(image_u8, sample.shape[1], sample.device))
     carry_blocks = carry_blocks or carry_stem
     carry = carry or carry_blocks
     disable_integer_inference(qnn)
@@ -669,6 +801,8 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         _plan_stem_carry(qnn, source)
     if fused_stem:
         _fuse_stems(qnn)
+    if image_u8 is not None:
+        _u8_stems(qnn, image_u8)
     if carry_head:
         _plan_head_carry(qnn, source, heads, report, sample)
     order = {m: i for i, m in enumerate(qnn.modules())}
@@ -829,6 +963,55 @@ def _fuse_stems(qnn):
         qnn._int_fused_stem[names[m]] = why
 
 
+def _u8_norm(image_u8, Ci, dev):
+    """(mean, std) of `image_u8` as fp32 (1, Ci, 1, 1) tensors on `dev`."""
+    mean, std = (torch.as_tensor(v, dtype=torch.float32).detach().reshape(-1).to(dev)
+                 for v in image_u8)
+    if mean.numel() != Ci or std.numel() != Ci:
+        raise ValueError(f"image_u8: mean and std must have one entry per input channel ({Ci})")
+    return mean.reshape(1, Ci, 1, 1), std.reshape(1, Ci, 1, 1)
+
+
+def _u8_stems(qnn, image_u8):
+    """image_u8: every installed StemEdge takes uint8 images from now on -- on K32 where its
+    producer passes `u8_stem_reason` (the blob from the hard weight's packed codes, the tables from
+    its scale and the caller's mean / std), normalised for its fp32 emit elsewhere;
+    `qnn._int_u8`: {producer name: why not, or None}."""
+    names = {m: n for n, m in qnn.named_modules()}
+    stems = _edges(qnn, StemEdge)
+    if not stems:
+        disable_integer_inference(qnn)
+        raise ValueError("enable_integer_inference: image_u8 found no stem edge installed on this "
+                         "model (no stem_chain, a stem that cannot emit, or readers that refuse the "
+                         "codes): a uint8 batch would have no route")
+    qnn._int_u8 = {}
+    for e in stems:
+        m = e.at
+        Co, Ci = int(m.weight.shape[0]), int(m.weight.shape[1])
+        norm = _u8_norm(image_u8, Ci, m.weight.device)
+        why = u8_stem_reason(m)
+        prep = tables = None
+        if why is None:
+            try:
+                packed, f = _weight_codes(m, per_ci=True)
+                why = u8_stem_reason(m, f)
+            except (TypeError, ValueError) as err:
+                why = str(err)
+        if why is None:
+            prep = K.stem_u8_weight_prepare(packed, tuple(m.weight.shape), f["zero_point"],
+                                            f["n_bits"], f["qmin"])
+            if int(prep.bad.item()):
+                why = "weight zero point is not an integer code"
+        if why is None:
+            tables = K.stem_u8_tables(norm[0], norm[1], f["scale"].to(m.weight.device), Co, Ci)
+            kw = m.fwd_kwargs
+            e.take_u8(norm, None, prep, tables, tuple(K._pair(kw.get("stride", 1))),
+                      tuple(K._pair(kw.get("padding", 0))))
+        else:
+            e.take_u8(norm, why)
+        qnn._int_u8[names[m]] = why
+
+
 def head_edges(qnn):
     """The (producer, pool, fc) chains of the pooling head, from the structure alone (no device,
     no forward): the `head_chain()` the model declares on `qnn.model`, [last stage, pool,
@@ -935,6 +1118,7 @@ def disable_integer_inference(qnn):
         m._int_plan = None
     qnn._int_edges, qnn._int_counter = [], None
     qnn._int_fused_stem = None
+    qnn._int_u8 = None
     # every enable passes here: a captured forward (IntegerGraph) of the previous plan is stale
     qnn._int_epoch = getattr(qnn, "_int_epoch", 0) + 1
 
@@ -991,7 +1175,10 @@ def stem_carry_report(qnn):
     installed with `fused_stem`, also "fused": {producer name: forwards whose conv emitted the
     codes itself (K31)} and "unfused": {producer name: why the edge stays on K27 (geometry,
     grouped conv), or {reason: forwards of a fused edge that took K27 (non-contiguous / non-fp32
-    input, the shape rule)}}."""
+    input, the shape rule)}}.  Under a plan installed with `image_u8`, also "u8": {producer name:
+    forwards of a uint8 batch on K32} and "un_u8": {producer name: {reason: forwards whose uint8
+    batch was normalised on the device for the fp32 emit}}, a producer K32 does not take at all
+    (`u8_stem_reason`) listed with its reason from the start."""
     names = {m: n for n, m in qnn.named_modules()}
     stems = _edges(qnn, StemEdge)
     rep = {"edges": [(names[e.at], [names[p] for p in e.pools], names[e.successor]) for e in stems],
@@ -1001,6 +1188,9 @@ def stem_carry_report(qnn):
     if why is not None:
         rep["fused"] = {names[e.at]: getattr(e, "fused", 0) for e in stems}
         rep["unfused"] = {names[e.at]: why[names[e.at]] or dict(e.unfused) for e in stems}
+    if getattr(qnn, "_int_u8", None) is not None:
+        rep["u8"] = {names[e.at]: e.u8 for e in stems}
+        rep["un_u8"] = {names[e.at]: dict(e.un_u8) for e in stems}
     return rep
 
 
@@ -1061,16 +1251,22 @@ class IntegerGraph:
 
     def _cells(self):
         """The Python-side forward counters: (object, None) for `calls`, (edge, name) for a named
-        counter, (edge, pool) for `pooled[pool]`."""
+        counter, (edge, (name, key)) for one entry of a named {reason: count}, (edge, pool) for
+        `pooled[pool]`."""
         qnn = self.qnn
         edges = list(qnn._int_edges) + [e.emitter for e in qnn._int_edges if e.emitter is not None]
         cells = [(p, None) for _, p in _plans(qnn)] + [(e, None) for e in edges]
-        cells += [(e, "fused") for e in edges if "emit" in e.__dict__]    # a fused StemEdge
+        cells += [(e, "fused") for e in edges if "fused" in e.__dict__]   # a fused StemEdge
+        for e in edges:
+            if "u8" in e.__dict__:                                        # one that takes uint8
+                whys = U8_FORWARD_REASONS + ((e.u8_why,) if e.u8_why is not None else ())
+                cells += [(e, "u8")] + [(e, ("un_u8", w)) for w in whys]
         return cells + [(e, m) for e in edges for m in e.pools]
 
     @staticmethod
     def _read(cells):
-        return [o.calls if m is None else getattr(o, m) if isinstance(m, str) else o.pooled[m]
+        return [o.calls if m is None else getattr(o, m) if isinstance(m, str)
+                else getattr(o, m[0]).get(m[1], 0) if isinstance(m, tuple) else o.pooled[m]
                 for o, m in cells]
 
     @staticmethod
@@ -1080,6 +1276,12 @@ class IntegerGraph:
                 o.calls += d
             elif isinstance(m, str):
                 setattr(o, m, getattr(o, m) + d)
+            elif isinstance(m, tuple):      # a {reason: count}: a reason at 0 is not listed
+                counts, v = getattr(o, m[0]), getattr(o, m[0]).get(m[1], 0) + d
+                if v or m[1] == o.u8_why:
+                    counts[m[1]] = v
+                else:
+                    counts.pop(m[1], None)
             else:
                 o.pooled[m] += d
 
