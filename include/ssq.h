@@ -893,7 +893,21 @@ int ssq_stem_conv_codes_fwd(const float* x, const void* prepared, size_t prepare
  * knob).  ssq_stem_u8_tiles: the workgroups of a launch of this geometry (codes: the code form's)
  * that take the interior and the border path.
  *
- * Refused with SSQ_E_ARG before any launch: a null pointer, the geometry above, strides < 1,
+ * Strided views.  ssq_stem_conv_u8_strided_fwd / _strided_codes_fwd take u as any view of
+ * [Nb, Ci, H, W] uint8 elements with four byte strides (sN, sC, sH, sW) >= 0: element (n, c, h, w)
+ * is the byte u[n sN + c sC + h sH + w sW].  The two calls above are the strided ones at the dense
+ * NCHW strides (Ci H W, H W, W, 1).  The output is the same bits whatever the strides; only how the
+ * patch is staged differs, in three forms chosen on the host: planar (0; sW == 1: NCHW, planar
+ * crops, batch-strided views), interleaved (1; sC == 1 and Ci <= sW <= 4: HWC pixels of 3 or 4
+ * bytes, 3 channels in 4-byte pixels, crops of either, at any alignment of the base) and generic
+ * (2; any other strides: correct, no speed claim).  No load touches a byte outside the view's
+ * span, offsets lo = 0 .. hi = (Nb-1) sN + (Ci-1) sC + (H-1) sH + (W-1) sW from u: a padded tap
+ * stands for x = 0, never for the byte next to the view, and a pixel's pad byte is not read.
+ * ssq_stem_u8_view_span (host only): lo, hi and the form of a view, with the view's refusals.
+ *
+ * Refused with SSQ_E_ARG before any launch: a negative stride (no channel reversal), a view that
+ * spans 2^31 bytes or more (hi, or a stride, >= 2^31), a null pointer, the geometry above,
+ * strides < 1,
  * pad_h >= R or pad_w >= S or negative, an empty output, prepared_bytes below the blob's size, a
  * prepared pointer that is not 16-byte aligned (the kernel reads the weight rows as 16-byte
  * vectors), a tensor of 2^31 elements or more.  No allocation, no sync, no float atomics,
@@ -918,6 +932,24 @@ int ssq_stem_conv_u8_codes_fwd(const uint8_t* u, const void* prepared, size_t pr
                                const float* phi, int act, float out_delta, float out_zero_point,
                                int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad,
                                ssq_stream_t stream);
+int ssq_stem_u8_view_span(int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t sN, int64_t sC,
+                          int64_t sH, int64_t sW, int64_t* lo, int64_t* hi, int* form);
+int ssq_stem_conv_u8_strided_fwd(const uint8_t* u, const void* prepared, size_t prepared_bytes,
+                                 const float* M, const float* s, int64_t Nb, int64_t Ci, int64_t H,
+                                 int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride_h,
+                                 int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t sN,
+                                 int64_t sC, int64_t sH, int64_t sW, int every_tile_border,
+                                 float* y, ssq_stream_t stream);
+int ssq_stem_conv_u8_strided_codes_fwd(const uint8_t* u, const void* prepared,
+                                       size_t prepared_bytes, const float* M, const float* s,
+                                       int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                                       int64_t R, int64_t S, int64_t stride_h, int64_t stride_w,
+                                       int64_t pad_h, int64_t pad_w, int64_t sN, int64_t sC,
+                                       int64_t sH, int64_t sW, int every_tile_border,
+                                       const float* bias, const float* gamma, const float* phi,
+                                       int act, float out_delta, float out_zero_point,
+                                       int out_qmin, int out_qmax, int8_t* out_codes,
+                                       uint32_t* bad, ssq_stream_t stream);
 
 /* ---------------------------------------------------------------- column-scaled weights
  * A weight with a per-column input scale on a common integer grid,

@@ -142,17 +142,32 @@ def to_u8(images):
     return ((images * std + mean) * 255).round().clamp(0, 255).to(torch.uint8)
 
 
+def u8_view(u, layout='nchw'):
+    """The uint8 batch `u` (N, 3, H, W) laid out as --int_infer_u8_layout says and handed back as an
+    (N, 3, H, W) view of it: 'nhwc' interleaved pixels, 'rgba' 4-byte pixels whose last byte is a
+    pad (255); 'nchw' is `u` itself."""
+    if layout == 'nchw':
+        return u
+    px = u.permute(0, 2, 3, 1)
+    if layout == 'rgba':
+        px = torch.cat([px, torch.full_like(px[..., :1], 255)], dim=3)
+    return px.contiguous()[..., :3].permute(0, 3, 1, 2)
+
+
 def run_u8_images(qnn, args, cali, loader, bs):
     """--int_infer_u8_images: validation (or one synthetic batch drawn as uint8) on uint8 images,
     then the same batches normalised to fp32 through the same plan, and the stem report."""
-    from shiftedscalequantization_amd.quant import IntegerGraph, stem_carry_report
+    from shiftedscalequantization_amd.quant import IntegerGraph, integer_report, stem_carry_report
     from shiftedscalequantization_amd.quant.integer import normalise_u8
+    layout = getattr(args, 'int_infer_u8_layout', 'nchw')
+    frame = getattr(args, 'int_infer_u8_frame', 0)
     dev = cali.device
     mean = torch.tensor(IMAGENET_MEAN, device=dev).reshape(1, 3, 1, 1)
     std = torch.tensor(IMAGENET_STD, device=dev).reshape(1, 3, 1, 1)
     if loader is not None:
         # one batch at a time in each pass: no second copy of the validation set
-        acc = validate_model(((to_u8(x), t) for x, t in loader), qnn, graph=args.int_infer_graph)
+        acc = validate_model(((u8_view(to_u8(x), layout), t) for x, t in loader), qnn,
+                             graph=args.int_infer_graph)
         print('Integer inference on uint8 images (W{}A{}) accuracy: {}'.format(
             args.n_bits_w, args.n_bits_a, acc))
         acc = validate_model(((normalise_u8(to_u8(x), mean.cpu(), std.cpu()), t) for x, t in loader),
@@ -161,11 +176,17 @@ def run_u8_images(qnn, args, cali, loader, bs):
             args.n_bits_w, args.n_bits_a, acc))
     else:
         g = torch.Generator().manual_seed(args.seed)
-        u = torch.randint(0, 256, (bs,) + tuple(cali.shape[1:]), generator=g, dtype=torch.uint8).to(dev)
+        C, H, W = (int(v) for v in cali.shape[1:])
+        if frame and (frame < H or frame < W):
+            raise SystemExit(f'--int_infer_u8_frame {frame} is smaller than the input {H} x {W}')
+        FH, FW = (frame, frame) if frame else (H, W)
+        u = torch.randint(0, 256, (bs, C, FH, FW), generator=g, dtype=torch.uint8).to(dev)
+        top, left = (FH - H) // 2, (FW - W) // 2
+        u = u8_view(u, layout)[:, :, top:top + H, left:left + W]      # the centre crop, a view
         forward = IntegerGraph(qnn) if args.int_infer_graph else qnn
         with torch.no_grad():
             out_u8 = forward(u).clone()
-            out_f32 = forward(normalise_u8(u, mean, std)).clone()
+            out_f32 = forward(normalise_u8(u.contiguous(), mean, std)).clone()
         diff = (out_u8 - out_f32).abs().max().item()
         same = (out_u8.argmax(1) == out_f32.argmax(1)).float().mean().item()
         print(f'integer inference: one uint8 batch of {bs}: max |logit difference| to the same batch '
@@ -173,6 +194,9 @@ def run_u8_images(qnn, args, cali, loader, bs):
     rep = stem_carry_report(qnn)
     print(f'integer inference: uint8 stem forwards on K32: {rep["u8"]}; normalised on the device '
           f'instead, by reason: {rep["un_u8"]}')
+    print(f'integer inference: uint8 stem forwards on K32 by staging form ({layout}'
+          + (f', {frame} x {frame} frames cropped' if frame else '')
+          + f'): {integer_report(qnn)["u8_form"]}')
 
 
 def main(argv=None):

@@ -162,6 +162,10 @@ SIGNATURES = {
     "ssq_stem_conv_u8_fwd": (_i, [_p, _p, _sz, _p, _p] + [_i64] * 11 + [_i, _p, _p]),
     "ssq_stem_conv_u8_codes_fwd": (_i, [_p, _p, _sz, _p, _p] + [_i64] * 11 + [_i, _p, _p, _p, _i, _f,
                                                                            _f, _i, _i, _p, _p, _p]),
+    "ssq_stem_u8_view_span": (_i, [_i64] * 8 + [_p, _p, _p]),
+    "ssq_stem_conv_u8_strided_fwd": (_i, [_p, _p, _sz, _p, _p] + [_i64] * 15 + [_i, _p, _p]),
+    "ssq_stem_conv_u8_strided_codes_fwd": (_i, [_p, _p, _sz, _p, _p] + [_i64] * 15
+                                           + [_i, _p, _p, _p, _i, _f, _f, _i, _i, _p, _p, _p]),
     "ssq_avgpool_i8_digits_fwd": (_i, [_p] + [_i64] * 4 + [_p, _p, _p, _p]),
     "ssq_qlinear_pooled_fwd": (_i, [_p] * 5 + [_i64] * 4 + [_f, _i, _i, _p, _p]),
     "ssq_qlinear_pooled_set_tile": (_i, [_i]),

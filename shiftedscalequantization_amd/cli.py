@@ -101,6 +101,15 @@ def build_parser():
                         'fed uint8 images (x = (u/255 - mean)/std, the ImageNet mean / std) and the '
                         'stem conv runs on the int8 MFMA (K32; DESIGN 4 "uint8 stem (K32)"); it '
                         'implies none of them and is an error without a stem edge')
+    p.add_argument('--int_infer_u8_layout', choices=('nchw', 'nhwc', 'rgba'), default='nchw',
+                   help='with --int_infer_u8_images: how the uint8 batch lies in memory -- planar '
+                        '(N, 3, H, W), interleaved (N, H, W, 3), or (N, H, W, 4) with a pad byte; '
+                        'the interleaved ones are handed over as views, read in place where the '
+                        'shape rule lets them (DESIGN 4 "uint8 stem (K32)", Strided views; '
+                        'SSQ_STEM_U8_STRIDED=auto|1|0)')
+    p.add_argument('--int_infer_u8_frame', type=int, default=0, metavar='F',
+                   help='with --int_infer_u8_images and no --data_path: the synthetic uint8 batch '
+                        'is drawn as F x F frames and centre-cropped to the input size as a view')
     p.add_argument('--int_infer_colscale', action='store_true',
                    help='--int_infer with column-scaled weights (ChannelQuantMSE, the --test path) '
                         'on integer codes too: the column scale as integers k / L, L <= 127, folded '
@@ -145,6 +154,10 @@ def parse_args(argv=None):
     if a.int_infer_u8_images and not a.int_infer_carry_stem:
         parser.error('--int_infer_u8_images needs a stem edge: --int_infer_carry_stem, '
                      '--int_infer_carry_head or --int_infer_fused_stem')
+    if (a.int_infer_u8_layout != 'nchw' or a.int_infer_u8_frame) and not a.int_infer_u8_images:
+        parser.error('--int_infer_u8_layout / --int_infer_u8_frame need --int_infer_u8_images')
+    if a.int_infer_u8_frame < 0:
+        parser.error('--int_infer_u8_frame must be positive')
     if a.int_infer_carry_stem:
         a.int_infer_carry_blocks = True
     if a.int_infer_carry_blocks:

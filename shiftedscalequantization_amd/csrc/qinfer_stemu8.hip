@@ -24,6 +24,13 @@
 // two rows) and up to 16 * NCH output channels, K31's tile.  The uint8 patch under the tile is
 // staged once in LDS as u_s (K31's patch, a quarter of its bytes); the B operand of (pixel, c) is
 // gathered from it through a table of the taps' offsets.
+//
+// Strided views.  The image is read through four byte strides (sN, sC, sH, sW), all >= 0, by the
+// one address rule u8_at; only the staging below knows of them.  Planar (sW == 1) and generic walk
+// the patch channel by channel; interleaved (sC == 1, Ci <= sW <= 4: HWC pixels) walks it in
+// memory order, a row's bytes one after the other, scatters them into the planar patch and drops
+// a pixel's pad byte.  No load touches a byte outside [0, u8_at(Nb-1, Ci-1, H-1, W-1)]: a padded
+// position and a pad byte read element 0 of their image and are replaced.
 #include <type_traits>
 
 #include "ssq_common.h"
@@ -39,6 +46,16 @@ constexpr int kU8TW = 32;                  // tile columns
 constexpr int kU8MaxTH = 8;                // tile rows at most (kBlock / kU8TW)
 constexpr size_t kU8MaxLds = 64 * 1024;
 
+// the staging forms (ssq_stem_u8_view_span's `form`)
+constexpr int kU8Planar = 0, kU8Interleaved = 1, kU8Generic = 2;
+
+// the byte offset of element (n, c, h, w) of a view with byte strides (sN, sC, sH, sW): the one
+// address rule, of the staging loops and of the host's span query
+template <typename T>
+__host__ __device__ __forceinline__ T u8_at(T n, T c, T h, T w, T sN, T sC, T sH, T sW) {
+  return n * sN + c * sC + h * sH + w * sW;
+}
+
 struct U8Geo {
   uint32_t Ci, H, W, Co, Cop, OH, OW, sh, sw;
   int ph, pw;
@@ -48,6 +65,10 @@ struct U8Geo {
   uint32_t pbytes, vbytes;          // LDS bytes of the u_s patch and of the validity patch
   uint32_t tiles_h, tiles_w, all_border;
   FastDiv div_tw, div_th, div_pw, div_ph, div_s;
+  // the view (stem_u8_view fills these; stem_u8_geo leaves them 0)
+  uint32_t sN, sC, sH, sW;          // the view's byte strides
+  uint32_t form, rowb;              // staging form; interleaved: the bytes of a patch row (PW * sW)
+  FastDiv div_rowb, div_px;         // interleaved: by rowb, by the pixel's bytes sW
 };
 
 // the image coordinate of patch index l along one axis (tile origin o0, stride st, kernel kk):
@@ -103,30 +124,65 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
     koff[tid] = tid < g.RS ? (int)(r * g.PW + s) : 0;
   }
   // the patch, four loads in flight per thread
-  const uint32_t plane = g.PH * g.PW, total = g.Ci * plane;
-  const uint8_t* un = u + (size_t)n * g.Ci * g.H * g.W;
-  for (uint32_t i0 = tid; i0 < total; i0 += 4 * nthr) {
-    uint8_t v[4];
-    bool ok[4];
+  const uint32_t plane = g.PH * g.PW;
+  // element 0 of this image: what an outside position or a pad byte reads before it is replaced,
+  // so no load leaves the view's span
+  const uint32_t at0 = u8_at<uint32_t>(n, 0, 0, 0, g.sN, g.sC, g.sH, g.sW);
+  if (g.form == kU8Interleaved) {
+    // memory order: patch row, then the row's bytes (column, then channel or pad byte), so
+    // consecutive lanes read consecutive bytes
+    const uint32_t total = g.PH * g.rowb;
+    for (uint32_t i0 = tid; i0 < total; i0 += 4 * nthr) {
+      uint8_t v[4];
+      bool ok[4];
+      uint32_t to[4];                      // b * plane + lr * PW + lc, or none (~0u)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t i = i0 + k * nthr;
-      const uint32_t row = fdiv(i, g.div_pw), lc = i - row * g.PW;
-      const uint32_t ci = fdiv(row, g.div_ph), lr = row - ci * g.PH;
-      const int gh = u8_coord(lr, oh0, g.sh, g.R, g.ph);
-      const int gw = u8_coord(lc, ow0, g.sw, g.S, g.pw);
-      ok[k] = i < total && gh >= 0 && gh < (int)g.H && gw >= 0 && gw < (int)g.W;
-      // an outside position reads element 0 of the image and is replaced: no load leaves the
-      // tensor
-      const size_t at = ok[k] ? ((size_t)ci * g.H + (uint32_t)gh) * g.W + (uint32_t)gw : 0;
-      v[k] = un[at];
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t i = i0 + k * nthr;
+        const uint32_t lr = fdiv(i, g.div_rowb), rem = i - lr * g.rowb;
+        const uint32_t lc = fdiv(rem, g.div_px), b = rem - lc * g.sW;
+        const int gh = u8_coord(lr, oh0, g.sh, g.R, g.ph);
+        const int gw = u8_coord(lc, ow0, g.sw, g.S, g.pw);
+        const bool real = i < total && b < g.Ci;
+        ok[k] = real && gh >= 0 && gh < (int)g.H && gw >= 0 && gw < (int)g.W;
+        to[k] = real ? b * plane + lr * g.PW + lc : ~0u;
+        const uint32_t at =
+            ok[k] ? u8_at<uint32_t>(n, b, (uint32_t)gh, (uint32_t)gw, g.sN, g.sC, g.sH, g.sW) : at0;
+        v[k] = u[at];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (to[k] != ~0u) {
+          patch[to[k]] = ok[k] ? (int8_t)(v[k] ^ 0x80u) : (int8_t)0;
+          if (border && to[k] < plane) vpatch[to[k]] = ok[k] ? 1 : 0;
+        }
+      }
     }
+  } else {
+    // planar (sW == 1) and generic: channel, patch row, column
+    const uint32_t total = g.Ci * plane;
+    for (uint32_t i0 = tid; i0 < total; i0 += 4 * nthr) {
+      uint8_t v[4];
+      bool ok[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t i = i0 + k * nthr;
-      if (i < total) {
-        patch[i] = ok[k] ? (int8_t)(v[k] ^ 0x80u) : (int8_t)0;
-        if (border && i < plane) vpatch[i] = ok[k] ? 1 : 0;
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t i = i0 + k * nthr;
+        const uint32_t row = fdiv(i, g.div_pw), lc = i - row * g.PW;
+        const uint32_t ci = fdiv(row, g.div_ph), lr = row - ci * g.PH;
+        const int gh = u8_coord(lr, oh0, g.sh, g.R, g.ph);
+        const int gw = u8_coord(lc, ow0, g.sw, g.S, g.pw);
+        ok[k] = i < total && gh >= 0 && gh < (int)g.H && gw >= 0 && gw < (int)g.W;
+        const uint32_t at =
+            ok[k] ? u8_at<uint32_t>(n, ci, (uint32_t)gh, (uint32_t)gw, g.sN, g.sC, g.sH, g.sW) : at0;
+        v[k] = u[at];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t i = i0 + k * nthr;
+        if (i < total) {
+          patch[i] = ok[k] ? (int8_t)(v[k] ^ 0x80u) : (int8_t)0;
+          if (border && i < plane) vpatch[i] = ok[k] ? 1 : 0;
+        }
       }
     }
   }
@@ -311,12 +367,37 @@ static int stem_u8_geo(const char* me, bool codes, int64_t Nb, int64_t Ci, int64
   return SSQ_OK;
 }
 
+// The view's span and staging form, checked: byte offsets lo .. hi are what a launch may read.
+static int stem_u8_view(const char* me, int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t sN,
+                        int64_t sC, int64_t sH, int64_t sW, int64_t* lo, int64_t* hi, int* form) {
+  SSQ_REQUIRE(Nb >= 1 && Ci >= 1 && H >= 1 && W >= 1 && Nb < (1ll << 31) && Ci < (1ll << 31) &&
+                  H < (1ll << 31) && W < (1ll << 31),
+              SSQ_E_ARG, "%s: bad geometry (sizes >= 1)", me);
+  SSQ_REQUIRE(sN >= 0 && sC >= 0 && sH >= 0 && sW >= 0, SSQ_E_ARG,
+              "%s: negative stride (%lld, %lld, %lld, %lld)", me, (long long)sN, (long long)sC,
+              (long long)sH, (long long)sW);
+  // sizes and the strides that count below 2^31: each term below 2^62, and below 2^31 before the
+  // four are summed (the stride of a dimension of size 1 addresses nothing)
+  const auto term = [](int64_t n, int64_t st) {
+    return n == 1 || (st < (1ll << 31) && (n - 1) * st < (1ll << 31));
+  };
+  SSQ_REQUIRE(term(Nb, sN) && term(Ci, sC) && term(H, sH) && term(W, sW) &&
+                  u8_at<int64_t>(Nb - 1, Ci - 1, H - 1, W - 1, sN, sC, sH, sW) < (1ll << 31),
+              SSQ_E_ARG, "%s: the view spans 2^31 bytes or more", me);
+  *lo = u8_at<int64_t>(0, 0, 0, 0, sN, sC, sH, sW);
+  *hi = u8_at<int64_t>(Nb - 1, Ci - 1, H - 1, W - 1, sN, sC, sH, sW);
+  // one channel has no channel stride to speak of
+  *form = sW == 1 ? kU8Planar
+                  : ((Ci == 1 || sC == 1) && sW >= Ci && sW <= 4) ? kU8Interleaved : kU8Generic;
+  return SSQ_OK;
+}
+
 template <bool CODES, typename Y>
 static int stem_u8_run(const char* me, const uint8_t* u, const void* prepared,
                        size_t prepared_bytes, const float* M, const float* s, int64_t Nb,
                        int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S,
-                       int64_t sh, int64_t sw, int64_t ph, int64_t pw, int every_tile_border, Y y,
-                       ssq_stream_t stream) {
+                       int64_t sh, int64_t sw, int64_t ph, int64_t pw, int64_t sN, int64_t sC,
+                       int64_t sH, int64_t sW, int every_tile_border, Y y, ssq_stream_t stream) {
   SSQ_REQUIRE(u && prepared && M && s, SSQ_E_ARG, "%s: null pointer", me);
   // the weight rows leave the blob as 16-byte vectors, cwz and T as int32 behind whole 64-byte rows
   SSQ_REQUIRE(((uintptr_t)prepared & 15u) == 0, SSQ_E_ARG,
@@ -331,6 +412,17 @@ static int stem_u8_run(const char* me, const uint8_t* u, const void* prepared,
   const ULayout L = ulayout(Co, Ci, R, S);
   SSQ_REQUIRE(prepared_bytes >= L.bytes, SSQ_E_ARG, "%s: prepared blob of %zu bytes, %zu needed",
               me, prepared_bytes, L.bytes);
+  int64_t lo, hi;
+  int form;
+  const int rv = stem_u8_view(me, Nb, Ci, H, W, sN, sC, sH, sW, &lo, &hi, &form);
+  if (rv) return rv;
+  g.sN = (uint32_t)sN, g.sC = (uint32_t)sC, g.sH = (uint32_t)sH, g.sW = (uint32_t)sW;
+  g.form = (uint32_t)form;
+  if (form == kU8Interleaved) {
+    g.rowb = g.PW * g.sW;
+    g.div_rowb = make_fastdiv(g.rowb);
+    g.div_px = make_fastdiv(g.sW);
+  }
   g.all_border = every_tile_border ? 1u : 0u;
   const int8_t* base = (const int8_t*)prepared;
   const int32_t* cwz = (const int32_t*)(base + L.off_cwz);
@@ -397,6 +489,44 @@ extern "C" int ssq_stem_u8_tiles(int64_t Nb, int64_t Ci, int64_t H, int64_t W, i
   return SSQ_OK;
 }
 
+extern "C" int ssq_stem_u8_view_span(int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t sN,
+                                     int64_t sC, int64_t sH, int64_t sW, int64_t* lo, int64_t* hi,
+                                     int* form) {
+  const char* me = "ssq_stem_u8_view_span";
+  SSQ_REQUIRE(lo && hi && form, SSQ_E_ARG, "%s: null pointer", me);
+  return stem_u8_view(me, Nb, Ci, H, W, sN, sC, sH, sW, lo, hi, form);
+}
+
+extern "C" int ssq_stem_conv_u8_strided_fwd(
+    const uint8_t* u, const void* prepared, size_t prepared_bytes, const float* M, const float* s,
+    int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S,
+    int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t sN, int64_t sC,
+    int64_t sH, int64_t sW, int every_tile_border, float* y, ssq_stream_t stream) {
+  const char* me = "ssq_stem_conv_u8_strided_fwd";
+  SSQ_REQUIRE(y, SSQ_E_ARG, "%s: null pointer", me);
+  return stem_u8_run<false>(me, u, prepared, prepared_bytes, M, s, Nb, Ci, H, W, Co, R, S,
+                            stride_h, stride_w, pad_h, pad_w, sN, sC, sH, sW, every_tile_border, y,
+                            stream);
+}
+
+extern "C" int ssq_stem_conv_u8_strided_codes_fwd(
+    const uint8_t* u, const void* prepared, size_t prepared_bytes, const float* M, const float* s,
+    int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S,
+    int64_t stride_h, int64_t stride_w, int64_t pad_h, int64_t pad_w, int64_t sN, int64_t sC,
+    int64_t sH, int64_t sW, int every_tile_border, const float* bias, const float* gamma,
+    const float* phi, int act, float out_delta, float out_zero_point, int out_qmin, int out_qmax,
+    int8_t* out_codes, uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_stem_conv_u8_strided_codes_fwd";
+  QEpi e;
+  const int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin,
+                           out_qmax, out_codes, bad, &e);
+  if (rc) return rc;
+  e.Cpo = (uint32_t)((Co + 15) / 16 * 16);
+  return stem_u8_run<true>(me, u, prepared, prepared_bytes, M, s, Nb, Ci, H, W, Co, R, S, stride_h,
+                           stride_w, pad_h, pad_w, sN, sC, sH, sW, every_tile_border, e, stream);
+}
+
+// the dense NCHW calls of the same run function
 extern "C" int ssq_stem_conv_u8_fwd(const uint8_t* u, const void* prepared, size_t prepared_bytes,
                                     const float* M, const float* s, int64_t Nb, int64_t Ci,
                                     int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S,
@@ -406,7 +536,8 @@ extern "C" int ssq_stem_conv_u8_fwd(const uint8_t* u, const void* prepared, size
   const char* me = "ssq_stem_conv_u8_fwd";
   SSQ_REQUIRE(y, SSQ_E_ARG, "%s: null pointer", me);
   return stem_u8_run<false>(me, u, prepared, prepared_bytes, M, s, Nb, Ci, H, W, Co, R, S,
-                            stride_h, stride_w, pad_h, pad_w, every_tile_border, y, stream);
+                            stride_h, stride_w, pad_h, pad_w, Ci * H * W, H * W, W, 1,
+                            every_tile_border, y, stream);
 }
 
 extern "C" int ssq_stem_conv_u8_codes_fwd(
@@ -423,5 +554,6 @@ extern "C" int ssq_stem_conv_u8_codes_fwd(
   if (rc) return rc;
   e.Cpo = (uint32_t)((Co + 15) / 16 * 16);
   return stem_u8_run<true>(me, u, prepared, prepared_bytes, M, s, Nb, Ci, H, W, Co, R, S, stride_h,
-                           stride_w, pad_h, pad_w, every_tile_border, e, stream);
+                           stride_w, pad_h, pad_w, Ci * H * W, H * W, W, 1, every_tile_border, e,
+                           stream);
 }

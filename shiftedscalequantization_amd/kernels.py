@@ -2681,15 +2681,48 @@ def stem_u8_tables(mean, std, scale, Co, Ci):
     return M, (inv.reshape(1, Ci) * d).contiguous()
 
 
+STEM_U8_FORMS = ("planar", "interleaved", "generic")
+
+
+def _stem_u8_view(u):
+    """(form, byte strides) of the uint8 view `u` (N, Ci, H, W) as K32 stages it, or ("copied",
+    None) where the ABI refuses the view (ssq_stem_u8_view_span: a span of 2^31 bytes or more) or
+    its span leaves the tensor's storage.  Host only."""
+    lo, hi, form = C.c_int64(0), C.c_int64(0), C.c_int(0)
+    strides = tuple(int(v) for v in u.stride())
+    rc = query("ssq_stem_u8_view_span", *(int(v) for v in u.shape), *strides, C.byref(lo),
+               C.byref(hi), C.byref(form))
+    off, size = int(u.storage_offset()), int(u.untyped_storage().nbytes())
+    if rc != 0 or off + lo.value < 0 or off + hi.value >= size:
+        return "copied", None
+    return STEM_U8_FORMS[form.value], strides
+
+
+def stem_u8_view_form(u):
+    """How stem_conv_u8 / stem_conv_u8_codes stage the uint8 view `u` (N, Ci, H, W): "planar"
+    (unit stride along W: NCHW, planar crops, batch-strided views), "interleaved" (HWC pixels of
+    Ci .. 4 bytes, `hwc.permute(0, 3, 1, 2)`), "generic" (any other non-negative strides), each
+    read in place, or "copied" (the view is made dense first)."""
+    if not isinstance(u, torch.Tensor) or u.dtype != torch.uint8 or u.dim() != 4:
+        raise A.SSQError("stem_u8_view_form: expected a 4-D uint8 tensor")
+    return _stem_u8_view(u)[0]
+
+
 def _stem_u8_args(name, u, prepared, M, s, stride, padding, every_tile_border):
     if not isinstance(prepared, StemU8Weight):
         raise A.SSQError(f"{name}: prepared must come from stem_u8_weight_prepare")
     if not isinstance(u, torch.Tensor) or u.dtype != torch.uint8:
         raise A.SSQError(f"{name}: the image must be a uint8 tensor")
-    u = _i8_dev(u, name)
+    if u.device.type != "cuda":
+        raise A.SSQError(f"{name}: ssq kernels run on the MI355X (HIP) device only")
     Co, Ci, R, S = prepared.shape
     if u.dim() != 4 or int(u.shape[1]) != Ci:
         raise A.SSQError(f"{name}: expected (N, {Ci}, H, W), got {tuple(u.shape)}")
+    # the view as it stands, through its byte strides; one the ABI refuses is copied dense
+    strides = _stem_u8_view(u)[1] if u.numel() else None
+    if strides is None:
+        u = u.contiguous()
+        strides = tuple(int(v) for v in u.stride())
     M, Mp = fptr(M.detach().reshape(-1), "M")
     s, sp = fptr(s.detach().reshape(-1), "s")
     if M.numel() != Ci or s.numel() != Co * Ci:
@@ -2699,7 +2732,7 @@ def _stem_u8_args(name, u, prepared, M, s, stride, padding, every_tile_border):
     OH = (H + 2 * ph - R) // max(sh, 1) + 1
     OW = (W + 2 * pw - S) // max(sw, 1) + 1
     args = (_vp(u), _vp(prepared.blob), prepared.blob.numel(), Mp, sp, N, Ci, H, W, Co, R, S, sh,
-            sw, ph, pw, int(bool(every_tile_border)))
+            sw, ph, pw, *strides, int(bool(every_tile_border)))
     return (u, M, s), args, (N, Co, max(OH, 0), max(OW, 0))
 
 
@@ -2717,21 +2750,22 @@ def stem_u8_tiles(prepared, ushape, stride=1, padding=0, codes=True):
 
 
 def stem_conv_u8(u, prepared, M, s, stride=1, padding=0, every_tile_border=False):
-    """K32's fp32 form (ssq_stem_conv_u8_fwd): the stem conv of the uint8 image u (N, Ci, H, W),
-    standing for x = (u/255 - mean)/std, with a prepared weight and the tables of stem_u8_tables,
+    """K32's fp32 form (ssq_stem_conv_u8_strided_fwd): the stem conv of the uint8 image u, any
+    (N, Ci, H, W)-shaped view read in place (`stem_u8_view_form`; an HWC batch is
+    `hwc.permute(0, 3, 1, 2)`), standing for x = (u/255 - mean)/std, with a prepared weight and the tables of stem_u8_tables,
     as fp32 (N, Co, OH, OW) in the stated operation order (include/ssq.h).  `stride`, `padding`:
     an int or (h, w).  `every_tile_border`: no workgroup takes the interior shortcut (the same
     bits)."""
     keep, args, (N, Co, OH, OW) = _stem_u8_args("stem_conv_u8", u, prepared, M, s, stride, padding,
                                                 every_tile_border)
     y = torch.empty((N, Co, OH, OW), dtype=torch.float32, device=keep[0].device)
-    call("ssq_stem_conv_u8_fwd", *args, _vp(y), stream_of(y))
+    call("ssq_stem_conv_u8_strided_fwd", *args, _vp(y), stream_of(y))
     return y
 
 
 def stem_conv_u8_codes(u, prepared, M, s, bias, gamma, phi, relu, out_delta, out_zp, out_bits,
                        out_sym, bad, stride=1, padding=0, every_tile_border=False):
-    """K32's code form (ssq_stem_conv_u8_codes_fwd): epilogue_codes(stem_conv_u8(u, ...), ...) byte
+    """K32's code form (ssq_stem_conv_u8_strided_codes_fwd): epilogue_codes(stem_conv_u8(u, ...), ...) byte
     for byte in one kernel, without the fp32 tensor.  The epilogue's arguments are
     stem_conv_codes'."""
     if bad is None:
@@ -2744,7 +2778,7 @@ def stem_conv_u8_codes(u, prepared, M, s, bias, gamma, phi, relu, out_delta, out
     out = torch.empty((N, OH, OW, query("ssq_qinfer_cpad", Co)), dtype=torch.int8,
                       device=keep[0].device)
     olo, ohi = qrange(out_bits, out_sym)
-    call("ssq_stem_conv_u8_codes_fwd", *args, *vecs, int(relu), float(out_delta), float(out_zp),
+    call("ssq_stem_conv_u8_strided_codes_fwd", *args, *vecs, int(relu), float(out_delta), float(out_zp),
          olo, ohi, _vp(out), _vp(bad), stream_of(out))
     return out
 

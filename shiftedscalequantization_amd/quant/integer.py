@@ -333,13 +333,18 @@ class StemEdge(Edge):
         self.u8_norm, self.u8_why = norm, why
         self.u8_blob, self.u8_tables, self.u8_geo = prepared, tables, (stride, padding)
         self.u8, self.un_u8 = 0, ({} if why is None else {why: 0})
+        self.u8_form = {}               # {staging form: forwards on K32} (K.stem_u8_view_form)
         self._emit_f32, self._u8_declined = self.emit, False
         self.emit = self.emit_u8
 
     def emit_u8(self, x):
         """K.stem_conv_u8_codes on a uint8 image: conv, epilogue and act quantizer in one kernel on
         the int8 MFMA; an fp32 input takes the edge's fp32 emit untouched, a uint8 input K32 is
-        not to take is normalised on the device and takes it too, counted by reason."""
+        not to take is normalised on the device and takes it too, counted by reason.  A view that is
+        not dense NCHW (an HWC batch as `hwc.permute(0, 3, 1, 2)`, an RGBA batch's first three
+        channels, a crop of a larger frame) is read in place where `stem_u8_takes` lets its staging
+        form, copied dense for K32 under SSQ_STEM_U8_STRIDED=0, and otherwise normalised as before;
+        the K32 forwards are counted by form (`u8_form`)."""
         if not (isinstance(x, torch.Tensor) and x.dtype == torch.uint8):
             # the normalised batch of the branch below, back through the module's forward: its
             # fp32 emit has already declined it
@@ -349,13 +354,21 @@ class StemEdge(Edge):
         if why is None:
             if not (x.dim() == 4 and x.is_cuda):
                 why = U8_NOT_4D
-            elif not x.is_contiguous():
-                why = (U8_NHWC if x.is_contiguous(memory_format=torch.channels_last)
-                       else U8_STRIDED)
-            elif not stem_u8_takes(self.u8_blob.shape, x.shape, *self.u8_geo):
-                why = U8_SHAPE_RULE
-            elif not (self.live() and can_emit(m, m.act_quantizer, True, x)):
-                why = U8_NOT_LIVE
+            else:
+                takes = stem_u8_takes(self.u8_blob.shape, x.shape, *self.u8_geo)
+                # a view reaches K32 only where K32 takes the shape at all: elsewhere it keeps the
+                # reason it had
+                form = "planar" if x.is_contiguous() else None
+                if form is None and takes:
+                    form = stem_u8_view_route(K.stem_u8_view_form(x), self.u8_blob.shape, x.shape,
+                                              *self.u8_geo)
+                if form is None:
+                    why = (U8_NHWC if x.is_contiguous(memory_format=torch.channels_last)
+                           else U8_STRIDED)
+                elif not takes:
+                    why = U8_SHAPE_RULE
+                elif not (self.live() and can_emit(m, m.act_quantizer, True, x)):
+                    why = U8_NOT_LIVE
         if why is not None:
             self.un_u8[why] = self.un_u8.get(why, 0) + 1
             # contiguous first (a quarter of the fp32 copy's bytes): the fp32 emit's own rules then
@@ -372,6 +385,9 @@ class StemEdge(Edge):
         gamma, phi = m.affine()
         self.calls += 1
         self.u8 += 1
+        if form == "copied":
+            x = x.contiguous()
+        self.u8_form[form] = self.u8_form.get(form, 0) + 1
         stride, padding = self.u8_geo
         codes = K.stem_conv_u8_codes(x, self.u8_blob, *self.u8_tables, m.bias, gamma, phi,
                                      m.act_code(), *self.grid, self.counter, stride=stride,
@@ -385,6 +401,7 @@ class StemEdge(Edge):
             self.fused, self.unfused = 0, {}
         if "u8" in self.__dict__:
             self.u8, self.un_u8 = 0, ({} if self.u8_why is None else {self.u8_why: 0})
+            self.u8_form = {}
 
 
 # what keeps one uint8 forward of an edge that takes K32 off it (`un_u8`'s per-forward reasons)
@@ -393,6 +410,8 @@ U8_NHWC, U8_STRIDED = "channels-last input", "non-contiguous input"
 U8_SHAPE_RULE = "shape rule: K31 is faster here (SSQ_STEM_U8=1 overrides)"
 U8_NOT_LIVE = "the stem edge does not carry in this state"
 U8_FORWARD_REASONS = (U8_NOT_4D, U8_NHWC, U8_STRIDED, U8_SHAPE_RULE, U8_NOT_LIVE)
+# how a K32 forward staged its image (`u8_form`): K.stem_u8_view_form's
+U8_FORMS = ("planar", "interleaved", "generic", "copied")
 
 
 def normalise_u8(u, mean, std):
@@ -428,7 +447,7 @@ def u8_stem_reason(m, fields=None):
     return None
 
 
-def stem_u8_takes(wshape, xshape, stride, padding):
+def stem_u8_takes(wshape, xshape, stride, padding, form=None):
     """The host shape rule of a uint8 stem edge ("uint8 stem (K32)"): K32 takes a shape
     class only where its measured median saving over K31 fed the normalised image exceeded that
     baseline's min-max spread (profiles/int_infer_u8_stem_rate.txt); elsewhere the batch is
@@ -438,13 +457,52 @@ def stem_u8_takes(wshape, xshape, stride, padding):
     real).  So auto takes K32 for the measured class, a 7x7 kernel at stride 2 on at most
     64 x 16 x 16 output pixels, and nothing else; a smaller batch of that class is taken by
     extrapolation (fewer pixels are more launch-bound, not measured).  SSQ_STEM_U8=1 / 0 forces
-    K32 / the normalised route for an A/B run; auto (the default) asks the rule."""
+    K32 / the normalised route for an A/B run; auto (the default) asks the rule.
+
+    `form` (None: the question above, of a dense NCHW batch): whether K32 reads a view of that
+    staging form ("planar", "interleaved", "generic": K.stem_u8_view_form) in place instead of a
+    dense copy of it ("uint8 stem (K32)", Strided views).  The same keep rule against the
+    copy route, torch's .contiguous() followed by the dense launch
+    (profiles/int_infer_u8_layout_rate.txt): a form is taken for a shape class where its median
+    beat the copy route's by more than that route's min-max spread, `U8_VIEW_CLASSES`; an
+    unmeasured class is not taken.  Measured at batch 64 on 224 x 224: the 7x7/2 stem saves
+    17.0 us on 3-byte pixels (303.2 -> 286.2, spread 0.3), 7.0 on 4-byte pixels (303.3 -> 296.3,
+    0.9), 18.1 on a planar 256 -> 224 crop (304.1 -> 286.0, 0.5) and 13.9 on an interleaved one;
+    the 3x3/2 stem 16.5, 10.8, 18.2 and 14.1 (spreads <= 0.4).  So auto takes the planar and the
+    interleaved form for these two classes from that many image pixels up; the generic form and
+    smaller batches were not measured.  SSQ_STEM_U8_STRIDED=1 / 0 forces the view / the copy; auto
+    asks the rule."""
+    if form is not None:
+        knob = os.environ.get("SSQ_STEM_U8_STRIDED", "auto")
+        if knob in ("0", "1"):
+            return knob == "1" and form in U8_FORMS[:3]
+        (_, _, R, S), (N, _, H, W), (sh, sw) = wshape, xshape, stride
+        return any(tuple(c) == (form, R, S, sh, sw) and int(N) * int(H) * int(W) >= px
+                   for *c, px in U8_VIEW_CLASSES)
     knob = os.environ.get("SSQ_STEM_U8", "auto")
     if knob in ("0", "1"):
         return knob == "1"
     (_, _, R, S), (N, _, H, W), (sh, sw), (ph, pw) = wshape, xshape, stride, padding
     pixels = int(N) * ((int(H) + 2 * ph - R) // sh + 1) * ((int(W) + 2 * pw - S) // sw + 1)
     return (R, S, sh, sw) == (7, 7, 2, 2) and pixels <= 64 * 16 * 16
+
+
+# (form, R, S, stride h, stride w, the fewest image pixels N * H * W measured): the classes whose
+# in-place form cleared the keep rule against the copy route at batch 64 on 224 x 224
+# (profiles/int_infer_u8_layout_rate.txt).  A smaller batch was not measured and is not taken.
+U8_VIEW_CLASSES = (("planar", 7, 7, 2, 2, 64 * 224 * 224), ("interleaved", 7, 7, 2, 2, 64 * 224 * 224),
+                   ("planar", 3, 3, 2, 2, 64 * 224 * 224), ("interleaved", 3, 3, 2, 2, 64 * 224 * 224))
+
+
+def stem_u8_view_route(form, wshape, xshape, stride, padding):
+    """How a uint8 view that is not dense NCHW reaches K32: `form` itself (read in place), "copied"
+    (made dense first: SSQ_STEM_U8_STRIDED=0, or a view the ABI refuses), or None: auto on a class
+    `stem_u8_takes` does not take in place, whose batch is normalised for the fp32 emit as before
+    strided views were read."""
+    knob = os.environ.get("SSQ_STEM_U8_STRIDED", "auto")
+    if form == "copied" or knob == "0":
+        return "copied" if knob in ("0", "1") else None
+    return form if stem_u8_takes(wshape, xshape, stride, padding, form) else None
 
 
 def fused_stem_reason(m):
@@ -1127,10 +1185,17 @@ def integer_report(qnn):
     """{"off_grid": elements seen by the integer layers that were not on their act quantizer's
     grid (0 = every integer layer computed what the decoded path computes up to fp32
     rounding), "calls": {layer name: forwards taken on the integer route}}.  Reads one device
-    word (the only sync of the integer path)."""
+    word (the only sync of the integer path).  Under a plan installed with `image_u8`, also
+    "u8_form": {producer name: {staging form: forwards of a uint8 batch on K32}}, the forms
+    K.stem_u8_view_form's: "planar", "interleaved", "generic" read in place, "copied" made dense
+    first; they sum to stem_carry_report's "u8"."""
     counter = getattr(qnn, "_int_counter", None)
-    return {"off_grid": int(counter.item()) if counter is not None else 0,
-            "calls": {n: p.calls for n, p in _plans(qnn)}}
+    rep = {"off_grid": int(counter.item()) if counter is not None else 0,
+           "calls": {n: p.calls for n, p in _plans(qnn)}}
+    if getattr(qnn, "_int_u8", None) is not None:
+        names = {m: n for n, m in qnn.named_modules()}
+        rep["u8_form"] = {names[e.at]: dict(e.u8_form) for e in _edges(qnn, StemEdge)}
+    return rep
 
 
 def split_report(qnn):
@@ -1243,7 +1308,7 @@ class IntegerGraph:
                 raise ValueError(f"IntegerGraph: module {name or type(m).__name__!r} carries a forward "
                                  "hook, which would run once, at capture")
         self.qnn, self.epoch = qnn, qnn._int_epoch
-        self._shapes = collections.OrderedDict()     # (shape, dtype) -> the captured entry
+        self._shapes = collections.OrderedDict()     # (shape, dtype, strides) -> the captured entry
 
     def shapes(self):
         """The captured input shapes, least recently used first."""
@@ -1261,6 +1326,7 @@ class IntegerGraph:
             if "u8" in e.__dict__:                                        # one that takes uint8
                 whys = U8_FORWARD_REASONS + ((e.u8_why,) if e.u8_why is not None else ())
                 cells += [(e, "u8")] + [(e, ("un_u8", w)) for w in whys]
+                cells += [(e, ("u8_form", f)) for f in U8_FORMS]
         return cells + [(e, m) for e in edges for m in e.pools]
 
     @staticmethod
@@ -1285,13 +1351,25 @@ class IntegerGraph:
             else:
                 o.pooled[m] += d
 
+    @staticmethod
+    def _static_like(x):
+        """A dense copy of `x` in `x`'s dimension order: a dense NCHW or HWC batch keeps its
+        strides (a later `copy_` is flat and the replay stages the same form), a crop view gets a
+        dense buffer with its dimensions in the same order."""
+        order = sorted(range(x.dim()), key=lambda d: (x.stride(d), -d))      # innermost first
+        strides, step = [0] * x.dim(), 1
+        for d in order:
+            strides[d], step = step, step * int(x.shape[d])
+        buf = torch.empty_strided(tuple(x.shape), strides, dtype=x.dtype, device=x.device)
+        return buf.copy_(x)
+
     @torch.no_grad()
     def _capture(self, x):
         qnn = self.qnn
         qnn.eval()
         cells = self._cells()
         before, word = self._read(cells), qnn._int_counter.clone()
-        e = {"in": x.clone(), "ws": {}}
+        e = {"in": self._static_like(x), "ws": {}}
         with L.frozen_weight_cache(), K.A.workspace_scope(e["ws"]):
             side = torch.cuda.Stream(device=x.device)
             side.wait_stream(torch.cuda.current_stream(x.device))
@@ -1319,7 +1397,7 @@ class IntegerGraph:
                                "this graph was built (enable / disable_integer_inference)")
         if not (isinstance(x, torch.Tensor) and x.is_cuda):
             raise K.A.SSQError("IntegerGraph: the input must be a tensor on the HIP device")
-        key = (tuple(x.shape), x.dtype)
+        key = (tuple(x.shape), x.dtype, tuple(x.stride()))
         e = self._shapes.get(key)
         if e is None:
             e = self._shapes[key] = self._capture(x)

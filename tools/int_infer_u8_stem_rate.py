@@ -3,6 +3,7 @@
     python tools/int_infer_u8_stem_rate.py [--batch 64] [--wbits 2] [--abits 4] [--rounds 7]
                                            [--out profiles/int_infer_u8_stem_rate.txt]
                                            [--parity profiles/int_infer_u8_stem_parity.jsonl]
+    python tools/int_infer_u8_stem_rate.py --layouts [--out profiles/int_infer_u8_layout_rate.txt]
 
 Kernel rows: the stem conv leaving as int8 codes from a uint8 image, K32
 (ssq_stem_conv_u8_codes_fwd), against K31's code form (ssq_stem_conv_codes_fwd, the parent
@@ -24,6 +25,14 @@ decoded conv Y64, in units of 2^-24 * sum |W_hat| (u + |M|) / (255 std).
 
 Model rows: per test model (ResNet-18, MobileNetV2, RegNetX-600M, restored from packed exports,
 batch 8) at 32 x 32 and 224 x 224, the share of stem code bytes that differ between the two routes.
+
+Layout rows (--layouts, a table of its own, profiles/int_infer_u8_layout_rate.txt): per stem shape
+at 224 x 224 and per view of the uint8 batch -- interleaved 3-byte pixels, 4-byte pixels with a pad
+byte, a 256 -> 224 centre crop of planar and of interleaved frames -- K32's code form reading the
+view in place against the copy route, torch's .contiguous() of the view followed by the dense
+launch, timed together, and the dense launch alone.  The interleaved staging loads single bytes;
+aligned wider loads were not tried.  The keep rule is the same: the in-place form is taken for a
+shape class when the median it saves exceeds the copy route's min-max spread.
 
 Every sample is a device-event time over enough back-to-back calls to fill >= 50 ms, after a
 warm-up of every form; the table holds medians over the rounds with min-max.  The keep rule is
@@ -110,6 +119,96 @@ def run_kernels(args):
                      "codes_differing_from_k31_route": differing, "us": us, "bytes": nbytes,
                      "op": 2.0 * N * OH * OH * Co * 3 * R * R})
     print(json.dumps({"rows": rows}), flush=True)
+
+
+LAYOUTS = ("HWC-3", "RGBA", "crop 256->224", "HWC crop 256->224")
+
+
+def layout_view(torch, u, layout, frame=256):
+    """The dense device batch u (N, 3, H, W) as a view of that layout, everything around it 255."""
+    N, C, H, W = u.shape
+    px = u.permute(0, 2, 3, 1)
+    top, left = (frame - H) // 2, (frame - W) // 2
+    if layout == "HWC-3":
+        return px.contiguous().permute(0, 3, 1, 2)
+    if layout == "RGBA":
+        return torch.cat([px, torch.full_like(px[..., :1], 255)], 3).contiguous()[..., :3].permute(0, 3, 1, 2)
+    if layout == "crop 256->224":
+        fr = torch.full((N, C, frame, frame), 255, dtype=torch.uint8, device=u.device)
+        fr[:, :, top:top + H, left:left + W] = u
+        return fr[:, :, top:top + H, left:left + W]
+    fr = torch.full((N, frame, frame, C), 255, dtype=torch.uint8, device=u.device)
+    fr[:, top:top + H, left:left + W, :] = px
+    return fr[:, top:top + H, left:left + W, :].permute(0, 3, 1, 2)
+
+
+def run_layouts(args):
+    import torch
+    sys.path.insert(0, ROOT)
+    from shiftedscalequantization_amd import kernels as K
+
+    N = args.batch
+    g = torch.Generator().manual_seed(6705)
+    counter = torch.zeros(1, dtype=torch.int32, device="cuda")
+    rows = []
+    for name, Co, R, st, pd, H in KERNEL_SHAPES[:2]:
+        u = torch.randint(0, 256, (N, 3, H, H), generator=g, dtype=torch.uint8).cuda()
+        _, prep, d = stem_weight(torch, K, Co, R, g)
+        bias = (torch.randn(Co, generator=g) * 0.1).cuda()
+        M, s = K.stem_u8_tables(MEAN, STD, d, Co, 3)
+        with torch.no_grad():
+            y = K.stem_conv_u8(u, prep, M, s, st, pd)
+            hi = float(torch.clamp(y + bias.view(1, -1, 1, 1), min=0.0).max())
+            epi = (bias, None, None, 1, hi / 255.0, 0.0, 8, False, counter)
+            run = lambda v: K.stem_conv_u8_codes(v, prep, M, s, *epi, stride=st, padding=pd)
+            dense = run(u)
+            for layout in LAYOUTS:
+                v = layout_view(torch, u, layout)
+                form = K.stem_u8_view_form(v)
+                assert torch.equal(v, u) and form != "copied" and not v.is_contiguous()
+                assert torch.equal(run(v), dense) and torch.equal(run(v.contiguous()), dense)
+                us = base.measure(torch, {"dense": lambda: run(u),
+                                          "copy + dense": lambda v=v: run(v.contiguous()),
+                                          "in place": lambda v=v: run(v)}, args.rounds)
+                rows.append({"shape": name, "N": N, "kernel": [R, R, st, st], "layout": layout,
+                             "form": form, "us": us})
+            assert int(counter.item()) == 0
+    print(json.dumps({"rows": rows}), flush=True)
+
+
+def layouts_table(args):
+    """The parent of --layouts: one child, the table, the keep rule per form and shape class."""
+    rows = child(["--layouts-child"], args)["rows"]
+    sys.path.insert(0, ROOT)
+    from shiftedscalequantization_amd.build import provenance
+
+    def cell(t):
+        return f"{t['median']:8.1f} ({t['min']:.1f}-{t['max']:.1f})".rjust(26)
+
+    lines = [f"provenance {json.dumps(provenance())}",
+             f"uint8 stem (K32) on views of the image batch, batch {args.batch} at 224 x 224, code form, "
+             f"a W8 asymmetric stem weight; median us over {args.rounds} rounds (min-max), forms "
+             "alternated round by round; every form's codes equal the dense launch's byte for byte",
+             "copy + dense: torch .contiguous() of the view, then the dense launch, timed together "
+             "(the route before views were read in place); in place: the strided launch on the view",
+             "the interleaved staging loads single bytes; aligned wider loads: not tried",
+             "",
+             f"{'shape':<20}{'view':<20}{'form':<13}{'dense us':>26}{'copy + dense us':>26}"
+             f"{'in place us':>26} {'saved':>8} {'spread':>8} {'old/new':>8} {'clear':>6}"]
+    for r in rows:
+        b, t = r["us"]["copy + dense"], r["us"]["in place"]
+        saved, spread = b["median"] - t["median"], b["max"] - b["min"]
+        lines.append(f"{r['shape']:<20}{r['layout']:<20}{r['form']:<13}{cell(r['us']['dense'])}{cell(b)}"
+                     f"{cell(t)} {saved:8.1f} {spread:8.1f} {b['median'] / t['median']:8.2f} "
+                     f"{'yes' if saved > spread else 'NO':>6}")
+    lines.append("saved: copy + dense - in place medians; spread: copy + dense's max - min; clear: saved "
+                 "> spread (the keep rule: auto reads a form in place for a shape class only where "
+                 "every measured view of that form clears it)")
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(text + "\n")
 
 
 def run_parity(args):
@@ -265,6 +364,9 @@ def main(argv=None):
     ap.add_argument("--models-child", action="store_true", help="(child) the per-model code shares")
     ap.add_argument("--chain", type=int, default=None, help="(child) run this chain only")
     ap.add_argument("--no-chains", action="store_true", help="skip the model fronts")
+    ap.add_argument("--layouts", action="store_true",
+                    help="the strided-view table instead (profiles/int_infer_u8_layout_rate.txt)")
+    ap.add_argument("--layouts-child", action="store_true", help="(child) the layout rows only")
     ap.add_argument("--out", default=None)
     ap.add_argument("--parity", default=None, help="append the parity records to this jsonl file")
     args = ap.parse_args(argv)
@@ -276,6 +378,10 @@ def main(argv=None):
         return run_models(args)
     if args.chain is not None:
         return run_chain(args.chain, args)
+    if args.layouts_child:
+        return run_layouts(args)
+    if args.layouts:
+        return layouts_table(args)
     kern = child(["--kernels"], args)
     par = child(["--parity-child"], args)["parity"]
     models = child(["--models-child"], args)["models"]
