@@ -1163,6 +1163,62 @@ int ssq_qlinear_pooled_fwd(const int8_t* hi, const int8_t* lo, const int32_t* sp
                            int act_qmax, float* y, ssq_stream_t stream);
 int ssq_qlinear_pooled_set_tile(int tile);
 
+/* ---------------------------------------------------------------- the wide operand on grouped convs and the pooled fc
+ * The wide operand (m = 128 h + l, |m| <= 16319, factors in [1, 16319]; see above) for the
+ * kernels that read one int8 digit otherwise: K26, K25 and K30.
+ *
+ * ssq_qweight_prepare_grouped_wide writes ssq_qweight_prepared_bytes_grouped_wide bytes from
+ * kfac, column factors [Cig*R*S] (per_ci = 0) or per-(co, ci) factors [Co*Cig] (per_ci = 1):
+ *   grouped (ssq_qconv_grouped_kind 2): the grouped blob with two digit planes, h rows
+ *     [G*Cogp][Kp], then l rows G*Cogp*Kp bytes behind, the 0/1 rows [G][Kp] (written, not
+ *     read), cwz[Co] = 0, T[Co] = sum m;
+ *   depthwise (kind 1): the int32 blob [R*S][Cp] holding m itself; per_ci = 0 only (a depthwise
+ *     row has no per-(co, ci) form: SSQ_E_ARG).
+ * *bad counts a factor outside [1, 16319], an |m| > 16319 and a zero point that is no code.
+ *
+ * ssq_qconv_i8_grouped_wide_fwd / _codes_fwd: ssq_qconv_i8_grouped_fwd / _codes_fwd's arguments,
+ * checks and epilogues on that blob.  Grouped: D_h = sum a_s h and D_l = sum a_s l are exact
+ * int32 sums (2 MFMAs per 16-row fragment and k step, no 0/1 row, no SA product),
+ * I = 128 D_h + D_l + az * T[co] in int64, K = Cig*R*S <= 65536; equal bit for bit to the grouped
+ * form on the centred int8 blob wherever |m| <= 127.  Depthwise: the int32 accumulator is exact
+ * (|I| <= 49 * 255 * 16319 < 2^31), but |I| may pass 2^24, so the one int -> fp32 conversion rounds
+ * to nearest even there, as K23's.
+ *
+ * ssq_qlinear_pooled_wide_fwd: ssq_qlinear_pooled_fwd's arguments and checks with `prepared` a
+ * blob of ssq_qweight_prepare_wide for (Co, Ci, 1, 1):
+ *     I = 128^2 D_hh + 128 (D_hl + D_lh) + D_ll + HW * az * T[co]   (activation digit first)
+ * in int64, four int8-MFMA products per fragment; sp is not read (cwz = 0) but must be valid.  The
+ * caller's scale_h[co] = fp32(fp32(delta_a * base[co]) / fp32(L * HW)); L * HW <= 129 024 is
+ * exact in fp32.  A scaled fc whose m fits int8 needs none of this: its centred blob
+ * (ssq_qweight_prepare_colscale / _perci) runs through ssq_qlinear_pooled_fwd as it stands.
+ *
+ * A blob of any other prepare gives wrong results.  Every refusal is SSQ_E_ARG before any
+ * launch.  No allocation, no sync, capturable. */
+size_t ssq_qweight_prepared_bytes_grouped_wide(int64_t Co, int64_t Cig, int64_t R, int64_t S,
+                                               int64_t groups);
+int ssq_qweight_prepare_grouped_wide(const void* packed, const float* zp, const int32_t* kfac,
+                                     int per_ci, int64_t Co, int64_t Cig, int64_t R, int64_t S,
+                                     int64_t groups, int n_bits, int qmin, void* prepared,
+                                     uint32_t* bad, ssq_stream_t stream);
+int ssq_qconv_i8_grouped_wide_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                                  int64_t Nb, int64_t C, int64_t H, int64_t W, int64_t Co,
+                                  int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                                  float act_zero_point, int act_qmin, int act_qmax, float* y,
+                                  ssq_stream_t stream);
+int ssq_qconv_i8_grouped_wide_codes_fwd(const int8_t* codes, const void* prepared,
+                                        const float* scale, int64_t Nb, int64_t C, int64_t H,
+                                        int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
+                                        int64_t pad, int64_t groups, float act_zero_point,
+                                        int act_qmin, int act_qmax, const float* bias,
+                                        const float* gamma, const float* phi, int act,
+                                        float out_delta, float out_zero_point, int out_qmin,
+                                        int out_qmax, int8_t* out_codes, uint32_t* bad,
+                                        ssq_stream_t stream);
+int ssq_qlinear_pooled_wide_fwd(const int8_t* hi, const int8_t* lo, const int32_t* sp,
+                                const void* prepared, const float* scale_h, int64_t Nb, int64_t Ci,
+                                int64_t Co, int64_t HW, float act_zero_point, int act_qmin,
+                                int act_qmax, float* y, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- bandwidth probe
  * float4 device copy, used by bench.py to report the measured stream bandwidth.      */
 int ssq_stream_copy(const float* src, float* dst, int64_t n, ssq_stream_t stream);

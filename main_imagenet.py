@@ -83,6 +83,7 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
                                     colscale=args.int_infer_colscale,
                                     splitk=args.int_infer_splitk,
                                     per_ci=args.int_infer_per_ci, wide=args.int_infer_wide,
+                                    wide_all=getattr(args, 'int_infer_wide_all', False),
                                     **fused, **image_u8)
     n_int = sum(v == 'int8' for v in plan.values())
     print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')

@@ -187,6 +187,14 @@ SIGNATURES["ssq_qweight_prepared_bytes_wide"] = SIGNATURES["ssq_qweight_prepared
 SIGNATURES["ssq_qweight_prepare_wide"] = (_i, [_p, _p, _p, _i, _i64, _i64, _i64, _i64, _i, _i, _p, _p, _p])
 for _n in ("fwd", "codes_fwd", "codes_res_fwd"):
     SIGNATURES[f"ssq_qconv_i8_wide_{_n}"] = SIGNATURES[f"ssq_qconv_i8_{_n}"]
+# the wide operand on the grouped kernels and the pooled fc: the grouped byte query, one prepare
+# (kfac, then per_ci, as ssq_qweight_prepare_wide with groups behind S), their plain twins' arguments
+SIGNATURES["ssq_qweight_prepared_bytes_grouped_wide"] = SIGNATURES["ssq_qweight_prepared_bytes_grouped"]
+SIGNATURES["ssq_qweight_prepare_grouped_wide"] = (_i, [_p, _p, _p, _i, _i64, _i64, _i64, _i64, _i64, _i, _i,
+                                                       _p, _p, _p])
+SIGNATURES["ssq_qconv_i8_grouped_wide_fwd"] = SIGNATURES["ssq_qconv_i8_grouped_fwd"]
+SIGNATURES["ssq_qconv_i8_grouped_wide_codes_fwd"] = SIGNATURES["ssq_qconv_i8_grouped_codes_fwd"]
+SIGNATURES["ssq_qlinear_pooled_wide_fwd"] = SIGNATURES["ssq_qlinear_pooled_fwd"]
 # the split-K convs take their parents' arguments with (splits, ws, ws_bytes) before the stream
 for _n in ("fwd", "codes_fwd", "codes_res_fwd"):
     _res, _args = SIGNATURES[f"ssq_qconv_i8_{_n}"]

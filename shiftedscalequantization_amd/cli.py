@@ -124,6 +124,10 @@ def build_parser():
                    help='--int_infer with a scaled weight operand (q - z) * k that leaves int8 run '
                         'as two int8 digits (|m| <= 16319, L <= 1024) instead of being refused; '
                         'goes with --int_infer_per_ci / --int_infer_colscale; implies --int_infer')
+    p.add_argument('--int_infer_wide_all', action='store_true',
+                   help='--int_infer_wide with the two-digit operand also on grouped and depthwise '
+                        'convs and on the pooled-operand fc of --int_infer_carry_head (which then '
+                        'takes a scaled fc); implies --int_infer_wide')
     p.add_argument('--int_infer_splitk', action='store_true',
                    help='--int_infer with the dense int8 convs of small planes split along K '
                         'where the host rule asks for it (two kernels, bit-identical); implies '
@@ -162,6 +166,8 @@ def parse_args(argv=None):
         a.int_infer_carry_blocks = True
     if a.int_infer_carry_blocks:
         a.int_infer_carry = True
+    if a.int_infer_wide_all:
+        a.int_infer_wide = True
     if (a.int_infer_grouped or a.int_infer_carry or a.int_infer_colscale or a.int_infer_splitk
             or a.int_infer_graph or a.int_infer_per_ci or a.int_infer_wide):
         a.int_infer = True

@@ -11,7 +11,8 @@
 // workgroup walks a run of consecutive 16-channel chunks for its 256 pixels, so the chunks
 // that share a cache line of the NHWC codes are read by one CU.  Per tap one 16-B code load
 // (a padded tap takes the pad value z_a - ca instead, its (q_a - z_a) = 0), 16 x
-// (a_s + az) * wc into int32 (|I| <= 49 * 255^2 < 2^24: exact, and so is the conversion);
+// (a_s + az) * wc into int32 (an int8-range blob: |I| <= 49 * 255^2 < 2^24, exact, and so is the
+// conversion; the wide blob below: exact sum, rounding conversion);
 // 16 fp32 stores per chunk, each coalesced across the wave's pixels of one NCHW channel
 // plane.  The prepared blob is the centred weight wc = q_w - z_w[c] as int32 [R*S][Cp] (0 on
 // padded channels); its address is wave-uniform, so the 16 values of a (tap, chunk) come
@@ -28,6 +29,18 @@
 // Cogp = 16*ceil(Cog/16) and a tile runs only the 16-row fragments it has (Cog = 8: one MFMA
 // + the SA MFMA per k step, not four).
 // Blob: int8 [G*Cogp][Kp], Kp = 64*ceil(R*S*Wc/64); the 0/1 rows [G][Kp]; cwz[Co], T[Co] (int32).
+//
+// The wide operand (ssq_qweight_prepare_grouped_wide and the *_grouped_wide_* convs), for a scaled
+// weight whose centred m = (q - z_w[co]) * k leaves int8 (|m| <= 16319, qinfer_prepare.h):
+// kind 2 holds m = 128 h + l as two int8 digit planes of the rows above (qinfer_layout.h) and K26's
+// WIDE instantiations stage one chunk of each plane per k step, 2 nf MFMAs, no 0/1 row and no SA
+// MFMA:  I = 128 D_h + D_l + az * T[co]  in int64 (K <= 65536 keeps D_h, D_l below 2^30 and T
+// inside int32); the epilogues are K26's own, and wherever |m| <= 127 the result is K26's on the
+// centred int8 blob bit for bit.  LDS 15 360 B.
+// kind 1 holds m in its int32 blob as it stands, column factors only (a depthwise row has no
+// per-(co, ci) form): |a| * |m| < 2^9 * 2^14 keeps __mul24 exact and |I| <= 49 * 255 * 16319 < 2^31
+// the int32 accumulator, but |I| may pass 2^24, so fp32(I) may round there: that is the
+// contract's one conversion, round to nearest even, as K23's -- it is exact for the int8 blobs only.
 #include <type_traits>
 
 #include "ssq_common.h"
@@ -49,12 +62,13 @@ constexpr uint32_t kDwBlocks = 2048;   // workgroups K25 aims for: 8 per CU
 // scale's k[co * Cig + ci]; *bad also counts what qscaled() counts.
 //
 // depthwise: one thread per (tap, padded channel) of K25's centred int32 blob [R*S][Cp],
-// wc = q - z_w[c]; COLSCALE multiplies it by kcol[tap]
+// wc = q - z_w[c]; COLSCALE multiplies it by kcol[tap], factors and |m| up to `lim` (127, or
+// kQWideMax for the wide form)
 template <bool COLSCALE>
 __global__ __launch_bounds__(kBlock) void qweight_prepare_dw_kernel(
     const uint8_t* __restrict__ packed, const float* __restrict__ zp,
-    const int32_t* __restrict__ kcol, int bs, int qmin, uint32_t C, uint32_t RS, uint32_t Cp,
-    FastDiv div_cp, int32_t* __restrict__ wc, uint32_t* __restrict__ bad) {
+    const int32_t* __restrict__ kcol, int lim, int bs, int qmin, uint32_t C, uint32_t RS,
+    uint32_t Cp, FastDiv div_cp, int32_t* __restrict__ wc, uint32_t* __restrict__ bad) {
   const uint32_t total = RS * Cp;
   uint32_t nbad = 0;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -67,7 +81,7 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_dw_kernel(
       const int z = ok ? (int)zf : qmin;
       if (!ok && tap == 0) ++nbad;   // counted once per channel
       v = (int)packed_code(packed, (size_t)c * RS + tap, bs) + qmin - z;
-      if constexpr (COLSCALE) v = qscaled(v, kcol[tap], 127, nbad);
+      if constexpr (COLSCALE) v = qscaled(v, kcol[tap], lim, nbad);
     }
     wc[i] = v;
   }
@@ -75,14 +89,17 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_dw_kernel(
 }
 
 // grouped: one workgroup per padded row (g, rl), then one per group for its 0/1 row.  K26's blob;
-// COLSCALE: m as the int8 operand, cwz = 0, T[co] = sum m, the 0/1 rows all the same
-template <bool COLSCALE>
+// COLSCALE: m as the int8 operand, cwz = 0, T[co] = sum m, the 0/1 rows all the same.  WIDE (with
+// COLSCALE): m leaves as its two digits, h into the first plane and l into the second,
+// G * Cogp * Kp bytes behind
+template <bool COLSCALE, bool WIDE = false>
 __global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_kernel(
     const uint8_t* __restrict__ packed, const float* __restrict__ zp, QFactor f, int bs, int qmin,
     uint32_t groups, uint32_t Cig,
     uint32_t Cog, uint32_t Cogp, uint32_t RS, uint32_t Wc, uint32_t Kp, FastDiv div_wc,
     FastDiv div_cogp, int8_t* __restrict__ wp, int8_t* __restrict__ mask,
     int32_t* __restrict__ cwz, int32_t* __restrict__ tt, uint32_t* __restrict__ bad) {
+  static_assert(COLSCALE || !WIDE, "the wide blob holds a centred operand");
   __shared__ int red[kBlock / kWave];
   const uint32_t row = blockIdx.x;
   const uint32_t nrows = groups * Cogp;
@@ -112,9 +129,14 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_kernel(
       const int u = (int)packed_code(packed, (size_t)co * Cig * RS + j, bs);   // q - qmin
       if constexpr (COLSCALE) v = qscaled(u + qmin - z, qfactor_at(f, co, cw - lo, tap), f.lim, nbad);
       else v = u - 128;   // q - cw, cw = qmin + 128
-      sum += v;
+      sum += v;   // WIDE: |sum| <= 65536 * 16319 < 2^31
     }
-    wp[(size_t)row * Kp + k] = (int8_t)v;
+    if constexpr (WIDE) {
+      wp[(size_t)row * Kp + k] = (int8_t)qdigit_hi(v);
+      wp[((size_t)nrows + row) * Kp + k] = (int8_t)qdigit_lo(v);
+    } else {
+      wp[(size_t)row * Kp + k] = (int8_t)v;
+    }
   }
   sum = (int)wave_sum((uint32_t)sum);
   nbad = wave_sum(nbad);
@@ -188,7 +210,7 @@ __global__ __launch_bounds__(kBlock) void qconv_dw_kernel(
 #pragma unroll
           for (int b = 0; b < 4; ++b) {
             const int a = ((int)(word << (24 - 8 * b)) >> 24) + g.az;   // sign-extended byte + az
-            acc[q * 4 + b] += __mul24(a, wt[q * 4 + b]);   // |a| < 2^9, |wc| < 2^10
+            acc[q * 4 + b] += __mul24(a, wt[q * 4 + b]);   // |a| < 2^9, |wc| < 2^14
           }
         }
       }
@@ -226,6 +248,18 @@ struct QGConvGeo {
   FastDiv div_p, div_ow, div_wc, div_s, div_tiles;
 };
 
+// the epilogue's integer sum of channel co: I = D + cwz[co] * SA_g + az * T[co], or, WIDE (`d` is
+// D_h, `dl` D_l), I = 128 D_h + D_l + az * T[co]
+template <bool WIDE>
+__device__ __forceinline__ long long qg_sum(int d, int dl, const int32_t* __restrict__ cwz,
+                                            long long sa, int az, const int32_t* __restrict__ tt,
+                                            uint32_t co) {
+  if constexpr (WIDE)
+    return 128ll * (long long)d + (long long)dl + (long long)az * (long long)tt[co];
+  else
+    return (long long)d + (long long)cwz[co] * sa + (long long)az * (long long)tt[co];
+}
+
 // one `T` per (pixel row, unit) of the transposed code tile, LDS -> the NHWC codes
 template <typename T>
 __device__ __forceinline__ void qg_store_units(const int8_t* lds, int8_t* out, uint32_t units,
@@ -239,14 +273,17 @@ __device__ __forceinline__ void qg_store_units(const int8_t* lds, int8_t* out, u
 // Cpo when that is the layer's last channel (the zero padding is its to write) -- and stores
 // them at the widest power of two up to 16 B that divides both c0 and c1 - c0: two workgroups
 // may own different bytes of one 16-B chunk, none writes a byte of another's.
-template <bool CODES>
+// WIDE: the blob's two digit planes (h, then l at `plane` bytes) take the place of the weight tile
+// and the 0/1 row: lB rows [0, 64) hold h, [64, 128) l; acc is D_h, accl D_l; `masks` and `cwz`
+// are not read.
+template <bool CODES, bool WIDE = false>
 __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
     const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ masks,
     const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
     const float* __restrict__ scale, QGConvGeo g,
     typename std::conditional<CODES, QEpi, float* __restrict__>::type y) {
   __shared__ __attribute__((aligned(16))) int8_t lA[kGT * kGRow];
-  __shared__ __attribute__((aligned(16))) int8_t lB[(kGT + 1) * kGRow];
+  __shared__ __attribute__((aligned(16))) int8_t lB[(WIDE ? 2 * kGT : kGT + 1) * kGRow];
   const uint32_t tid = threadIdx.x;
   const uint32_t lane = tid & (kWave - 1), wave = tid / kWave;
   const uint32_t fr = lane & 15, fq = lane >> 4;
@@ -273,6 +310,7 @@ __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
   const bool bval = srow < nrow;
   const int8_t* wrow = wp + (size_t)(grp * g.Cogp + row0 + (bval ? srow : 0u)) * g.Kp + sc * 16;
   const int8_t* mrow = masks + (size_t)grp * g.Kp;
+  const size_t plane = WIDE ? (size_t)(gridDim.y / g.tiles) * g.Cogp * g.Kp : 0;   // G * Cogp * Kp
   const int pv = (g.padv & 0xff) * 0x01010101;
   const i32x4 padfill = {pv, pv, pv, pv};
   const i32x4 zero4 = {0, 0, 0, 0};
@@ -291,12 +329,19 @@ __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
 
   i32x4 ra = load_a(0);
   i32x4 rb = bval ? *(const i32x4*)wrow : zero4;
-  i32x4 rm = zero4;
-  if (tid < 4) rm = *(const i32x4*)(mrow + tid * 16);
+  i32x4 rm = zero4;   // WIDE: the thread's chunk of the l plane
+  if constexpr (WIDE) {
+    if (bval) rm = *(const i32x4*)(wrow + plane);
+  } else {
+    if (tid < 4) rm = *(const i32x4*)(mrow + tid * 16);
+  }
 
   i32x4 acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc[j] = zero4;
+  i32x4 accl[WIDE ? 4 : 1];
+#pragma unroll
+  for (int j = 0; j < (WIDE ? 4 : 1); ++j) accl[j] = zero4;
   i32x4 accs = zero4;
 
   const uint32_t nk = g.Kp / kGT;
@@ -304,21 +349,35 @@ __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
     __syncthreads();   // the previous step's fragment reads are done
     *(i32x4*)(lA + srow * kGRow + sc * 16) = ra;
     if (bval) *(i32x4*)(lB + srow * kGRow + sc * 16) = rb;
-    if (tid < 4) *(i32x4*)(lB + kGT * kGRow + tid * 16) = rm;
+    if constexpr (WIDE) {
+      if (bval) *(i32x4*)(lB + (kGT + srow) * kGRow + sc * 16) = rm;
+    } else {
+      if (tid < 4) *(i32x4*)(lB + kGT * kGRow + tid * 16) = rm;
+    }
     __syncthreads();
     if (kt + 1 < nk) {
       ra = load_a(kt + 1);
       if (bval) rb = *(const i32x4*)(wrow + (size_t)(kt + 1) * kGT);
-      if (tid < 4) rm = *(const i32x4*)(mrow + (size_t)(kt + 1) * kGT + tid * 16);
+      if constexpr (WIDE) {
+        if (bval) rm = *(const i32x4*)(wrow + plane + (size_t)(kt + 1) * kGT);
+      } else {
+        if (tid < 4) rm = *(const i32x4*)(mrow + (size_t)(kt + 1) * kGT + tid * 16);
+      }
     }
     const i32x4 af = *(const i32x4*)(lA + (wave * 16 + fr) * kGRow + fq * 16);
-    const i32x4 mf = *(const i32x4*)(lB + kGT * kGRow + fq * 16);
-    accs = __builtin_amdgcn_mfma_i32_16x16x64_i8(mf, af, accs, 0, 0, 0);
+    if constexpr (!WIDE) {
+      const i32x4 mf = *(const i32x4*)(lB + kGT * kGRow + fq * 16);
+      accs = __builtin_amdgcn_mfma_i32_16x16x64_i8(mf, af, accs, 0, 0, 0);
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if ((uint32_t)j < nf) {
         const i32x4 wf = *(const i32x4*)(lB + (j * 16 + fr) * kGRow + fq * 16);
         acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, af, acc[j], 0, 0, 0);
+        if constexpr (WIDE) {
+          const i32x4 lf = *(const i32x4*)(lB + (kGT + j * 16 + fr) * kGRow + fq * 16);
+          accl[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(lf, af, accl[j], 0, 0, 0);
+        }
       }
     }
   }
@@ -343,8 +402,7 @@ __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
         c[r] = 0;
         if (pval && rl < g.Cog) {
           const uint32_t co = grp * g.Cog + rl;
-          const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
-                              (long long)g.az * (long long)tt[co];
+          const long long I = qg_sum<WIDE>(acc[j][r], accl[WIDE ? j : 0][r], cwz, sa, g.az, tt, co);
           c[r] = qepi_code((float)I, co, scale, e, nbad);
         }
       }
@@ -379,8 +437,7 @@ __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
         const uint32_t rl = row0 + j * 16 + fq * 4 + r;
         if (rl < g.Cog) {
           const uint32_t co = grp * g.Cog + rl;
-          const long long I = (long long)acc[j][r] + (long long)cwz[co] * sa +
-                              (long long)g.az * (long long)tt[co];
+          const long long I = qg_sum<WIDE>(acc[j][r], accl[WIDE ? j : 0][r], cwz, sa, g.az, tt, co);
           y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
         }
       }
@@ -390,7 +447,7 @@ __global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
 
 // C < 0: the caller has no C of its own (prepare); else C must be Cig * groups
 static int ggeo_ok(const char* what, const char* plain, int64_t C, int64_t Co, int64_t Cig,
-                   int64_t R, int64_t S, int64_t groups) {
+                   int64_t R, int64_t S, int64_t groups, int planes = 1) {
   SSQ_REQUIRE(groups >= 2, SSQ_E_ARG, "%s: groups = %lld (groups >= 2 only; groups == 1 is %s)",
               what, (long long)groups, plain);
   SSQ_REQUIRE(C < 0 || (C >= 1 && C % groups == 0), SSQ_E_ARG,
@@ -406,7 +463,7 @@ static int ggeo_ok(const char* what, const char* plain, int64_t C, int64_t Co, i
               "%s: K = Cig*R*S = %lld exceeds 65536 (int32 accumulator range)", what,
               (long long)(Cig * R * S));
   SSQ_REQUIRE(Cig <= (1ll << 31) / groups, SSQ_E_ARG, "%s: C = Cig*groups exceeds 2^31", what);
-  const GLayout L = glayout(Co, Cig, R, S, groups);
+  const GLayout L = glayout(Co, Cig, R, S, groups, planes);
   SSQ_REQUIRE(L.kind != 0, SSQ_E_ARG, "%s: bad geometry", what);
   SSQ_REQUIRE(L.bytes < (1ull << 31), SSQ_E_ARG, "%s: prepared weights exceed 2^31 bytes", what);
   SSQ_REQUIRE(L.kind == 1 ? L.Cp / 16 <= 65535 : groups * L.tiles <= 65535, SSQ_E_ARG,
@@ -430,9 +487,10 @@ extern "C" size_t ssq_qweight_prepared_bytes_grouped(int64_t Co, int64_t Cig, in
 
 // kcol: the factors of a scaled weight (the COLSCALE kernels), or null: one per column, or,
 // per_ci, one per (co, ci) (grouped only: a depthwise weight has no such form); `plain`: the
-// groups == 1 entry point an error message points to
+// groups == 1 entry point an error message points to; wide: the wide forms (kind 2 the two-plane
+// blob, kind 1 its int32 blob), factors and |m| up to kQWideMax
 static int qweight_prepare_grouped_launch(const char* me, const char* plain, bool colscale,
-                                          bool per_ci, const void* packed, const float* zp,
+                                          bool per_ci, bool wide, const void* packed, const float* zp,
                                           const int32_t* kcol, int64_t Co, int64_t Cig, int64_t R,
                                           int64_t S, int64_t groups, int n_bits, int qmin,
                                           void* prepared, uint32_t* bad, ssq_stream_t stream) {
@@ -440,9 +498,11 @@ static int qweight_prepare_grouped_launch(const char* me, const char* plain, boo
               "%s: null pointer", me);
   int rc = qrange_ok(me, n_bits, qmin);
   if (rc) return rc;
-  rc = ggeo_ok(me, plain, -1, Co, Cig, R, S, groups);
+  SSQ_REQUIRE(colscale || !wide, SSQ_E_ARG, "%s: the wide blob holds a scaled weight", me);
+  rc = ggeo_ok(me, plain, -1, Co, Cig, R, S, groups, wide ? 2 : 1);
   if (rc) return rc;
-  const GLayout L = glayout(Co, Cig, R, S, groups);
+  const GLayout L = glayout(Co, Cig, R, S, groups, wide ? 2 : 1);
+  const int lim = wide ? kQWideMax : 127;
   int8_t* base = (int8_t*)prepared;
   const int bs = packed_bits(n_bits);
   const uint32_t RS = (uint32_t)(R * S);
@@ -451,15 +511,16 @@ static int qweight_prepare_grouped_launch(const char* me, const char* plain, boo
   if (L.kind == 1) {
     auto* kernel = colscale ? qweight_prepare_dw_kernel<true> : qweight_prepare_dw_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(grid_for((int64_t)RS * L.Cp, kBlock)), dim3(kBlock), 0,
-                       (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, bs, qmin,
+                       (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, lim, bs, qmin,
                        (uint32_t)L.C, RS, (uint32_t)L.Cp, make_fastdiv((uint32_t)L.Cp),
                        (int32_t*)base, bad);
   } else {
-    auto* kernel =
-        colscale ? qweight_prepare_grouped_kernel<true> : qweight_prepare_grouped_kernel<false>;
+    auto* kernel = wide ? qweight_prepare_grouped_kernel<true, true>
+                        : (colscale ? qweight_prepare_grouped_kernel<true>
+                                    : qweight_prepare_grouped_kernel<false>);
     hipLaunchKernelGGL(kernel, dim3((uint32_t)(groups * L.Cogp + groups)), dim3(kBlock), 0,
                        (hipStream_t)stream, (const uint8_t*)packed, zp,
-                       qfactor(kcol, per_ci, (uint32_t)Cig, RS, 127), bs, qmin,
+                       qfactor(kcol, per_ci, (uint32_t)Cig, RS, lim), bs, qmin,
                        (uint32_t)groups, (uint32_t)Cig, (uint32_t)L.Cog, (uint32_t)L.Cogp, RS,
                        (uint32_t)L.Wc, (uint32_t)L.Kp, make_fastdiv((uint32_t)L.Wc),
                        make_fastdiv((uint32_t)L.Cogp), base, base + L.off_mask,
@@ -473,7 +534,7 @@ extern "C" int ssq_qweight_prepare_grouped(const void* packed, const float* zp, 
                                            int n_bits, int qmin, void* prepared, uint32_t* bad,
                                            ssq_stream_t stream) {
   return qweight_prepare_grouped_launch("ssq_qweight_prepare_grouped", "ssq_qweight_prepare",
-                                        false, false, packed, zp, nullptr, Co, Cig, R, S, groups,
+                                        false, false, false, packed, zp, nullptr, Co, Cig, R, S, groups,
                                         n_bits, qmin, prepared, bad, stream);
 }
 
@@ -483,7 +544,7 @@ extern "C" int ssq_qweight_prepare_grouped_colscale(const void* packed, const fl
                                                     int n_bits, int qmin, void* prepared,
                                                     uint32_t* bad, ssq_stream_t stream) {
   return qweight_prepare_grouped_launch("ssq_qweight_prepare_grouped_colscale",
-                                        "ssq_qweight_prepare_colscale", true, false, packed, zp,
+                                        "ssq_qweight_prepare_colscale", true, false, false, packed, zp,
                                         kcol, Co, Cig, R, S, groups, n_bits, qmin, prepared, bad,
                                         stream);
 }
@@ -494,12 +555,30 @@ extern "C" int ssq_qweight_prepare_grouped_perci(const void* packed, const float
                                                  int qmin, void* prepared, uint32_t* bad,
                                                  ssq_stream_t stream) {
   return qweight_prepare_grouped_launch("ssq_qweight_prepare_grouped_perci",
-                                        "ssq_qweight_prepare_perci", true, true, packed, zp, kfac,
+                                        "ssq_qweight_prepare_perci", true, true, false, packed, zp, kfac,
                                         Co, Cig, R, S, groups, n_bits, qmin, prepared, bad, stream);
 }
 
-// y: the fp32 output (ssq_qconv_i8_grouped_fwd) or null with `epi` set (..._codes_fwd)
-static int qconv_grouped_launch(const char* me, const int8_t* codes, const void* prepared,
+extern "C" size_t ssq_qweight_prepared_bytes_grouped_wide(int64_t Co, int64_t Cig, int64_t R,
+                                                          int64_t S, int64_t groups) {
+  if (R > 7 || S > 7 || Cig > kGMaxK || groups > (1ll << 31)) return 0;
+  return glayout(Co, Cig, R, S, groups, 2).bytes;
+}
+
+extern "C" int ssq_qweight_prepare_grouped_wide(const void* packed, const float* zp,
+                                                const int32_t* kfac, int per_ci, int64_t Co,
+                                                int64_t Cig, int64_t R, int64_t S, int64_t groups,
+                                                int n_bits, int qmin, void* prepared, uint32_t* bad,
+                                                ssq_stream_t stream) {
+  return qweight_prepare_grouped_launch("ssq_qweight_prepare_grouped_wide",
+                                        "ssq_qweight_prepare_wide", true, per_ci != 0, true, packed,
+                                        zp, kfac, Co, Cig, R, S, groups, n_bits, qmin, prepared,
+                                        bad, stream);
+}
+
+// y: the fp32 output (ssq_qconv_i8_grouped_fwd) or null with `epi` set (..._codes_fwd); wide: the
+// *_grouped_wide_* forms on a blob of ssq_qweight_prepare_grouped_wide
+static int qconv_grouped_launch(const char* me, bool wide, const int8_t* codes, const void* prepared,
                                 const float* scale, int64_t Nb, int64_t C, int64_t H, int64_t W,
                                 int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
                                 int64_t groups, float act_zero_point, int act_qmin, int act_qmax,
@@ -512,14 +591,14 @@ static int qconv_grouped_launch(const char* me, const int8_t* codes, const void*
               "%s: C = %lld is not divisible by groups = %lld", me, (long long)C,
               (long long)groups);
   const int64_t Cig = C / groups;
-  int rc = ggeo_ok(me, "ssq_qconv_i8_fwd", C, Co, Cig, R, S, groups);
+  int rc = ggeo_ok(me, "ssq_qconv_i8_fwd", C, Co, Cig, R, S, groups, wide ? 2 : 1);
   if (rc) return rc;
   SSQ_REQUIRE(Nb >= 1 && H >= 1 && W >= 1 && stride >= 1 && pad >= 0 && H + 2 * pad >= R &&
                   W + 2 * pad >= S,
               SSQ_E_ARG, "%s: bad geometry", me);
   rc = qquant_ok(me, "activation ", nullptr, act_zero_point, act_qmin, act_qmax);
   if (rc) return rc;
-  const GLayout L = glayout(Co, Cig, R, S, groups);
+  const GLayout L = glayout(Co, Cig, R, S, groups, wide ? 2 : 1);
   const int64_t OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
   SSQ_REQUIRE(Nb * H * W * L.Cp < (1ll << 31) && Nb * OH * OW * Co < (1ll << 31), SSQ_E_ARG,
               "%s: tensor exceeds 2^31 elements", me);
@@ -596,15 +675,18 @@ static int qconv_grouped_launch(const char* me, const int8_t* codes, const void*
   g.div_s = make_fastdiv(g.S);
   g.div_tiles = make_fastdiv(g.tiles);
   const dim3 grid((g.M + kGT - 1) / kGT, (uint32_t)(groups * L.tiles));
+  const int8_t* masks = base + L.off_mask;
+  const int32_t* cwz = (const int32_t*)(base + L.off_cwz);
+  const int32_t* tt = (const int32_t*)(base + L.off_t);
   if (epi) {
-    hipLaunchKernelGGL(qconv_grouped_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)stream,
-                       codes, base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
-                       (const int32_t*)(base + L.off_t), scale, g, *epi);
+    auto* kernel = wide ? qconv_grouped_kernel<true, true> : qconv_grouped_kernel<true>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base, masks, cwz,
+                       tt, scale, g, *epi);
     return check_launch(me);
   }
-  hipLaunchKernelGGL(qconv_grouped_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)stream,
-                     codes, base, base + L.off_mask, (const int32_t*)(base + L.off_cwz),
-                     (const int32_t*)(base + L.off_t), scale, g, y);
+  auto* kernel = wide ? qconv_grouped_kernel<false, true> : qconv_grouped_kernel<false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base, masks, cwz,
+                     tt, scale, g, y);
   return check_launch(me);
 }
 
@@ -614,7 +696,7 @@ extern "C" int ssq_qconv_i8_grouped_fwd(const int8_t* codes, const void* prepare
                                         int64_t pad, int64_t groups, float act_zero_point,
                                         int act_qmin, int act_qmax, float* y, ssq_stream_t stream) {
   SSQ_REQUIRE(y, SSQ_E_ARG, "ssq_qconv_i8_grouped_fwd: null pointer");
-  return qconv_grouped_launch("ssq_qconv_i8_grouped_fwd", codes, prepared, scale, Nb, C, H, W, Co,
+  return qconv_grouped_launch("ssq_qconv_i8_grouped_fwd", false, codes, prepared, scale, Nb, C, H, W, Co,
                               R, S, stride, pad, groups, act_zero_point, act_qmin, act_qmax, y,
                               nullptr, stream);
 }
@@ -630,6 +712,36 @@ extern "C" int ssq_qconv_i8_grouped_codes_fwd(
   const int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin,
                            out_qmax, out_codes, bad, &e);
   if (rc) return rc;
-  return qconv_grouped_launch(me, codes, prepared, scale, Nb, C, H, W, Co, R, S, stride, pad,
+  return qconv_grouped_launch(me, false, codes, prepared, scale, Nb, C, H, W, Co, R, S, stride,
+                              pad, groups, act_zero_point, act_qmin, act_qmax, nullptr, &e, stream);
+}
+
+// The wide forms: the grouped forms' arguments, checks and epilogues on a blob of
+// ssq_qweight_prepare_grouped_wide (kind 2: two int8 digit planes, 2 nf MFMAs per k step;
+// kind 1: K25 on its int32 blob).
+extern "C" int ssq_qconv_i8_grouped_wide_fwd(const int8_t* codes, const void* prepared,
+                                             const float* scale, int64_t Nb, int64_t C, int64_t H,
+                                             int64_t W, int64_t Co, int64_t R, int64_t S,
+                                             int64_t stride, int64_t pad, int64_t groups,
+                                             float act_zero_point, int act_qmin, int act_qmax,
+                                             float* y, ssq_stream_t stream) {
+  SSQ_REQUIRE(y, SSQ_E_ARG, "ssq_qconv_i8_grouped_wide_fwd: null pointer");
+  return qconv_grouped_launch("ssq_qconv_i8_grouped_wide_fwd", true, codes, prepared, scale, Nb, C,
+                              H, W, Co, R, S, stride, pad, groups, act_zero_point, act_qmin,
+                              act_qmax, y, nullptr, stream);
+}
+
+extern "C" int ssq_qconv_i8_grouped_wide_codes_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t C, int64_t H,
+    int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+    float act_zero_point, int act_qmin, int act_qmax, const float* bias, const float* gamma,
+    const float* phi, int act, float out_delta, float out_zero_point, int out_qmin, int out_qmax,
+    int8_t* out_codes, uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_grouped_wide_codes_fwd";
+  QEpi e;
+  const int rc = qepi_init(me, bias, gamma, phi, act, out_delta, out_zero_point, out_qmin,
+                           out_qmax, out_codes, bad, &e);
+  if (rc) return rc;
+  return qconv_grouped_launch(me, true, codes, prepared, scale, Nb, C, H, W, Co, R, S, stride, pad,
                               groups, act_zero_point, act_qmin, act_qmax, nullptr, &e, stream);
 }

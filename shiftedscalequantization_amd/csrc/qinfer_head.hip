@@ -20,6 +20,16 @@
 // K29 ssq_avgpool_i8_digits_fwd: codes NHWC int8 [N][H*W][Cp] -> hi, lo [N][Cp] int8 and
 // sp [N] int32; padded channels 0 in both planes, every output byte written by one thread.
 // K30 ssq_qlinear_pooled_fwd: hi, lo, sp and the fc's K22 blob -> y [N][Co] fp32.
+//
+// A scaled fc (W_hat = (q_w - z_w[co]) d1[co] k / L, qinfer_prepare.h) whose centred operand
+// m = (q_w - z_w[co]) k fits int8 is K22's centred blob in the kernel above as it stands: cwz = 0
+// makes the cwz * SP term vanish, and the caller's sh[co] = fp32(fp32(delta_a * base[co]) /
+// fp32(L * HW)) carries the grid (L * HW <= 1024 * 126 is exact in fp32: one division).  Beyond
+// int8, ssq_qlinear_pooled_wide_fwd reads the dense wide blob (ssq_qweight_prepare_wide:
+// m = 128 h + l, |m| <= 16319) with the WIDE instantiations: four products per fragment,
+//     I = 128^2 D_hh + 128 (D_hl + D_lh) + D_ll + HW * az * T[co]     (D_xy = sum_c x_a y_w)
+// in int64; C <= 65536 keeps every D below 2^30 (|hi| <= 126, |h| <= 127), and at HW = 126,
+// C = 65536, |m| = 16319 |I| < 2^47.  SP is not read.
 #include "ssq_common.h"
 #include "qinfer_check.h"
 #include "qinfer_layout.h"
@@ -135,7 +145,10 @@ struct QHeadGeo {
 // weight fragment; no SA product, SP arrives from K29.
 // IT = 64: wave w owns images 16w..16w+15 against all 64 channels (8 MFMAs per step).
 // IT = 16: wave w owns channels 16w..16w+15 against the tile's 16 images (2 MFMAs per step).
-template <int IT>
+// WIDE: lW rows [0, 64) hold the h plane's tile, [64, 128) the l plane's (`plane` bytes behind);
+// acch / accl are then D_hh / D_lh and acchl / accll D_hl / D_ll (activation digit first), twice
+// the MFMAs; `sp` and `cwz` are not read.
+template <int IT, bool WIDE = false>
 __global__ __launch_bounds__(kBlock) void qlinear_pooled_kernel(
     const int8_t* __restrict__ hi, const int8_t* __restrict__ lo, const int32_t* __restrict__ sp,
     const int8_t* __restrict__ wp, const int32_t* __restrict__ cwz,
@@ -143,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void qlinear_pooled_kernel(
     float* __restrict__ y) {
   static_assert(IT == 64 || IT == 16, "image tile");
   constexpr int NJ = IT == 64 ? 4 : 1;
-  __shared__ __attribute__((aligned(16))) int8_t lW[kQT * kQRow];
+  __shared__ __attribute__((aligned(16))) int8_t lW[(WIDE ? 2 : 1) * kQT * kQRow];
   __shared__ __attribute__((aligned(16))) int8_t lH[IT * kQRow];
   __shared__ __attribute__((aligned(16))) int8_t lL[IT * kQRow];
   const uint32_t tid = threadIdx.x;
@@ -158,6 +171,7 @@ __global__ __launch_bounds__(kBlock) void qlinear_pooled_kernel(
   const bool ival = stage && gi < g.N;
   const size_t aoff = (size_t)(ival ? gi : 0u) * g.Cp + sc * 16;
   const int8_t* wrow = wp + (size_t)(blockIdx.y * kQT + srow) * g.Kp + sc * 16;
+  const size_t plane = WIDE ? (size_t)gridDim.y * kQT * g.Kp : 0;   // Cop * Kp
   const i32x4 zero = {0, 0, 0, 0};
 
   // Cp is a multiple of 16: a chunk that starts below Cp lies inside the row
@@ -168,15 +182,21 @@ __global__ __launch_bounds__(kBlock) void qlinear_pooled_kernel(
 
   i32x4 rh = load_a(hi, 0), rl = load_a(lo, 0);
   i32x4 rb = *(const i32x4*)wrow;
+  i32x4 rb2 = zero;   // WIDE: the l plane's chunk
+  if constexpr (WIDE) rb2 = *(const i32x4*)(wrow + plane);
 
   i32x4 acch[NJ], accl[NJ];
+  i32x4 acchl[WIDE ? NJ : 1], accll[WIDE ? NJ : 1];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) acch[j] = accl[j] = zero;
+#pragma unroll
+  for (int j = 0; j < (WIDE ? NJ : 1); ++j) acchl[j] = accll[j] = zero;
 
   const uint32_t nk = g.Kp / kQT;
   for (uint32_t kt = 0; kt < nk; ++kt) {
     __syncthreads();   // the previous step's fragment reads are done
     *(i32x4*)(lW + srow * kQRow + sc * 16) = rb;
+    if constexpr (WIDE) *(i32x4*)(lW + (kQT + srow) * kQRow + sc * 16) = rb2;
     if (stage) {
       *(i32x4*)(lH + srow * kQRow + sc * 16) = rh;
       *(i32x4*)(lL + srow * kQRow + sc * 16) = rl;
@@ -186,6 +206,7 @@ __global__ __launch_bounds__(kBlock) void qlinear_pooled_kernel(
       rh = load_a(hi, kt + 1);
       rl = load_a(lo, kt + 1);
       rb = *(const i32x4*)(wrow + (size_t)(kt + 1) * kQT);
+      if constexpr (WIDE) rb2 = *(const i32x4*)(wrow + plane + (size_t)(kt + 1) * kQT);
     }
     const i32x4 hf = *(const i32x4*)(lH + (ib * 16 + fr) * kQRow + fq * 16);
     const i32x4 lf = *(const i32x4*)(lL + (ib * 16 + fr) * kQRow + fq * 16);
@@ -195,13 +216,18 @@ __global__ __launch_bounds__(kBlock) void qlinear_pooled_kernel(
       const i32x4 wf = *(const i32x4*)(lW + (crow + fr) * kQRow + fq * 16);
       acch[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, hf, acch[j], 0, 0, 0);
       accl[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, lf, accl[j], 0, 0, 0);
+      if constexpr (WIDE) {
+        const i32x4 wl = *(const i32x4*)(lW + (kQT + crow + fr) * kQRow + fq * 16);
+        acchl[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wl, hf, acchl[j], 0, 0, 0);
+        accll[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wl, lf, accll[j], 0, 0, 0);
+      }
     }
   }
 
   // C/D map: column (image) = lane & 15, row (channel) = 4 * (lane >> 4) + reg
   const uint32_t image = blockIdx.x * IT + ib * 16 + fr;
   if (image >= g.N) return;
-  const long long spn = (long long)sp[image];
+  const long long spn = WIDE ? 0ll : (long long)sp[image];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const uint32_t crow = (IT == 64 ? (uint32_t)j : wave) * 16;
@@ -209,8 +235,14 @@ __global__ __launch_bounds__(kBlock) void qlinear_pooled_kernel(
     for (int r = 0; r < 4; ++r) {
       const uint32_t co = blockIdx.y * kQT + crow + fq * 4 + r;
       if (co < g.Co) {
-        const long long I = 128ll * (long long)acch[j][r] + (long long)accl[j][r] +
-                            (long long)cwz[co] * spn + g.hwaz * (long long)tt[co];
+        long long I;
+        if constexpr (WIDE)
+          I = 16384ll * (long long)acch[j][r] +
+              128ll * ((long long)acchl[j][r] + (long long)accl[j][r]) +
+              (long long)accll[WIDE ? j : 0][r] + g.hwaz * (long long)tt[co];
+        else
+          I = 128ll * (long long)acch[j][r] + (long long)accl[j][r] + (long long)cwz[co] * spn +
+              g.hwaz * (long long)tt[co];
         y[(size_t)image * g.Co + co] = __fmul_rn((float)I, sh[co]);
       }
     }
@@ -255,11 +287,12 @@ extern "C" int ssq_avgpool_i8_digits_fwd(const int8_t* codes, int64_t Nb, int64_
   return check_launch(me);
 }
 
-extern "C" int ssq_qlinear_pooled_fwd(const int8_t* hi, const int8_t* lo, const int32_t* sp,
-                                      const void* prepared, const float* scale_h, int64_t Nb,
-                                      int64_t Ci, int64_t Co, int64_t HW, float act_zero_point,
-                                      int act_qmin, int act_qmax, float* y, ssq_stream_t stream) {
-  const char* me = "ssq_qlinear_pooled_fwd";
+// wide: ssq_qlinear_pooled_wide_fwd, on a blob of ssq_qweight_prepare_wide
+static int qlinear_pooled_launch(const char* me, bool wide, const int8_t* hi, const int8_t* lo,
+                                 const int32_t* sp, const void* prepared, const float* scale_h,
+                                 int64_t Nb, int64_t Ci, int64_t Co, int64_t HW,
+                                 float act_zero_point, int act_qmin, int act_qmax, float* y,
+                                 ssq_stream_t stream) {
   SSQ_REQUIRE(hi && lo && sp && prepared && scale_h && y, SSQ_E_ARG, "%s: null pointer", me);
   SSQ_REQUIRE(Nb >= 1 && Ci >= 1 && Co >= 1, SSQ_E_ARG, "%s: bad geometry", me);
   SSQ_REQUIRE(Nb < (1ll << 31) && Co < (1ll << 31), SSQ_E_ARG,
@@ -270,7 +303,7 @@ extern "C" int ssq_qlinear_pooled_fwd(const int8_t* hi, const int8_t* lo, const 
               (long long)Ci);
   const int rc = qquant_ok(me, "activation ", nullptr, act_zero_point, act_qmin, act_qmax);
   if (rc) return rc;
-  const QLayout L = qlayout(Co, Ci, 1, 1);
+  const QLayout L = qlayout(Co, Ci, 1, 1, wide ? 2 : 1);
   SSQ_REQUIRE(L.off_mask < (1ull << 31), SSQ_E_ARG, "%s: prepared weights exceed 2^31 bytes", me);
   SSQ_REQUIRE(Nb * L.Cp < (1ll << 31) && Nb * Co < (1ll << 31), SSQ_E_ARG,
               "%s: tensor exceeds 2^31 elements", me);
@@ -284,11 +317,27 @@ extern "C" int ssq_qlinear_pooled_fwd(const int8_t* hi, const int8_t* lo, const 
   const int32_t* cwz = (const int32_t*)(base + L.off_cwz);
   const int32_t* tt = (const int32_t*)(base + L.off_t);
   const uint32_t ctiles = (uint32_t)(L.Cop / kQT);
-  if (head_tile() == 64)
-    hipLaunchKernelGGL(qlinear_pooled_kernel<64>, dim3((g.N + 63) / 64, ctiles), dim3(kBlock), 0,
-                       (hipStream_t)stream, hi, lo, sp, base, cwz, tt, scale_h, g, y);
-  else
-    hipLaunchKernelGGL(qlinear_pooled_kernel<16>, dim3((g.N + 15) / 16, ctiles), dim3(kBlock), 0,
-                       (hipStream_t)stream, hi, lo, sp, base, cwz, tt, scale_h, g, y);
+  const int it = head_tile();
+  auto* kernel = it == 64 ? (wide ? qlinear_pooled_kernel<64, true> : qlinear_pooled_kernel<64>)
+                          : (wide ? qlinear_pooled_kernel<16, true> : qlinear_pooled_kernel<16>);
+  hipLaunchKernelGGL(kernel, dim3((g.N + (uint32_t)it - 1) / (uint32_t)it, ctiles), dim3(kBlock), 0,
+                     (hipStream_t)stream, hi, lo, sp, base, cwz, tt, scale_h, g, y);
   return check_launch(me);
+}
+
+extern "C" int ssq_qlinear_pooled_fwd(const int8_t* hi, const int8_t* lo, const int32_t* sp,
+                                      const void* prepared, const float* scale_h, int64_t Nb,
+                                      int64_t Ci, int64_t Co, int64_t HW, float act_zero_point,
+                                      int act_qmin, int act_qmax, float* y, ssq_stream_t stream) {
+  return qlinear_pooled_launch("ssq_qlinear_pooled_fwd", false, hi, lo, sp, prepared, scale_h, Nb,
+                               Ci, Co, HW, act_zero_point, act_qmin, act_qmax, y, stream);
+}
+
+extern "C" int ssq_qlinear_pooled_wide_fwd(const int8_t* hi, const int8_t* lo, const int32_t* sp,
+                                           const void* prepared, const float* scale_h, int64_t Nb,
+                                           int64_t Ci, int64_t Co, int64_t HW,
+                                           float act_zero_point, int act_qmin, int act_qmax,
+                                           float* y, ssq_stream_t stream) {
+  return qlinear_pooled_launch("ssq_qlinear_pooled_wide_fwd", true, hi, lo, sp, prepared, scale_h,
+                               Nb, Ci, Co, HW, act_zero_point, act_qmin, act_qmax, y, stream);
 }

@@ -13,6 +13,11 @@
 // Grouped (K26): int8 [G*Cogp][Kp], Kp = 64*ceil(R*S*Wc/64), k = tap * Wc + (c - w0_g) inside
 // group g's 16-aligned channel window; then the 0/1 rows [G][Kp]; then cwz[Co], T[Co] (int32).
 //
+// The wide grouped blob (glayout(..., 2), ssq_qweight_prepare_grouped_wide; read by K26's WIDE
+// instantiations only): the grouped rows above as two int8 digit planes of m = 128 h + l, first h,
+// then l at a distance of G * Cogp * Kp bytes; then the 0/1 rows [G][Kp] (written, not read),
+// cwz[Co] = 0 and T[Co] = sum m (int32).  The depthwise blob has one form: int32 holds m as it is.
+//
 // SLayout, K31's blob (qinfer_stemconv.hip): the fp32 weight in the order the 16x16x4 fp32 MFMA
 // takes its A operand, float [Kp / 4][Cop / 16][4][16] with Kp = 4*ceil(K/4), K = Ci*R*S,
 // k = (ci*R + r)*S + s (the weight's own memory order) and Cop = 16*ceil(Co/16): entry
@@ -105,7 +110,9 @@ struct GLayout {
   size_t off_mask, off_cwz, off_t, bytes;
 };
 
-static inline GLayout glayout(int64_t Co, int64_t Cig, int64_t R, int64_t S, int64_t groups) {
+// planes: 1, K24's blob; 2, the wide grouped blob (the depthwise blob is the same for both)
+static inline GLayout glayout(int64_t Co, int64_t Cig, int64_t R, int64_t S, int64_t groups,
+                              int planes = 1) {
   GLayout L = {};
   L.kind = qg_kind(Co, Cig, groups);
   if (!L.kind || R < 1 || S < 1) {
@@ -127,7 +134,7 @@ static inline GLayout glayout(int64_t Co, int64_t Cig, int64_t R, int64_t S, int
     if (w > L.Wc) L.Wc = w;
   }
   L.Kp = rup(R * S * L.Wc, kGT);
-  L.off_mask = (size_t)(groups * L.Cogp) * (size_t)L.Kp;
+  L.off_mask = (size_t)planes * (size_t)(groups * L.Cogp) * (size_t)L.Kp;
   L.off_cwz = L.off_mask + (size_t)groups * (size_t)L.Kp;
   L.off_t = L.off_cwz + (size_t)Co * 4;
   L.bytes = L.off_t + (size_t)Co * 4;

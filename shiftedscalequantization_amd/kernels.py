@@ -1952,13 +1952,16 @@ class QPrepared:
     (qweight_prepare(..., kcol=...)), cwz = 0: the dense convs run it without the window sum,
     and `bad` also counts the elements whose |m| exceeds 127.  `wide` (with `centred`, dense
     only): the blob holds m as two int8 digits (qweight_prepare(..., wide=True)), |m| up to
-    QWIDE_MAX; only K23's wide forms read it."""
+    QWIDE_MAX; only K23's wide forms read it.  `wide_all` (with `wide`, `groups` > 1): the blob is
+    the grouped kernels' wide one (qweight_prepare(..., wide=True, wide_all=True)): K26's two digit
+    planes, or K25's int32 blob with |m| up to QWIDE_MAX; only the grouped wide forms read it."""
 
-    def __init__(self, blob, shape, bad, groups=1, centred=False, wide=False):
+    def __init__(self, blob, shape, bad, groups=1, centred=False, wide=False, wide_all=False):
         self.blob, self.shape, self.bad = blob, tuple(int(s) for s in shape), bad
         self.groups = int(groups)
         self.centred = bool(centred)
         self.wide = bool(wide)
+        self.wide_all = bool(wide_all)
 
     def geometry(self):
         Co, Ci = self.shape[:2]
@@ -2104,14 +2107,17 @@ if QCONV_WIDE not in ("auto", "1"):
     raise ValueError(f"SSQ_QCONV_WIDE={QCONV_WIDE!r}: expected auto or 1")
 
 
-def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=None, wide=False):
+def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=None, wide=False,
+                    wide_all=False):
     """Packed codes (pack_encode's layout) + zp[co] -> QPrepared.  `shape` is the weight's own
     (Co, Cig, R, S); `groups` > 1 prepares for the grouped kernels (K24).  `kcol`: the int32
     column factors k[j], j = (ci, r, s) (colscale_grid), of a column-scaled weight: the blob then
     holds the centred operand (q - zp[co]) * k[j] (`centred`).  `kfac`: the int32 factors
     k[co, ci] (perci_grid) of a per-(co, ci) scaled weight instead, the operand
     (q - zp[co]) * k[co, ci].  `wide` (with either, dense only): the two-digit blob, factors and
-    |m| up to QWIDE_MAX instead of 127."""
+    |m| up to QWIDE_MAX instead of 127.  `wide_all` (with `wide`): a grouped weight too, on the
+    grouped kernels' wide blob (K26's two digit planes; a depthwise weight's int32 blob, column
+    factors only)."""
     if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
         raise A.SSQError("qweight_prepare: packed codes must be a uint8 tensor")
     packed = _i8_dev(packed, "qweight_prepare")
@@ -2124,7 +2130,7 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=N
         raise A.SSQError("qweight_prepare: a column scale and a per-(co, ci) scale do not go together")
     if wide and kcol is None and kfac is None:
         raise A.SSQError("qweight_prepare: the wide blob holds a scaled weight (kcol or kfac)")
-    if wide and groups > 1:
+    if wide and groups > 1 and not wide_all:
         raise A.SSQError("qweight_prepare: the wide blob is dense only: the grouped kernels (K26) "
                          "read int8 operands")
     prep = QPrepared(None, shape, torch.zeros(1, dtype=torch.int32, device=packed.device), groups)
@@ -2146,10 +2152,13 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=N
             raise A.SSQError(f"qweight_prepare: {name} must lie in [1, {lim}]")
         kc = kc.to(device=packed.device, dtype=torch.int32).contiguous()
         prep.centred, prep.wide = True, bool(wide)
+        prep.wide_all = bool(wide) and groups > 1
         extra = (_vp(kc),)
     geo = (Co, Ci, R, S) + ((groups,) if groups > 1 else ())
     if wide:
-        size_fn, prepare_fn = "ssq_qweight_prepared_bytes_wide", "ssq_qweight_prepare_wide"
+        size_fn, prepare_fn = (("ssq_qweight_prepared_bytes_grouped_wide", "ssq_qweight_prepare_grouped_wide")
+                               if groups > 1 else
+                               ("ssq_qweight_prepared_bytes_wide", "ssq_qweight_prepare_wide"))
         extra += (int(kfac is not None),)
     else:
         size_fn, prepare_fn = _QPREPARE_FNS[groups > 1, factors]
@@ -2160,14 +2169,15 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=N
 
 
 def qweight_prepare_scaled(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=None,
-                           wide=False):
+                           wide=False, wide_all=False):
     """qweight_prepare for a scaled weight whose operand may leave int8: the int8 blob where it
     holds the weight (every factor <= 127 and `bad` zero, one device word read), else, with
     `wide` and a dense weight, the wide blob; elsewhere the int8 blob with its `bad` set (no
     factor above 127 reaches it: None then).  SSQ_QCONV_WIDE=1: with `wide`, every dense scaled
-    weight takes the wide blob."""
+    weight takes the wide blob.  `wide_all` (with `wide`): a grouped or depthwise weight counts as
+    a dense one here and takes the grouped kernels' wide blob by the same rule."""
     k = torch.as_tensor(kcol if kfac is None else kfac)
-    dense = int(groups) == 1
+    dense = int(groups) == 1 or bool(wide_all)
     fits = int(k.max()) <= COLSCALE_MAX_L
     if not (wide and dense and (QCONV_WIDE == "1" or not fits)):
         if not fits:
@@ -2175,7 +2185,8 @@ def qweight_prepare_scaled(packed, shape, zp, n_bits, qmin, groups=1, kcol=None,
         prep = qweight_prepare(packed, shape, zp, n_bits, qmin, groups, kcol, kfac)
         if not (wide and dense and int(prep.bad.item())):
             return prep
-    return qweight_prepare(packed, shape, zp, n_bits, qmin, groups, kcol, kfac, wide=True)
+    return qweight_prepare(packed, shape, zp, n_bits, qmin, groups, kcol, kfac, wide=True,
+                           wide_all=wide_all)
 
 
 QCONV_KINDS = {1: "depthwise", 2: "grouped"}
@@ -2190,8 +2201,12 @@ def _qconv_fn(prepared, groups, form):
     """The entry point of `form` ("fwd" | "codes_fwd" | "codes_res_fwd") for a prepared weight."""
     if getattr(prepared, "wide", False):
         if int(groups) > 1:
-            raise A.SSQError("qconv: a wide blob is dense only: the grouped kernels (K26) read int8 "
-                             "operands")
+            if not getattr(prepared, "wide_all", False):
+                raise A.SSQError("qconv: a wide blob is dense only: the grouped kernels (K26) read "
+                                 "int8 operands")
+            if form == "codes_res_fwd":
+                raise A.SSQError("qconv: the grouped kernels (K25 / K26) take no residual operand")
+            return f"ssq_qconv_i8_grouped_wide_{form}"
         return f"ssq_qconv_i8_wide_{form}"
     if int(groups) > 1:
         return f"ssq_qconv_i8_grouped_{form}"
@@ -2823,12 +2838,15 @@ def head_scale(scale, HW):
     return torch.from_numpy((s / np.float32(int(HW))).astype(np.float32)).to(scale.device)
 
 
-def qlinear_pooled(hi, lo, sp, prepared, scale_h, HW, act_zp=0.0, act_bits=8, act_sym=False):
+def qlinear_pooled(hi, lo, sp, prepared, scale_h, HW, act_zp=0.0, act_bits=8, act_sym=False,
+                   wide_all=False):
     """The fc on avgpool_codes's digits (ssq_qlinear_pooled_fwd): y[n, co] = fp32(I) *
     scale_h[co] (fp32 (N, Co)), I = sum_c P[n, c] (q_w[co, c] - z_w[co]) the exact integer with
     P[n, c] = sum_hw (q_a - z_a) over the HW pooled pixels.  `prepared`: the Linear's
     qweight_prepare output; `scale_h`: head_scale(s, HW); (act_zp, act_bits, act_sym): the
-    pooled codes' act quantizer.  No bias."""
+    pooled codes' act quantizer.  No bias.  A scaled Linear's centred int8 blob runs as it stands
+    with scale_h = head_scale(s, L * HW); `wide_all`: its dense wide blob too
+    (ssq_qlinear_pooled_wide_fwd), refused otherwise."""
     for t, nm in ((hi, "hi"), (lo, "lo")):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.int8:
             raise A.SSQError(f"qlinear_pooled: {nm} must be int8 digits")
@@ -2837,7 +2855,8 @@ def qlinear_pooled(hi, lo, sp, prepared, scale_h, HW, act_zp=0.0, act_bits=8, ac
     hi, lo, sp = (_i8_dev(t, "qlinear_pooled") for t in (hi, lo, sp))
     if len(prepared.shape) != 2 or getattr(prepared, "groups", 1) != 1:
         raise A.SSQError("qlinear_pooled: the weight must be a prepared Linear")
-    if getattr(prepared, "wide", False):
+    wide = bool(getattr(prepared, "wide", False))
+    if wide and not wide_all:
         raise A.SSQError("qlinear_pooled: a wide blob is not K30's operand (the pooled-operand fc "
                          "reads one int8 weight plane)")
     Co, Ci, _, _ = prepared.geometry()
@@ -2853,7 +2872,8 @@ def qlinear_pooled(hi, lo, sp, prepared, scale_h, HW, act_zp=0.0, act_bits=8, ac
         raise A.SSQError("qlinear_pooled: scale_h must have one entry per output channel")
     alo, ahi = qrange(act_bits, act_sym)
     y = torch.empty((N, Co), dtype=torch.float32, device=hi.device)
-    call("ssq_qlinear_pooled_fwd", _vp(hi), _vp(lo), _vp(sp), _vp(prepared.blob), shp, N, Ci, Co,
+    call("ssq_qlinear_pooled_wide_fwd" if wide else "ssq_qlinear_pooled_fwd", _vp(hi), _vp(lo),
+         _vp(sp), _vp(prepared.blob), shp, N, Ci, Co,
          int(HW), float(act_zp), alo, ahi, _vp(y), stream_of(y))
     return y
 

@@ -11,7 +11,9 @@ integer grid k[j] / L, L <= 127 (K.colscale_grid), with the centred integer (q -
 int8 operand.  `per_ci=True` plans weights whose scale is per (co, ci) on a grid base[co] * k / L
 (ChannelQuant's shifted scale; K.perci_grid) the same way, with (q - z) * k[co, ci] as the operand,
 and `wide=True` lets either kind of scaled weight whose operand leaves int8 run as two int8
-digits (|m| <= 16319) on K23's wide forms.
+digits (|m| <= 16319) on K23's wide forms; `wide_all=True` (with `wide`) extends that operand to
+the grouped and depthwise kernels (K26 / K25) and to the pooled-operand fc (K30), which then also
+takes a scaled weight.
 
 The carry flags keep a tensor between integer layers as int8 codes.  Each such tensor is one
 Edge: an emitting layer whose kernel applies the epilogue and the act quantizer and stores the
@@ -73,6 +75,7 @@ class IntPlan:
         self.calls = 0
         self.carry = None                       # a PairEdge when this layer emits codes
         self.head = None                        # a HeadEdge: the fc, on pooled digits only
+        self.head_grid = None                   # a scaled fc: (fp32(delta_a * base[co]), L)
         self.splitk = False                     # dense only: ask K.qconv_splits per call
         self.splits = None                      # the Z of the last run / run_codes
         Co, Ci, R, S = prepared.geometry()
@@ -549,10 +552,15 @@ class HeadEdge(Edge):
         p, g = self.fc._int_plan, self.grid
         sh = self._scale_h.get(pc.HW)
         if sh is None:
-            sh = self._scale_h[pc.HW] = K.head_scale(p.scale, pc.HW)
+            # a scaled fc: one division by fp32(L * HW), exact for L <= 1024, HW <= 126
+            sh = self._scale_h[pc.HW] = (K.head_scale(p.scale, pc.HW) if p.head_grid is None else
+                                         K.head_scale(p.head_grid[0], p.head_grid[1] * pc.HW))
         self.calls += 1
         p.calls += 1
-        return K.qlinear_pooled(hi, pc.lo, pc.sp, p.prepared, sh, pc.HW, g.zp, g.n_bits, g.sym)
+        if p.head_grid is None:
+            return K.qlinear_pooled(hi, pc.lo, pc.sp, p.prepared, sh, pc.HW, g.zp, g.n_bits, g.sym)
+        return K.qlinear_pooled(hi, pc.lo, pc.sp, p.prepared, sh, pc.HW, g.zp, g.n_bits, g.sym,
+                                wide_all=True)
 
 
 def _layers(qnn):
@@ -676,7 +684,8 @@ def _weight_codes(m, colscale=False, per_ci=False):
 @torch.no_grad()
 def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
                              carry_stem=False, carry_head=False, colscale=False, splitk=False,
-                             per_ci=False, wide=False, fused_stem=False, image_u8=None):
+                             per_ci=False, wide=False, fused_stem=False, image_u8=None,
+                             wide_all=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
@@ -701,8 +710,13 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     int8 (|m| > 127, or a grid beyond 127) runs as two int8 digits, |m| <= 16319, L <= 1024, on
     K23's wide forms (dense layers only: never split along K, not the grouped kernels, not the
     pooled-operand fc); off, it is refused as leaving int8.  A weight with both a column scale and
-    a per-(co, ci) scale is refused.  `fused_stem`: on every stem edge that `carry_stem` (or
-    `carry_head`) installs and whose producer is an ungrouped conv inside K31's geometry
+    a per-(co, ci) scale is refused.  `wide_all` (with `wide`; nothing changes without it): the
+    wide operand also on grouped convs (K26, two digit planes), on column-scaled depthwise convs
+    (K25, its int32 blob with |m| <= 16319) and on the pooled-operand fc (K30), and a scaled fc is
+    planned under `carry_head` at all -- on its centred int8 blob where (q - z) * k fits int8, on
+    the dense wide blob beyond, with sh[co] = fp32(fp32(delta_a * base[co]) / fp32(L * HW)).
+    SSQ_QCONV_WIDE=auto|1 governs these blobs as it does the dense one.
+    `fused_stem`: on every stem edge that `carry_stem` (or `carry_head`) installs and whose producer is an ungrouped conv inside K31's geometry
     (`fused_stem_reason`), the conv itself emits the codes (K.stem_conv_codes, a weight blob
     prepared here from the producer's hard weight) instead of the fp32 conv + K27; it plans no
     edge of its own, and `stem_carry_report` then also counts the fused forwards and names what
@@ -718,6 +732,7 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     K32 forwards ("u8") and the normalised ones by reason ("un_u8").  The stem codes of a uint8
     forward are K32's own contract's, not pinned to the fp32 routes'; `sample` may be uint8."""
     carry_stem = carry_stem or carry_head
+    wide_all = bool(wide and wide_all)
     if image_u8 is not None:
         if not carry_stem:
             raise ValueError("enable_integer_inference: image_u8 needs a stem edge (carry_stem or "
@@ -815,7 +830,7 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
             if L == 1 and int(kcol.max()) == 1:
                 kcol = None                     # all ones: a plain weight, the plain K22 blob
         scaled = kcol is not None or kfac is not None
-        if scaled and m in head_fc:
+        if scaled and m in head_fc and not wide_all:
             report[name] = ((f"weight has a column scale ({f['kind']})" if kcol is not None else
                              f"weight scale is per (co, ci) ({f['kind']})")
                             + ": the pooled-operand fc takes plain weights only")
@@ -826,7 +841,7 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         else:
             prep = K.qweight_prepare_scaled(packed, tuple(m.weight.shape), f["zero_point"],
                                             f["n_bits"], f["qmin"], groups=groups, kcol=kcol,
-                                            kfac=kfac, wide=wide)
+                                            kfac=kfac, wide=wide, wide_all=wide_all)
         if prep is None:
             report[name] = ("scaled weight's grid leaves int8 (k > 127): the wide operand is dense "
                             "only, the grouped kernels (K26) read int8")
@@ -837,17 +852,20 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
                             "zero point is not an integer code" if prep.wide else
                             "scaled weight (q - z) * k leaves int8 (|m| > 127), or a zero point "
                             "is not an integer code")
-            if scaled and wide and groups != 1:
+            if scaled and wide and groups != 1 and not wide_all:
                 report[name] += "; the wide operand is dense only, the grouped kernels (K26) read int8"
             continue
         # s[co] = fp32(delta_a * d1[co]): one fp32 product of the two stored fp32 values (per
         # (co, ci): of delta_a and the grid's base[co])
         scale = (torch.full((1,), act.delta, dtype=torch.float32, device=dev)
                  * d1.detach().reshape(-1).float()).contiguous()
+        scale0 = scale
         if scaled:
             # ... / fp32(L): the grid's common denominator, one more rounding
             scale = (scale / torch.full((1,), float(L), dtype=torch.float32, device=dev)).contiguous()
         m._int_plan = IntPlan(prep, scale, act, stride, padding, counter)
+        if scaled and m in head_fc:
+            m._int_plan.head_grid = (scale0, int(L))
         # a wide layer is never asked to split: K23's split form holds one accumulator set
         m._int_plan.splitk = bool(splitk) and m._int_plan.kind == "dense" and not prep.wide
         report[name] = INT8
