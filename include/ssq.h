@@ -1219,6 +1219,39 @@ int ssq_qlinear_pooled_wide_fwd(const int8_t* hi, const int8_t* lo, const int32_
                                 int64_t Co, int64_t HW, float act_zero_point, int act_qmin,
                                 int act_qmax, float* y, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- K33 shifted-scale activations
+ * ChannelQuantAct 'shiftFeature' (the evident intent of channelQuantAct.py:69-134, whose
+ * own code never ran; contract in DESIGN.md section 6).  x is (N, C, HW) in NCHW order
+ * ((N, C): HW = 1); delta / zp are the replaced per-tensor quantizer's device scalars;
+ * shifts is a HOST array of S <= 4 scale multipliers; p / dp / mse are (C, S).
+ * Candidate i is the 'none'-mode q/dq at d_i = fp32(delta * shifts[i]), the arithmetic of
+ * ssq_fq_round_fwd with qmin = 0:
+ *   v_i = rint(x / d_i) + zp;  Q_i = (clamp(v_i, 0, qmax) - zp) * d_i;  in_i = [0 <= v_i <= qmax]
+ * fwd   soft: y = Q_0*p[c,0]; y = y + Q_i*p[c,i], i = 1..S-1 (each product and each sum
+ *             rounded in fp32, no fma);   hard: y = Q_k, k = first argmax of p[c,:]
+ * bwd   soft: dx = g * m, m = +0 + p[c,0]*in_0 + ... in i order (separate fp32 products
+ *             and sums); dp[c,i] = sum over (n, hw) of g*Q_i
+ *       hard: dx = g * in_k; dp = 0 (dp may be NULL: the zeros are then not written)
+ * init  mse[c,i] = sum over (n, hw) of (x - Q_i)^2  (ChannelQuant.init_alpha's errors)
+ * The channel sums are exact products accumulated in double in a fixed order (per-plane
+ * partials in `ws`, then summed over n ascending): no atomics, the same bits on every run.
+ * Refused with SSQ_E_ARG before any launch: S outside 1..4, a null pointer, N*C*HW >= 2^31,
+ * qmax < 1; SSQ_E_WS for a workspace smaller than its *_workspace_size (8-B aligned; the
+ * forward needs none).  No allocation, no sync, capturable. */
+size_t ssq_actshift_fwd_workspace_size(int64_t N, int64_t C, int64_t HW, int S);
+int ssq_actshift_fwd(const float* x, const float* p, const float* delta, const float* zp,
+                     const float* shifts, int S, int64_t N, int64_t C, int64_t HW, int qmax,
+                     int hard, float* y, void* ws, size_t ws_bytes, ssq_stream_t stream);
+size_t ssq_actshift_bwd_workspace_size(int64_t N, int64_t C, int64_t HW, int S);
+int ssq_actshift_bwd(const float* x, const float* g, const float* p, const float* delta,
+                     const float* zp, const float* shifts, int S, int64_t N, int64_t C,
+                     int64_t HW, int qmax, int hard, float* dx, float* dp, void* ws,
+                     size_t ws_bytes, ssq_stream_t stream);
+size_t ssq_actshift_init_workspace_size(int64_t N, int64_t C, int64_t HW, int S);
+int ssq_actshift_init(const float* x, const float* delta, const float* zp, const float* shifts,
+                      int S, int64_t N, int64_t C, int64_t HW, int qmax, float* mse, void* ws,
+                      size_t ws_bytes, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- bandwidth probe
  * float4 device copy, used by bench.py to report the measured stream bandwidth.      */
 int ssq_stream_copy(const float* src, float* dst, int64_t n, ssq_stream_t stream);

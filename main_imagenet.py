@@ -297,6 +297,19 @@ def main(argv=None):
         if loader is not None:
             print('Full quantization (W{}A{}) accuracy: {}'.format(args.n_bits_w, args.n_bits_a,
                                                                    validate_model(loader, qnn)))
+        if args.act_shift:
+            # the activation half of the shifted scale: per block, which of delta * s_i each
+            # activation channel uses (K33); top-1 after it is not pinned by any golden
+            t_phase = time.time()
+            shifts = [float(s) for s in args.act_shift_targets.split(',')]
+            act_report = D.act_shift_recon(qnn, cali, bs, device, shifts, args.act_shift_iters)
+            qnn.set_quant_state(weight_quant=True, act_quant=True)
+            torch.cuda.synchronize(device)
+            phases['act_shift'] = time.time() - t_phase
+            print(f'activation shift rec losses [soft, hard] per block: {act_report}')
+            if loader is not None:
+                print('Shifted activations (W{}A{}) accuracy: {}'.format(
+                    args.n_bits_w, args.n_bits_a, validate_model(loader, qnn)))
     if args.int_infer and args.act_quant:
         run_integer_inference(qnn, args, cali, loader, bs)
     print(f'calibration finished in {time.time() - t0:.1f}s '

@@ -169,6 +169,13 @@ SIGNATURES = {
     "ssq_avgpool_i8_digits_fwd": (_i, [_p] + [_i64] * 4 + [_p, _p, _p, _p]),
     "ssq_qlinear_pooled_fwd": (_i, [_p] * 5 + [_i64] * 4 + [_f, _i, _i, _p, _p]),
     "ssq_qlinear_pooled_set_tile": (_i, [_i]),
+    "ssq_actshift_fwd_workspace_size": (_sz, [_i64, _i64, _i64, _i]),
+    "ssq_actshift_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i64, _i64, _i64, _i, _i, _p, _p, _sz, _p]),
+    "ssq_actshift_bwd_workspace_size": (_sz, [_i64, _i64, _i64, _i]),
+    "ssq_actshift_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64, _i64, _i64, _i, _i, _p, _p, _p,
+                              _sz, _p]),
+    "ssq_actshift_init_workspace_size": (_sz, [_i64, _i64, _i64, _i]),
+    "ssq_actshift_init": (_i, [_p, _p, _p, _p, _i, _i64, _i64, _i64, _i, _p, _p, _sz, _p]),
     "ssq_stream_copy": (_i, [_p, _p, _i64, _p]),
     "ssq_stream_probe": (_i, [_p, _p, _i64, _i, _p]),
 }

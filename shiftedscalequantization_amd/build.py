@@ -20,7 +20,7 @@ ARCH = os.environ.get("SSQ_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["fq.hip", "adashift.hip", "adashift_prep.hip", "scale_init.hip", "recon.hip", "pack.hip", "conv_wgrad.hip",
            "dwconv.hip", "fc_recon.hip", "fisher.hip", "qinfer.hip", "qinfer_grouped.hip",
-           "qinfer_stem.hip", "qinfer_head.hip", "qinfer_stemconv.hip", "qinfer_stemu8.hip"]
+           "qinfer_stem.hip", "qinfer_head.hip", "qinfer_stemconv.hip", "qinfer_stemu8.hip", "actshift.hip"]
 HEADERS = ["ssq_common.h", "adashift_common.h", "fin_tasks.h", "prep_ride.h", "qinfer_epi.h", "qinfer_layout.h", "qinfer_check.h",
            "qinfer_prepare.h", os.path.join("..", "..", "include", "ssq.h")]
 CFLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-ffp-contract=off",

@@ -70,6 +70,13 @@ def build_parser():
     p.add_argument('--test', default=False, type=bool, help='ChannelQuantMSE path (channelShift_wMSE)')
     p.add_argument('--skip_test', default=False, type=bool)
     p.add_argument('--keep_features_on_host', default=False, type=bool)
+    p.add_argument('--act_shift', action='store_true',
+                   help='after the act phase, learn per block which shifted scale delta * s_i each '
+                        'activation channel uses (ChannelQuantAct, K33); needs --act_quant')
+    p.add_argument('--act_shift_targets', default='1.0,0.5', type=str,
+                   help='the scale multipliers s_i of --act_shift (at most 4)')
+    p.add_argument('--act_shift_iters', default=625, type=int,
+                   help='iterations of the --act_shift loop per block')
     p.add_argument('--int_infer', action='store_true',
                    help='after calibration, validate again with the interior layers on their '
                         'integer codes (int8 MFMA conv / linear) and print the per-layer report')
@@ -153,6 +160,13 @@ def parse_args(argv=None):
     a = parser.parse_args(argv)
     if a.run_device:
         a.device_gpu = a.run_device
+    if a.act_shift:
+        if not a.act_quant:
+            parser.error('--act_shift learns the activation quantizers: it needs --act_quant')
+        if not 1 <= len(a.act_shift_targets.split(',')) <= 4:
+            parser.error('--act_shift_targets takes 1 to 4 scale multipliers')
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1 or a.gpus > 1:
+            parser.error('--act_shift runs on one device (world 1)')
     if a.int_infer_carry_head or a.int_infer_fused_stem:
         a.int_infer_carry_stem = True
     if a.int_infer_u8_images and not a.int_infer_carry_stem:

@@ -215,6 +215,24 @@ def QuantRecursiveShiftRecon(model, layerEnabled, qnn, test_loader, prv_name="",
     return ret
 
 
+def act_shift_recon(qnn, cali_data, batch_size, device, targets=(1.0, 0.5), iters=625,
+                    verbose=True):
+    """--act_shift: after the act phase, per block -- cache its features in the current
+    (weight + act quantized) state, learn the per-channel shifted scale of its activation
+    quantizers (block_recon_fused_shiftedScale(act=True)), clear the cache.
+    -> {block path: [soft rec loss, hard rec loss]}."""
+    out = {}
+    for path in block_paths(qnn):
+        block = cache_block_features(qnn, path, cali_data, batch_size, device)
+        # (caching the FP outputs switched quantization off and restores the weight side only)
+        qnn.set_quant_state(True, True)
+        out[path] = block_recon_fused_shiftedScale(block, iters, model=qnn, act=True,
+                                                   batch_size=batch_size, verbose=verbose,
+                                                   act_shift_targets=list(targets))
+        block.clear_cached_features()
+    return out
+
+
 def block_paths(qnn):
     """Paths ('.model.layer1.0', ...) of every reconstructable block, in forward order."""
     return ['.' + n for n, m in qnn.named_modules()

@@ -1873,6 +1873,115 @@ def set_variant(v):
     return query("ssq_set_variant", int(v))
 
 
+# ------------------------------------------------------------------ K33 shifted-scale activations
+ACTSHIFT_MAX_S = 4
+
+
+def _actshift_geometry(x):
+    """(N, C, HW) of an activation: (N, C, H, W), or (N, C) read as H = W = 1."""
+    if x.dim() < 2:
+        raise ValueError(f"actshift: activation must be (N, C, ...), got {tuple(x.shape)}")
+    N, C_ = int(x.shape[0]), int(x.shape[1])
+    hw = 1
+    for d in x.shape[2:]:
+        hw *= int(d)
+    return N, C_, hw
+
+
+def _actshift_table(t, C_, S, what):
+    if tuple(t.shape) != (C_, S):
+        raise A.SSQError(f"actshift: {what} must be (C, S) = ({C_}, {S}), got {tuple(t.shape)}")
+    return fptr(t.detach(), what)
+
+
+def _actshift_scalars(delta, zp):
+    if delta.numel() != 1 or zp.numel() != 1:
+        raise A.SSQError("actshift: delta and zero_point are the per-tensor quantizer's scalars")
+    return fptr(delta.detach(), "delta"), fptr(zp.detach(), "zero_point")
+
+
+def actshift_fwd(x, p, delta, zp, shifts, n_bits, hard=False):
+    """ChannelQuantAct 'shiftFeature' forward (ssq_actshift_fwd): the soft mix sum_i Q_i(x) *
+    p[c, i] of the per-channel candidates, or the hard choice Q_k(x), k = argmax_i p[c, i]."""
+    x, xp = fptr(x.detach(), "x")
+    N, C_, hw = _actshift_geometry(x)
+    S = len(shifts)
+    p, pp = _actshift_table(p, C_, S, "p")
+    (delta, dp_), (zp, zpp) = _actshift_scalars(delta, zp)
+    y = torch.empty_like(x)
+    wsb = query("ssq_actshift_fwd_workspace_size", N, C_, hw, S)
+    ws, wsn = workspace(wsb, x.device)
+    call("ssq_actshift_fwd", xp, pp, dp_, zpp, A.shifts_arg(shifts), S, N, C_, hw,
+         2 ** n_bits - 1, int(bool(hard)), _vp(y), ws, wsn, stream_of(x))
+    return y
+
+
+def actshift_bwd(x, g, p, delta, zp, shifts, n_bits, hard=False, want_dp=True):
+    """(dx, dp) of actshift_fwd (ssq_actshift_bwd): dx = g * sum_i p[c, i] * in_i(x) (hard:
+    g * in_k(x)), dp[c, i] = sum_{n,h,w} g * Q_i(x) (hard: zeros), deterministic.
+    want_dp=False (hard only): dp is None and the launch that writes its zeros is saved."""
+    x, xp = fptr(x.detach(), "x")
+    g, gp = fptr(g.detach(), "g")
+    if g.shape != x.shape:
+        raise A.SSQError("actshift_bwd: g must be shaped like x")
+    N, C_, hw = _actshift_geometry(x)
+    S = len(shifts)
+    p, pp = _actshift_table(p, C_, S, "p")
+    (delta, dp_), (zp, zpp) = _actshift_scalars(delta, zp)
+    dx = torch.empty_like(x)
+    if not want_dp and not hard:
+        raise A.SSQError("actshift_bwd: the soft backward always computes dp")
+    dpt = torch.empty((C_, S), dtype=torch.float32, device=x.device) if want_dp else None
+    wsb = query("ssq_actshift_bwd_workspace_size", N, C_, hw, S)
+    ws, wsn = workspace(wsb, x.device)
+    call("ssq_actshift_bwd", xp, gp, pp, dp_, zpp, A.shifts_arg(shifts), S, N, C_, hw,
+         2 ** n_bits - 1, int(bool(hard)), _vp(dx), _vp(dpt), ws, wsn, stream_of(x))
+    return dx, dpt
+
+
+def actshift_init(x, delta, zp, shifts, n_bits):
+    """mse[c, i] = sum_{n,h,w} (x - Q_i(x))^2 in one pass over x (ssq_actshift_init): the
+    errors ChannelQuantAct.init_v picks each channel's starting shift from."""
+    x, xp = fptr(x.detach(), "x")
+    N, C_, hw = _actshift_geometry(x)
+    S = len(shifts)
+    (delta, dp_), (zp, zpp) = _actshift_scalars(delta, zp)
+    mse = torch.empty((C_, S), dtype=torch.float32, device=x.device)
+    wsb = query("ssq_actshift_init_workspace_size", N, C_, hw, S)
+    ws, wsn = workspace(wsb, x.device)
+    call("ssq_actshift_init", xp, dp_, zpp, A.shifts_arg(shifts), S, N, C_, hw, 2 ** n_bits - 1,
+         _vp(mse), ws, wsn, stream_of(x))
+    return mse
+
+
+class ActShiftFn(torch.autograd.Function):
+    """ChannelQuantAct 'shiftFeature': the kernels take the probabilities p (C, S) and return
+    dp; the softmax, the (zeta - gamma) stretch and the clamp that make p from alpha stay in
+    autograd.  x gets the clamp-masked straight-through gradient of each candidate mixed by
+    p -- the 'none' mode's zero gradient would leave every quantizer of a block but its last
+    without a signal."""
+
+    @staticmethod
+    def forward(ctx, x, p, delta, zp, shifts, n_bits, hard):
+        y = actshift_fwd(x, p, delta, zp, shifts, n_bits, hard)
+        ctx.save_for_backward(x, p, delta, zp)
+        ctx.cfg = (shifts, n_bits, hard)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, p, delta, zp = ctx.saved_tensors
+        shifts, n_bits, hard = ctx.cfg
+        dx, dp = actshift_bwd(x, g, p, delta, zp, shifts, n_bits, hard, want_dp=not hard)
+        return (dx if ctx.needs_input_grad[0] else None,
+                dp if ctx.needs_input_grad[1] and not hard else None, None, None, None, None, None)
+
+
+def actshift(x, p, delta, zp, shifts, n_bits, hard=False):
+    return ActShiftFn.apply(x, p, delta, zp, tuple(float(s) for s in shifts), int(n_bits),
+                            bool(hard))
+
+
 # ------------------------------------------------------------------ K15/K16 packed export
 def pack_encode(what, zp, d1, per_ci, d2, n_bits, qmin, qmax):
     """Hard W_hat -> (packed codes as a uint8 tensor, number of elements whose decode is not

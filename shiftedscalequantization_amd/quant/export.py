@@ -22,6 +22,7 @@ import torch.nn as nn
 from .. import kernels as K
 from .adaptive_rounding import AdaRoundQuantizer
 from .channelQuant import ChannelQuant
+from .channelQuantAct import ChannelQuantAct
 from .channelQuantMSE import ChannelQuantMSE
 from .quant_layer import QuantModule, UniformAffineQuantizer
 
@@ -126,6 +127,35 @@ class PackedWeight(nn.Module):
         return super()._apply(fn, *args, **kwargs)
 
 
+def _export_act(name, aq, tensors):
+    """An act quantizer's tensors into `tensors` and its metadata.  A ChannelQuantAct in
+    'shiftFeature' mode also stores its shift targets and the chosen index per channel; one
+    whose choice is still soft is refused, as soft weights are."""
+    tensors[f"{name}.act_delta"] = aq.delta.detach().reshape(-1).contiguous()
+    tensors[f"{name}.act_zero_point"] = aq.zero_point.detach().reshape(-1).contiguous()
+    act = dict(n_bits=aq.n_bits, sym=aq.sym)
+    if isinstance(aq, ChannelQuantAct) and aq.opt_mode == "shiftFeature":
+        if not aq.hard_targets:
+            raise ValueError(f"{name}: ChannelQuantAct is still soft (per-channel shifted act "
+                             "quantizer); finish the reconstruction first")
+        tensors[f"{name}.act_shift_index"] = aq.shift_index().to(torch.int32).contiguous()
+        act["shift_targets"] = [float(s) for s in aq.shiftTarget]
+    return act
+
+
+def _restore_shifted_act(aq, act, index, name):
+    """A hard ChannelQuantAct over the restored per-tensor (delta, zero_point): its alpha is
+    a one-hot logit table of the stored choice (the hard forward reads only its argmax)."""
+    q = ChannelQuantAct(aq, shiftTarget=list(act["shift_targets"]), name=name + ".act")
+    S = len(q.shiftTarget)
+    alpha = torch.full((index.numel(), S), -4.0, dtype=torch.float32, device=index.device)
+    alpha.scatter_(1, index.long().view(-1, 1), 4.0)
+    q.alpha = nn.Parameter(alpha)
+    q.opt_mode = "shiftFeature"
+    q.hard_targets = q.shiftedDone = q.inited = True
+    return q
+
+
 def _layers(qnn):
     return [(n, m) for n, m in qnn.named_modules() if isinstance(m, QuantModule)]
 
@@ -156,9 +186,7 @@ def export_quantized(qnn, path=None):
         aq = m.act_quantizer
         act = None
         if not m.disable_act_quant and aq.inited and aq.delta is not None:
-            tensors[f"{name}.act_delta"] = aq.delta.detach().reshape(-1).contiguous()
-            tensors[f"{name}.act_zero_point"] = aq.zero_point.detach().reshape(-1).contiguous()
-            act = dict(n_bits=aq.n_bits, sym=aq.sym)
+            act = _export_act(name, aq, tensors)
         layers[name] = dict(shape=list(m.weight.shape), n_bits=f["n_bits"], qmin=f["qmin"],
                             qmax=f["qmax"], per_ci=f["per_ci"], kind=f["kind"], act=act,
                             disable_act_quant=bool(m.disable_act_quant))
@@ -166,9 +194,7 @@ def export_quantized(qnn, path=None):
         aq = getattr(b, "act_quantizer", None)
         if name and not isinstance(b, QuantModule) and aq is not None and aq.inited \
                 and aq.delta is not None:
-            tensors[f"{name}.act_delta"] = aq.delta.detach().reshape(-1).contiguous()
-            tensors[f"{name}.act_zero_point"] = aq.zero_point.detach().reshape(-1).contiguous()
-            layers[name] = dict(block=True, act=dict(n_bits=aq.n_bits, sym=aq.sym))
+            layers[name] = dict(block=True, act=_export_act(name, aq, tensors))
     meta = {"format": FORMAT, "layers": json.dumps(layers)}
     if path is not None:
         from safetensors.torch import save_file
@@ -202,6 +228,9 @@ def load_quantized(qnn, src, device=None):
                                                                    else ()).clone())
             aq.zero_point = nn.Parameter(t[f"{name}.act_zero_point"].reshape(aq.delta.shape).clone())
             aq.inited = True
+            if info["act"].get("shift_targets") is not None:
+                m.act_quantizer = _restore_shifted_act(aq, info["act"], t[f"{name}.act_shift_index"],
+                                                       name)
         if info.get("block"):
             continue
         m.disable_act_quant = info["disable_act_quant"]

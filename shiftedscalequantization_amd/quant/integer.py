@@ -51,6 +51,7 @@ import torch.nn.functional as F
 
 from .. import kernels as K
 from . import quant_layer as L
+from .channelQuantAct import ChannelQuantAct
 from .export import PackedWeight, dequant_form
 from .fold_bn import StraightThrough as FoldedBN
 from .quant_block import BaseQuantBlock
@@ -647,6 +648,10 @@ def _trace_inputs(qnn, sample, pools=False, heads=()):
 def _input_reason(q):
     if q is None:
         return None, "input is not the direct output of an act quantizer"
+    if isinstance(q, ChannelQuantAct) and q.opt_mode == "shiftFeature":
+        # (the follow-up, DESIGN.md section 8: fold s[ci] into the consumer's per-ci grid, L = 2)
+        return None, ("input is a per-channel shifted act quantizer (ChannelQuantAct "
+                      "'shiftFeature'): the integer route does not cover shifted activations")
     if type(q) is not UniformAffineQuantizer or not q.inited or q.delta is None:
         return None, "input act quantizer is not an initialised UniformAffineQuantizer"
     if q.delta.numel() != 1 or q.zero_point.numel() != 1:

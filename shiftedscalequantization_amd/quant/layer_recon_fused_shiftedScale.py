@@ -20,7 +20,7 @@ from tqdm import tqdm
 from .. import kernels as K
 from ..parallel_dp import GradBucket, world
 from ._engine import (BatchFeeder, IterationGraph, LazyValue, SsqAdam, as_float, clear_stash,
-                      lazy_tail, loss_backward, probe, stash_block_weights)
+                      frozen_except, lazy_tail, loss_backward, probe, stash_block_weights)
 from .quant_block import BaseQuantBlock
 from .quant_layer import QuantModule
 
@@ -215,18 +215,143 @@ def _fused_loop(block, modules, iters, lmda, model, p, lr, bias_cal, batch_size,
     return rec_loss_out
 
 
+ACT_SHIFT_TARGETS = (1.0, 0.5)      # layer_recon_fused_shiftedScale.py:42 shiftTarget=[2/2, 1/2]
+
+
+def act_quantizer_sites(block):
+    """The modules of `block` whose act quantizer the act path replaces: every QuantModule
+    with an enabled one (not disable_act_quant, initialised), then the block itself (the
+    reference's second branch, layer_recon_fused_shiftedScale.py:49-56, evidently means the
+    block's own quantizer but rebinds a local)."""
+    owners = [m for m in _weight_quantizers(block) if not m.disable_act_quant]
+    if isinstance(block, BaseQuantBlock):
+        owners.append(block)
+    return [m for m in owners
+            if getattr(m.act_quantizer, 'inited', False) and m.act_quantizer.delta is not None]
+
+
+def _act_hard_flags(quantizers):
+    """Hard shift choice on every act quantizer (the reference's loop over them sets nothing,
+    layer_recon_fused_shiftedScale.py:125: its act quantizers would stay soft)."""
+    for q in quantizers:
+        q.hard_targets = True
+        q.shiftedDone = True
+
+
+def _act_loop(block, iters, lmda, model, p, lr, bias_cal, batch_size, verbose, iter_hook,
+              targets):
+    """The act half of the fused loop (evident intent of layer_recon_fused_shiftedScale.py:
+    37-57): every enabled act quantizer of the block becomes a ChannelQuantAct in
+    'shiftFeature' mode, its alpha (C, S) starts from the errors of one forward of the block in
+    its incoming state over cached_inp[:batch_size], and Adam learns the alphas against the
+    cached FP outputs (lp loss, no regulariser) over the weight loop's batch draws.  The
+    weight quantizers are not touched.  -> [soft rec loss, hard rec loss]."""
+    from .channelQuantAct import ChannelQuantAct
+    if bias_cal:
+        raise ValueError("act=True learns the activation shifts only: bias_cal=True is the "
+                         "weight loop's (act=False)")
+    if world() > 1:
+        raise NotImplementedError("act=True runs on one device: data-parallel learning of the "
+                                  "activation alphas (world > 1) is not implemented")
+    targets = [float(s) for s in (ACT_SHIFT_TARGETS if targets is None else targets)]
+    device = next(model.parameters()).device
+    owners = act_quantizer_sites(block)
+    if not owners:
+        raise ValueError("act=True: the block has no enabled, initialised act quantizer")
+    feeder = BatchFeeder(torch.cat(block.cached_inp_features), torch.cat(block.cached_out_features),
+                         batch_size, device)
+    cur_inp, cur_out = feeder.head(batch_size)
+
+    # one forward in the incoming state: each quantizer's input, captured by a pre-hook
+    seen, hooks = {}, []
+    for m in owners:
+        def grab(mod, args, m=m):
+            seen[m] = K.materialize_epi(args[0]).detach().clone()
+        hooks.append(m.act_quantizer.register_forward_pre_hook(grab))
+    try:
+        with torch.no_grad():
+            block(cur_inp)
+    finally:
+        for h in hooks:
+            h.remove()
+    missing = [m for m in owners if m not in seen]
+    if missing:
+        raise RuntimeError("act=True: an enabled act quantizer did not run in the block's "
+                           "forward; turn activation quantization on (set_quant_state) first")
+    quantizers = []
+    for m in owners:
+        old = m.act_quantizer
+        if old.delta.numel() != 1:
+            raise ValueError("act=True needs per-tensor act quantizers")
+        name = (getattr(m, 'pathName', '') or type(m).__name__) + '.act'
+        q = ChannelQuantAct(old, shiftTarget=list(targets), name=name).to(device)
+        q.init_v(seen.pop(m))
+        m.act_quantizer = q
+        quantizers.append(q)
+    opt_params = [q.alpha for q in quantizers]
+    on_gpu = opt_params[0].is_cuda
+    optimizer = SsqAdam(opt_params, lr=lr) if on_gpu else torch.optim.Adam(opt_params, lr=lr)
+    if verbose:
+        print("number of elements in opt_params: {}".format(sum(t.numel() for t in opt_params)))
+    loss_func = FusedScaleLossFunction(block, quantizers, round_loss='none', lmda=lmda,
+                                       max_count=iters, b_range=(20, 2), decay_start=0,
+                                       warmup=0.2, p=p)
+    start_loss = 0.0
+    # only the alphas need a gradient: no weight gradient, no delta / zero_point gradient
+    with frozen_except(block, opt_params):
+        t = tqdm(range(iters), desc='', dynamic_ncols=True, disable=not verbose)
+        for i in t:
+            probe(i, opt_params)
+            if iter_hook is not None:
+                iter_hook(i)
+            optimizer.zero_grad()
+            inp, out = feeder.next()
+            loss = loss_func(block(inp), out)
+            loss.backward()
+            optimizer.step()
+            if i % 500 == 0 and verbose:
+                start_loss = max(start_loss, as_float(loss_func.rec_loss))
+                t.set_description(f"{start_loss:.6f} -> {as_float(loss_func.rec_loss):.6f}")
+    probe(iters, opt_params)
+    if iter_hook is not None:
+        iter_hook(iters)
+
+    rec_loss_out = []
+    optimizer.zero_grad()
+    with torch.no_grad():
+        loss_func(block(cur_inp), cur_out)
+    if verbose:
+        print(f"Soft Shift : {start_loss:.6f} -> {as_float(loss_func.rec_loss):.6f}")
+    rec_loss_out.append(as_float(loss_func.rec_loss))
+    _act_hard_flags(quantizers)
+    with torch.no_grad():
+        loss_func(block(cur_inp), cur_out)
+    if verbose:
+        print(f"Hard Shift : {start_loss:.6f} -> {as_float(loss_func.rec_loss):.6f}")
+    rec_loss_out.append(as_float(loss_func.rec_loss))
+    if verbose:
+        print_ratio(quantizers)
+    model.eval()
+    return rec_loss_out
+
+
 def block_recon_fused_shiftedScale(block: BaseQuantBlock, iters: int = 20000, lmda: list = [1., 1.],
                                    model=None, test_loader=None, act=False, adaround=False,
                                    useShiftedScale=True, bias_cal=False, batch_size=32,
-                                   dp_average=False, verbose=True, iter_hook=None, graph=True):
+                                   dp_average=False, verbose=True, iter_hook=None, graph=True,
+                                   act_shift_targets=None):
     """layer_recon_fused_shiftedScale.py:23-141 -> [soft rec loss, hard rec loss].
     graph=True replays the iteration body from a HIP graph after GRAPH_WARMUP eager
     iterations (at world > 1 as two graphs around the bucket all-reduce); the arithmetic
-    and the batch draws are unchanged."""
+    and the batch draws are unchanged.  act=True learns the per-channel shifted scale of the
+    block's activation quantizers instead (_act_loop; `graph` is ignored there,
+    act_shift_targets defaults to [1.0, 0.5])."""
     if act:
-        # the reference's act branch builds ChannelQuantAct and calls its init_v, which
-        # crashes (channelQuantAct.py:126-134): no working semantics exist to reproduce
-        raise NotImplementedError("block_recon_fused_shiftedScale(act=True) is broken in the reference")
+        # the reference's act branch crashes in ChannelQuantAct.init_v (channelQuantAct.py:
+        # 126-134); its evident intent (:37-57) is implemented (DESIGN.md section 6)
+        block.train()
+        return _act_loop(block, iters, lmda, model, 2.0, 0.001, bias_cal, batch_size, verbose,
+                         iter_hook, act_shift_targets)
     block.train()
     return _fused_loop(block, _weight_quantizers(block), iters, lmda, model, 2.0, 0.001, bias_cal,
                        batch_size, dp_average, verbose, iter_hook, graph)
@@ -235,7 +360,8 @@ def block_recon_fused_shiftedScale(block: BaseQuantBlock, iters: int = 20000, lm
 def layer_recon_fused_shiftedScale(layer: QuantModule, iters: int = 20000, lmda: list = [1., 1.],
                                    model=None, test_loader=None, act=False, adaround=False,
                                    useShiftedScale=True, bias_cal=False, batch_size=32,
-                                   dp_average=False, verbose=True, graph=True):
+                                   dp_average=False, verbose=True, graph=True,
+                                   act_shift_targets=None):
     """layer_recon_fused_shiftedScale.py:144-221.  The reference raises UnboundLocalError
     (`opt_params += ...` before assignment, :156); this implements its evident intent: the
     block loop on one layer with p = 1.0 (:165) and Adam's default lr, finished with the
@@ -243,6 +369,10 @@ def layer_recon_fused_shiftedScale(layer: QuantModule, iters: int = 20000, lmda:
     the hard flag lands on the LAYER (not its quantizer), so the final 'Hard Round'
     evaluation keeps the soft rounding h(beta) either way -- reproduced as written."""
     model.train()
+    if act:
+        # the layer variant of the act path: the same loop on one QuantModule, p = 1 (:165)
+        return _act_loop(layer, iters, lmda, model, 1.0, 0.001, bias_cal, batch_size, verbose,
+                         None, act_shift_targets)
 
     def set_hard(quantizers):
         if adaround:
