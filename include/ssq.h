@@ -834,6 +834,52 @@ int ssq_epilogue_codes_fwd(const float* y, const float* bias, const float* gamma
 int ssq_maxpool_i8_fwd(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W, int64_t K,
                        int64_t stride, int64_t pad, int8_t* out, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- per-channel act grids (_chq)
+ * The act quantizer's scale is per channel: d[c] = dch[c], a device array of C positive finite
+ * fp32 values (a shifted-scale act quantizer's fp32(delta * s_k(c))), beside the scalar zero
+ * point and code range.  Layouts, stored form and operation order are those of the scalar entry
+ * point each one is named after, with d[c] wherever that one uses delta:
+ *   ssq_act_encode_chq    q = clamp(rint(x / dch[c]) + z, qmin, qmax), IEEE divide; *bad counts the
+ *                         elements whose (q - z) * dch[c] is not bit-identical to x (NaN / +-inf
+ *                         stored as qmin and counted);
+ *   ssq_act_decode_chq    x = (q - z) * dch[c] (no counter: the entries were counted where the
+ *                         codes were made);
+ *   ssq_qconv_i8_codes_chq_fwd   the dense code-emitting conv (K23, one-kernel form) with
+ *                         out_dch[Co] for out_delta.  form: 0 the blob of ssq_qweight_prepare, 1 a
+ *                         centred blob, 2 the wide blob.  At most one of res_f32 / res_codes (both
+ *                         null: no residual); res_codes enters as (q_r - res_zero_point) *
+ *                         res_dch[co], the value ssq_act_decode_chq writes.  A tail whose two
+ *                         grids differ in kind passes null for the per-tensor one's array and its
+ *                         scalar in out_delta / res_delta (not read beside an array); at least
+ *                         one array must be given;
+ *   ssq_epilogue_codes_chq_fwd   K27 with out_dch[C] for out_delta.
+ * Null arrays and the scalar quantizer rules (zero point an integer in [qmin, qmin + 255],
+ * qmax - qmin <= 255) are SSQ_E_ARG before any launch.  The entries of dch are checked on the
+ * device: each real channel whose entry is not positive and finite is ADDED to *bad once per
+ * launch, with no host sync.  No allocation, no sync, the caller's stream: capturable.
+ * The max-pool on codes (ssq_maxpool_i8_fwd) needs no per-channel form: every d[c] > 0, so the
+ * decode is non-decreasing per channel and the pooled tensor lies on its producer's grid.     */
+int ssq_act_encode_chq(const float* x, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                       const float* dch, float zero_point, int qmin, int qmax, int8_t* codes,
+                       uint32_t* bad, ssq_stream_t stream);
+int ssq_act_decode_chq(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                       const float* dch, float zero_point, int qmin, float* x,
+                       ssq_stream_t stream);
+int ssq_qconv_i8_codes_chq_fwd(const int8_t* codes, const void* prepared, const float* scale,
+                               int64_t Nb, int64_t Ci, int64_t H, int64_t W, int64_t Co,
+                               int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+                               float act_zero_point, int act_qmin, int act_qmax,
+                               const float* bias, const float* gamma, const float* phi, int act,
+                               int form, const float* out_dch, float out_delta,
+                               float out_zero_point, int out_qmin, int out_qmax, int8_t* out_codes,
+                               uint32_t* bad, const float* res_f32, const int8_t* res_codes,
+                               const float* res_dch, float res_delta, float res_zero_point,
+                               int res_qmin, int res_qmax, ssq_stream_t stream);
+int ssq_epilogue_codes_chq_fwd(const float* y, const float* bias, const float* gamma,
+                               const float* phi, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                               int act, const float* out_dch, float out_zero_point, int out_qmin,
+                               int out_qmax, int8_t* out_codes, uint32_t* bad, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- fused stem (K31)
  * The stem conv itself, on the fp32 MFMA, with a stated summation order.  For an fp32 NCHW image
  * x [Nb, Ci, H, W] and an fp32 OIHW weight w [Co, Ci, R, S], stride (stride_h, stride_w), padding

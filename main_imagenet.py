@@ -84,6 +84,7 @@ def run_integer_inference(qnn, args, cali, loader, bs=32):
                                     splitk=args.int_infer_splitk,
                                     per_ci=args.int_infer_per_ci, wide=args.int_infer_wide,
                                     wide_all=getattr(args, 'int_infer_wide_all', False),
+                                    act_shift=getattr(args, 'int_infer_act_shift', False),
                                     **fused, **image_u8)
     n_int = sum(v == 'int8' for v in plan.values())
     print(f'integer inference: {n_int} of {len(plan)} layers on int8 codes')

@@ -151,6 +151,13 @@ SIGNATURES = {
     "ssq_epilogue_codes_fwd": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _f, _f, _i, _i, _p,
                                     _p, _p]),
     "ssq_maxpool_i8_fwd": (_i, [_p] + [_i64] * 7 + [_p, _p]),
+    "ssq_act_encode_chq": (_i, [_p, _i64, _i64, _i64, _i64, _p, _f, _i, _i, _p, _p, _p]),
+    "ssq_act_decode_chq": (_i, [_p, _i64, _i64, _i64, _i64, _p, _f, _i, _p, _p]),
+    "ssq_qconv_i8_codes_chq_fwd": (_i, [_p, _p, _p] + [_i64] * 10 + [_f, _i, _i, _p, _p, _p, _i, _i,
+                                                                  _p, _f, _f, _i, _i, _p, _p, _p,
+                                                                  _p, _p, _f, _f, _i, _i, _p]),
+    "ssq_epilogue_codes_chq_fwd": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _f, _i, _i,
+                                        _p, _p, _p]),
     "ssq_stem_weight_prepared_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "ssq_stem_weight_prepare": (_i, [_p, _i64, _i64, _i64, _i64, _p, _p]),
     "ssq_stem_conv_fwd": (_i, [_p, _p, _sz] + [_i64] * 11 + [_p, _p]),

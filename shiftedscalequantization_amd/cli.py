@@ -135,6 +135,10 @@ def build_parser():
                    help='--int_infer_wide with the two-digit operand also on grouped and depthwise '
                         'convs and on the pooled-operand fc of --int_infer_carry_head (which then '
                         'takes a scaled fc); implies --int_infer_wide')
+    p.add_argument('--int_infer_act_shift', action='store_true',
+                   help='--int_infer with the layers behind a shifted-scale act quantizer '
+                        '(--act_shift) on int8 codes of per-channel grids, on whichever '
+                        '--int_infer* route was chosen; implies --int_infer')
     p.add_argument('--int_infer_splitk', action='store_true',
                    help='--int_infer with the dense int8 convs of small planes split along K '
                         'where the host rule asks for it (two kernels, bit-identical); implies '
@@ -183,7 +187,8 @@ def parse_args(argv=None):
     if a.int_infer_wide_all:
         a.int_infer_wide = True
     if (a.int_infer_grouped or a.int_infer_carry or a.int_infer_colscale or a.int_infer_splitk
-            or a.int_infer_graph or a.int_infer_per_ci or a.int_infer_wide):
+            or a.int_infer_graph or a.int_infer_per_ci or a.int_infer_wide
+            or a.int_infer_act_shift):
         a.int_infer = True
     return a
 

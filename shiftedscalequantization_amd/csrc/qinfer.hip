@@ -220,18 +220,29 @@ struct QPartial {
   int32_t* SA;   // [Z][M]: slice z's window sum (not CENTRED)
 };
 
-template <bool CODES, int RES = 0, bool CENTRED = false, bool PARTIAL = false, bool WIDE = false>
-__global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
+// CHQ (with CODES; qconv_i8_chq_kernel): the output quantizer's scale, and a code residual's, is
+// per output channel (QEpiCh / QResCh).  A lane's 16 channels are fixed before the epilogue, so
+// their out_dch (and, RES == 2, res_dch) entries are fetched once, with the residual, right after
+// the K loop, and the epilogue is the scalar one with t / od[..] for t / e.d.  The first pixel
+// tile's wave 0 counts the entries of its channel tile that are no scale (qdch_bad) into *bad.
+template <bool CODES, int RES, bool PARTIAL, bool CHQ>
+using QConvOut = typename std::conditional<
+    PARTIAL, QPartial,
+    typename std::conditional<
+        CODES,
+        typename std::conditional<CHQ, typename std::conditional<RES != 0, QEpiResCh, QEpiCh>::type,
+                                  typename std::conditional<RES != 0, QEpiRes, QEpi>::type>::type,
+        float* __restrict__>::type>::type;
+
+template <bool CODES, int RES, bool CENTRED, bool PARTIAL, bool WIDE, bool CHQ>
+__device__ __forceinline__ void qconv_i8_body(
     const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ mask,
     const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
-    const float* __restrict__ scale, QConvGeo g,
-    typename std::conditional<
-        PARTIAL, QPartial,
-        typename std::conditional<CODES, typename std::conditional<RES != 0, QEpiRes, QEpi>::type,
-                                  float* __restrict__>::type>::type y) {
+    const float* __restrict__ scale, const QConvGeo& g, const QConvOut<CODES, RES, PARTIAL, CHQ>& y) {
   static_assert(CODES || RES == 0, "a residual goes with the code-emitting epilogue");
   static_assert(!PARTIAL || (!CODES && RES == 0), "a partial walk has no epilogue");
   static_assert(!WIDE || (CENTRED && !PARTIAL), "the wide operand is centred and has no split form");
+  static_assert(!CHQ || CODES, "a per-channel output grid goes with the code-emitting epilogue");
   __shared__ __attribute__((aligned(16))) int8_t lA[kQT * kQRow];
   __shared__ __attribute__((aligned(16))) int8_t lB[(WIDE ? 2 * kQT : kQT + 1) * kQRow];
   const uint32_t tid = threadIdx.x;
@@ -347,7 +358,7 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
       if (blockIdx.y == 0 && fq == 0) y.SA[(size_t)blockIdx.z * g.M + pixel] = accs[0];
     }
   } else if constexpr (CODES) {
-    const QEpi& e = qepi_of(y);
+    const auto& e = qepi_of(y);
     const bool pval = pixel < g.M;
     uint32_t nbad = 0;
     float rf[RES == 1 ? 16 : 1];
@@ -372,6 +383,25 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
         rw[j] = (pval && co0 < g.Co) ? *(const int*)(y.r.codes + (size_t)pixel * e.Cpo + co0) : 0;
       }
     }
+    float od[CHQ ? 16 : 1];               // out_dch of the lane's channels
+    float rd[CHQ && RES == 2 ? 16 : 1];   // res_dch likewise
+    if constexpr (CHQ) {
+      const bool counts = blockIdx.x == 0 && wave == 0 && fr == 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const uint32_t co = blockIdx.y * kQT + j * 16 + fq * 4 + r;
+          const bool cval = co < g.Co;
+          od[j * 4 + r] = cval ? qdch_at(e.dch, e.d, co) : 1.0f;
+          if (counts && cval && qdch_bad(od[j * 4 + r])) nbad += 1u;
+          if constexpr (RES == 2) {
+            rd[j * 4 + r] = cval ? qdch_at(y.r.dch, y.r.d, co) : 1.0f;
+            if (counts && cval && qdch_bad(rd[j * 4 + r])) nbad += 1u;
+          }
+        }
+      }
+    }
     __syncthreads();   // the last step's fragment reads are done: lA is free
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -383,7 +413,14 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
         if (pval && co < g.Co) {
           const long long I = qconv_sum_of<CENTRED, WIDE>(acc[j][r], accl[WIDE ? j : 0][r], cwz, sa,
                                                           g.az, tt, co);
-          if constexpr (RES == 1) {
+          if constexpr (CHQ) {
+            const float yv = __fmul_rn((float)I, scale[co]);   // qepi_code's product
+            float rv = 0.0f;
+            if constexpr (RES == 1) rv = rf[j * 4 + r];
+            if constexpr (RES == 2)
+              rv = qres_decode_d((int)(int8_t)((uint32_t)rw[j] >> (8 * r)), y.r, rd[j * 4 + r]);
+            c[r] = qepi_code_yd<RES != 0>(yv, co, e, od[j * 4 + r], nbad, rv);
+          } else if constexpr (RES == 1) {
             c[r] = qepi_code<true>((float)I, co, scale, e, nbad, rf[j * 4 + r]);
           } else if constexpr (RES == 2) {
             const int code = (int)(int8_t)((uint32_t)rw[j] >> (8 * r));
@@ -423,6 +460,23 @@ __global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
       }
     }
   }
+}
+
+template <bool CODES, int RES = 0, bool CENTRED = false, bool PARTIAL = false, bool WIDE = false>
+__global__ __launch_bounds__(kBlock) void qconv_i8_kernel(
+    const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ mask,
+    const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
+    const float* __restrict__ scale, QConvGeo g, QConvOut<CODES, RES, PARTIAL, false> y) {
+  qconv_i8_body<CODES, RES, CENTRED, PARTIAL, WIDE, false>(act, wp, mask, cwz, tt, scale, g, y);
+}
+
+// the per-channel forms of the code-emitting instantiations (ssq_qconv_i8_codes_chq_fwd)
+template <int RES, bool CENTRED, bool WIDE>
+__global__ __launch_bounds__(kBlock) SSQ_NO_PK_F32 void qconv_i8_chq_kernel(
+    const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ mask,
+    const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
+    const float* __restrict__ scale, QConvGeo g, QConvOut<true, RES, false, true> y) {
+  qconv_i8_body<true, RES, CENTRED, false, WIDE, true>(act, wp, mask, cwz, tt, scale, g, y);
 }
 
 // ---------------------------------------------------------------- K23 split along K
@@ -582,6 +636,91 @@ __global__ __launch_bounds__(kBlock) void act_decode_kernel(const int8_t* __rest
   }
 }
 
+// ---------------------------------------------------------------- K21 and its inverse, per channel
+// The grid is d[c] = dch[c] (ssq_act_encode_chq / ssq_act_decode_chq).  blockIdx.y is the
+// 16-channel chunk, so the chunk is uniform over the workgroup: the 16 dch entries are read once,
+// before the pixel loop, through uniform addresses (scalar registers, no LDS), and the chunk index
+// costs no division.  The walk along pixels is K21's: consecutive threads take consecutive pixels,
+// the 16 channel-plane accesses are each coalesced, the codes are one 16-B word per thread.
+// Thread 0 of the chunk's first workgroup counts the chunk's entries that are no scale (qdch_bad).
+__device__ __forceinline__ uint32_t qdch_stage(const float* __restrict__ dch, uint32_t c0,
+                                               uint32_t C, float (&d)[16]) {
+  uint32_t nbad = 0;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    d[j] = c0 + j < C ? dch[c0 + j] : 1.0f;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && c0 + j < C && qdch_bad(d[j])) nbad += 1u;
+  }
+  return nbad;
+}
+
+__global__ __launch_bounds__(kBlock) SSQ_NO_PK_F32 void act_encode_chq_kernel(
+    const float* __restrict__ x, uint32_t npix, uint32_t HW, uint32_t C, uint32_t Cp,
+    FastDiv div_hw, const float* __restrict__ dch, float z, float lo, float hi,
+    int8_t* __restrict__ out, uint32_t* __restrict__ bad) {
+  const uint32_t c0 = blockIdx.y * 16;
+  float d[16];
+  uint32_t nbad = qdch_stage(dch, c0, C, d);
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < npix; pix += stride) {
+    const uint32_t n = fdiv(pix, div_hw);
+    const float* src = x + ((size_t)n * C + c0) * HW + (pix - n * HW);
+    union {
+      i32x4 v;
+      int8_t b[16];
+    } o;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      int8_t code = 0;
+      if (c0 + j < C) {
+        const float xv = src[(size_t)j * HW];
+        float q = lo;   // NaN / +-inf: counted below, stored as qmin
+        if (isfinite(xv)) {
+          const float v = __fadd_rn(rintf(xv / d[j]), z);
+          q = v >= lo ? (v <= hi ? v : hi) : lo;
+        }
+        const float back = __fmul_rn(__fsub_rn(q, z), d[j]);
+        const bool ok = __builtin_bit_cast(uint32_t, back) == __builtin_bit_cast(uint32_t, xv);
+        nbad += ok ? 0u : 1u;
+        code = (int8_t)((int)__fsub_rn(q, lo) - 128);
+      }
+      o.b[j] = code;
+    }
+    *(i32x4*)(out + (size_t)pix * Cp + c0) = o.v;
+  }
+  qepi_count(nbad, bad);
+}
+
+__global__ __launch_bounds__(kBlock) SSQ_NO_PK_F32 void act_decode_chq_kernel(
+    const int8_t* __restrict__ codes, uint32_t npix, uint32_t HW, uint32_t C, uint32_t Cp,
+    FastDiv div_hw, const float* __restrict__ dch, float z, float lo, float* __restrict__ x) {
+  const uint32_t c0 = blockIdx.y * 16;
+  float d[16];
+  qdch_stage(dch, c0, C, d);   // (counted where the codes were made: the decode has no counter)
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < npix; pix += stride) {
+    const uint32_t n = fdiv(pix, div_hw);
+    union {
+      i32x4 v;
+      int8_t b[16];
+    } in;
+    in.v = *(const i32x4*)(codes + (size_t)pix * Cp + c0);
+    float* dst = x + ((size_t)n * C + c0) * HW + (pix - n * HW);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      if (c0 + j < C) {
+        const float q = __fadd_rn((float)((int)in.b[j] + 128), lo);   // exact: |q| <= 255
+        dst[(size_t)j * HW] = __fmul_rn(__fsub_rn(q, z), d[j]);
+      }
+    }
+  }
+}
+
+// the two's shared launch geometry: (pixel blocks, chunks), about 8192 workgroups at the most
+static dim3 qchq_grid(uint32_t npix, uint32_t nch) {
+  return dim3(grid_for(npix, kBlock, (int)(8192u / nch > 0 ? 8192u / nch : 1u)), nch);
+}
+
 static int qgeo_ok(const char* what, int64_t Co, int64_t Ci, int64_t R, int64_t S,
                    int planes = 1) {
   SSQ_REQUIRE(Co >= 1 && Ci >= 1 && R >= 1 && S >= 1 && R <= 7 && S <= 7, SSQ_E_ARG,
@@ -703,7 +842,8 @@ static size_t qsplit_ws_bytes(int64_t M, int64_t Co, int64_t Z, bool centred) {
 template <bool CENTRED, bool WIDE = false>
 static void qconv_i8_run(dim3 grid, ssq_stream_t stream, const int8_t* codes, const int8_t* base,
                          const QLayout& L, const float* scale, const QConvGeo& g, float* y,
-                         const QEpi* epi, const QRes* res, const QSplit* sp) {
+                         const QEpi* epi, const QRes* res, const QSplit* sp, bool chq = false,
+                         const float* out_dch = nullptr, const float* res_dch = nullptr) {
   const int8_t* mask = base + L.off_mask;
   const int32_t* cwz = (const int32_t*)(base + L.off_cwz);
   const int32_t* tt = (const int32_t*)(base + L.off_t);
@@ -711,6 +851,17 @@ static void qconv_i8_run(dim3 grid, ssq_stream_t stream, const int8_t* codes, co
     hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base, mask, cwz,
                        tt, scale, g, out);
   };
+  if (chq) {   // the per-channel forms: code-emitting, never split (qconv_i8_launch)
+    const QEpiCh ec = {*epi, out_dch};
+    if (!res) {
+      run(qconv_i8_chq_kernel<0, CENTRED, WIDE>, ec);
+    } else {
+      const QEpiResCh er = {ec, QResCh{*res, res_dch}};
+      if (res->f32) run(qconv_i8_chq_kernel<1, CENTRED, WIDE>, er);
+      else run(qconv_i8_chq_kernel<2, CENTRED, WIDE>, er);
+    }
+    return;
+  }
   if constexpr (WIDE) {
     if (!epi) run(qconv_i8_kernel<false, 0, true, false, true>, y);
     else if (!res) run(qconv_i8_kernel<true, 0, true, false, true>, *epi);
@@ -756,12 +907,14 @@ struct QConvIn {
 // `sp`: the split-K forms; wide: the *_wide_* forms on the two-digit blob (centred, never split)
 static int qconv_i8_launch(const char* me, bool centred, const QConvIn& a, float* y, QEpi* epi,
                            const QRes* res, ssq_stream_t stream, const QSplit* sp = nullptr,
-                           bool wide = false) {
+                           bool wide = false, bool chq = false, const float* out_dch = nullptr,
+                           const float* res_dch = nullptr) {
   SSQ_REQUIRE(a.codes && a.prepared && a.scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
   SSQ_REQUIRE(a.groups == 1, SSQ_E_ARG, "%s: groups = %lld (only groups == 1)", me,
               (long long)a.groups);
   const int64_t Nb = a.Nb, H = a.H, W = a.W, Co = a.Co, R = a.R, S = a.S, pad = a.pad;
   SSQ_REQUIRE(!wide || (centred && !sp), SSQ_E_ARG, "%s: the wide blob has no split-K form", me);
+  SSQ_REQUIRE(!chq || (epi && !sp), SSQ_E_ARG, "%s: a per-channel grid has no split-K form", me);
   int rc = qgeo_ok(me, Co, a.Ci, R, S, wide ? 2 : 1);
   if (rc) return rc;
   SSQ_REQUIRE(Nb >= 1 && H >= 1 && W >= 1 && a.stride >= 1 && pad >= 0 &&
@@ -808,9 +961,15 @@ static int qconv_i8_launch(const char* me, bool centred, const QConvIn& a, float
   }
   const dim3 grid((g.M + kQT - 1) / kQT, (uint32_t)(L.Cop / kQT));
   const int8_t* base = (const int8_t*)a.prepared;
-  if (wide) qconv_i8_run<true, true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, nullptr);
-  else if (centred) qconv_i8_run<true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, sp);
-  else qconv_i8_run<false>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, sp);
+  if (wide)
+    qconv_i8_run<true, true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, nullptr,
+                             chq, out_dch, res_dch);
+  else if (centred)
+    qconv_i8_run<true>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, sp, chq,
+                       out_dch, res_dch);
+  else
+    qconv_i8_run<false>(grid, stream, a.codes, base, L, a.scale, g, y, epi, res, sp, chq,
+                       out_dch, res_dch);
   return check_launch(me);
 }
 
@@ -998,6 +1157,83 @@ extern "C" int ssq_act_decode(const int8_t* codes, int64_t Nb, int64_t C, int64_
                      HW, (uint32_t)C, (uint32_t)Cp, make_fastdiv(npix), make_fastdiv(HW), delta,
                      zero_point, (float)qmin, x);
   return check_launch("ssq_act_decode");
+}
+
+// ---------------------------------------------------------------- per-channel act grids: the ABI
+// the geometry checks of ssq_act_encode / ssq_act_decode -> (npix, HW, Cp)
+static int qchq_geo(const char* me, int64_t Nb, int64_t C, int64_t H, int64_t W, uint32_t* npix,
+                    uint32_t* HW, int64_t* Cp) {
+  SSQ_REQUIRE(Nb >= 1 && C >= 1 && H >= 1 && W >= 1, SSQ_E_ARG, "%s: bad geometry", me);
+  *Cp = rup(C, 16);
+  SSQ_REQUIRE(*Cp / 16 <= 65535, SSQ_E_ARG, "%s: more than 65535 * 16 channels", me);
+  SSQ_REQUIRE(Nb * H * W * *Cp < (1ll << 31), SSQ_E_ARG, "%s: tensor exceeds 2^31 elements", me);
+  *npix = (uint32_t)(Nb * H * W);
+  *HW = (uint32_t)(H * W);
+  return SSQ_OK;
+}
+
+extern "C" int ssq_act_encode_chq(const float* x, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                                  const float* dch, float zero_point, int qmin, int qmax,
+                                  int8_t* codes, uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_act_encode_chq";
+  SSQ_REQUIRE(x && dch && codes && bad, SSQ_E_ARG, "%s: null pointer", me);
+  uint32_t npix, HW;
+  int64_t Cp;
+  int rc = qchq_geo(me, Nb, C, H, W, &npix, &HW, &Cp);
+  if (!rc) rc = qquant_ok(me, "", nullptr, zero_point, qmin, qmax);
+  if (rc) return rc;
+  hipLaunchKernelGGL(act_encode_chq_kernel, qchq_grid(npix, (uint32_t)(Cp / 16)), dim3(kBlock), 0,
+                     (hipStream_t)stream, x, npix, HW, (uint32_t)C, (uint32_t)Cp, make_fastdiv(HW),
+                     dch, zero_point, (float)qmin, (float)qmax, codes, bad);
+  return check_launch(me);
+}
+
+extern "C" int ssq_act_decode_chq(const int8_t* codes, int64_t Nb, int64_t C, int64_t H, int64_t W,
+                                  const float* dch, float zero_point, int qmin, float* x,
+                                  ssq_stream_t stream) {
+  const char* me = "ssq_act_decode_chq";
+  SSQ_REQUIRE(codes && dch && x, SSQ_E_ARG, "%s: null pointer", me);
+  SSQ_REQUIRE(qmin >= -128 && qmin <= 0, SSQ_E_ARG, "%s: qmin %d not in [-128, 0]", me, qmin);
+  uint32_t npix, HW;
+  int64_t Cp;
+  int rc = qchq_geo(me, Nb, C, H, W, &npix, &HW, &Cp);
+  if (!rc) rc = qquant_ok(me, "", nullptr, zero_point, qmin, qmin + 255);   // as ssq_act_decode
+  if (rc) return rc;
+  hipLaunchKernelGGL(act_decode_chq_kernel, qchq_grid(npix, (uint32_t)(Cp / 16)), dim3(kBlock), 0,
+                     (hipStream_t)stream, codes, npix, HW, (uint32_t)C, (uint32_t)Cp,
+                     make_fastdiv(HW), dch, zero_point, (float)qmin, x);
+  return check_launch(me);
+}
+
+// The dense code-emitting conv on a per-channel output grid.  form: 0 the plain blob, 1 a centred
+// one, 2 the wide one (the *_codes_*, *_centred_codes_* and *_wide_codes_* entries' kernels);
+// res_f32 / res_codes: at most one, both null for no residual.  out_dch null: the per-tensor grid
+// out_delta; res_dch null (with res_codes): res_delta -- a tail whose two grids differ in kind.
+extern "C" int ssq_qconv_i8_codes_chq_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t Ci,
+    int64_t H, int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
+    int64_t groups, float act_zero_point, int act_qmin, int act_qmax, const float* bias,
+    const float* gamma, const float* phi, int act, int form, const float* out_dch, float out_delta,
+    float out_zero_point, int out_qmin, int out_qmax, int8_t* out_codes, uint32_t* bad,
+    const float* res_f32, const int8_t* res_codes, const float* res_dch, float res_delta,
+    float res_zero_point, int res_qmin, int res_qmax, ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_codes_chq_fwd";
+  SSQ_REQUIRE(form >= 0 && form <= 2, SSQ_E_ARG, "%s: form %d not in [0, 2]", me, form);
+  QEpiCh e;
+  QResCh r = {};
+  const bool res = res_f32 || res_codes;
+  SSQ_REQUIRE(out_dch || (res_codes && res_dch), SSQ_E_ARG,
+              "%s: no per-channel grid (out_dch, or res_dch with res_codes)", me);
+  int rc = qepi_init_ch(me, bias, gamma, phi, act, out_dch, out_delta, true, out_zero_point,
+                        out_qmin, out_qmax, out_codes, bad, &e);
+  if (!rc && res)
+    rc = qres_init_ch(me, res_f32, res_codes, res_dch, res_delta, res_zero_point, res_qmin,
+                      res_qmax, &r);
+  if (rc) return rc;
+  return qconv_i8_launch(me, form != 0,
+                         {codes, prepared, scale, Nb, Ci, H, W, Co, R, S, stride, pad, groups,
+                          act_zero_point, act_qmin, act_qmax},
+                         nullptr, &e, res ? &r : nullptr, stream, nullptr, form == 2, true, e.dch, r.dch);
 }
 
 // ---------------------------------------------------------------- K23 split along K: the ABI

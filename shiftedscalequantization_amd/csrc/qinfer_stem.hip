@@ -14,6 +14,8 @@
 // every window a real tap); padded channels stay 0, the maximum of zeros.
 //
 // Layouts: fp32 NCHW in (K27), NHWC int8 with C padded to Cp = 16*ceil(C/16) otherwise.
+#include <type_traits>
+
 #include "ssq_common.h"
 #include "qinfer_epi.h"
 #include "qinfer_layout.h"
@@ -29,11 +31,15 @@ typedef short i16x8 __attribute__((ext_vector_type(8)));
 // loads is 256 contiguous bytes and the chunk index is wave-uniform (bias / gamma / phi are
 // scalar loads).  Consecutive waves take the chunks of the same 64 pixels, so the 16-B stores of
 // a workgroup fill one contiguous 64 * Cp-byte span of the output.
-__global__ __launch_bounds__(kBlock) void epilogue_codes_kernel(const float* __restrict__ y,
-                                                                uint32_t npix, uint32_t HW,
-                                                                uint32_t C, uint32_t nch,
-                                                                uint32_t nwork, FastDiv div_nch,
-                                                                FastDiv div_hw, QEpi e) {
+// E = QEpiCh (ssq_epilogue_codes_chq_fwd): the chunk's 16 out_dch entries are wave-uniform too, read
+// beside bias / gamma / phi, and lane 0 of a chunk's first wave (pb == 0) counts those that are no
+// scale (qdch_bad).
+template <typename E>
+__device__ __forceinline__ void epilogue_codes_body(const float* __restrict__ y, uint32_t npix,
+                                                    uint32_t HW, uint32_t C, uint32_t nch,
+                                                    uint32_t nwork, FastDiv div_nch, FastDiv div_hw,
+                                                    const E& e) {
+  constexpr bool CHQ = std::is_same<E, QEpiCh>::value;
   const uint32_t lane = threadIdx.x & (kWave - 1);
   const uint32_t wstride = gridDim.x * (kBlock / kWave);
   uint32_t nbad = 0;
@@ -43,6 +49,14 @@ __global__ __launch_bounds__(kBlock) void epilogue_codes_kernel(const float* __r
     const uint32_t pb = fdiv(w, div_nch);
     const uint32_t c0 = (w - pb * nch) * 16;
     const uint32_t pix = pb * kWave + lane;
+    float d[CHQ ? 16 : 1];
+    if constexpr (CHQ) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        d[j] = c0 + j < C ? e.dch[c0 + j] : 1.0f;
+        if (pb == 0 && lane == 0 && c0 + j < C && qdch_bad(d[j])) nbad += 1u;
+      }
+    }
     if (pix < npix) {
       const uint32_t n = fdiv(pix, div_hw);
       const float* src = y + ((size_t)n * C + c0) * HW + (pix - n * HW);
@@ -51,7 +65,10 @@ __global__ __launch_bounds__(kBlock) void epilogue_codes_kernel(const float* __r
       for (int j = 0; j < 16; ++j) v[j] = c0 + j < C ? src[(size_t)j * HW] : 0.0f;
       int c[16];
 #pragma unroll
-      for (int j = 0; j < 16; ++j) c[j] = c0 + j < C ? qepi_code_y(v[j], c0 + j, e, nbad) : 0;
+      for (int j = 0; j < 16; ++j) {
+        if constexpr (CHQ) c[j] = c0 + j < C ? qepi_code_yd(v[j], c0 + j, e, d[j], nbad) : 0;
+        else c[j] = c0 + j < C ? qepi_code_y(v[j], c0 + j, e, nbad) : 0;
+      }
       i32x4 o;
 #pragma unroll
       for (int k = 0; k < 4; ++k) o[k] = qepi_pack4(c[4 * k], c[4 * k + 1], c[4 * k + 2], c[4 * k + 3]);
@@ -59,6 +76,20 @@ __global__ __launch_bounds__(kBlock) void epilogue_codes_kernel(const float* __r
     }
   }
   qepi_count(nbad, e.bad);
+}
+
+__global__ __launch_bounds__(kBlock) void epilogue_codes_kernel(const float* __restrict__ y,
+                                                                uint32_t npix, uint32_t HW,
+                                                                uint32_t C, uint32_t nch,
+                                                                uint32_t nwork, FastDiv div_nch,
+                                                                FastDiv div_hw, QEpi e) {
+  epilogue_codes_body(y, npix, HW, C, nch, nwork, div_nch, div_hw, e);
+}
+
+__global__ __launch_bounds__(kBlock) SSQ_NO_PK_F32 void epilogue_codes_chq_kernel(
+    const float* __restrict__ y, uint32_t npix, uint32_t HW, uint32_t C, uint32_t nch,
+    uint32_t nwork, FastDiv div_nch, FastDiv div_hw, QEpiCh e) {
+  epilogue_codes_body(y, npix, HW, C, nch, nwork, div_nch, div_hw, e);
 }
 
 // ---------------------------------------------------------------- K28 max-pool on codes
@@ -158,6 +189,31 @@ extern "C" int ssq_epilogue_codes_fwd(const float* y, const float* bias, const f
   e.Cpo = (uint32_t)Cp;
   const dim3 grid(grid_for((int64_t)nwork * kWave, kBlock, 8192));
   hipLaunchKernelGGL(epilogue_codes_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, y, npix,
+                     (uint32_t)(H * W), (uint32_t)C, nch, nwork, make_fastdiv(nch),
+                     make_fastdiv((uint32_t)(H * W)), e);
+  return check_launch(me);
+}
+
+// K27 on a per-channel output grid: out_dch[C] for out_delta, everything else as above
+extern "C" int ssq_epilogue_codes_chq_fwd(const float* y, const float* bias, const float* gamma,
+                                          const float* phi, int64_t Nb, int64_t C, int64_t H,
+                                          int64_t W, int act, const float* out_dch,
+                                          float out_zero_point, int out_qmin, int out_qmax,
+                                          int8_t* out_codes, uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_epilogue_codes_chq_fwd";
+  SSQ_REQUIRE(y, SSQ_E_ARG, "%s: null pointer", me);
+  QEpiCh e;
+  const int rc = qepi_init_ch(me, bias, gamma, phi, act, out_dch, 0.0f, false, out_zero_point,
+                              out_qmin, out_qmax, out_codes, bad, &e);
+  if (rc) return rc;
+  SSQ_REQUIRE(Nb >= 1 && C >= 1 && H >= 1 && W >= 1, SSQ_E_ARG, "%s: bad geometry", me);
+  const int64_t Cp = rup(C, 16);
+  SSQ_REQUIRE(Nb * H * W * Cp < (1ll << 31), SSQ_E_ARG, "%s: tensor exceeds 2^31 elements", me);
+  const uint32_t npix = (uint32_t)(Nb * H * W), nch = (uint32_t)(Cp / 16);
+  const uint32_t nwork = (npix + kWave - 1) / kWave * nch;
+  e.Cpo = (uint32_t)Cp;
+  const dim3 grid(grid_for((int64_t)nwork * kWave, kBlock, 8192));
+  hipLaunchKernelGGL(epilogue_codes_chq_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, y, npix,
                      (uint32_t)(H * W), (uint32_t)C, nch, nwork, make_fastdiv(nch),
                      make_fastdiv((uint32_t)(H * W)), e);
   return check_launch(me);

@@ -2048,6 +2048,11 @@ def act_encode(x, delta, zp, n_bits, sym=False, bad=None):
                         device=x.device)
     if bad is None:
         bad = torch.zeros(1, dtype=torch.int32, device=x.device)
+    if isinstance(delta, ChannelScale):
+        # a per-channel grid (ssq_act_encode_chq): `bad` also counts the scales that are none
+        call("ssq_act_encode_chq", xp, N, Cc, H, W, delta.ptr("act_encode", Cc), float(zp), lo, hi,
+             _vp(codes), _vp(bad), stream_of(x))
+        return codes, bad
     call("ssq_act_encode", xp, N, Cc, H, W, float(delta), float(zp), lo, hi, _vp(codes), _vp(bad),
          stream_of(x))
     return codes, bad
@@ -2484,6 +2489,72 @@ def _qconv_args(name, codes_or_x, prepared, scale, stride, padding, groups, act_
 ActQuant = collections.namedtuple("ActQuant", "delta zp n_bits sym")   # a per-tensor act quantizer
 
 
+class ChannelScale:
+    """A per-channel act scale in the place of an ActQuant's (a CarriedCodes') scalar `delta`:
+    `dch`, the fp32 device tensor [C] of positive finite scales d[c] the *_chq kernels read (a
+    hard ChannelQuantAct's fp32(delta * s_k(c))); `base`, the scalar delta a consumer's layer
+    scale is built from, and `fold` = (L, k[C] int32 CPU tensor), the integer grid d[c] =
+    fp32(base * fp32(k[c] / L)) that consumer multiplies into its weight operand (both None for a
+    scale that is nobody's planned input).  Two are equal when their scales are, bit for
+    bit (a host copy kept from construction: comparing syncs nothing), so ActQuant's tuple
+    equality -- IntPlan.accepts -- compares the per-channel scales too.  act_encode, act_decode,
+    qconv, qconv_codes and epilogue_codes take one wherever they take a scalar delta."""
+
+    def __init__(self, dch, base=None, fold=None):
+        self.dch = dch.detach().reshape(-1).float().contiguous()
+        self.key = self.dch.cpu().numpy().tobytes()
+        self.base = None if base is None else float(base)
+        self.fold = fold
+
+    def __eq__(self, other):
+        return self is other or (isinstance(other, ChannelScale) and self.key == other.key)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self.key)
+
+    def __repr__(self):
+        return f"ChannelScale(C={self.dch.numel()}, base={self.base})"
+
+    def ptr(self, name, C):
+        if self.dch.numel() != int(C) or not self.dch.is_cuda:
+            raise A.SSQError(f"{name}: the per-channel scale holds {self.dch.numel()} channels, the "
+                             f"tensor {int(C)} (one device entry per channel)")
+        return _vp(self.dch)
+
+
+def _delta_of(delta):
+    return delta if isinstance(delta, ChannelScale) else float(delta)
+
+
+ACTSHIFT_MAX_L = 127
+
+
+def actshift_grid(delta, targets, max_l=ACTSHIFT_MAX_L):
+    """The common integer grid of a shifted-scale act quantizer's targets s_i: the smallest L in
+    1..max_l with, for every i, an integer 1 <= k_i <= 127 such that
+    fp32(delta * fp32(k_i / L)) == fp32(delta * fp32(s_i)) bit for bit (k_i = rint(s_i * L); the
+    products are single fp32 multiplications of the stored fp32 delta) -> (L, k as a list of S
+    ints); None when there is no such L (a zero, negative or non-finite target or delta included).
+    The consumer of such a quantizer folds k_i of its input channel into its integer weight
+    operand, and its layer scale is fp32(fp32(delta * d1[co]) / fp32(L)).  Host arithmetic."""
+    import numpy as np
+    d = np.float32(delta)
+    s = np.asarray([float(t) for t in targets], dtype=np.float32)
+    if s.size == 0 or not np.all(np.isfinite(s)) or not np.all(s > 0) or not (np.isfinite(d) and d > 0):
+        return None
+    want = (d * s).view(np.int32)
+    for L in range(1, int(max_l) + 1):
+        k = np.rint(s.astype(np.float64) * L)
+        if k.min() < 1 or k.max() > 127:
+            continue
+        if np.array_equal((d * (k.astype(np.float32) / np.float32(L))).view(np.int32), want):
+            return L, [int(v) for v in k]
+    return None
+
+
 class _Quantized:
     """A tagged tensor's act quantizer: `q`, an ActQuant (what quantizer() returns), with its
     fields also as plain attributes.  Built in the subclass's __init__ by tuple.__new__: one is
@@ -2502,7 +2573,7 @@ class CarriedCodes(_Quantized):
 
     def __init__(self, shape, delta, zp, n_bits, sym):
         self.shape = tuple(int(v) for v in shape)
-        self.q = q = tuple.__new__(ActQuant, (float(delta), float(zp), int(n_bits), bool(sym)))
+        self.q = q = tuple.__new__(ActQuant, (_delta_of(delta), float(zp), int(n_bits), bool(sym)))
         self.delta, self.zp, self.n_bits, self.sym = q
 
     def decode(self, codes):
@@ -2541,7 +2612,8 @@ def carried(codes, shape, delta, zp, n_bits, sym):
 
 def act_decode(codes, C, delta, zp, n_bits, sym=False):
     """act_encode's inverse: int8 codes (N, H, W, Cpad) or (N, Cpad) with C real channels ->
-    fp32 (N, C, H, W) / (N, C), (q - zp) * delta."""
+    fp32 (N, C, H, W) / (N, C), (q - zp) * delta.  `delta` a ChannelScale: (q - zp) * d[c]
+    (ssq_act_decode_chq)."""
     if not isinstance(codes, torch.Tensor) or codes.dtype != torch.int8:
         raise A.SSQError("act_decode: expected int8 codes")
     codes = _i8_dev(codes, "act_decode")
@@ -2552,6 +2624,10 @@ def act_decode(codes, C, delta, zp, n_bits, sym=False):
     H, W = (int(codes.shape[1]), int(codes.shape[2])) if codes.dim() == 4 else (1, 1)
     x = torch.empty((N, C, H, W) if codes.dim() == 4 else (N, C), dtype=torch.float32,
                     device=codes.device)
+    if isinstance(delta, ChannelScale):
+        call("ssq_act_decode_chq", _vp(codes), N, C, H, W, delta.ptr("act_decode", C), float(zp),
+             qrange(n_bits, sym)[0], _vp(x), stream_of(x))
+        return x
     call("ssq_act_decode", _vp(codes), N, C, H, W, float(delta), float(zp),
          qrange(n_bits, sym)[0], _vp(x), stream_of(x))
     return x
@@ -2603,6 +2679,25 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
                                  f"codes, got {residual.dtype} {tuple(residual.shape)}")
             res, rp = fptr(residual.detach(), "residual")
             rargs = (rp, None, 0.0, 0.0, 0, 0)
+    cc = None if residual is None else getattr(residual, "_ssq_codes", None)
+    if isinstance(out_delta, ChannelScale) or (cc is not None and isinstance(cc.delta, ChannelScale)):
+        # a per-channel grid on either side: the one entry point of both (a per-tensor grid beside
+        # it passes its scalar and a null array), dense and unsplit
+        if int(groups) > 1 or (splits is not None and int(splits) != 1):
+            raise A.SSQError("qconv_codes: a per-channel act grid needs the dense one-kernel form "
+                             "(groups == 1, no splits)")
+        def grid(d):     # (the array or null, the scalar or 0)
+            return (d.ptr("qconv_codes", Co), 0.0) if isinstance(d, ChannelScale) else (None, float(d))
+        rtail = (None, None, None, 0.0, 0.0, 0, 0)
+        if cc is not None:
+            rtail = (None, rargs[1], *grid(cc.delta), *rargs[3:])
+        elif residual is not None:
+            rtail = (rargs[0], None, None, 0.0, 0.0, 0, 0)
+        form = 2 if getattr(prepared, "wide", False) else int(
+            QCONV_CENTRED and getattr(prepared, "centred", False))
+        call("ssq_qconv_i8_codes_chq_fwd", *args, *vecs, int(relu), form, *grid(out_delta),
+             float(out_zp), olo, ohi, _vp(out), _vp(bad), *rtail, stream_of(out))
+        return out
     epi = (*vecs, int(relu), float(out_delta), float(out_zp), olo, ohi, _vp(out), _vp(bad), *rargs)
     if splits is not None and int(splits) != 1:
         fn, ws, tail = _qconv_split("qconv_codes", prepared, groups, form, splits, workspace,
@@ -2630,6 +2725,11 @@ def epilogue_codes(y, bias, gamma, phi, relu, out_delta, out_zp, out_bits, out_s
     held, vecs = _channel_vecs("epilogue_codes", Cc, bias, gamma, phi, per="channel")
     out = torch.empty((N, H, W, query("ssq_qinfer_cpad", Cc)), dtype=torch.int8, device=y.device)
     olo, ohi = qrange(out_bits, out_sym)
+    if isinstance(out_delta, ChannelScale):
+        call("ssq_epilogue_codes_chq_fwd", yp, *vecs, N, Cc, H, W, int(relu),
+             out_delta.ptr("epilogue_codes", Cc), float(out_zp), olo, ohi, _vp(out), _vp(bad),
+             stream_of(out))
+        return out
     call("ssq_epilogue_codes_fwd", yp, *vecs, N, Cc, H, W, int(relu),
          float(out_delta), float(out_zp), olo, ohi, _vp(out), _vp(bad), stream_of(out))
     return out

@@ -116,10 +116,17 @@ class IntPlan:
         o = edge.grid
         self.calls += 1
         edge.calls += 1
+        # a per-channel grid on the output or on a code residual: the one-kernel form (the split-K
+        # emitters take scalar grids; reported at plan time, _unsplit_shifted)
+        rc = getattr(residual, '_ssq_codes', None)
+        split = self.splitk and not (isinstance(o.delta, K.ChannelScale) or (
+            rc is not None and isinstance(rc.delta, K.ChannelScale)))
+        if self.splitk and not split:
+            self.splits = 1
         codes = K.qconv_codes(x, self.prepared, self.scale, self.stride, self.padding, bias=bias,
                               gamma=gamma, phi=phi, relu=relu, out_delta=o.delta, out_zp=o.zp,
                               out_bits=o.n_bits, out_sym=o.sym, residual=residual, **self._operand,
-                              **(self._splits(x) if self.splitk else {}))
+                              **(self._splits(x) if split else {}))
         N, H, W, _ = codes.shape
         return K.carried(codes, (N, self.prepared.shape[0], H, W), *o)
 
@@ -135,20 +142,26 @@ def _hooked(*mods):
     return any(m._forward_hooks or m._forward_pre_hooks for m in mods)
 
 
-def can_emit(m, q, own, x=None):
+def can_emit(m, q, own, x=None, act_shift=False):
     """Layer `m` can leave as codes of act quantizer `q`: its own (`own`; the layer then has
     act quantization of its own), or its block's, whose tail `m` then is with neither activation
     nor act quantizer of its own.  Its epilogue is one the kernels apply (a conv, no SE module, a
     known activation: epilogue_fusable) and `q` one they apply (fusable_act_quantizer).  `x`: the
     input at run time; None at plan time, where the weight stands in for it and `q`'s values
-    must be ones a plan can hold (_input_reason)."""
+    must be ones a plan can hold (_input_reason; `act_shift`: the plan's flag).  A hard shifted
+    act quantizer (shifted_act_quantizer) is one the per-channel kernels apply: an edge onto one
+    exists only under a plan installed with `act_shift`."""
     if own == m.disable_act_quant or not (own or isinstance(m.activation_function, StraightThrough)):
         return False
-    if x is None and _input_reason(q)[0] is None:
+    if x is None and _input_reason(q, act_shift)[0] is None:
         return False
     x = m.weight if x is None else x
-    return (isinstance(x, torch.Tensor) and m.epilogue_fusable(x)
-            and fusable_act_quantizer(q, True) is not None)
+    if not (isinstance(x, torch.Tensor) and m.epilogue_fusable(x)):
+        return False
+    if fusable_act_quantizer(q, True) is not None:
+        return True
+    # (the grouped and depthwise emitters, K25 / K26, take scalar grids only)
+    return shifted_act_quantizer(q) is not None and m.fwd_kwargs.get("groups", 1) == 1
 
 
 def readers_refuse(q, readers, source, around, watched):
@@ -645,11 +658,51 @@ def _trace_inputs(qnn, sample, pools=False, heads=()):
     return source
 
 
-def _input_reason(q):
+def shifted_act_quantizer(q):
+    """The act quantizer `q` if it is one the per-channel kernels (*_chq) apply: a hard
+    ChannelQuantAct 'shiftFeature' (hard_targets and shiftedDone) with a scalar device delta and
+    zero point and no hooks, else None."""
+    if not (isinstance(q, ChannelQuantAct) and q.opt_mode == "shiftFeature" and q.hard_targets
+            and q.shiftedDone and q.alpha is not None):
+        return None
+    if q.delta is None or q.delta.numel() != 1 or q.zero_point.numel() != 1 or not q.delta.is_cuda:
+        return None
+    return None if q._forward_hooks or q._forward_pre_hooks else q
+
+
+def _shifted_grid(q):
+    """_input_reason for a shifted act quantizer under `act_shift`: the grid is
+    K.ActQuant(K.ChannelScale, zp, n_bits, False) -- the clamp is [0, 2^n - 1] whatever `sym` says
+     -- whose ChannelScale holds d[c] = fp32(delta * s_k(c)), base = delta and `fold` =
+    (L, k_a[C] int32): the integer grid of the targets (K.actshift_grid), which the consumer
+    multiplies into its weight operand."""
+    if shifted_act_quantizer(q) is None:
+        return None, ("input is a soft per-channel shifted act quantizer (ChannelQuantAct "
+                      "'shiftFeature' without hard targets, or hooked): refused, as soft weights are")
+    delta, zp = float(q.delta.detach().float()), float(q.zero_point.detach().float())
+    if not (delta > 0.0 and delta != float("inf")):
+        return None, "input act quantizer's delta is not positive and finite"
+    if zp != round(zp) or not 0 <= zp <= 255:
+        return None, f"input act quantizer's zero point {zp} is not an integer in [0, 255]"
+    if q.n_bits < 2:
+        return None, "activation bits below 2"
+    grid = K.actshift_grid(delta, q.shiftTarget)
+    if grid is None:
+        return None, (f"input is a per-channel shifted act quantizer whose targets {list(q.shiftTarget)} "
+                      f"lie on no integer grid k / L, L <= {K.ACTSHIFT_MAX_L}")
+    idx = q.shift_index()
+    fold = (grid[0], torch.tensor(grid[1], dtype=torch.int32)[idx.cpu()])
+    return K.ActQuant(K.ChannelScale(q.get_delta().reshape(-1), delta, fold), zp, q.n_bits, False), None
+
+
+def _input_reason(q, act_shift=False):
     if q is None:
         return None, "input is not the direct output of an act quantizer"
     if isinstance(q, ChannelQuantAct) and q.opt_mode == "shiftFeature":
-        # (the follow-up, DESIGN.md section 8: fold s[ci] into the consumer's per-ci grid, L = 2)
+        if act_shift:
+            return _shifted_grid(q)
+        # (enable_integer_inference(..., act_shift=True) plans them: DESIGN 4, "Shifted
+        # activations on codes")
         return None, ("input is a per-channel shifted act quantizer (ChannelQuantAct "
                       "'shiftFeature'): the integer route does not cover shifted activations")
     if type(q) is not UniformAffineQuantizer or not q.inited or q.delta is None:
@@ -690,8 +743,17 @@ def _weight_codes(m, colscale=False, per_ci=False):
 def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
                              carry_stem=False, carry_head=False, colscale=False, splitk=False,
                              per_ci=False, wide=False, fused_stem=False, image_u8=None,
-                             wide_all=False):
+                             wide_all=False, act_shift=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
+    `act_shift` (off: nothing changes, a layer behind a shifted act quantizer is refused): also
+    plan dense layers whose input comes from a hard ChannelQuantAct 'shiftFeature' whose targets
+    lie on an integer grid k / L (K.actshift_grid).  The input codes lie on each channel's own
+    scale d[ci] = fp32(delta * s_k(ci)) (K.ChannelScale; the *_chq kernels), k_a[ci] multiplies the
+    layer's integer weight operand -- a plain weight becomes a column-scaled one, a scaled one
+    takes k * k_a and L_w * L_a (beyond int8 the wide blob, with `wide`) -- and scale[co] =
+    fp32(fp32(delta * d1[co]) / fp32(L)).  Pair, tail and stem edges may emit onto such a
+    quantizer; grouped and depthwise layers, the split-K emitters, K31 / K32 and the pooling head
+    do not, and are reported ("Shifted activations on codes").
     `sample` is one input batch (any batch size) for the planning forward, run in the model's
     current quantization state with weight and act quantization expected on.  `grouped`: also
     plan grouped and depthwise convs (K24-K26); off, they are reported as refused.  `carry`:
@@ -751,6 +813,7 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     if not layers:
         return {}
     qnn._int_edges = []
+    qnn._int_act_shift = bool(act_shift)
     heads = head_edges(qnn) if carry_head else []
     source = _trace_inputs(qnn, sample, pools=carry_stem, heads=heads)
     head_fc = {fc: pool for _, pool, fc in heads}
@@ -787,7 +850,7 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         if not (m.use_weight_quant and m.use_act_quant):
             report[name] = "weight and act quantization are not both on"
             continue
-        act, why = _input_reason(source[m])
+        act, why = _input_reason(source[m], act_shift)
         if act is None:
             report[name] = why
             continue
@@ -834,6 +897,29 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
             L, kcol = grid
             if L == 1 and int(kcol.max()) == 1:
                 kcol = None                     # all ones: a plain weight, the plain K22 blob
+        shifted = isinstance(act.delta, K.ChannelScale)
+        if shifted and (groups != 1 or m in head_fc):
+            report[name] = ("input is a per-channel shifted act quantizer: " +
+                            ("the grouped and depthwise kernels (K25 / K26) read a scalar act grid"
+                             if groups != 1 else
+                             "the pooling head (K29 / K30) sums codes of one scalar grid"))
+            continue
+        if shifted:
+            # k_a[ci] into the operand: a plain weight becomes a column-scaled one
+            La, ka = act.delta.fold
+            RS = m.weight[0, 0].numel() if m.weight.dim() == 4 else 1
+            if kfac is not None:
+                kfac = torch.as_tensor(kfac).reshape(-1, len(ka)).to(torch.int64) * ka.view(1, -1)
+            elif kcol is not None:
+                kcol = torch.as_tensor(kcol).reshape(-1).to(torch.int64) * ka.repeat_interleave(RS)
+            elif La != 1 or int(ka.max()) != 1:
+                kcol = ka.repeat_interleave(RS).to(torch.int64)
+            L = L * La
+            if L > max_l or (kcol is not None and int(kcol.max()) > K.QWIDE_MAX) or (
+                    kfac is not None and int(kfac.max()) > K.QWIDE_MAX):
+                report[name] = (f"shifted act grid folded into the weight's leaves the operand's "
+                                f"grid (L = {L} > {max_l}, or a factor above {K.QWIDE_MAX})")
+                continue
         scaled = kcol is not None or kfac is not None
         if scaled and m in head_fc and not wide_all:
             report[name] = ((f"weight has a column scale ({f['kind']})" if kcol is not None else
@@ -862,7 +948,8 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
             continue
         # s[co] = fp32(delta_a * d1[co]): one fp32 product of the two stored fp32 values (per
         # (co, ci): of delta_a and the grid's base[co])
-        scale = (torch.full((1,), act.delta, dtype=torch.float32, device=dev)
+        scale = (torch.full((1,), act.delta.base if shifted else act.delta, dtype=torch.float32,
+                            device=dev)
                  * d1.detach().reshape(-1).float()).contiguous()
         scale0 = scale
         if scaled:
@@ -880,6 +967,8 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         _plan_block_carry(qnn, source)
     if carry_stem:
         _plan_stem_carry(qnn, source)
+    if splitk and act_shift:
+        _unsplit_shifted(qnn)
     if fused_stem:
         _fuse_stems(qnn)
     if image_u8 is not None:
@@ -906,7 +995,7 @@ def _plan_carry(qnn, source):
     for blk in qnn.modules():
         for prod, cons in blk.interior_chain() if isinstance(blk, BaseQuantBlock) else ():
             q = prod.act_quantizer
-            if (prod._int_plan is not None and can_emit(prod, q, True)
+            if (prod._int_plan is not None and can_emit(prod, q, True, act_shift=qnn._int_act_shift)
                     and readers_refuse(q, [cons], source, (), (prod, cons)) is None):
                 _install(qnn, PairEdge(prod, cons))
 
@@ -961,14 +1050,14 @@ def edge_readers(successor):
     return entry, None, False
 
 
-def _emitting_tail(blk):
+def _emitting_tail(blk, act_shift=False):
     """The block's last conv when its tail can emit codes onto the block's act quantizer: a
     planned dense conv under `can_emit`, the block's activation one the kernel applies."""
     last = blk.last_conv()
     plan = None if last is None else last._int_plan
     if plan is None or plan.kind != "dense" or act_code(blk.activation_function) is None:
         return None
-    return last if can_emit(last, blk.act_quantizer, False) else None
+    return last if can_emit(last, blk.act_quantizer, False, act_shift=act_shift) else None
 
 
 def _plan_block_carry(qnn, source):
@@ -977,7 +1066,7 @@ def _plan_block_carry(qnn, source):
     decoded path: without `grouped=True` a MobileNetV2 / RegNetX block has one in its middle,
     and such a block keeps its fp32 edges."""
     for blk, succ in block_edges(qnn):
-        last = _emitting_tail(blk)
+        last = _emitting_tail(blk, qnn._int_act_shift)
         entry, readers, _ = edge_readers(succ)
         if last is not None and readers_refuse(blk.act_quantizer, readers, source, (blk, entry),
                                                (blk, last, succ, entry, *(readers or ()))) is None:
@@ -1023,10 +1112,30 @@ def _plan_stem_carry(qnn, source):
     for prod, pools, succ in stem_edges(qnn):
         q = prod.act_quantizer
         entry, readers, _ = edge_readers(succ)
-        if (prod._int_plan is None and can_emit(prod, q, True)
+        if (prod._int_plan is None and can_emit(prod, q, True, act_shift=qnn._int_act_shift)
                 and readers_refuse(q, readers, source, (entry,),
                                    (prod, succ, entry, *pools, *(readers or ()))) is None):
             _install(qnn, StemEdge(prod, pools, succ, entry, readers))
+
+
+UNSPLIT_SHIFTED = ("emits on K23's one-kernel form: the split-K emitters take per-tensor act grids, "
+                   "and its output or its code residual lies on a per-channel shifted one")
+
+
+def _unsplit_shifted(qnn):
+    """splitk with act_shift: `qnn._int_unsplit`, {layer name: UNSPLIT_SHIFTED} for every emitting
+    layer planned with `splitk` whose edge's grid, or whose block's input grid (an identity
+    residual's), is per-channel -- IntPlan.run_codes keeps such a forward unsplit; the layer's
+    fp32 form still asks the rule.  `integer_report` lists them under "unsplit"."""
+    names = {m: n for n, m in qnn.named_modules()}
+    qnn._int_unsplit = {}
+    for e in _edges(qnn, PairEdge) + _edges(qnn, TailEdge):
+        m = e.last if isinstance(e, TailEdge) else e.at
+        grids = [e.grid]
+        if isinstance(e, TailEdge):
+            grids += [r._int_plan.grid for r in edge_readers(e.at)[1] or () if r._int_plan is not None]
+        if m._int_plan.splitk and any(isinstance(g.delta, K.ChannelScale) for g in grids):
+            qnn._int_unsplit[names[m]] = UNSPLIT_SHIFTED
 
 
 def _fuse_stems(qnn):
@@ -1037,6 +1146,8 @@ def _fuse_stems(qnn):
     for e in _edges(qnn, StemEdge):
         m = e.at
         why = fused_stem_reason(m)
+        if isinstance(e.grid.delta, K.ChannelScale):
+            why = "K31 does not emit onto a per-channel shifted act grid (K27 does)"
         if why is None:
             kw = m.fwd_kwargs
             e.fuse(K.stem_weight_prepare(m._weight_bias()[0]), tuple(kw["stride"]),
@@ -1071,6 +1182,8 @@ def _u8_stems(qnn, image_u8):
         Co, Ci = int(m.weight.shape[0]), int(m.weight.shape[1])
         norm = _u8_norm(image_u8, Ci, m.weight.device)
         why = u8_stem_reason(m)
+        if isinstance(e.grid.delta, K.ChannelScale):
+            why = "K32 does not emit onto a per-channel shifted act grid (K27 does)"
         prep = tables = None
         if why is None:
             try:
@@ -1159,14 +1272,15 @@ def _plan_head_carry(qnn, source, heads, report, sample):
             continue        # refused by the weight / input rules: the report says why
         q, why = prod.act_quantizer, None
         if isinstance(prod, BaseQuantBlock):
-            last = _emitting_tail(prod)
+            last = _emitting_tail(prod, qnn._int_act_shift)
             if last is None:
                 why = "the last block's tail cannot emit codes"
             elif prod._int_tail is not None:
                 why = "the last block already emits codes for another edge"
             watched = (prod, pool, fc, last)
         else:
-            if prod._int_plan is None or not can_emit(prod, q, True) or prod._int_plan.carry is not None:
+            if (prod._int_plan is None or not can_emit(prod, q, True, act_shift=qnn._int_act_shift)
+                    or prod._int_plan.carry is not None):
                 why = "the last layer cannot emit codes"
             watched = (prod, pool, fc)
         if why is None:
@@ -1200,6 +1314,7 @@ def disable_integer_inference(qnn):
     qnn._int_edges, qnn._int_counter = [], None
     qnn._int_fused_stem = None
     qnn._int_u8 = None
+    qnn._int_unsplit = None
     # every enable passes here: a captured forward (IntegerGraph) of the previous plan is stale
     qnn._int_epoch = getattr(qnn, "_int_epoch", 0) + 1
 
@@ -1208,13 +1323,16 @@ def integer_report(qnn):
     """{"off_grid": elements seen by the integer layers that were not on their act quantizer's
     grid (0 = every integer layer computed what the decoded path computes up to fp32
     rounding), "calls": {layer name: forwards taken on the integer route}}.  Reads one device
-    word (the only sync of the integer path).  Under a plan installed with `image_u8`, also
+    word (the only sync of the integer path).  Under `splitk` with `act_shift`, also "unsplit":
+    {layer name: why its emitting forward keeps the one-kernel form}.  Under a plan installed with `image_u8`, also
     "u8_form": {producer name: {staging form: forwards of a uint8 batch on K32}}, the forms
     K.stem_u8_view_form's: "planar", "interleaved", "generic" read in place, "copied" made dense
     first; they sum to stem_carry_report's "u8"."""
     counter = getattr(qnn, "_int_counter", None)
     rep = {"off_grid": int(counter.item()) if counter is not None else 0,
            "calls": {n: p.calls for n, p in _plans(qnn)}}
+    if getattr(qnn, "_int_unsplit", None):
+        rep["unsplit"] = dict(qnn._int_unsplit)     # splitk with act_shift: {layer: why}
     if getattr(qnn, "_int_u8", None) is not None:
         names = {m: n for n, m in qnn.named_modules()}
         rep["u8_form"] = {names[e.at]: dict(e.u8_form) for e in _edges(qnn, StemEdge)}
