@@ -24,8 +24,11 @@ module inputs, not residual adds or pooling:
   carry_blocks  TailEdge  a block's last conv with the residual add, the block's activation and
                           act quantizer in its kernel, read by the next block (`block_edges`)
   carry_stem    StemEdge  the stem conv's fp32 epilogue leaves as codes, max-pools behind it pool
-                          the codes, the first block reads them (`stem_edges`); with
-                          `fused_stem` the conv itself emits them (K31, fp32 MFMA)
+                          the codes, the first block reads them (`stem_edges`).  The edge holds
+                          its routes as a list, asked in order by its one `emit` (StemRoute):
+                          K32, a uint8 image on the int8 MFMA (`image_u8`); K31, the conv itself
+                          emits (`fused_stem`, fp32 MFMA); K27, the fp32 conv's epilogue emits
+                          (every edge).  A route a forward's input does not take counts why
   carry_head    HeadEdge  the global average pool sums the last producer's codes and the fc runs
                           on the sums (`head_edges`); its logits are a function of the codes
                           alone, not bit for bit those of an fp32 mean and GEMM
@@ -132,10 +135,11 @@ class IntPlan:
 
     def run(self, x):
         self.calls += 1
-        if self.splitk:
-            return K.qconv(x, self.prepared, self.scale, self.stride, self.padding, **self._operand,
-                           **self._splits(x))
-        return K.qconv(x, self.prepared, self.scale, self.stride, self.padding, **self._operand)
+        return K.qconv(x, self.prepared, self.scale, self.stride, self.padding, **self._operand,
+                       **(self._splits(x) if self.splitk else {}))
+
+    def cells(self):
+        return [(self, "calls", None, False)]
 
 
 def _hooked(*mods):
@@ -177,6 +181,25 @@ def readers_refuse(q, readers, source, around, watched):
     return "hook" if _hooked(*watched) else None
 
 
+def _read(cells):
+    """The counts of `Edge.cells` (an absent entry counts 0)."""
+    return [getattr(o, a) if k is None else getattr(o, a).get(k, 0) for o, a, k, _ in cells]
+
+
+def _write(cells, counts):
+    for (o, a, k, keep), v in zip(cells, counts):
+        if k is None:
+            setattr(o, a, v)
+        elif v or keep:
+            getattr(o, a)[k] = v
+        else:
+            getattr(o, a).pop(k, None)
+
+
+def _add(cells, by):
+    _write(cells, [v + d for v, d in zip(_read(cells), by)])
+
+
 class Edge:
     """One carried tensor of the installed plan: `readers`, the QuantModules whose planned
     operand the codes are; `grid`, the act quantizer the codes lie on, as the readers' plans
@@ -190,6 +213,7 @@ class Edge:
         self.at, self.readers, self.pools = at, list(readers), list(pools)
         self.grid = self.readers[0]._int_plan.grid
         self._watched, self._marks = list(dict.fromkeys(watched)), list(marks)
+        self.pooled = {}
         self.reset()
 
     def watched(self):
@@ -215,9 +239,15 @@ class Edge:
                 return False
         return True
 
+    def cells(self):
+        """The forward counters the edge owns, one (owner, attribute, key, keep) each: key None, the
+        plain count `owner.attribute`; else the entry `key` of the {key: count} there, which is not
+        listed at 0 unless `keep`.  `reset` and IntegerGraph go by this list alone."""
+        return [(self, "calls", None, False)] + [(self, "pooled", m, True) for m in self.pools]
+
     def reset(self):
-        self.calls = 0
-        self.pooled = {m: 0 for m in self.pools}
+        cells = self.cells()
+        _write(cells, [0] * len(cells))
         if self.emitter is not None:
             self.emitter.reset()
 
@@ -283,143 +313,125 @@ class TailEdge(Edge):
 
 
 class StemEdge(Edge):
-    """The stem's carried output (carry_stem): the producing conv stays on the fp32 route (its
-    input is an unquantized image), its epilogue emits, the pools pool the codes (a max-pool
-    commutes with the decode, which is non-decreasing in the code) and the successor's readers
-    behind its `entry` take them."""
+    """The stem's carried output (carry_stem): the producing conv's input is an unquantized image,
+    so it stays off the integer route and leaves as codes by one of the edge's `routes`, the pools
+    pool the codes (a max-pool commutes with the decode, which is non-decreasing in the code) and
+    the successor's readers behind its `entry` take them.  `routes`: the StemRoutes in the order
+    `emit` asks them, K32, K31, K27 -- every edge has K27; `fused_stem` and `image_u8` add the
+    other two (`add_route`)."""
 
     def __init__(self, producer, pools, successor, entry, readers):
+        self.routes = [K27Route()]
         super().__init__(producer, readers, [producer, successor, *pools, entry, *readers],
                          [(m, "_int_stem") for m in (producer, *pools)], pools)
         self.successor, self.entry = successor, entry
         self.counter = readers[0]._int_plan.counter
 
+    def add_route(self, route):
+        self.routes = sorted(self.routes + [route], key=lambda r: r.order)
+        self.reset()
+        return route
+
+    def route(self, name):
+        """The edge's route of that name ("K32", "K31", "K27"), None without one."""
+        return next((r for r in self.routes if r.name == name), None)
+
     def live(self):
         return super().live() and all(m._plan() is not None for m in self.pools)
 
+    def carries(self, x):
+        """The edge is live and its producer can emit for the input `x`."""
+        return self.live() and can_emit(self.at, self.at.act_quantizer, True, x)
+
+    def cells(self):
+        return super().cells() + [c for r in self.routes for c in r.cells()]
+
     def emit(self, x):
-        """The conv on its fp32 route, then K.epilogue_codes."""
-        m = self.at
-        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 4
-                and self.live() and can_emit(m, m.act_quantizer, True, x)):
-            return None
-        out, bias = m.forward_raw(x)
-        gamma, phi = m.affine()
-        self.calls += 1
-        codes = K.epilogue_codes(out, bias, gamma, phi, m.act_code(), *self.grid, self.counter)
-        return K.carried(codes, tuple(out.shape), *self.grid)
+        """QuantModule.forward's question: the forward as carried codes, by the first route that
+        takes `x`.  When none does: None, or -- a route that declined `x` passed another tensor on
+        (a uint8 batch, normalised on the device) -- that untagged fp32 tensor, with which the
+        module's fp32 forward goes on."""
+        given = x
+        for r in self.routes:
+            why, how = r.asks(self, x)
+            if why is None:
+                m = self.at
+                gamma, phi = m.affine()
+                self.calls += 1
+                r.taken += 1
+                codes = r.launch(self, x, how, (gamma, phi, m.act_code(), *self.grid, self.counter))
+                N, H, W, _ = codes.shape
+                return K.carried(codes, (N, m.weight.shape[0], H, W), *self.grid)
+            if why is not SKIP:
+                r.declined[why] = r.declined.get(why, 0) + 1
+                x = r.passes_on(x)
+        return None if x is given else x
 
-    # fused_stem: `fuse` replaces `emit` on this instance; an edge planned without it has neither
-    # attribute below and runs the method above
-    def fuse(self, blob, stride, padding):
-        """From now on the conv itself emits (K31) wherever `stem_fused_takes` lets it."""
+
+SKIP = object()     # StemRoute.asks: an input the route has nothing to say about
+
+
+class StemRoute:
+    """One way a stem edge's conv leaves as codes.  `why`: what keeps the route off this edge
+    altogether (plan time; None: it is on it).  `asks(edge, x)` -> (why not, how): None when the
+    route takes this forward's input (`how` goes to `launch`); one of `reasons`, or `why`, which
+    `emit` counts before it asks the next route about `passes_on(x)`; SKIP, nothing counted.
+    `launch(edge, x, how, epi)`: the codes (N, H, W, Cpad), `epi` the kernels' common arguments
+    behind the bias (gamma, phi, relu, the grid, the off-grid counter).  Counters: `taken`, the
+    forwards the route emitted, and `declined`, {reason: forwards}: a reason at 0 is not listed,
+    except `why`."""
+    name, order, reasons = None, None, ()
+
+    def __init__(self, why=None):
+        self.why, self.taken, self.declined = why, 0, {}
+
+    def cells(self):
+        whys = self.reasons + (() if self.why is None else (self.why,))
+        return [(self, "taken", None, False)] + [(self, "declined", w, w == self.why) for w in whys]
+
+    def passes_on(self, x):
+        return x
+
+
+class K27Route(StemRoute):
+    """The conv on its fp32 route, then K.epilogue_codes."""
+    name, order = "K27", 2
+
+    def asks(self, edge, x):
+        fp32 = isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 4
+        return (None if fp32 and edge.carries(x) else SKIP), None
+
+    def launch(self, edge, x, how, epi):
+        out, bias = edge.at.forward_raw(x)
+        return K.epilogue_codes(out, bias, *epi)
+
+
+class K31Route(StemRoute):
+    """fused_stem: K.stem_conv_codes, conv, epilogue and act quantizer in one kernel wherever
+    `stem_fused_takes` lets it; an input or a shape K31 is not to take goes the K27 way, counted
+    by reason.  `blob`: K.stem_weight_prepare of the producer's hard weight."""
+    name, order = "K31", 1
+    reasons = ("input is not a 4-D device tensor", "non-contiguous / non-fp32 input",
+               "shape rule: K27 is faster here (SSQ_STEM_FUSED=1 overrides)")
+
+    def __init__(self, why, blob=None, stride=None, padding=None):
+        super().__init__(why)
         self.blob, self.stride, self.padding = blob, stride, padding
-        self.fused, self.unfused = 0, {}
-        self.emit = self.emit_fused
 
-    def emit_fused(self, x):
-        """K.stem_conv_codes: conv, epilogue and act quantizer in one kernel; an input or a
-        shape K31 is not to take goes the K27 way, counted by reason."""
-        m = self.at
-        why = None
+    def asks(self, edge, x):
+        if self.why is not None:
+            return SKIP, None
         if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_cuda):
-            why = "input is not a 4-D device tensor"
-        elif x.dtype != torch.float32 or not x.is_contiguous():
-            why = "non-contiguous / non-fp32 input"
-        elif not stem_fused_takes(self.blob.shape, x.shape, self.stride, self.padding):
-            why = "shape rule: K27 is faster here (SSQ_STEM_FUSED=1 overrides)"
-        if why is None and not (self.live() and can_emit(m, m.act_quantizer, True, x)):
-            return None
-        if why is not None:
-            self.unfused[why] = self.unfused.get(why, 0) + 1
-            return StemEdge.emit(self, x)
-        gamma, phi = m.affine()
-        self.calls += 1
-        self.fused += 1
-        codes = K.stem_conv_codes(x, self.blob, m.bias, gamma, phi, m.act_code(), *self.grid,
-                                  self.counter, stride=self.stride, padding=self.padding)
-        N, H, W, _ = codes.shape
-        return K.carried(codes, (N, self.blob.shape[0], H, W), *self.grid)
+            return self.reasons[0], None
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            return self.reasons[1], None
+        if not stem_fused_takes(self.blob.shape, x.shape, self.stride, self.padding):
+            return self.reasons[2], None
+        return (None if edge.carries(x) else SKIP), None
 
-    # image_u8: `take_u8` puts `emit_u8` in front of whichever emit the edge has; an edge planned
-    # without it has none of the attributes below
-    def take_u8(self, norm, why, prepared=None, tables=None, stride=None, padding=None):
-        """From now on a uint8 image goes to K32 wherever `stem_u8_takes` lets it; `why`: what
-        keeps this edge's conv off K32 altogether (`u8_stem_reason`), its uint8 batches are then
-        normalised (`norm`: mean, std as (1, Ci, 1, 1) device tensors) for the fp32 emit."""
-        self.u8_norm, self.u8_why = norm, why
-        self.u8_blob, self.u8_tables, self.u8_geo = prepared, tables, (stride, padding)
-        self.u8, self.un_u8 = 0, ({} if why is None else {why: 0})
-        self.u8_form = {}               # {staging form: forwards on K32} (K.stem_u8_view_form)
-        self._emit_f32, self._u8_declined = self.emit, False
-        self.emit = self.emit_u8
-
-    def emit_u8(self, x):
-        """K.stem_conv_u8_codes on a uint8 image: conv, epilogue and act quantizer in one kernel on
-        the int8 MFMA; an fp32 input takes the edge's fp32 emit untouched, a uint8 input K32 is
-        not to take is normalised on the device and takes it too, counted by reason.  A view that is
-        not dense NCHW (an HWC batch as `hwc.permute(0, 3, 1, 2)`, an RGBA batch's first three
-        channels, a crop of a larger frame) is read in place where `stem_u8_takes` lets its staging
-        form, copied dense for K32 under SSQ_STEM_U8_STRIDED=0, and otherwise normalised as before;
-        the K32 forwards are counted by form (`u8_form`)."""
-        if not (isinstance(x, torch.Tensor) and x.dtype == torch.uint8):
-            # the normalised batch of the branch below, back through the module's forward: its
-            # fp32 emit has already declined it
-            return None if self._u8_declined else self._emit_f32(x)
-        m = self.at
-        why = self.u8_why
-        if why is None:
-            if not (x.dim() == 4 and x.is_cuda):
-                why = U8_NOT_4D
-            else:
-                takes = stem_u8_takes(self.u8_blob.shape, x.shape, *self.u8_geo)
-                # a view reaches K32 only where K32 takes the shape at all: elsewhere it keeps the
-                # reason it had
-                form = "planar" if x.is_contiguous() else None
-                if form is None and takes:
-                    form = stem_u8_view_route(K.stem_u8_view_form(x), self.u8_blob.shape, x.shape,
-                                              *self.u8_geo)
-                if form is None:
-                    why = (U8_NHWC if x.is_contiguous(memory_format=torch.channels_last)
-                           else U8_STRIDED)
-                elif not takes:
-                    why = U8_SHAPE_RULE
-                elif not (self.live() and can_emit(m, m.act_quantizer, True, x)):
-                    why = U8_NOT_LIVE
-        if why is not None:
-            self.un_u8[why] = self.un_u8.get(why, 0) + 1
-            # contiguous first (a quarter of the fp32 copy's bytes): the fp32 emit's own rules then
-            # see the layout K31 takes
-            xf = normalise_u8(x.contiguous(), *self.u8_norm)
-            out = self._emit_f32(xf)
-            if out is not None:
-                return out
-            self._u8_declined = True        # the fp32 emit is asked once per forward
-            try:
-                return m.forward(xf)
-            finally:
-                self._u8_declined = False
-        gamma, phi = m.affine()
-        self.calls += 1
-        self.u8 += 1
-        if form == "copied":
-            x = x.contiguous()
-        self.u8_form[form] = self.u8_form.get(form, 0) + 1
-        stride, padding = self.u8_geo
-        codes = K.stem_conv_u8_codes(x, self.u8_blob, *self.u8_tables, m.bias, gamma, phi,
-                                     m.act_code(), *self.grid, self.counter, stride=stride,
-                                     padding=padding)
-        N, H, W, _ = codes.shape
-        return K.carried(codes, (N, self.u8_blob.shape[0], H, W), *self.grid)
-
-    def reset(self):
-        super().reset()
-        if "fused" in self.__dict__:
-            self.fused, self.unfused = 0, {}
-        if "u8" in self.__dict__:
-            self.u8, self.un_u8 = 0, ({} if self.u8_why is None else {self.u8_why: 0})
-            self.u8_form = {}
-
+    def launch(self, edge, x, how, epi):
+        return K.stem_conv_codes(x, self.blob, edge.at.bias, *epi, stride=self.stride,
+                                 padding=self.padding)
 
 # what keeps one uint8 forward of an edge that takes K32 off it (`un_u8`'s per-forward reasons)
 U8_NOT_4D = "input is not a 4-D device tensor"
@@ -429,6 +441,58 @@ U8_NOT_LIVE = "the stem edge does not carry in this state"
 U8_FORWARD_REASONS = (U8_NOT_4D, U8_NHWC, U8_STRIDED, U8_SHAPE_RULE, U8_NOT_LIVE)
 # how a K32 forward staged its image (`u8_form`): K.stem_u8_view_form's
 U8_FORMS = ("planar", "interleaved", "generic", "copied")
+
+
+class K32Route(StemRoute):
+    """image_u8: K.stem_conv_u8_codes on a uint8 image, conv, epilogue and act quantizer in one
+    kernel on the int8 MFMA, wherever `stem_u8_takes` lets it; an fp32 input is not its to judge, a
+    uint8 input K32 is not to take is normalised on the device (`norm`: mean, std as (1, Ci, 1, 1)
+    device tensors) for the routes behind, counted by reason -- every uint8 batch of an edge whose
+    conv K32 cannot run at all (`why`: `u8_stem_reason`) is.  A view that is
+    not dense NCHW (an HWC batch as `hwc.permute(0, 3, 1, 2)`, an RGBA batch's first three
+    channels, a crop of a larger frame) is read in place where `stem_u8_takes` lets its staging
+    form, copied dense for K32 under SSQ_STEM_U8_STRIDED=0, and otherwise normalised as before;
+    the K32 forwards are counted by form (`forms`: {staging form: forwards}, K.stem_u8_view_form)."""
+    name, order, reasons = "K32", 0, U8_FORWARD_REASONS
+
+    def __init__(self, why, norm, blob=None, tables=None, stride=None, padding=None):
+        super().__init__(why)
+        self.norm, self.blob, self.tables, self.geo = norm, blob, tables, (stride, padding)
+        self.forms = {}
+
+    def cells(self):
+        return super().cells() + [(self, "forms", f, False) for f in U8_FORMS]
+
+    def asks(self, edge, x):
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.uint8):
+            return SKIP, None
+        if self.why is not None:
+            return self.why, None
+        if not (x.dim() == 4 and x.is_cuda):
+            return U8_NOT_4D, None
+        takes = stem_u8_takes(self.blob.shape, x.shape, *self.geo)
+        # a view reaches K32 only where K32 takes the shape at all: elsewhere it keeps the reason
+        # it had
+        form = "planar" if x.is_contiguous() else None
+        if form is None and takes:
+            form = stem_u8_view_route(K.stem_u8_view_form(x), self.blob.shape, x.shape, *self.geo)
+        if form is None:
+            return (U8_NHWC if x.is_contiguous(memory_format=torch.channels_last)
+                    else U8_STRIDED), None
+        if not takes:
+            return U8_SHAPE_RULE, None
+        return (None if edge.carries(x) else U8_NOT_LIVE), form
+
+    def passes_on(self, x):
+        # contiguous first (a quarter of the fp32 copy's bytes): the fp32 routes' own rules then
+        # see the layout K31 takes
+        return normalise_u8(x.contiguous(), *self.norm)
+
+    def launch(self, edge, x, form, epi):
+        self.forms[form] = self.forms.get(form, 0) + 1
+        stride, padding = self.geo
+        return K.stem_conv_u8_codes(x.contiguous() if form == "copied" else x, self.blob,
+                                    *self.tables, edge.at.bias, *epi, stride=stride, padding=padding)
 
 
 def normalise_u8(u, mean, std):
@@ -442,14 +506,7 @@ def u8_stem_reason(m, fields=None):
     F.conv2d inside ssq_stem_conv_u8_fwd's geometry (K.stem_u8_geometry_reason), no forward hook
     on it, and -- `fields`, the hard weight's dequant fields -- a weight without a column scale
     whose zero points are integer codes."""
-    if m.fwd_func is not F.conv2d:
-        return "not a conv"
-    kw = m.fwd_kwargs
-    if isinstance(kw.get("padding", 0), str):
-        return "padding given as a string"
-    Co, Ci, R, S = (int(v) for v in m.weight.shape)
-    why = K.stem_u8_geometry_reason(Co, Ci, R, S, kw.get("stride", 1), kw.get("padding", 0),
-                                    kw.get("dilation", 1), int(kw.get("groups", 1)))
+    why = _stem_conv_reason(m, K.stem_u8_geometry_reason, "padding given as a string")
     if why is not None:
         return why
     if _hooked(m):
@@ -522,17 +579,23 @@ def stem_u8_view_route(form, wshape, xshape, stride, padding):
     return form if stem_u8_takes(wshape, xshape, stride, padding, form) else None
 
 
-def fused_stem_reason(m):
-    """Why K31 cannot run QuantModule `m`'s conv, None when it can: an ungrouped F.conv2d inside
-    ssq_stem_conv_fwd's geometry (K.stem_geometry_reason)."""
+def _stem_conv_reason(m, geometry_reason, string_padding):
+    """What `fused_stem_reason` and `u8_stem_reason` ask first: a conv, its padding numbers
+    (`string_padding`: the reason otherwise), its geometry one `geometry_reason` takes."""
     if m.fwd_func is not F.conv2d:
         return "not a conv"
     kw = m.fwd_kwargs
     if isinstance(kw.get("padding", 0), str):
-        return "geometry (padding given as a string)"
+        return string_padding
     Co, Ci, R, S = (int(v) for v in m.weight.shape)
-    return K.stem_geometry_reason(Co, Ci, R, S, kw.get("stride", 1), kw.get("padding", 0),
-                                  kw.get("dilation", 1), int(kw.get("groups", 1)))
+    return geometry_reason(Co, Ci, R, S, kw.get("stride", 1), kw.get("padding", 0),
+                           kw.get("dilation", 1), int(kw.get("groups", 1)))
+
+
+def fused_stem_reason(m):
+    """Why K31 cannot run QuantModule `m`'s conv, None when it can: an ungrouped F.conv2d inside
+    ssq_stem_conv_fwd's geometry (K.stem_geometry_reason)."""
+    return _stem_conv_reason(m, K.stem_geometry_reason, "geometry (padding given as a string)")
 
 
 def stem_fused_takes(wshape, xshape, stride, padding):
@@ -571,14 +634,16 @@ class HeadEdge(Edge):
                                          K.head_scale(p.head_grid[0], p.head_grid[1] * pc.HW))
         self.calls += 1
         p.calls += 1
-        if p.head_grid is None:
-            return K.qlinear_pooled(hi, pc.lo, pc.sp, p.prepared, sh, pc.HW, g.zp, g.n_bits, g.sym)
         return K.qlinear_pooled(hi, pc.lo, pc.sp, p.prepared, sh, pc.HW, g.zp, g.n_bits, g.sym,
-                                wide_all=True)
+                                **({} if p.head_grid is None else {"wide_all": True}))
 
 
 def _layers(qnn):
     return [(n, m) for n, m in qnn.named_modules() if isinstance(m, QuantModule)]
+
+
+def _names(qnn):
+    return {m: n for n, m in qnn.named_modules()}
 
 
 def _act_quantizers(qnn):
@@ -739,67 +804,244 @@ def _weight_codes(m, colscale=False, per_ci=False):
     return packed, f
 
 
+# enable_integer_inference's keywords that decide a layer's plan (its docstring says what each does)
+PlanFlags = collections.namedtuple("PlanFlags", "grouped colscale per_ci wide wide_all act_shift splitk",
+                                   defaults=(False,) * 7)
+
+
+def _geometry(m, grouped):
+    """(stride, padding, groups) of a layer inside the integer kernels' geometry, or the reason it
+    is not: a conv (square stride and padding, no dilation, at most 7x7; grouped only with
+    `grouped`) or a linear, K = Ci*R*S <= 65536, weight and act quantization on."""
+    if m.fwd_func is F.conv2d:
+        kw = m.fwd_kwargs
+        groups = int(kw["groups"])
+        if groups != 1 and not grouped:
+            return f"grouped conv (groups = {kw['groups']})"
+        st, pd, dl = kw["stride"], kw["padding"], kw["dilation"]
+        if isinstance(pd, str) or st[0] != st[1] or pd[0] != pd[1] or tuple(dl) != (1, 1):
+            return "stride / padding not square or dilation != 1"
+        if max(m.weight.shape[2:]) > 7:
+            return "kernel larger than 7x7"
+        geo = int(st[0]), int(pd[0]), groups
+    elif m.fwd_func is F.linear:
+        geo = 1, 0, 1
+    else:
+        return "neither a conv nor a linear"
+    if m.weight[0].numel() > 65536:
+        return "K = Ci*R*S exceeds 65536"
+    if not (m.use_weight_quant and m.use_act_quant):
+        return "weight and act quantization are not both on"
+    return geo
+
+
+def weight_operand(f, shape, groups, act, pooled_fc, flags):
+    """The integer weight operand of a layer, from host values alone (CPU tensors and Python ints;
+    no module, no device): `f`, the hard weight's dequant fields; `shape`, `groups`, the weight's;
+    `act`, the input grid (K.ActQuant); `pooled_fc`, the layer is a carried head's fc; `flags`,
+    PlanFlags.  -> (kcol, kfac, L, d1), or the reason the layer is refused: the operand is
+    (q - z) * kcol[j] (column factors, j = (ci, r, s)) or (q - z) * kfac[co, ci], both None for a
+    plain weight, and the layer scale is fp32(fp32(delta_a * d1[co]) / fp32(L)).  A column scale
+    or a per-(co, ci) scale goes onto its grid (K.colscale_grid, K.perci_grid; with `wide`, the
+    wide operand's limits where the int8 ones fail), all ones or every k = L collapse to a plain
+    weight, and a shifted input grid's k_a[ci] / L_a is multiplied in."""
+    if f["per_ci"] and not flags.per_ci:
+        return f"weight scale is per (co, ci) ({f['kind']})"
+    if f["per_ci"] and f["col_scale"] is not None:
+        return f"weight has both a column scale and a per-(co, ci) scale ({f['kind']})"
+    kcol, kfac, L, d1 = None, None, 1, f["scale"]
+    max_l = K.QWIDE_MAX_L if flags.wide else K.COLSCALE_MAX_L
+    if f["per_ci"]:
+        Co, Cig = int(shape[0]), int(shape[1])
+        grid = K.perci_grid(f["scale"], Co, Cig)
+        if grid is None and flags.wide:
+            grid = K.perci_grid(f["scale"], Co, Cig, K.QWIDE_MAX)
+        if grid is None:
+            return (f"weight scale is per (co, ci) ({f['kind']}) and not on an integer "
+                    f"grid base[co] * k / L, L <= {max_l}")
+        L, d1, kfac = grid
+        if K.perci_plain(grid):
+            kfac, L = None, 1               # every k = L: a plain weight with scale = base
+    elif f["col_scale"] is not None:
+        grid = K.colscale_grid(f["col_scale"]) if flags.colscale else None
+        if grid is None and flags.colscale and flags.wide:
+            grid = K.colscale_grid(f["col_scale"], K.QWIDE_MAX_L, K.QWIDE_MAX)
+        if grid is None:
+            return f"weight has a column scale ({f['kind']})" + (
+                f" that is not on an integer grid k / L, L <= {max_l}" if flags.colscale else "")
+        L, kcol = grid
+        if L == 1 and int(kcol.max()) == 1:
+            kcol = None                     # all ones: a plain weight, the plain K22 blob
+    if isinstance(act.delta, K.ChannelScale):
+        if groups != 1 or pooled_fc:
+            return ("input is a per-channel shifted act quantizer: " +
+                    ("the grouped and depthwise kernels (K25 / K26) read a scalar act grid"
+                     if groups != 1 else
+                     "the pooling head (K29 / K30) sums codes of one scalar grid"))
+        # k_a[ci] into the operand: a plain weight becomes a column-scaled one
+        La, ka = act.delta.fold
+        RS = int(shape[2]) * int(shape[3]) if len(shape) == 4 else 1
+        if kfac is not None:
+            kfac = torch.as_tensor(kfac).reshape(-1, len(ka)).to(torch.int64) * ka.view(1, -1)
+        elif kcol is not None:
+            kcol = torch.as_tensor(kcol).reshape(-1).to(torch.int64) * ka.repeat_interleave(RS)
+        elif La != 1 or int(ka.max()) != 1:
+            kcol = ka.repeat_interleave(RS).to(torch.int64)
+        L = L * La
+        if L > max_l or (kcol is not None and int(kcol.max()) > K.QWIDE_MAX) or (
+                kfac is not None and int(kfac.max()) > K.QWIDE_MAX):
+            return (f"shifted act grid folded into the weight's leaves the operand's "
+                    f"grid (L = {L} > {max_l}, or a factor above {K.QWIDE_MAX})")
+    if (kcol is not None or kfac is not None) and pooled_fc and not flags.wide_all:
+        return ((f"weight has a column scale ({f['kind']})" if kcol is not None else
+                 f"weight scale is per (co, ci) ({f['kind']})")
+                + ": the pooled-operand fc takes plain weights only")
+    return kcol, kfac, L, d1
+
+
+def _bad_operand(prep, scaled, narrow_grouped):
+    """What a prepared blob's `bad` word says; `narrow_grouped`: a scaled grouped layer planned with
+    `wide` but without `wide_all`."""
+    if not scaled:
+        return "weight zero point is not an integer code"
+    return (("scaled weight (q - z) * k leaves the wide operand (|m| > 16319), or a "
+             "zero point is not an integer code" if prep.wide else
+             "scaled weight (q - z) * k leaves int8 (|m| > 127), or a zero point "
+             "is not an integer code")
+            + ("; the wide operand is dense only, the grouped kernels (K26) read int8"
+               if narrow_grouped else ""))
+
+
+def _layer_scale(act, d1, L, scaled, dev):
+    """(scale, undivided): s[co] = fp32(delta_a * d1[co]), one fp32 product of the two stored
+    fp32 values (per (co, ci): of delta_a and the grid's base[co]; a shifted input grid: of its
+    base), and for a scaled weight ... / fp32(L), the grid's common denominator, one more rounding
+    (DESIGN 4); `undivided`, the product alone, is what a scaled pooled fc keeps (`head_grid`)."""
+    delta = act.delta.base if isinstance(act.delta, K.ChannelScale) else act.delta
+    s0 = (torch.full((1,), delta, dtype=torch.float32, device=dev)
+          * d1.detach().reshape(-1).float().to(dev)).contiguous()
+    if not scaled:
+        return s0, s0
+    return (s0 / torch.full((1,), float(L), dtype=torch.float32, device=dev)).contiguous(), s0
+
+
+def _plan_layer(m, q, pooled_hw, flags, counter):
+    """The IntPlan of layer `m`, or the reason of the first rule that refuses it.  `q`: the act
+    quantizer whose output its traced input is; `pooled_hw`: the pooled plane's H * W when `m` is a
+    carried head's fc, else None."""
+    geo = _geometry(m, flags.grouped)
+    if isinstance(geo, str):
+        return geo
+    stride, padding, groups = geo
+    act, why = _input_reason(q, flags.act_shift)
+    if act is None:
+        return why
+    if pooled_hw is not None and not 1 <= pooled_hw <= K.HEAD_MAX_HW:
+        return f"pooled plane H*W exceeds {K.HEAD_MAX_HW} (int8 digit range)"
+    if not m.weight.is_cuda:
+        return "weight is not on the HIP device"
+    try:
+        packed, f = _weight_codes(m, flags.colscale, flags.per_ci)
+    except TypeError as e:
+        return str(e)
+    operand = weight_operand(f, tuple(m.weight.shape), groups, act, pooled_hw is not None, flags)
+    if isinstance(operand, str):
+        return operand
+    kcol, kfac, L, d1 = operand
+    scaled = kcol is not None or kfac is not None
+    if not scaled:
+        prep = K.qweight_prepare(packed, tuple(m.weight.shape), f["zero_point"], f["n_bits"],
+                                 f["qmin"], groups=groups)
+    else:
+        prep = K.qweight_prepare_scaled(packed, tuple(m.weight.shape), f["zero_point"],
+                                        f["n_bits"], f["qmin"], groups=groups, kcol=kcol,
+                                        kfac=kfac, wide=flags.wide, wide_all=flags.wide_all)
+    if prep is None:
+        return ("scaled weight's grid leaves int8 (k > 127): the wide operand is dense "
+                "only, the grouped kernels (K26) read int8")
+    if int(prep.bad.item()):
+        return _bad_operand(prep, scaled, scaled and flags.wide and groups != 1 and not flags.wide_all)
+    scale, undivided = _layer_scale(act, d1, L, scaled, counter.device)
+    plan = IntPlan(prep, scale, act, stride, padding, counter)
+    if scaled and pooled_hw is not None:
+        plan.head_grid = (undivided, int(L))
+    # a wide layer is never asked to split: K23's split form holds one accumulator set
+    plan.splitk = flags.splitk and plan.kind == "dense" and not prep.wide
+    return plan
+
+
 @torch.no_grad()
 def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_blocks=False,
                              carry_stem=False, carry_head=False, colscale=False, splitk=False,
                              per_ci=False, wide=False, fused_stem=False, image_u8=None,
                              wide_all=False, act_shift=False):
     """Plan and install the integer route; returns {QuantModule name: "int8" | reason}.
-    `act_shift` (off: nothing changes, a layer behind a shifted act quantizer is refused): also
-    plan dense layers whose input comes from a hard ChannelQuantAct 'shiftFeature' whose targets
-    lie on an integer grid k / L (K.actshift_grid).  The input codes lie on each channel's own
-    scale d[ci] = fp32(delta * s_k(ci)) (K.ChannelScale; the *_chq kernels), k_a[ci] multiplies the
-    layer's integer weight operand -- a plain weight becomes a column-scaled one, a scaled one
-    takes k * k_a and L_w * L_a (beyond int8 the wide blob, with `wide`) -- and scale[co] =
-    fp32(fp32(delta * d1[co]) / fp32(L)).  Pair, tail and stem edges may emit onto such a
-    quantizer; grouped and depthwise layers, the split-K emitters, K31 / K32 and the pooling head
-    do not, and are reported ("Shifted activations on codes").
-    `sample` is one input batch (any batch size) for the planning forward, run in the model's
-    current quantization state with weight and act quantization expected on.  `grouped`: also
-    plan grouped and depthwise convs (K24-K26); off, they are reported as refused.  `carry`:
-    also carry int8 codes between the integer layers of a block (`carry_report`).
+
+    `sample`: one input batch (any batch size) for the planning forward, run in the model's
+        current quantization state with weight and act quantization expected on.
+    `grouped`: also plan grouped and depthwise convs (K24-K26); off, they are reported as refused.
+    `carry`: also carry int8 codes between the integer layers of a block (`carry_report`).
     `carry_blocks`: `carry`, and the codes also cross block tails and block boundaries
-    (`block_carry_report`).  `carry_stem`: `carry_blocks`, and the stem's epilogue emits codes
-    that a max-pool behind it pools as codes (`stem_carry_report`); the layers behind such a
-    pool are planned too.  `carry_head`: `carry_stem`, and the global average pool in front of
-    the fc sums the codes and the fc runs on the sums (`head_carry_report`); the fc is planned
-    for that operand only, and reported with the reason when the head edge is not installed.
+        (`block_carry_report`).
+    `carry_stem`: `carry_blocks`, and the stem's epilogue emits codes that a max-pool behind it
+        pools as codes (`stem_carry_report`); the layers behind such a pool are planned too.
+    `carry_head`: `carry_stem`, and the global average pool in front of the fc sums the codes and
+        the fc runs on the sums (`head_carry_report`); the fc is planned for that operand only, and
+        reported with the reason when the head edge is not installed.
     `colscale`: also plan column-scaled weights (ChannelQuantMSE) whose column scale lies on an
-    integer grid k[j] / L, L <= 127 (K.colscale_grid), with the centred integer (q - z) * k[j] as
-    the int8 operand; off, they are reported as refused.  An all-ones column scale is
-    a plain weight and takes the plain route.  `splitk`: a dense layer asks the host rule
-    K.qconv_splits on every forward and takes K23's split-K form where it returns Z > 1
-    (bit-identical; `split_report`); off, no layer does.  `per_ci`: also plan weights whose scale
-    is per (co, ci) (ChannelQuant's shifted scale) and lies on a grid base[co] * k / L
-    (K.perci_grid), with (q - z) * k[co, ci] as the operand and
-    scale[co] = fp32(fp32(delta_a * base[co]) / fp32(L)); off, they are reported as refused.  Every
-    k equal to L is a plain weight.  `wide`: a scaled weight of either kind whose operand leaves
-    int8 (|m| > 127, or a grid beyond 127) runs as two int8 digits, |m| <= 16319, L <= 1024, on
-    K23's wide forms (dense layers only: never split along K, not the grouped kernels, not the
-    pooled-operand fc); off, it is refused as leaving int8.  A weight with both a column scale and
-    a per-(co, ci) scale is refused.  `wide_all` (with `wide`; nothing changes without it): the
-    wide operand also on grouped convs (K26, two digit planes), on column-scaled depthwise convs
-    (K25, its int32 blob with |m| <= 16319) and on the pooled-operand fc (K30), and a scaled fc is
-    planned under `carry_head` at all -- on its centred int8 blob where (q - z) * k fits int8, on
-    the dense wide blob beyond, with sh[co] = fp32(fp32(delta_a * base[co]) / fp32(L * HW)).
-    SSQ_QCONV_WIDE=auto|1 governs these blobs as it does the dense one.
-    `fused_stem`: on every stem edge that `carry_stem` (or `carry_head`) installs and whose producer is an ungrouped conv inside K31's geometry
-    (`fused_stem_reason`), the conv itself emits the codes (K.stem_conv_codes, a weight blob
-    prepared here from the producer's hard weight) instead of the fp32 conv + K27; it plans no
-    edge of its own, and `stem_carry_report` then also counts the fused forwards and names what
-    kept an edge or a forward on K27.  The stem's fp32 values are K31's fma chain, not the
-    library conv's: the logits are those of the `carry_stem` route up to that summation order.
+        integer grid k[j] / L, L <= 127 (K.colscale_grid), with the centred integer (q - z) * k[j]
+        as the int8 operand; off, they are reported as refused.  An all-ones column
+        scale is a plain weight and takes the plain route.
+    `splitk`: a dense layer asks the host rule K.qconv_splits on every forward and takes K23's
+        split-K form where it returns Z > 1 (bit-identical; `split_report`); off, no layer does.
+    `per_ci`: also plan weights whose scale is per (co, ci) (ChannelQuant's shifted scale) and lies
+        on a grid base[co] * k / L (K.perci_grid), with (q - z) * k[co, ci] as the operand and
+        scale[co] = fp32(fp32(delta_a * base[co]) / fp32(L)); off, they are reported as refused.
+        Every k equal to L is a plain weight.  A weight with both a column scale and a
+        per-(co, ci) scale is refused.
+    `wide`: a scaled weight of either kind whose operand leaves int8 (|m| > 127, or a grid beyond
+        127) runs as two int8 digits, |m| <= 16319, L <= 1024, on K23's wide forms (dense layers
+        only: never split along K, not the grouped kernels, not the pooled-operand fc); off, it is
+        refused as leaving int8.
+    `wide_all` (with `wide`; nothing changes without it): the wide operand also on grouped convs
+        (K26, two digit planes), on column-scaled depthwise convs (K25, its int32 blob with
+        |m| <= 16319) and on the pooled-operand fc (K30), and a scaled fc is planned under
+        `carry_head` at all -- on its centred int8 blob where (q - z) * k fits int8, on the dense
+        wide blob beyond, with sh[co] = fp32(fp32(delta_a * base[co]) / fp32(L * HW)).
+        SSQ_QCONV_WIDE=auto|1 governs these blobs as it does the dense one.
+    `fused_stem`: on every stem edge that `carry_stem` (or `carry_head`) installs and whose
+        producer is an ungrouped conv inside K31's geometry (`fused_stem_reason`), the conv itself
+        emits the codes (K.stem_conv_codes, a weight blob prepared here from the producer's hard
+        weight) instead of the fp32 conv + K27; it plans no edge of its own, and
+        `stem_carry_report` then also counts the fused forwards and names what kept an edge or a
+        forward on K27.  The stem's fp32 values are K31's fma chain, not the library conv's: the
+        logits are those of the `carry_stem` route up to that summation order.
     `image_u8` = (mean, std), the loader's per-channel normalisation: a forward whose input is a
-    uint8 image batch (N, Ci, H, W; x = (u/255 - mean)/std) runs the stem conv on the int8 MFMA
-    (K32, K.stem_conv_u8_codes; DESIGN 4 "uint8 stem (K32)") on every stem edge whose producer
-    passes `u8_stem_reason`, its blob and tables prepared here.  It plans no edge of its own and
-    needs `carry_stem` and an installed stem edge (ValueError without either, the plan removed); it is independent of `fused_stem`.  An fp32 input
-    takes exactly the path it takes without the keyword; a uint8 input K32 does not take is
-    normalised on the device and takes that path too.  `stem_carry_report` then also counts the
-    K32 forwards ("u8") and the normalised ones by reason ("un_u8").  The stem codes of a uint8
-    forward are K32's own contract's, not pinned to the fp32 routes'; `sample` may be uint8."""
+        uint8 image batch (N, Ci, H, W; x = (u/255 - mean)/std) runs the stem conv on the int8 MFMA
+        (K32, K.stem_conv_u8_codes; DESIGN 4 "uint8 stem (K32)") on every stem edge whose producer
+        passes `u8_stem_reason`, its blob and tables prepared here.  It plans no edge of its own
+        and needs `carry_stem` and an installed stem edge (ValueError without either, the plan
+        removed); it is independent of `fused_stem`.  An fp32 input takes exactly the path it takes
+        without the keyword; a uint8 input K32 does not take is normalised on the device and takes
+        that path too.  `stem_carry_report` then also counts the K32 forwards ("u8") and the
+        normalised ones by reason ("un_u8").  The stem codes of a uint8 forward are K32's own
+        contract's, not pinned to the fp32 routes'; `sample` may be uint8.
+    `act_shift` (off: nothing changes, a layer behind a shifted act quantizer is refused): also
+        plan dense layers whose input comes from a hard ChannelQuantAct 'shiftFeature' whose
+        targets lie on an integer grid k / L (K.actshift_grid).  The input codes lie on each
+        channel's own scale d[ci] = fp32(delta * s_k(ci)) (K.ChannelScale; the *_chq kernels),
+        k_a[ci] multiplies the layer's integer weight operand -- a plain weight becomes a
+        column-scaled one, a scaled one takes k * k_a and L_w * L_a (beyond int8 the wide blob,
+        with `wide`) -- and scale[co] = fp32(fp32(delta * d1[co]) / fp32(L)).  Pair, tail and stem
+        edges may emit onto such a quantizer; grouped and depthwise layers, the split-K emitters,
+        K31 / K32 and the pooling head do not, and are reported ("Shifted activations on
+        codes").
+
+    A layer's plan is the first of these that fails, or an IntPlan (`_plan_layer`): reached by the
+    planning forward, the geometry (`_geometry`), the input grid (`_input_reason`), the weight
+    operand (`weight_operand`), the prepared blob, the scale (`_layer_scale`)."""
     carry_stem = carry_stem or carry_head
-    wide_all = bool(wide and wide_all)
+    flags = PlanFlags(grouped, colscale, per_ci, wide, bool(wide and wide_all), act_shift, bool(splitk))
     if image_u8 is not None:
         if not carry_stem:
             raise ValueError("enable_integer_inference: image_u8 needs a stem edge (carry_stem or "
@@ -817,150 +1059,18 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
     heads = head_edges(qnn) if carry_head else []
     source = _trace_inputs(qnn, sample, pools=carry_stem, heads=heads)
     head_fc = {fc: pool for _, pool, fc in heads}
-    dev = layers[0][1].weight.device
-    counter = torch.zeros(1, dtype=torch.int32, device=dev)
+    counter = torch.zeros(1, dtype=torch.int32, device=layers[0][1].weight.device)
     qnn._int_counter = counter
     report = {}
     for name, m in layers:
         if m not in source:
             report[name] = "not reached by the planning forward"
             continue
-        if m.fwd_func is F.conv2d:
-            kw = m.fwd_kwargs
-            groups = int(kw["groups"])
-            if groups != 1 and not grouped:
-                report[name] = f"grouped conv (groups = {kw['groups']})"
-                continue
-            st, pd, dl = kw["stride"], kw["padding"], kw["dilation"]
-            if isinstance(pd, str) or st[0] != st[1] or pd[0] != pd[1] or tuple(dl) != (1, 1):
-                report[name] = "stride / padding not square or dilation != 1"
-                continue
-            if max(m.weight.shape[2:]) > 7:
-                report[name] = "kernel larger than 7x7"
-                continue
-            stride, padding = int(st[0]), int(pd[0])
-        elif m.fwd_func is F.linear:
-            stride, padding, groups = 1, 0, 1
-        else:
-            report[name] = "neither a conv nor a linear"
-            continue
-        if m.weight[0].numel() > 65536:
-            report[name] = "K = Ci*R*S exceeds 65536"
-            continue
-        if not (m.use_weight_quant and m.use_act_quant):
-            report[name] = "weight and act quantization are not both on"
-            continue
-        act, why = _input_reason(source[m], act_shift)
-        if act is None:
-            report[name] = why
-            continue
-        if m in head_fc and not 1 <= source.get(head_fc[m], 0) <= K.HEAD_MAX_HW:
-            report[name] = f"pooled plane H*W exceeds {K.HEAD_MAX_HW} (int8 digit range)"
-            continue
-        if not m.weight.is_cuda:
-            report[name] = "weight is not on the HIP device"
-            continue
-        try:
-            packed, f = _weight_codes(m, colscale, per_ci)
-        except TypeError as e:
-            report[name] = str(e)
-            continue
-        if f["per_ci"] and not per_ci:
-            report[name] = f"weight scale is per (co, ci) ({f['kind']})"
-            continue
-        if f["per_ci"] and f["col_scale"] is not None:
-            report[name] = f"weight has both a column scale and a per-(co, ci) scale ({f['kind']})"
-            continue
-        kcol, kfac, L, d1 = None, None, 1, f["scale"]
-        max_l = K.QWIDE_MAX_L if wide else K.COLSCALE_MAX_L
-        if f["per_ci"]:
-            Co, Cig = int(m.weight.shape[0]), int(m.weight.shape[1])
-            grid = K.perci_grid(f["scale"], Co, Cig)
-            if grid is None and wide:
-                grid = K.perci_grid(f["scale"], Co, Cig, K.QWIDE_MAX)
-            if grid is None:
-                report[name] = (f"weight scale is per (co, ci) ({f['kind']}) and not on an integer "
-                                f"grid base[co] * k / L, L <= {max_l}")
-                continue
-            L, d1, kfac = grid
-            d1 = d1.to(dev)
-            if K.perci_plain(grid):
-                kfac, L = None, 1               # every k = L: a plain weight with scale = base
-        elif f["col_scale"] is not None:
-            grid = K.colscale_grid(f["col_scale"]) if colscale else None
-            if grid is None and colscale and wide:
-                grid = K.colscale_grid(f["col_scale"], K.QWIDE_MAX_L, K.QWIDE_MAX)
-            if grid is None:
-                report[name] = f"weight has a column scale ({f['kind']})" + (
-                    f" that is not on an integer grid k / L, L <= {max_l}" if colscale else "")
-                continue
-            L, kcol = grid
-            if L == 1 and int(kcol.max()) == 1:
-                kcol = None                     # all ones: a plain weight, the plain K22 blob
-        shifted = isinstance(act.delta, K.ChannelScale)
-        if shifted and (groups != 1 or m in head_fc):
-            report[name] = ("input is a per-channel shifted act quantizer: " +
-                            ("the grouped and depthwise kernels (K25 / K26) read a scalar act grid"
-                             if groups != 1 else
-                             "the pooling head (K29 / K30) sums codes of one scalar grid"))
-            continue
-        if shifted:
-            # k_a[ci] into the operand: a plain weight becomes a column-scaled one
-            La, ka = act.delta.fold
-            RS = m.weight[0, 0].numel() if m.weight.dim() == 4 else 1
-            if kfac is not None:
-                kfac = torch.as_tensor(kfac).reshape(-1, len(ka)).to(torch.int64) * ka.view(1, -1)
-            elif kcol is not None:
-                kcol = torch.as_tensor(kcol).reshape(-1).to(torch.int64) * ka.repeat_interleave(RS)
-            elif La != 1 or int(ka.max()) != 1:
-                kcol = ka.repeat_interleave(RS).to(torch.int64)
-            L = L * La
-            if L > max_l or (kcol is not None and int(kcol.max()) > K.QWIDE_MAX) or (
-                    kfac is not None and int(kfac.max()) > K.QWIDE_MAX):
-                report[name] = (f"shifted act grid folded into the weight's leaves the operand's "
-                                f"grid (L = {L} > {max_l}, or a factor above {K.QWIDE_MAX})")
-                continue
-        scaled = kcol is not None or kfac is not None
-        if scaled and m in head_fc and not wide_all:
-            report[name] = ((f"weight has a column scale ({f['kind']})" if kcol is not None else
-                             f"weight scale is per (co, ci) ({f['kind']})")
-                            + ": the pooled-operand fc takes plain weights only")
-            continue
-        if not scaled:
-            prep = K.qweight_prepare(packed, tuple(m.weight.shape), f["zero_point"], f["n_bits"],
-                                     f["qmin"], groups=groups)
-        else:
-            prep = K.qweight_prepare_scaled(packed, tuple(m.weight.shape), f["zero_point"],
-                                            f["n_bits"], f["qmin"], groups=groups, kcol=kcol,
-                                            kfac=kfac, wide=wide, wide_all=wide_all)
-        if prep is None:
-            report[name] = ("scaled weight's grid leaves int8 (k > 127): the wide operand is dense "
-                            "only, the grouped kernels (K26) read int8")
-            continue
-        if int(prep.bad.item()):
-            report[name] = ("weight zero point is not an integer code" if not scaled else
-                            "scaled weight (q - z) * k leaves the wide operand (|m| > 16319), or a "
-                            "zero point is not an integer code" if prep.wide else
-                            "scaled weight (q - z) * k leaves int8 (|m| > 127), or a zero point "
-                            "is not an integer code")
-            if scaled and wide and groups != 1 and not wide_all:
-                report[name] += "; the wide operand is dense only, the grouped kernels (K26) read int8"
-            continue
-        # s[co] = fp32(delta_a * d1[co]): one fp32 product of the two stored fp32 values (per
-        # (co, ci): of delta_a and the grid's base[co])
-        scale = (torch.full((1,), act.delta.base if shifted else act.delta, dtype=torch.float32,
-                            device=dev)
-                 * d1.detach().reshape(-1).float()).contiguous()
-        scale0 = scale
-        if scaled:
-            # ... / fp32(L): the grid's common denominator, one more rounding
-            scale = (scale / torch.full((1,), float(L), dtype=torch.float32, device=dev)).contiguous()
-        m._int_plan = IntPlan(prep, scale, act, stride, padding, counter)
-        if scaled and m in head_fc:
-            m._int_plan.head_grid = (scale0, int(L))
-        # a wide layer is never asked to split: K23's split form holds one accumulator set
-        m._int_plan.splitk = bool(splitk) and m._int_plan.kind == "dense" and not prep.wide
-        report[name] = INT8
+        pooled_hw = source.get(head_fc[m], 0) if m in head_fc else None
+        plan = _plan_layer(m, source[m], pooled_hw, flags, counter)
+        if isinstance(plan, IntPlan):
+            m._int_plan = plan
+        report[name] = INT8 if isinstance(plan, IntPlan) else plan
     if carry:
         _plan_carry(qnn, source)
     if carry_blocks:
@@ -1127,7 +1237,7 @@ def _unsplit_shifted(qnn):
     layer planned with `splitk` whose edge's grid, or whose block's input grid (an identity
     residual's), is per-channel -- IntPlan.run_codes keeps such a forward unsplit; the layer's
     fp32 form still asks the rule.  `integer_report` lists them under "unsplit"."""
-    names = {m: n for n, m in qnn.named_modules()}
+    names = _names(qnn)
     qnn._int_unsplit = {}
     for e in _edges(qnn, PairEdge) + _edges(qnn, TailEdge):
         m = e.last if isinstance(e, TailEdge) else e.at
@@ -1139,20 +1249,24 @@ def _unsplit_shifted(qnn):
 
 
 def _fuse_stems(qnn):
-    """fused_stem: every installed StemEdge whose producer K31 can run gets its weight blob and
-    emits through K.stem_conv_codes; `qnn._int_fused_stem`: {producer name: why not, or None}."""
-    names = {m: n for n, m in qnn.named_modules()}
+    """fused_stem: every installed StemEdge gets a K31Route, with its weight blob where the
+    producer is one K31 can run; `qnn._int_fused_stem`: {producer name: why not, or None}."""
+    names = _names(qnn)
     qnn._int_fused_stem = {}
     for e in _edges(qnn, StemEdge):
-        m = e.at
-        why = fused_stem_reason(m)
-        if isinstance(e.grid.delta, K.ChannelScale):
-            why = "K31 does not emit onto a per-channel shifted act grid (K27 does)"
-        if why is None:
-            kw = m.fwd_kwargs
-            e.fuse(K.stem_weight_prepare(m._weight_bias()[0]), tuple(kw["stride"]),
-                   tuple(kw["padding"]))
+        m, kw = e.at, e.at.fwd_kwargs
+        why = _shifted_grid_reason(e, "K31") or fused_stem_reason(m)
+        e.add_route(K31Route(why) if why is not None else
+                    K31Route(None, K.stem_weight_prepare(m._weight_bias()[0]), tuple(kw["stride"]),
+                             tuple(kw["padding"])))
         qnn._int_fused_stem[names[m]] = why
+
+
+def _shifted_grid_reason(edge, kernel):
+    """Why `kernel` (K31 / K32) is on no route of an edge whose grid is per-channel."""
+    if isinstance(edge.grid.delta, K.ChannelScale):
+        return f"{kernel} does not emit onto a per-channel shifted act grid (K27 does)"
+    return None
 
 
 def _u8_norm(image_u8, Ci, dev):
@@ -1165,11 +1279,11 @@ def _u8_norm(image_u8, Ci, dev):
 
 
 def _u8_stems(qnn, image_u8):
-    """image_u8: every installed StemEdge takes uint8 images from now on -- on K32 where its
-    producer passes `u8_stem_reason` (the blob from the hard weight's packed codes, the tables from
-    its scale and the caller's mean / std), normalised for its fp32 emit elsewhere;
+    """image_u8: every installed StemEdge gets a K32Route and takes uint8 images from now on -- on
+    K32 where its producer passes `u8_stem_reason` (the blob from the hard weight's packed codes,
+    the tables from its scale and the caller's mean / std), normalised for its fp32 routes elsewhere;
     `qnn._int_u8`: {producer name: why not, or None}."""
-    names = {m: n for n, m in qnn.named_modules()}
+    names = _names(qnn)
     stems = _edges(qnn, StemEdge)
     if not stems:
         disable_integer_inference(qnn)
@@ -1181,10 +1295,8 @@ def _u8_stems(qnn, image_u8):
         m = e.at
         Co, Ci = int(m.weight.shape[0]), int(m.weight.shape[1])
         norm = _u8_norm(image_u8, Ci, m.weight.device)
-        why = u8_stem_reason(m)
-        if isinstance(e.grid.delta, K.ChannelScale):
-            why = "K32 does not emit onto a per-channel shifted act grid (K27 does)"
-        prep = tables = None
+        why = _shifted_grid_reason(e, "K32") or u8_stem_reason(m)
+        route = None
         if why is None:
             try:
                 packed, f = _weight_codes(m, per_ci=True)
@@ -1199,10 +1311,9 @@ def _u8_stems(qnn, image_u8):
         if why is None:
             tables = K.stem_u8_tables(norm[0], norm[1], f["scale"].to(m.weight.device), Co, Ci)
             kw = m.fwd_kwargs
-            e.take_u8(norm, None, prep, tables, tuple(K._pair(kw.get("stride", 1))),
-                      tuple(K._pair(kw.get("padding", 0))))
-        else:
-            e.take_u8(norm, why)
+            route = K32Route(None, norm, prep, tables, tuple(K._pair(kw.get("stride", 1))),
+                             tuple(K._pair(kw.get("padding", 0))))
+        e.add_route(route or K32Route(why, norm))
         qnn._int_u8[names[m]] = why
 
 
@@ -1266,7 +1377,7 @@ def _plan_head_carry(qnn, source, heads, report, sample):
     and whose dry forward of `sample` under the installed plan shows the pooled digits arriving
     at the fc.  An fc whose edge is not installed loses its plan -- it is planned for pooled
     digits only -- and is reported with the reason."""
-    names = {m: n for n, m in qnn.named_modules()}
+    names = _names(qnn)
     for prod, pool, fc in heads:
         if fc._int_plan is None:
             continue        # refused by the weight / input rules: the report says why
@@ -1334,8 +1445,8 @@ def integer_report(qnn):
     if getattr(qnn, "_int_unsplit", None):
         rep["unsplit"] = dict(qnn._int_unsplit)     # splitk with act_shift: {layer: why}
     if getattr(qnn, "_int_u8", None) is not None:
-        names = {m: n for n, m in qnn.named_modules()}
-        rep["u8_form"] = {names[e.at]: dict(e.u8_form) for e in _edges(qnn, StemEdge)}
+        names = _names(qnn)
+        rep["u8_form"] = {names[e.at]: dict(e.route("K32").forms) for e in _edges(qnn, StemEdge)}
     return rep
 
 
@@ -1348,7 +1459,7 @@ def split_report(qnn):
 def carry_report(qnn):
     """{"pairs": [(producer name, consumer name), ...] the installed plan carries int8 codes
     between, "calls": {producer name: forwards that emitted codes}}; empty without a plan."""
-    names = {m: n for n, m in qnn.named_modules()}
+    names = _names(qnn)
     pairs = _edges(qnn, PairEdge)
     return {"pairs": [(names[e.at], names[e.readers[0]]) for e in pairs],
             "calls": {names[e.at]: e.calls for e in pairs}}
@@ -1359,7 +1470,7 @@ def block_carry_report(qnn):
     emit int8 codes, "calls": {block name: forwards whose tail emitted codes}, "residual":
     {block name: "none" | "fp32" | "codes", the residual operand of the emitting tail: as the
     last emitting forward had it, before one as the plan expects it}}; empty without a plan."""
-    names = {m: n for n, m in qnn.named_modules()}
+    names = _names(qnn)
     tails = _edges(qnn, TailEdge)
     fed = {e.entry for e in tails + _edges(qnn, StemEdge)}
     residual = {}
@@ -1385,18 +1496,19 @@ def stem_carry_report(qnn):
     forwards of a uint8 batch on K32} and "un_u8": {producer name: {reason: forwards whose uint8
     batch was normalised on the device for the fp32 emit}}, a producer K32 does not take at all
     (`u8_stem_reason`) listed with its reason from the start."""
-    names = {m: n for n, m in qnn.named_modules()}
+    names = _names(qnn)
     stems = _edges(qnn, StemEdge)
     rep = {"edges": [(names[e.at], [names[p] for p in e.pools], names[e.successor]) for e in stems],
            "calls": {names[e.at]: e.calls for e in stems},
            "pooled": {names[p]: k for e in stems for p, k in e.pooled.items()}}
-    why = getattr(qnn, "_int_fused_stem", None)
-    if why is not None:
-        rep["fused"] = {names[e.at]: getattr(e, "fused", 0) for e in stems}
-        rep["unfused"] = {names[e.at]: why[names[e.at]] or dict(e.unfused) for e in stems}
+    if getattr(qnn, "_int_fused_stem", None) is not None:
+        k31 = {names[e.at]: e.route("K31") for e in stems}
+        rep["fused"] = {n: r.taken for n, r in k31.items()}
+        rep["unfused"] = {n: r.why or dict(r.declined) for n, r in k31.items()}
     if getattr(qnn, "_int_u8", None) is not None:
-        rep["u8"] = {names[e.at]: e.u8 for e in stems}
-        rep["un_u8"] = {names[e.at]: dict(e.un_u8) for e in stems}
+        k32 = {names[e.at]: e.route("K32") for e in stems}
+        rep["u8"] = {n: r.taken for n, r in k32.items()}
+        rep["un_u8"] = {n: dict(r.declined) for n, r in k32.items()}
     return rep
 
 
@@ -1405,7 +1517,7 @@ def head_carry_report(qnn):
     codes along, "calls": {producer name: forwards that emitted codes for the pool}, "pooled":
     {pool name: forwards that summed codes (ssq_avgpool_i8_digits_fwd)}, "fc": {fc name: forwards
     on ssq_qlinear_pooled_fwd}}; empty without a plan."""
-    names = {m: n for n, m in qnn.named_modules()}
+    names = _names(qnn)
     heads = _edges(qnn, HeadEdge)
     return {"edges": [(names[e.producer], names[e.at], names[e.fc]) for e in heads],
             "calls": {names[e.producer]: e.emitter.calls for e in heads},
@@ -1456,41 +1568,10 @@ class IntegerGraph:
         return [k[0] for k in self._shapes]
 
     def _cells(self):
-        """The Python-side forward counters: (object, None) for `calls`, (edge, name) for a named
-        counter, (edge, (name, key)) for one entry of a named {reason: count}, (edge, pool) for
-        `pooled[pool]`."""
+        """The Python-side forward counters, as the plans and the edges list them (`Edge.cells`)."""
         qnn = self.qnn
         edges = list(qnn._int_edges) + [e.emitter for e in qnn._int_edges if e.emitter is not None]
-        cells = [(p, None) for _, p in _plans(qnn)] + [(e, None) for e in edges]
-        cells += [(e, "fused") for e in edges if "fused" in e.__dict__]   # a fused StemEdge
-        for e in edges:
-            if "u8" in e.__dict__:                                        # one that takes uint8
-                whys = U8_FORWARD_REASONS + ((e.u8_why,) if e.u8_why is not None else ())
-                cells += [(e, "u8")] + [(e, ("un_u8", w)) for w in whys]
-                cells += [(e, ("u8_form", f)) for f in U8_FORMS]
-        return cells + [(e, m) for e in edges for m in e.pools]
-
-    @staticmethod
-    def _read(cells):
-        return [o.calls if m is None else getattr(o, m) if isinstance(m, str)
-                else getattr(o, m[0]).get(m[1], 0) if isinstance(m, tuple) else o.pooled[m]
-                for o, m in cells]
-
-    @staticmethod
-    def _add(cells, by):
-        for (o, m), d in zip(cells, by):
-            if m is None:
-                o.calls += d
-            elif isinstance(m, str):
-                setattr(o, m, getattr(o, m) + d)
-            elif isinstance(m, tuple):      # a {reason: count}: a reason at 0 is not listed
-                counts, v = getattr(o, m[0]), getattr(o, m[0]).get(m[1], 0) + d
-                if v or m[1] == o.u8_why:
-                    counts[m[1]] = v
-                else:
-                    counts.pop(m[1], None)
-            else:
-                o.pooled[m] += d
+        return [c for o in [p for _, p in _plans(qnn)] + edges for c in o.cells()]
 
     @staticmethod
     def _static_like(x):
@@ -1509,7 +1590,7 @@ class IntegerGraph:
         qnn = self.qnn
         qnn.eval()
         cells = self._cells()
-        before, word = self._read(cells), qnn._int_counter.clone()
+        before, word = _read(cells), qnn._int_counter.clone()
         e = {"in": self._static_like(x), "ws": {}}
         with L.frozen_weight_cache(), K.A.workspace_scope(e["ws"]):
             side = torch.cuda.Stream(device=x.device)
@@ -1518,16 +1599,16 @@ class IntegerGraph:
                 for _ in range(2):
                     qnn(e["in"])
             torch.cuda.current_stream(x.device).wait_stream(side)
-            mid = self._read(cells)
+            mid = _read(cells)
             e["graph"] = torch.cuda.CUDAGraph()
             with torch.cuda.graph(e["graph"]):
                 e["out"] = qnn(e["in"])
             e["frozen"] = dict(L._FROZEN_W)
-        after = self._read(cells)
+        after = _read(cells)
         e["cells"], e["by"] = cells, [a - b for a, b in zip(after, mid)]
         e["residual"] = [(t, t.residual) for t in {c[0] for c in cells} if isinstance(t, TailEdge)]
         # the warm-up and the capture count as no forward: the first replay is the first
-        self._add(cells, [b - a for a, b in zip(after, before)])
+        _add(cells, [b - a for a, b in zip(after, before)])
         qnn._int_counter.copy_(word)
         return e
 
@@ -1548,7 +1629,7 @@ class IntegerGraph:
             self._shapes.move_to_end(key)
             e["in"].copy_(x)
         e["graph"].replay()
-        self._add(e["cells"], e["by"])
+        _add(e["cells"], e["by"])
         for t, kind in e["residual"]:
             t.residual = kind
         return e["out"]

@@ -452,8 +452,10 @@ class QuantModule(nn.Module):
                 return out
         elif getattr(self, '_int_stem', None) is not None:
             out = self._int_stem.emit(input)
-            if out is not None:
+            if getattr(out, '_ssq_codes', None) is not None:
                 return out
+            if out is not None:         # a uint8 batch, normalised for the fp32 forward
+                input = out
         act_q = self.use_act_quant and not self.disable_act_quant
         if self.epilogue_fusable(input):
             out, bias = self.forward_raw(input)

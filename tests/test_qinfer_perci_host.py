@@ -361,7 +361,7 @@ def test_planner_defaults_and_todays_reasons():
     from shiftedscalequantization_amd.quant import enable_integer_inference, integer
     p = inspect.signature(enable_integer_inference).parameters
     assert p["per_ci"].default is False and p["wide"].default is False
-    src = inspect.getsource(integer.enable_integer_inference)
-    assert 'f"weight scale is per (co, ci) ({f[\'kind\']})"' in src
+    # (the planner's rules that state them: the weight operand's and the prepared blob's)
+    assert 'f"weight scale is per (co, ci) ({f[\'kind\']})"' in inspect.getsource(integer.weight_operand)
     assert ('"scaled weight (q - z) * k leaves int8 (|m| > 127), or a zero point "\n'
-            '                            "is not an integer code"') in src
+            '             "is not an integer code"') in inspect.getsource(integer._bad_operand)

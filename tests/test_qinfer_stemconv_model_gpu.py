@@ -82,17 +82,19 @@ def test_fused_stem_forward(Q, net, monkeypatch):
     # the emitted bytes: K27 on K31's fp32 form
     with torch.no_grad():
         codes = edge.emit(x)
-        y = K.stem_conv(x, edge.blob, edge.stride, edge.padding)
+        k31 = edge.route("K31")
+        y = K.stem_conv(x, k31.blob, k31.stride, k31.padding)
         gamma, phi = mod.affine()
         want = K.epilogue_codes(y, mod.bias, gamma, phi, mod.act_code(), *edge.grid, edge.counter)
     assert codes.dtype == torch.int8 and codes._ssq_codes.shape == tuple(y.shape)
     assert torch.equal(codes, want) and not entered
     # K27's route for the same edge, from the library conv: recorded, not asserted
+    monkeypatch.setenv("SSQ_STEM_FUSED", "0")
     with torch.no_grad():
-        lib_codes = type(edge).emit(edge, x)
+        lib_codes = edge.emit(x)
         w = mod._weight_bias()[0]
         y_lib = mod._conv(x, w)
-        mag = K.stem_conv(x.abs(), K.stem_weight_prepare(w.abs()), edge.stride, edge.padding)
+        mag = K.stem_conv(x.abs(), K.stem_weight_prepare(w.abs()), k31.stride, k31.padding)
     assert len(entered) == 2                     # (the counter does see the unfused route)
     diff = (codes.to(torch.int32) - lib_codes.to(torch.int32)).abs()
     parity_log({"test": "int_infer_fused_stem_parity", "arch": arch, "batch": list(BATCH),
@@ -110,7 +112,8 @@ def test_everything_behind_the_stem_is_exact(Q, net, monkeypatch):
     arch, qnn, x, grouped, stem, _ = net
     Q.enable_integer_inference(qnn, x, grouped=grouped, carry_head=True, fused_stem=True)
     edge = stem_edge(qnn)
-    blob, stride, padding = edge.blob, edge.stride, edge.padding
+    k31 = edge.route("K31")
+    blob, stride, padding = k31.blob, k31.stride, k31.padding
     fused = run(qnn, x)
     Q.enable_integer_inference(qnn, x, grouped=grouped, carry_head=True, fused_stem=False)
     mod = dict(qnn.named_modules())[stem]

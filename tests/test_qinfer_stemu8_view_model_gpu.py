@@ -1,4 +1,4 @@
-"""uint8 image views in a whole model (quant/integer.py, StemEdge.emit_u8 on a view that is not
+"""uint8 image views in a whole model (quant/integer.py, the stem edge's K32 route on a view that is not
 dense NCHW): a random-init ResNet-18 restored from its packed export, on a (2, 3, 32, 32) uint8
 batch with carry_head=True.
 
