@@ -1265,6 +1265,40 @@ int ssq_qlinear_pooled_wide_fwd(const int8_t* hi, const int8_t* lo, const int32_
                                 int64_t Co, int64_t HW, float act_zero_point, int act_qmin,
                                 int act_qmax, float* y, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- per-channel act grids on grouped and depthwise convs
+ * A hard shifted-scale act quantizer's grid d[c] = fp32(delta * s_k(c)) (ssq_act_encode_chq) on
+ * K24-K26.  Read: the conv kernels take the codes as they are; the grid's integer k_a[ci] goes into
+ * the weight operand.  A grouped weight (ssq_qconv_grouped_kind 2) takes it as per-(co, ci)
+ * factors kfac[co, ci] = k_a[g(co) * Cig + ci] through ssq_qweight_prepare_grouped_perci / _wide.
+ * A depthwise weight (kind 1) has no such form:
+ *
+ * ssq_qweight_prepare_grouped_chfac: ssq_qweight_prepare_grouped_colscale for a depthwise weight
+ * with kch (device int32 [C]) beside kcol (device int32 [R*S], or null: all ones): the int32 blob
+ * holds m[tap][c] = (q - zp[c]) * kcol[tap] * kch[c].  wide = 0: every factor in [1, 127] and
+ * |m| <= 127; wide != 0: 16319 for both (K25 reads either blob).  ADDS to *bad what the colscale
+ * prepare adds, the factors and products of kch included.  SSQ_E_ARG for a weight of kind 2.
+ *
+ * ssq_qconv_i8_grouped_codes_chq_fwd: ssq_qconv_i8_grouped_codes_fwd emitting onto a per-channel
+ * output grid: out_dch (device fp32 [Co], positive and finite; null is SSQ_E_ARG) in the place of
+ * out_delta, code = clamp(round(t / out_dch[co]) + out_zero_point), the scalar epilogue otherwise.
+ * wide = 0: a blob of the int8 prepares; wide != 0: one of ssq_qweight_prepare_grouped_wide (the
+ * *_grouped_wide_codes_fwd kernel).  ADDS to *bad the NaN results and, once per launch, the
+ * out_dch entries that are no positive finite scale.  No residual operand, no split form.  No
+ * allocation, no sync, capturable. */
+int ssq_qweight_prepare_grouped_chfac(const void* packed, const float* zp, const int32_t* kcol,
+                                      const int32_t* kch, int wide, int64_t Co, int64_t Cig,
+                                      int64_t R, int64_t S, int64_t groups, int n_bits, int qmin,
+                                      void* prepared, uint32_t* bad, ssq_stream_t stream);
+int ssq_qconv_i8_grouped_codes_chq_fwd(const int8_t* codes, const void* prepared,
+                                       const float* scale, int64_t Nb, int64_t C, int64_t H,
+                                       int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride,
+                                       int64_t pad, int64_t groups, float act_zero_point,
+                                       int act_qmin, int act_qmax, const float* bias,
+                                       const float* gamma, const float* phi, int act, int wide,
+                                       const float* out_dch, float out_zero_point, int out_qmin,
+                                       int out_qmax, int8_t* out_codes, uint32_t* bad,
+                                       ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- K33 shifted-scale activations
  * ChannelQuantAct 'shiftFeature' (the evident intent of channelQuantAct.py:69-134, whose
  * own code never ran; contract in DESIGN.md section 6).  x is (N, C, HW) in NCHW order

@@ -209,6 +209,12 @@ SIGNATURES["ssq_qweight_prepare_grouped_wide"] = (_i, [_p, _p, _p, _i, _i64, _i6
 SIGNATURES["ssq_qconv_i8_grouped_wide_fwd"] = SIGNATURES["ssq_qconv_i8_grouped_fwd"]
 SIGNATURES["ssq_qconv_i8_grouped_wide_codes_fwd"] = SIGNATURES["ssq_qconv_i8_grouped_codes_fwd"]
 SIGNATURES["ssq_qlinear_pooled_wide_fwd"] = SIGNATURES["ssq_qlinear_pooled_fwd"]
+# per-channel act grids on K24-K26: a depthwise weight's per-channel factors (kcol or null, kch,
+# wide), and the grouped code emitters with (wide, out_dch) in the place of out_delta
+SIGNATURES["ssq_qweight_prepare_grouped_chfac"] = (_i, [_p, _p, _p, _p, _i, _i64, _i64, _i64, _i64, _i64,
+                                                        _i, _i, _p, _p, _p])
+SIGNATURES["ssq_qconv_i8_grouped_codes_chq_fwd"] = (_i, [_p, _p, _p] + [_i64] * 10 + [
+    _f, _i, _i, _p, _p, _p, _i, _i, _p, _f, _i, _i, _p, _p, _p])
 # the split-K convs take their parents' arguments with (splits, ws, ws_bytes) before the stream
 for _n in ("fwd", "codes_fwd", "codes_res_fwd"):
     _res, _args = SIGNATURES[f"ssq_qconv_i8_{_n}"]

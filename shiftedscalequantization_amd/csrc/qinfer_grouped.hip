@@ -37,22 +37,23 @@
 // MFMA:  I = 128 D_h + D_l + az * T[co]  in int64 (K <= 65536 keeps D_h, D_l below 2^30 and T
 // inside int32); the epilogues are K26's own, and wherever |m| <= 127 the result is K26's on the
 // centred int8 blob bit for bit.  LDS 15 360 B.
-// kind 1 holds m in its int32 blob as it stands, column factors only (a depthwise row has no
-// per-(co, ci) form): |a| * |m| < 2^9 * 2^14 keeps __mul24 exact and |I| <= 49 * 255 * 16319 < 2^31
+// kind 1 holds m in its int32 blob as it stands, with column factors and per-channel ones
+// (ssq_qweight_prepare_grouped_chfac; a depthwise row has no per-(co, ci) form):
+// |a| * |m| < 2^9 * 2^14 keeps __mul24 exact and |I| <= 49 * 255 * 16319 < 2^31 stays inside
 // the int32 accumulator, but |I| may pass 2^24, so fp32(I) may round there: that is the
 // contract's one conversion, round to nearest even, as K23's -- it is exact for the int8 blobs only.
-#include <type_traits>
-
-#include "ssq_common.h"
-#include "qinfer_epi.h"
-#include "qinfer_layout.h"
+//
+// Per-channel act grids (a hard shifted-scale act quantizer's d[c] = fp32(delta * s_k(c))).  Read:
+// the conv kernels are unchanged, the grid's integer k_a[ci] is multiplied into the operand by K24
+// (kind 2 as per-(co, ci) factors k_a[g(co) * Cig + ci], kind 1 as the per-channel factors above).
+// Emitted (ssq_qconv_i8_grouped_codes_chq_fwd): the CHQ instantiations of the two kernel templates
+// (qinfer_grouped_kernels.h, built in qinfer_grouped_chq.hip) are the code-emitting kernels with the
+// output scale out_dch[co] for the scalar one, fetched once per chunk (K25) or per lane (K26).
+#include "qinfer_grouped_kernels.h"
 #include "qinfer_prepare.h"
 
 namespace ssq {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kGRow = 80;    // LDS row stride in bytes (64 + 16), as K23
 constexpr uint32_t kDwBlocks = 2048;   // workgroups K25 aims for: 8 per CU
 
 // ---------------------------------------------------------------- K24 weight prepare
@@ -63,12 +64,16 @@ constexpr uint32_t kDwBlocks = 2048;   // workgroups K25 aims for: 8 per CU
 //
 // depthwise: one thread per (tap, padded channel) of K25's centred int32 blob [R*S][Cp],
 // wc = q - z_w[c]; COLSCALE multiplies it by kcol[tap], factors and |m| up to `lim` (127, or
-// kQWideMax for the wide form)
-template <bool COLSCALE>
+// kQWideMax for the wide form).  CHFAC (ssq_qweight_prepare_grouped_chfac): a per-channel factor
+// kch[c] beside it, m = (q - z_w[c]) * kcol[tap] * kch[c] (kcol null: 1) -- a shifted act grid's
+// k_a[c], which a depthwise row cannot take as a per-(co, ci) factor; each factor and each product
+// is held to `lim` (factors are >= 1, so a product that leaves it on the way has left it at the end)
+template <bool COLSCALE, bool CHFAC = false>
 __global__ __launch_bounds__(kBlock) void qweight_prepare_dw_kernel(
     const uint8_t* __restrict__ packed, const float* __restrict__ zp,
-    const int32_t* __restrict__ kcol, int lim, int bs, int qmin, uint32_t C, uint32_t RS,
-    uint32_t Cp, FastDiv div_cp, int32_t* __restrict__ wc, uint32_t* __restrict__ bad) {
+    const int32_t* __restrict__ kcol, const int32_t* __restrict__ kch, int lim, int bs, int qmin,
+    uint32_t C, uint32_t RS, uint32_t Cp, FastDiv div_cp, int32_t* __restrict__ wc,
+    uint32_t* __restrict__ bad) {
   const uint32_t total = RS * Cp;
   uint32_t nbad = 0;
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
@@ -82,6 +87,7 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_dw_kernel(
       if (!ok && tap == 0) ++nbad;   // counted once per channel
       v = (int)packed_code(packed, (size_t)c * RS + tap, bs) + qmin - z;
       if constexpr (COLSCALE) v = qscaled(v, kcol[tap], lim, nbad);
+      if constexpr (CHFAC) v = qscaled(v, kch[c], lim, nbad);   // |v| <= lim, kch <= lim: < 2^31
     }
     wc[i] = v;
   }
@@ -155,296 +161,6 @@ __global__ __launch_bounds__(kBlock) void qweight_prepare_grouped_kernel(
   }
 }
 
-// ---------------------------------------------------------------- K25 depthwise direct conv
-struct QDwGeo {
-  uint32_t M, P, OW, H, W, C, Cp, R, S, nch, per;   // per: chunks per workgroup (blockIdx.y)
-  int stride, pad, az, padv;
-  FastDiv div_p, div_ow;
-};
-
-// KS: the square kernel size the s loop is unrolled for (its loads fly together); 0: any R x S
-// CODES: the code-emitting epilogue (qinfer_epi.h), `y` then being the QEpi: the thread's 16
-// channels of its pixel leave as one 16-B store of the NHWC codes instead of 16 fp32 stores.
-template <int KS, bool CODES>
-__global__ __launch_bounds__(kBlock) void qconv_dw_kernel(
-    const int8_t* __restrict__ act, const int32_t* __restrict__ wc, const float* __restrict__ scale,
-    QDwGeo g, typename std::conditional<CODES, QEpi, float* __restrict__>::type y) {
-  const uint32_t pix0 = blockIdx.x * blockDim.x + threadIdx.x;
-  if (!CODES && pix0 >= g.M) return;
-  // CODES: a thread past M stays for the wave's count, computing pixel 0 and storing nothing
-  const bool pval = pix0 < g.M;
-  const uint32_t pix = pval ? pix0 : 0u;
-  uint32_t nbad = 0;
-  const uint32_t n = fdiv(pix, g.div_p);
-  const uint32_t p = pix - n * g.P;
-  const uint32_t oh = fdiv(p, g.div_ow);
-  const uint32_t ow = p - oh * g.OW;
-  const int ih0 = (int)oh * g.stride - g.pad, iw0 = (int)ow * g.stride - g.pad;
-  const uint32_t R = KS ? KS : g.R, S = KS ? KS : g.S;
-  const int pv = (g.padv & 0xff) * 0x01010101;
-  const i32x4 padfill = {pv, pv, pv, pv};
-  const uint32_t ch0 = blockIdx.y * g.per;
-  const uint32_t ch1 = min(ch0 + g.per, g.nch);
-  for (uint32_t ch = ch0; ch < ch1; ++ch) {
-    // byte offsets fit 32 bits: the host checked Nb*H*W*Cp < 2^31
-    const int8_t* abase = act + (n * g.H * g.W * g.Cp + ch * 16);
-    int acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0;
-#pragma unroll 1
-    for (uint32_t r = 0; r < R; ++r) {
-      const int ih = ih0 + (int)r;
-      const bool rok = (uint32_t)ih < g.H;
-      const int8_t* arow = abase + (uint32_t)(rok ? ih : 0) * g.W * g.Cp;
-      const int32_t* wr = wc + (r * S * g.Cp + ch * 16);   // wave-uniform
-#pragma unroll
-      for (uint32_t s = 0; s < S; ++s) {
-        const int iw = iw0 + (int)s;
-        const bool ok = rok && (uint32_t)iw < g.W;
-        i32x4 v = *(const i32x4*)(arow + (uint32_t)(ok ? iw : 0) * g.Cp);   // in bounds either way
-        if (!ok) v = padfill;
-        const int32_t* wt = wr + s * g.Cp;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint32_t word = (uint32_t)v[q];
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            const int a = ((int)(word << (24 - 8 * b)) >> 24) + g.az;   // sign-extended byte + az
-            acc[q * 4 + b] += __mul24(a, wt[q * 4 + b]);   // |a| < 2^9, |wc| < 2^14
-          }
-        }
-      }
-    }
-    if constexpr (CODES) {
-      const QEpi& e = y;
-      i32x4 o;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        int c4[4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const uint32_t c = ch * 16 + q * 4 + b;
-          c4[b] = (pval && c < g.C) ? qepi_code((float)acc[q * 4 + b], c, scale, e, nbad) : 0;
-        }
-        o[q] = qepi_pack4(c4[0], c4[1], c4[2], c4[3]);
-      }
-      if (pval) *(i32x4*)(e.out + (size_t)pix * g.Cp + ch * 16) = o;
-    } else {
-      float* yo = y + (size_t)((n * g.C + ch * 16) * g.P + p);   // Nb*OH*OW*Co < 2^31, so is this
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const uint32_t c = ch * 16 + j;
-        if (c < g.C) yo[(size_t)(j * g.P)] = __fmul_rn((float)acc[j], scale[c]);
-      }
-    }
-  }
-  if constexpr (CODES) qepi_count(nbad, y.bad);
-}
-
-// ---------------------------------------------------------------- K26 grouped int8 MFMA conv
-struct QGConvGeo {
-  uint32_t M, P, OW, H, W, Cp, Co, Cig, Cog, Cogp, Wc, Kp, RS, S, tiles;
-  int stride, pad, az, padv;
-  FastDiv div_p, div_ow, div_wc, div_s, div_tiles;
-};
-
-// the epilogue's integer sum of channel co: I = D + cwz[co] * SA_g + az * T[co], or, WIDE (`d` is
-// D_h, `dl` D_l), I = 128 D_h + D_l + az * T[co]
-template <bool WIDE>
-__device__ __forceinline__ long long qg_sum(int d, int dl, const int32_t* __restrict__ cwz,
-                                            long long sa, int az, const int32_t* __restrict__ tt,
-                                            uint32_t co) {
-  if constexpr (WIDE)
-    return 128ll * (long long)d + (long long)dl + (long long)az * (long long)tt[co];
-  else
-    return (long long)d + (long long)cwz[co] * sa + (long long)az * (long long)tt[co];
-}
-
-// one `T` per (pixel row, unit) of the transposed code tile, LDS -> the NHWC codes
-template <typename T>
-__device__ __forceinline__ void qg_store_units(const int8_t* lds, int8_t* out, uint32_t units,
-                                               uint32_t sub) {
-  for (uint32_t u = sub; u < units; u += 4) ((T*)out)[u] = ((const T*)lds)[u];
-}
-
-// CODES: the code-emitting epilogue (qinfer_epi.h), `y` then being the QEpi.  The workgroup's
-// code tile is transposed through the (then free) activation tile; it owns the bytes
-// [c0, c1) of every pixel, c0 = the tile's first channel, c1 one past its last real one -- or
-// Cpo when that is the layer's last channel (the zero padding is its to write) -- and stores
-// them at the widest power of two up to 16 B that divides both c0 and c1 - c0: two workgroups
-// may own different bytes of one 16-B chunk, none writes a byte of another's.
-// WIDE: the blob's two digit planes (h, then l at `plane` bytes) take the place of the weight tile
-// and the 0/1 row: lB rows [0, 64) hold h, [64, 128) l; acc is D_h, accl D_l; `masks` and `cwz`
-// are not read.
-template <bool CODES, bool WIDE = false>
-__global__ __launch_bounds__(kBlock) void qconv_grouped_kernel(
-    const int8_t* __restrict__ act, const int8_t* __restrict__ wp, const int8_t* __restrict__ masks,
-    const int32_t* __restrict__ cwz, const int32_t* __restrict__ tt,
-    const float* __restrict__ scale, QGConvGeo g,
-    typename std::conditional<CODES, QEpi, float* __restrict__>::type y) {
-  __shared__ __attribute__((aligned(16))) int8_t lA[kGT * kGRow];
-  __shared__ __attribute__((aligned(16))) int8_t lB[(WIDE ? 2 * kGT : kGT + 1) * kGRow];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t lane = tid & (kWave - 1), wave = tid / kWave;
-  const uint32_t fr = lane & 15, fq = lane >> 4;
-
-  // the workgroup's group, channel tile and number of 16-row fragments (uniform)
-  const uint32_t grp = fdiv(blockIdx.y, g.div_tiles);
-  const uint32_t tile = blockIdx.y - grp * g.tiles;
-  const uint32_t row0 = tile * kGT;                       // first row inside the group
-  const uint32_t nrow = min(g.Cogp - row0, (uint32_t)kGT);   // multiple of 16
-  const uint32_t nf = nrow >> 4;
-  const uint32_t w0 = grp * g.Cig / 16 * 16;              // window start channel
-
-  // staging role: one 16-byte chunk of each operand tile per thread
-  const uint32_t srow = tid >> 2, sc = tid & 3;
-  const uint32_t gm = blockIdx.x * kGT + srow;
-  const bool mval = gm < g.M;
-  const uint32_t gmc = mval ? gm : 0u;
-  const uint32_t sn = fdiv(gmc, g.div_p);
-  const uint32_t sp = gmc - sn * g.P;
-  const uint32_t soh = fdiv(sp, g.div_ow);
-  const uint32_t sow = sp - soh * g.OW;
-  const int ih0 = (int)soh * g.stride - g.pad, iw0 = (int)sow * g.stride - g.pad;
-  const int8_t* abase = act + (size_t)sn * g.H * g.W * g.Cp;
-  const bool bval = srow < nrow;
-  const int8_t* wrow = wp + (size_t)(grp * g.Cogp + row0 + (bval ? srow : 0u)) * g.Kp + sc * 16;
-  const int8_t* mrow = masks + (size_t)grp * g.Kp;
-  const size_t plane = WIDE ? (size_t)(gridDim.y / g.tiles) * g.Cogp * g.Kp : 0;   // G * Cogp * Kp
-  const int pv = (g.padv & 0xff) * 0x01010101;
-  const i32x4 padfill = {pv, pv, pv, pv};
-  const i32x4 zero4 = {0, 0, 0, 0};
-
-  auto load_a = [&](uint32_t kt) -> i32x4 {
-    const uint32_t k = kt * kGT + sc * 16;
-    const uint32_t tap = fdiv(k, g.div_wc);
-    const uint32_t c0 = w0 + (k - tap * g.Wc);
-    const uint32_t r = fdiv(tap, g.div_s);
-    const uint32_t s = tap - r * g.S;
-    const int ih = ih0 + (int)r, iw = iw0 + (int)s;
-    if (mval && tap < g.RS && c0 < g.Cp && (uint32_t)ih < g.H && (uint32_t)iw < g.W)
-      return *(const i32x4*)(abase + ((size_t)ih * g.W + (size_t)iw) * g.Cp + c0);
-    return padfill;
-  };
-
-  i32x4 ra = load_a(0);
-  i32x4 rb = bval ? *(const i32x4*)wrow : zero4;
-  i32x4 rm = zero4;   // WIDE: the thread's chunk of the l plane
-  if constexpr (WIDE) {
-    if (bval) rm = *(const i32x4*)(wrow + plane);
-  } else {
-    if (tid < 4) rm = *(const i32x4*)(mrow + tid * 16);
-  }
-
-  i32x4 acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = zero4;
-  i32x4 accl[WIDE ? 4 : 1];
-#pragma unroll
-  for (int j = 0; j < (WIDE ? 4 : 1); ++j) accl[j] = zero4;
-  i32x4 accs = zero4;
-
-  const uint32_t nk = g.Kp / kGT;
-  for (uint32_t kt = 0; kt < nk; ++kt) {
-    __syncthreads();   // the previous step's fragment reads are done
-    *(i32x4*)(lA + srow * kGRow + sc * 16) = ra;
-    if (bval) *(i32x4*)(lB + srow * kGRow + sc * 16) = rb;
-    if constexpr (WIDE) {
-      if (bval) *(i32x4*)(lB + (kGT + srow) * kGRow + sc * 16) = rm;
-    } else {
-      if (tid < 4) *(i32x4*)(lB + kGT * kGRow + tid * 16) = rm;
-    }
-    __syncthreads();
-    if (kt + 1 < nk) {
-      ra = load_a(kt + 1);
-      if (bval) rb = *(const i32x4*)(wrow + (size_t)(kt + 1) * kGT);
-      if constexpr (WIDE) {
-        if (bval) rm = *(const i32x4*)(wrow + plane + (size_t)(kt + 1) * kGT);
-      } else {
-        if (tid < 4) rm = *(const i32x4*)(mrow + (size_t)(kt + 1) * kGT + tid * 16);
-      }
-    }
-    const i32x4 af = *(const i32x4*)(lA + (wave * 16 + fr) * kGRow + fq * 16);
-    if constexpr (!WIDE) {
-      const i32x4 mf = *(const i32x4*)(lB + kGT * kGRow + fq * 16);
-      accs = __builtin_amdgcn_mfma_i32_16x16x64_i8(mf, af, accs, 0, 0, 0);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if ((uint32_t)j < nf) {
-        const i32x4 wf = *(const i32x4*)(lB + (j * 16 + fr) * kGRow + fq * 16);
-        acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, af, acc[j], 0, 0, 0);
-        if constexpr (WIDE) {
-          const i32x4 lf = *(const i32x4*)(lB + (kGT + j * 16 + fr) * kGRow + fq * 16);
-          accl[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(lf, af, accl[j], 0, 0, 0);
-        }
-      }
-    }
-  }
-
-  // C/D map: column (pixel) = lane & 15, row (channel) = 4 * (lane >> 4) + reg
-  const uint32_t pixel = blockIdx.x * kGT + wave * 16 + fr;
-  const long long sa = (long long)accs[0];
-  if constexpr (CODES) {
-    const QEpi& e = y;
-    const bool pval = pixel < g.M;
-    uint32_t nbad = 0;
-    __syncthreads();   // the last step's fragment reads are done: lA is free
-    // chunks the codes below do not write: zero (the layer's channel padding lies there)
-    if (sc + 1 >= nf) *(i32x4*)(lA + srow * kGRow + (sc + 1) * 16) = zero4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if ((uint32_t)j >= nf) continue;
-      int c[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const uint32_t rl = row0 + j * 16 + fq * 4 + r;
-        c[r] = 0;
-        if (pval && rl < g.Cog) {
-          const uint32_t co = grp * g.Cog + rl;
-          const long long I = qg_sum<WIDE>(acc[j][r], accl[WIDE ? j : 0][r], cwz, sa, g.az, tt, co);
-          c[r] = qepi_code((float)I, co, scale, e, nbad);
-        }
-      }
-      *(int*)(lA + (wave * 16 + fr) * kGRow + j * 16 + fq * 4) = qepi_pack4(c[0], c[1], c[2], c[3]);
-    }
-    __syncthreads();
-    const uint32_t c0 = grp * g.Cog + row0;
-    uint32_t c1 = grp * g.Cog + min(row0 + nrow, g.Cog);
-    if (c1 == g.Co) c1 = e.Cpo;          // at most row0's 64 + 15 bytes: inside the 80-B row
-    const uint32_t len = c1 - c0;
-    const uint32_t a = (c0 | len | 16u);
-    const uint32_t w = a & (0u - a);     // lowest set bit: 1, 2, 4, 8 or 16
-    if (mval) {
-      const int8_t* src = lA + srow * kGRow;
-      int8_t* dst = e.out + (size_t)gm * e.Cpo + c0;
-      if (w == 16) qg_store_units<i32x4>(src, dst, len >> 4, sc);
-      else if (w == 8) qg_store_units<uint64_t>(src, dst, len >> 3, sc);
-      else if (w == 4) qg_store_units<uint32_t>(src, dst, len >> 2, sc);
-      else if (w == 2) qg_store_units<uint16_t>(src, dst, len >> 1, sc);
-      else qg_store_units<uint8_t>(src, dst, len, sc);
-    }
-    qepi_count(nbad, e.bad);
-  } else {
-    if (pixel >= g.M) return;
-    const uint32_t n = fdiv(pixel, g.div_p);
-    const uint32_t p = pixel - n * g.P;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if ((uint32_t)j >= nf) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const uint32_t rl = row0 + j * 16 + fq * 4 + r;
-        if (rl < g.Cog) {
-          const uint32_t co = grp * g.Cog + rl;
-          const long long I = qg_sum<WIDE>(acc[j][r], accl[WIDE ? j : 0][r], cwz, sa, g.az, tt, co);
-          y[((size_t)n * g.Co + co) * g.P + p] = __fmul_rn((float)I, scale[co]);
-        }
-      }
-    }
-  }
-}
-
 // C < 0: the caller has no C of its own (prepare); else C must be Cig * groups
 static int ggeo_ok(const char* what, const char* plain, int64_t C, int64_t Co, int64_t Cig,
                    int64_t R, int64_t S, int64_t groups, int planes = 1) {
@@ -488,17 +204,19 @@ extern "C" size_t ssq_qweight_prepared_bytes_grouped(int64_t Co, int64_t Cig, in
 // kcol: the factors of a scaled weight (the COLSCALE kernels), or null: one per column, or,
 // per_ci, one per (co, ci) (grouped only: a depthwise weight has no such form); `plain`: the
 // groups == 1 entry point an error message points to; wide: the wide forms (kind 2 the two-plane
-// blob, kind 1 its int32 blob), factors and |m| up to kQWideMax
+// blob, kind 1 its int32 blob), factors and |m| up to kQWideMax; kch: a depthwise weight's
+// per-channel factors beside kcol (ssq_qweight_prepare_grouped_chfac), or null
 static int qweight_prepare_grouped_launch(const char* me, const char* plain, bool colscale,
                                           bool per_ci, bool wide, const void* packed, const float* zp,
                                           const int32_t* kcol, int64_t Co, int64_t Cig, int64_t R,
                                           int64_t S, int64_t groups, int n_bits, int qmin,
-                                          void* prepared, uint32_t* bad, ssq_stream_t stream) {
+                                          void* prepared, uint32_t* bad, ssq_stream_t stream,
+                                          const int32_t* kch = nullptr) {
   SSQ_REQUIRE(packed && zp && (kcol || !colscale) && prepared && bad, SSQ_E_ARG,
               "%s: null pointer", me);
   int rc = qrange_ok(me, n_bits, qmin);
   if (rc) return rc;
-  SSQ_REQUIRE(colscale || !wide, SSQ_E_ARG, "%s: the wide blob holds a scaled weight", me);
+  SSQ_REQUIRE(colscale || kch || !wide, SSQ_E_ARG, "%s: the wide blob holds a scaled weight", me);
   rc = ggeo_ok(me, plain, -1, Co, Cig, R, S, groups, wide ? 2 : 1);
   if (rc) return rc;
   const GLayout L = glayout(Co, Cig, R, S, groups, wide ? 2 : 1);
@@ -508,10 +226,15 @@ static int qweight_prepare_grouped_launch(const char* me, const char* plain, boo
   const uint32_t RS = (uint32_t)(R * S);
   SSQ_REQUIRE(!per_ci || L.kind == 2, SSQ_E_ARG,
               "%s: a depthwise weight has one input channel per row: no per-(co, ci) scale", me);
+  SSQ_REQUIRE(!kch || L.kind == 1, SSQ_E_ARG,
+              "%s: per-channel factors go with a depthwise weight (a grouped one takes them per "
+              "(co, ci): ssq_qweight_prepare_grouped_perci)", me);
   if (L.kind == 1) {
-    auto* kernel = colscale ? qweight_prepare_dw_kernel<true> : qweight_prepare_dw_kernel<false>;
+    auto* kernel = kch ? (colscale ? qweight_prepare_dw_kernel<true, true>
+                                   : qweight_prepare_dw_kernel<false, true>)
+                       : (colscale ? qweight_prepare_dw_kernel<true> : qweight_prepare_dw_kernel<false>);
     hipLaunchKernelGGL(kernel, dim3(grid_for((int64_t)RS * L.Cp, kBlock)), dim3(kBlock), 0,
-                       (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, lim, bs, qmin,
+                       (hipStream_t)stream, (const uint8_t*)packed, zp, kcol, kch, lim, bs, qmin,
                        (uint32_t)L.C, RS, (uint32_t)L.Cp, make_fastdiv((uint32_t)L.Cp),
                        (int32_t*)base, bad);
   } else {
@@ -576,14 +299,32 @@ extern "C" int ssq_qweight_prepare_grouped_wide(const void* packed, const float*
                                         bad, stream);
 }
 
+// A depthwise weight (ssq_qconv_grouped_kind 1) with per-channel factors kch[C] -- a shifted act
+// grid's k_a[c] -- beside its column factors kcol[R*S], or alone (kcol null):
+// m[tap][c] = (q - z_w[c]) * kcol[tap] * kch[c] in K25's int32 blob; wide: factors and |m| up to
+// kQWideMax for 127, as ssq_qweight_prepare_grouped_wide holds a depthwise weight
+extern "C" int ssq_qweight_prepare_grouped_chfac(const void* packed, const float* zp,
+                                                 const int32_t* kcol, const int32_t* kch, int wide,
+                                                 int64_t Co, int64_t Cig, int64_t R, int64_t S,
+                                                 int64_t groups, int n_bits, int qmin,
+                                                 void* prepared, uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_qweight_prepare_grouped_chfac";
+  SSQ_REQUIRE(kch, SSQ_E_ARG, "%s: null pointer (kch)", me);
+  return qweight_prepare_grouped_launch(me, "ssq_qweight_prepare_colscale", kcol != nullptr, false,
+                                        wide != 0, packed, zp, kcol, Co, Cig, R, S, groups, n_bits,
+                                        qmin, prepared, bad, stream, kch);
+}
+
 // y: the fp32 output (ssq_qconv_i8_grouped_fwd) or null with `epi` set (..._codes_fwd); wide: the
-// *_grouped_wide_* forms on a blob of ssq_qweight_prepare_grouped_wide
+// *_grouped_wide_* forms on a blob of ssq_qweight_prepare_grouped_wide; chq: `epi` is a QEpiCh, the
+// per-channel forms (ssq_qconv_i8_grouped_codes_chq_fwd)
 static int qconv_grouped_launch(const char* me, bool wide, const int8_t* codes, const void* prepared,
                                 const float* scale, int64_t Nb, int64_t C, int64_t H, int64_t W,
                                 int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
                                 int64_t groups, float act_zero_point, int act_qmin, int act_qmax,
-                                float* y, QEpi* epi, ssq_stream_t stream) {
+                                float* y, QEpi* epi, ssq_stream_t stream, bool chq = false) {
   SSQ_REQUIRE(codes && prepared && scale && (y || epi), SSQ_E_ARG, "%s: null pointer", me);
+  SSQ_REQUIRE(!chq || epi, SSQ_E_ARG, "%s: a per-channel grid goes with the code-emitting form", me);
   SSQ_REQUIRE(groups >= 2, SSQ_E_ARG,
               "%s: groups = %lld (groups >= 2 only; groups == 1 is ssq_qconv_i8_fwd)", me,
               (long long)groups);
@@ -633,6 +374,11 @@ static int qconv_grouped_launch(const char* me, bool wide, const int8_t* codes, 
     g.per = (g.nch + runs - 1) / runs;
     const dim3 grid(pixblocks, (g.nch + g.per - 1) / g.per);
     const int32_t* wc = (const int32_t*)base;
+    if (chq) {
+      qconv_dw_chq_launch(R, S, grid, (hipStream_t)stream, codes, wc, scale, g,
+                          *static_cast<QEpiCh*>(epi));
+      return check_launch(me);
+    }
 #define SSQ_DW_LAUNCH(KS)                                                                       \
   do {                                                                                          \
     if (epi)                                                                                    \
@@ -678,6 +424,11 @@ static int qconv_grouped_launch(const char* me, bool wide, const int8_t* codes, 
   const int8_t* masks = base + L.off_mask;
   const int32_t* cwz = (const int32_t*)(base + L.off_cwz);
   const int32_t* tt = (const int32_t*)(base + L.off_t);
+  if (chq) {
+    qconv_grouped_chq_launch(wide, grid, (hipStream_t)stream, codes, base, masks, cwz, tt, scale, g,
+                             *static_cast<QEpiCh*>(epi));
+    return check_launch(me);
+  }
   if (epi) {
     auto* kernel = wide ? qconv_grouped_kernel<true, true> : qconv_grouped_kernel<true>;
     hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, codes, base, masks, cwz,
@@ -744,4 +495,25 @@ extern "C" int ssq_qconv_i8_grouped_wide_codes_fwd(
   if (rc) return rc;
   return qconv_grouped_launch(me, true, codes, prepared, scale, Nb, C, H, W, Co, R, S, stride, pad,
                               groups, act_zero_point, act_qmin, act_qmax, nullptr, &e, stream);
+}
+
+// The code-emitting grouped and depthwise convs on a per-channel output grid: the arguments of
+// ssq_qconv_i8_grouped_codes_fwd with out_dch[Co] in the place of the scalar out_delta (null is
+// refused: a per-tensor grid is the scalar entry points'), and `wide` in front of it: 0 a blob of
+// the int8 prepares, 1 one of ssq_qweight_prepare_grouped_wide (for a depthwise weight the same
+// kernel either way).  *bad also counts, once per launch, the out_dch entries that are no scale.
+extern "C" int ssq_qconv_i8_grouped_codes_chq_fwd(
+    const int8_t* codes, const void* prepared, const float* scale, int64_t Nb, int64_t C, int64_t H,
+    int64_t W, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t groups,
+    float act_zero_point, int act_qmin, int act_qmax, const float* bias, const float* gamma,
+    const float* phi, int act, int wide, const float* out_dch, float out_zero_point, int out_qmin,
+    int out_qmax, int8_t* out_codes, uint32_t* bad, ssq_stream_t stream) {
+  const char* me = "ssq_qconv_i8_grouped_codes_chq_fwd";
+  QEpiCh e;
+  const int rc = qepi_init_ch(me, bias, gamma, phi, act, out_dch, 0.0f, false, out_zero_point,
+                              out_qmin, out_qmax, out_codes, bad, &e);
+  if (rc) return rc;
+  return qconv_grouped_launch(me, wide != 0, codes, prepared, scale, Nb, C, H, W, Co, R, S, stride,
+                              pad, groups, act_zero_point, act_qmin, act_qmax, nullptr, &e, stream,
+                              true);
 }

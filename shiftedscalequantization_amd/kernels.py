@@ -2222,7 +2222,7 @@ if QCONV_WIDE not in ("auto", "1"):
 
 
 def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=None, wide=False,
-                    wide_all=False):
+                    wide_all=False, kch=None):
     """Packed codes (pack_encode's layout) + zp[co] -> QPrepared.  `shape` is the weight's own
     (Co, Cig, R, S); `groups` > 1 prepares for the grouped kernels (K24).  `kcol`: the int32
     column factors k[j], j = (ci, r, s) (colscale_grid), of a column-scaled weight: the blob then
@@ -2231,7 +2231,9 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=N
     (q - zp[co]) * k[co, ci].  `wide` (with either, dense only): the two-digit blob, factors and
     |m| up to QWIDE_MAX instead of 127.  `wide_all` (with `wide`): a grouped weight too, on the
     grouped kernels' wide blob (K26's two digit planes; a depthwise weight's int32 blob, column
-    factors only)."""
+    factors only).  `kch` (a depthwise weight only, alone or beside `kcol`): int32 per-channel
+    factors k[c] -- a shifted act grid's k_a, which a depthwise row cannot take as `kfac` -- the
+    operand (q - zp[c]) * kcol[tap] * k[c] (ssq_qweight_prepare_grouped_chfac)."""
     if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
         raise A.SSQError("qweight_prepare: packed codes must be a uint8 tensor")
     packed = _i8_dev(packed, "qweight_prepare")
@@ -2242,8 +2244,9 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=N
         raise A.SSQError(f"qweight_prepare: groups = {groups} needs a Conv2d weight and groups >= 1")
     if kcol is not None and kfac is not None:
         raise A.SSQError("qweight_prepare: a column scale and a per-(co, ci) scale do not go together")
-    if wide and kcol is None and kfac is None:
-        raise A.SSQError("qweight_prepare: the wide blob holds a scaled weight (kcol or kfac)")
+    if wide and kcol is None and kfac is None and kch is None:
+        raise A.SSQError("qweight_prepare: the wide blob holds a scaled weight (kcol or kfac; kch "
+                         "on a depthwise one)")
     if wide and groups > 1 and not wide_all:
         raise A.SSQError("qweight_prepare: the wide blob is dense only: the grouped kernels (K26) "
                          "read int8 operands")
@@ -2255,6 +2258,24 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=N
     if z.numel() != Co:
         raise A.SSQError("qweight_prepare: zero point must have one entry per output channel")
     extra, factors = (), None
+    if kch is not None:
+        if kfac is not None or groups < 2 or (Co, Ci) != (groups, 1):
+            raise A.SSQError("qweight_prepare: kch goes with a depthwise weight and without kfac (a "
+                             "grouped weight takes per-(co, ci) factors)")
+        lim, ks = QWIDE_MAX if wide else COLSCALE_MAX_L, []
+        for t, name, want in ((kcol, "kcol", R * S), (kch, "kch", Co)):
+            kc = None if t is None else torch.as_tensor(t).detach().reshape(-1)
+            if kc is not None and (kc.dtype.is_floating_point or kc.numel() != want
+                                   or int(kc.min()) < 1 or int(kc.max()) > lim):
+                raise A.SSQError(f"qweight_prepare: {name} must hold {want} integers in [1, {lim}]")
+            ks.append(None if kc is None else kc.to(device=packed.device, dtype=torch.int32).contiguous())
+        prep.centred, prep.wide, prep.wide_all = True, bool(wide), bool(wide)
+        prep.blob = torch.empty(max(query("ssq_qweight_prepared_bytes_grouped", Co, Ci, R, S, groups), 1),
+                                dtype=torch.uint8, device=packed.device)
+        call("ssq_qweight_prepare_grouped_chfac", _vp(packed), zpp, None if ks[0] is None else _vp(ks[0]),
+             _vp(ks[1]), int(bool(wide)), Co, Ci, R, S, groups, int(n_bits), int(qmin), _vp(prep.blob),
+             _vp(prep.bad), stream_of(packed))
+        return prep
     if kcol is not None or kfac is not None:
         factors, name, want = (("col", "kcol", Ci * R * S) if kfac is None else ("perci", "kfac", Co * Ci))
         kc = torch.as_tensor(kcol if kfac is None else kfac).detach().reshape(-1)
@@ -2283,24 +2304,25 @@ def qweight_prepare(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=N
 
 
 def qweight_prepare_scaled(packed, shape, zp, n_bits, qmin, groups=1, kcol=None, kfac=None,
-                           wide=False, wide_all=False):
+                           wide=False, wide_all=False, kch=None):
     """qweight_prepare for a scaled weight whose operand may leave int8: the int8 blob where it
     holds the weight (every factor <= 127 and `bad` zero, one device word read), else, with
     `wide` and a dense weight, the wide blob; elsewhere the int8 blob with its `bad` set (no
     factor above 127 reaches it: None then).  SSQ_QCONV_WIDE=1: with `wide`, every dense scaled
     weight takes the wide blob.  `wide_all` (with `wide`): a grouped or depthwise weight counts as
-    a dense one here and takes the grouped kernels' wide blob by the same rule."""
-    k = torch.as_tensor(kcol if kfac is None else kfac)
+    a dense one here and takes the grouped kernels' wide blob by the same rule.  `kch`: a
+    depthwise weight's per-channel factors, beside `kcol` or alone (qweight_prepare)."""
+    ks = [torch.as_tensor(k) for k in (kcol if kfac is None else kfac, kch) if k is not None]
     dense = int(groups) == 1 or bool(wide_all)
-    fits = int(k.max()) <= COLSCALE_MAX_L
+    fits = max(int(k.max()) for k in ks) <= COLSCALE_MAX_L
     if not (wide and dense and (QCONV_WIDE == "1" or not fits)):
         if not fits:
             return None
-        prep = qweight_prepare(packed, shape, zp, n_bits, qmin, groups, kcol, kfac)
+        prep = qweight_prepare(packed, shape, zp, n_bits, qmin, groups, kcol, kfac, kch=kch)
         if not (wide and dense and int(prep.bad.item())):
             return prep
     return qweight_prepare(packed, shape, zp, n_bits, qmin, groups, kcol, kfac, wide=True,
-                           wide_all=wide_all)
+                           wide_all=wide_all, kch=kch)
 
 
 QCONV_KINDS = {1: "depthwise", 2: "grouped"}
@@ -2682,10 +2704,20 @@ def qconv_codes(codes_or_x, prepared, scale, stride=1, padding=0, groups=1, act_
     cc = None if residual is None else getattr(residual, "_ssq_codes", None)
     if isinstance(out_delta, ChannelScale) or (cc is not None and isinstance(cc.delta, ChannelScale)):
         # a per-channel grid on either side: the one entry point of both (a per-tensor grid beside
-        # it passes its scalar and a null array), dense and unsplit
-        if int(groups) > 1 or (splits is not None and int(splits) != 1):
-            raise A.SSQError("qconv_codes: a per-channel act grid needs the dense one-kernel form "
-                             "(groups == 1, no splits)")
+        # it passes its scalar and a null array), unsplit; a grouped or depthwise conv (K25 / K26,
+        # no residual operand) emits onto one through its own entry point
+        if splits is not None and int(splits) != 1:
+            raise A.SSQError("qconv_codes: a per-channel act grid needs the one-kernel form (no splits)")
+        if int(groups) > 1:
+            if residual is not None:
+                raise A.SSQError("qconv: the grouped kernels (K25 / K26) take no residual operand")
+            if getattr(prepared, "wide", False) and not getattr(prepared, "wide_all", False):
+                raise A.SSQError("qconv: a wide blob is dense only: the grouped kernels (K26) read "
+                                 "int8 operands")
+            call("ssq_qconv_i8_grouped_codes_chq_fwd", *args, *vecs, int(relu),
+                 int(getattr(prepared, "wide", False)), out_delta.ptr("qconv_codes", Co), float(out_zp),
+                 olo, ohi, _vp(out), _vp(bad), stream_of(out))
+            return out
         def grid(d):     # (the array or null, the scalar or 0)
             return (d.ptr("qconv_codes", Co), 0.0) if isinstance(d, ChannelScale) else (None, float(d))
         rtail = (None, None, None, 0.0, 0.0, 0, 0)

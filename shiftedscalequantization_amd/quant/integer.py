@@ -162,10 +162,7 @@ def can_emit(m, q, own, x=None, act_shift=False):
     x = m.weight if x is None else x
     if not (isinstance(x, torch.Tensor) and m.epilogue_fusable(x)):
         return False
-    if fusable_act_quantizer(q, True) is not None:
-        return True
-    # (the grouped and depthwise emitters, K25 / K26, take scalar grids only)
-    return shifted_act_quantizer(q) is not None and m.fwd_kwargs.get("groups", 1) == 1
+    return fusable_act_quantizer(q, True) is not None or shifted_act_quantizer(q) is not None
 
 
 def readers_refuse(q, readers, source, around, watched):
@@ -835,7 +832,7 @@ def _geometry(m, grouped):
     return geo
 
 
-def weight_operand(f, shape, groups, act, pooled_fc, flags):
+def weight_operand(f, shape, groups, act, pooled_fc, flags, kind=None):
     """The integer weight operand of a layer, from host values alone (CPU tensors and Python ints;
     no module, no device): `f`, the hard weight's dequant fields; `shape`, `groups`, the weight's;
     `act`, the input grid (K.ActQuant); `pooled_fc`, the layer is a carried head's fc; `flags`,
@@ -844,7 +841,13 @@ def weight_operand(f, shape, groups, act, pooled_fc, flags):
     plain weight, and the layer scale is fp32(fp32(delta_a * d1[co]) / fp32(L)).  A column scale
     or a per-(co, ci) scale goes onto its grid (K.colscale_grid, K.perci_grid; with `wide`, the
     wide operand's limits where the int8 ones fail), all ones or every k = L collapse to a plain
-    weight, and a shifted input grid's k_a[ci] / L_a is multiplied in."""
+    weight, and a shifted input grid's k_a[ci] / L_a is multiplied in.  On a grouped layer that
+    fold goes by `kind`, K.qconv_kind's name of the kernel that reads the operand: "grouped" (K26)
+    takes it per (co, ci), kfac[co, ci] = k_a[g(co) * Cig + ci] times the weight's own kfac or
+    kcol[ci, r, s] -- a weight with both stays refused; "depthwise" (K25), whose row has one input
+    channel, as kfac of shape [C, 1] = k_a, the per-channel factors K24 takes as `kch`, which may
+    stand beside kcol[r, s]; None, a caller that names no kernel: refused, as the kernels
+    themselves know no per-channel grid."""
     if f["per_ci"] and not flags.per_ci:
         return f"weight scale is per (co, ci) ({f['kind']})"
     if f["per_ci"] and f["col_scale"] is not None:
@@ -873,7 +876,7 @@ def weight_operand(f, shape, groups, act, pooled_fc, flags):
         if L == 1 and int(kcol.max()) == 1:
             kcol = None                     # all ones: a plain weight, the plain K22 blob
     if isinstance(act.delta, K.ChannelScale):
-        if groups != 1 or pooled_fc:
+        if (groups != 1 and kind is None) or pooled_fc:
             return ("input is a per-channel shifted act quantizer: " +
                     ("the grouped and depthwise kernels (K25 / K26) read a scalar act grid"
                      if groups != 1 else
@@ -881,7 +884,27 @@ def weight_operand(f, shape, groups, act, pooled_fc, flags):
         # k_a[ci] into the operand: a plain weight becomes a column-scaled one
         La, ka = act.delta.fold
         RS = int(shape[2]) * int(shape[3]) if len(shape) == 4 else 1
-        if kfac is not None:
+        if kind == "depthwise":
+            if kfac is not None:
+                return f"depthwise weight scale is per (co, ci) ({f['kind']})"
+            if La != 1 or int(ka.max()) != 1:
+                kfac = ka.to(torch.int64).view(-1, 1)
+        elif groups != 1:
+            Cig = int(shape[1])
+            kg = ka.to(torch.int64).view(groups, 1, Cig)          # group g's own channels
+            if kfac is not None:
+                kfac = (torch.as_tensor(kfac).to(torch.int64).view(groups, -1, Cig) * kg).reshape(-1, Cig)
+            else:
+                own = 1 if kcol is None else torch.as_tensor(kcol).to(torch.int64).view(1, 1, Cig, RS)
+                full = own * kg.view(groups, 1, Cig, 1)
+                if not bool((full == full[..., :1]).all()):
+                    return ("input is a per-channel shifted act quantizer and the grouped weight has a "
+                            f"column scale ({f['kind']}) that varies over (r, s): K24 holds no "
+                            "per-(group, ci, r, s) factor")
+                if kcol is not None or La != 1 or int(ka.max()) != 1:
+                    kfac = full[..., 0].expand(groups, int(shape[0]) // groups, Cig).reshape(-1, Cig)
+                    kcol = None
+        elif kfac is not None:
             kfac = torch.as_tensor(kfac).reshape(-1, len(ka)).to(torch.int64) * ka.view(1, -1)
         elif kcol is not None:
             kcol = torch.as_tensor(kcol).reshape(-1).to(torch.int64) * ka.repeat_interleave(RS)
@@ -944,18 +967,24 @@ def _plan_layer(m, q, pooled_hw, flags, counter):
         packed, f = _weight_codes(m, flags.colscale, flags.per_ci)
     except TypeError as e:
         return str(e)
-    operand = weight_operand(f, tuple(m.weight.shape), groups, act, pooled_hw is not None, flags)
+    shape = tuple(m.weight.shape)
+    kind = None if groups == 1 else K.QCONV_KINDS.get(
+        K.query("ssq_qconv_grouped_kind", shape[0], shape[1], groups))
+    operand = weight_operand(f, shape, groups, act, pooled_hw is not None, flags, kind)
     if isinstance(operand, str):
         return operand
     kcol, kfac, L, d1 = operand
     scaled = kcol is not None or kfac is not None
+    kch = None
+    if kind == "depthwise" and kfac is not None:      # a shifted input grid's k_a[c]
+        kch, kfac = kfac.reshape(-1), None
     if not scaled:
         prep = K.qweight_prepare(packed, tuple(m.weight.shape), f["zero_point"], f["n_bits"],
                                  f["qmin"], groups=groups)
     else:
         prep = K.qweight_prepare_scaled(packed, tuple(m.weight.shape), f["zero_point"],
                                         f["n_bits"], f["qmin"], groups=groups, kcol=kcol,
-                                        kfac=kfac, wide=flags.wide, wide_all=flags.wide_all)
+                                        kfac=kfac, wide=flags.wide, wide_all=flags.wide_all, kch=kch)
     if prep is None:
         return ("scaled weight's grid leaves int8 (k > 127): the wide operand is dense "
                 "only, the grouped kernels (K26) read int8")
@@ -1027,15 +1056,17 @@ def enable_integer_inference(qnn, sample, grouped=False, carry=False, carry_bloc
         normalised ones by reason ("un_u8").  The stem codes of a uint8 forward are K32's own
         contract's, not pinned to the fp32 routes'; `sample` may be uint8.
     `act_shift` (off: nothing changes, a layer behind a shifted act quantizer is refused): also
-        plan dense layers whose input comes from a hard ChannelQuantAct 'shiftFeature' whose
+        plan layers whose input comes from a hard ChannelQuantAct 'shiftFeature' whose
         targets lie on an integer grid k / L (K.actshift_grid).  The input codes lie on each
         channel's own scale d[ci] = fp32(delta * s_k(ci)) (K.ChannelScale; the *_chq kernels),
         k_a[ci] multiplies the layer's integer weight operand -- a plain weight becomes a
         column-scaled one, a scaled one takes k * k_a and L_w * L_a (beyond int8 the wide blob,
         with `wide`) -- and scale[co] = fp32(fp32(delta * d1[co]) / fp32(L)).  Pair, tail and stem
-        edges may emit onto such a quantizer; grouped and depthwise layers, the split-K emitters,
-        K31 / K32 and the pooling head do not, and are reported ("Shifted activations on
-        codes").
+        edges may emit onto such a quantizer.  With `grouped`, grouped and depthwise convs read
+        and emit such grids too: K24 folds k_a per (co, ci) (K26) or per channel (K25), beyond int8
+        under `wide_all`, and the *_chq forms of K25 / K26 emit.  The split-K emitters, K31 / K32,
+        the pooling head and a residual on K25 / K26 do not, and are reported ("Shifted
+        activations on codes").
 
     A layer's plan is the first of these that fails, or an IntPlan (`_plan_layer`): reached by the
     planning forward, the geometry (`_geometry`), the input grid (`_input_reason`), the weight
