@@ -1327,6 +1327,29 @@ int ssq_actshift_bwd(const float* x, const float* g, const float* p, const float
                      const float* zp, const float* shifts, int S, int64_t N, int64_t C,
                      int64_t HW, int qmax, int hard, float* dx, float* dp, void* ws,
                      size_t ws_bytes, ssq_stream_t stream);
+/* ssq_actshift_bwd_delta: ssq_actshift_bwd with the gradient of the per-tensor delta.  dx and dp
+ * are bit for bit ssq_actshift_bwd's for the same arguments.  With c_i = clamp(v_i, 0, qmax)
+ * (the forward's fp32 values) and the LSQ straight-through rule per candidate
+ * (dQ_i/dd_i = (c_i - zp) - in_i*x/d_i, dd_i/ddelta = s_i):
+ *   soft: ddelta = sum over (n, c, hw) of g * sum_i p[c,i]*s_i*((c_i - zp) - in_i*x/d_i)
+ *   hard: ddelta = sum over (n, c, hw) of g * s_k*((c_k - zp) - in_k*x/d_k), k as in the forward
+ * Each element is worked in double from the fp32 values: t_i = (c_i - zp) - in_i*(x/d_i) with the
+ * IEEE double divide (never a reciprocal), e = fma(p[c,i]*s_i, t_i, e) over i ascending from
+ * e = 0 with p[c,i]*s_i the exact double product (hard: e = s_k*t_k), then the sum takes
+ * fma(g, e, .): at most five double roundings per term ahead of the sum.  The sum is in double in
+ * dp's fixed order: inside the group that owns a plane, one partial per (n, c) plane in `ws`
+ * (behind dp's partials), then a finish kernel adds the N*C partials -- thread t of 256 takes
+ * planes t, t + 256, ... ascending, then a halving tree over the threads -- and stores one fp32.
+ * No atomics: the same bits on every run.  NaN and +-inf in x or g propagate as the formula
+ * says (in_i * x/d_i is a product: 0 * inf is NaN).  ddelta: one device float, required
+ * (SSQ_E_ARG when null, with ssq_actshift_bwd's other refusals); dp may be NULL when hard.
+ * SSQ_E_WS for a workspace below ssq_actshift_bwd_delta_workspace_size.  No allocation, no
+ * sync, capturable. */
+size_t ssq_actshift_bwd_delta_workspace_size(int64_t N, int64_t C, int64_t HW, int S);
+int ssq_actshift_bwd_delta(const float* x, const float* g, const float* p, const float* delta,
+                           const float* zp, const float* shifts, int S, int64_t N, int64_t C,
+                           int64_t HW, int qmax, int hard, float* dx, float* dp, float* ddelta,
+                           void* ws, size_t ws_bytes, ssq_stream_t stream);
 size_t ssq_actshift_init_workspace_size(int64_t N, int64_t C, int64_t HW, int S);
 int ssq_actshift_init(const float* x, const float* delta, const float* zp, const float* shifts,
                       int S, int64_t N, int64_t C, int64_t HW, int qmax, float* mse, void* ws,

@@ -303,7 +303,9 @@ def main(argv=None):
             # activation channel uses (K33); top-1 after it is not pinned by any golden
             t_phase = time.time()
             shifts = [float(s) for s in args.act_shift_targets.split(',')]
-            act_report = D.act_shift_recon(qnn, cali, bs, device, shifts, args.act_shift_iters)
+            act_report = D.act_shift_recon(qnn, cali, bs, device, shifts, args.act_shift_iters,
+                                           act_shift_learn_delta=args.act_shift_learn_delta,
+                                           act_shift_delta_lr=args.act_shift_delta_lr)
             qnn.set_quant_state(weight_quant=True, act_quant=True)
             torch.cuda.synchronize(device)
             phases['act_shift'] = time.time() - t_phase

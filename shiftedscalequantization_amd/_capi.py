@@ -181,6 +181,9 @@ SIGNATURES = {
     "ssq_actshift_bwd_workspace_size": (_sz, [_i64, _i64, _i64, _i]),
     "ssq_actshift_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64, _i64, _i64, _i, _i, _p, _p, _p,
                               _sz, _p]),
+    "ssq_actshift_bwd_delta_workspace_size": (_sz, [_i64, _i64, _i64, _i]),
+    "ssq_actshift_bwd_delta": (_i, [_p, _p, _p, _p, _p, _p, _i, _i64, _i64, _i64, _i, _i, _p, _p,
+                                    _p, _p, _sz, _p]),
     "ssq_actshift_init_workspace_size": (_sz, [_i64, _i64, _i64, _i]),
     "ssq_actshift_init": (_i, [_p, _p, _p, _p, _i, _i64, _i64, _i64, _i, _p, _p, _sz, _p]),
     "ssq_stream_copy": (_i, [_p, _p, _i64, _p]),

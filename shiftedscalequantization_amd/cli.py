@@ -77,6 +77,12 @@ def build_parser():
                    help='the scale multipliers s_i of --act_shift (at most 4)')
     p.add_argument('--act_shift_iters', default=625, type=int,
                    help='iterations of the --act_shift loop per block')
+    p.add_argument('--act_shift_learn_delta', action='store_true',
+                   help='--act_shift also learns each act quantizer\'s per-tensor delta (the LSQ '
+                        'straight-through rule per shifted candidate), with an Adam of its own')
+    p.add_argument('--act_shift_delta_lr', default=None, type=float,
+                   help='learning rate of --act_shift_learn_delta, cosine-annealed to 0 '
+                        '(default: block_reconstruction\'s lr, 4e-5)')
     p.add_argument('--int_infer', action='store_true',
                    help='after calibration, validate again with the interior layers on their '
                         'integer codes (int8 MFMA conv / linear) and print the per-layer report')

@@ -18,14 +18,31 @@
 // products accumulated in double, reduced in a fixed order inside the group, stored per
 // plane in the workspace and summed over n in ascending order by a finish kernel: no
 // atomics, the same bits on every run.
+//
+// ssq_actshift_bwd_delta is the backward with the gradient of the per-tensor delta beside dx
+// and dp (the LSQ straight-through rule per candidate, d_i = delta * s_i):
+//   soft: ddelta = sum g * sum_i p[c,i]*s_i * ((c_i - z) - in_i * x/d_i),  c_i = clamp(v_i, 0, qmax)
+//   hard: ddelta = sum g * s_k * ((c_k - z) - in_k * x/d_k)
+// It is the backward's pass (the same 12 B/elem, the same geometry, the same dx and dp bits)
+// with one more double accumulator.  c_i and in_i are the forward's fp32 values; from there
+// every element is worked in double: t_i = (c_i - z) - in_i * (x / d_i) with the IEEE double
+// divide (a wave-uniform reciprocal would save instructions but is not the same double for
+// every x, and t_i is a difference of nearly equal numbers: an ulp of x/d_i is many ulps of
+// t_i), e = fma(p_i*s_i, t_i, e) with the exact double product p_i*s_i held per plane, and
+// acc = fma(g, e, acc): at most five double roundings per term ahead of the sum.  The plane
+// sums are reduced like dp's and stored behind dp's partials; act_finish_delta adds the
+// N*C partials (thread t takes planes t, t + 256, ... ascending, then a halving tree over the
+// 256 threads in LDS) and stores one fp32.
 #include "ssq_common.h"
+#include "qinfer_epi.h"   // SSQ_NO_PK_F32
 
 namespace ssq {
 
 constexpr int kActMaxS = 4;
 constexpr int kActU = 4;                 // loads in flight per thread and step
 
-enum ActOp { kFwdSoft = 0, kFwdHard = 1, kBwdSoft = 2, kBwdHard = 3, kInit = 4 };
+enum ActOp { kFwdSoft = 0, kFwdHard = 1, kBwdSoft = 2, kBwdHard = 3, kInit = 4,
+             kBwdSoftD = 5, kBwdHardD = 6 };   // the backwards with ddelta
 
 struct ActShifts {
   float s[kActMaxS];
@@ -37,17 +54,24 @@ struct ActGrid {
   float z, hi;
   int k;
   bool fast;
+  double ps[S];   // ddelta forms only: p[c,i] * s_i (exact in double); hard: s_i
 };
+
+// t_i of the ddelta rule, in double from the forward's fp32 c_i and in_i
+__device__ __forceinline__ double act_dterm(double xd, float c, float in, float z, float d) {
+  return ((double)c - (double)z) - (double)in * (xd / (double)d);
+}
 
 template <int S, int OP, bool FAST>
 __device__ __forceinline__ float act_elem(float x, float gv, const ActGrid<S>& G, double* acc) {
-  float Q[S], in[S];
+  float Q[S], in[S], cl[S];
 #pragma unroll
   for (int i = 0; i < S; ++i) {
     const float t = FAST ? div_fast(x, G.d[i], G.r[i]) : x / G.d[i];
     const float v = __fadd_rn(rintf(t), G.z);
     in[i] = (v >= 0.0f && v <= G.hi) ? 1.0f : 0.0f;
-    Q[i] = __fmul_rn(__fsub_rn(clampf(v, 0.0f, G.hi), G.z), G.d[i]);
+    cl[i] = clampf(v, 0.0f, G.hi);
+    Q[i] = __fmul_rn(__fsub_rn(cl[i], G.z), G.d[i]);
   }
   if (OP == kFwdSoft) {
     float y = __fmul_rn(Q[0], G.p[0]);
@@ -72,6 +96,33 @@ __device__ __forceinline__ float act_elem(float x, float gv, const ActGrid<S>& G
 #pragma unroll
     for (int i = 1; i < S; ++i) mk = i == G.k ? in[i] : mk;
     return __fmul_rn(gv, mk);
+  } else if (OP == kBwdSoftD) {
+    // kBwdSoft's dx and dp, operation for operation; acc[S] is the ddelta sum
+    const double xd = (double)x, gd = (double)gv;
+    float m = 0.0f;
+    double e = 0.0;
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+      m = __fadd_rn(m, __fmul_rn(G.p[i], in[i]));
+      acc[i] = fma(gd, (double)Q[i], acc[i]);
+      e = fma(G.ps[i], act_dterm(xd, cl[i], in[i], G.z, G.d[i]), e);
+    }
+    acc[S] = fma(gd, e, acc[S]);
+    return __fmul_rn(gv, m);
+  } else if (OP == kBwdHardD) {
+    // kBwdHard's dx; acc[0] is the ddelta sum over the chosen candidate
+    float mk = in[0], ck = cl[0], dk = G.d[0];
+    double sk = G.ps[0];
+#pragma unroll
+    for (int i = 1; i < S; ++i) {
+      const bool sel = i == G.k;
+      mk = sel ? in[i] : mk;
+      ck = sel ? cl[i] : ck;
+      dk = sel ? G.d[i] : dk;
+      sk = sel ? G.ps[i] : sk;
+    }
+    acc[0] = fma((double)gv, sk * act_dterm((double)x, ck, mk, G.z, dk), acc[0]);
+    return __fmul_rn(gv, mk);
   } else {
 #pragma unroll
     for (int i = 0; i < S; ++i) {
@@ -83,7 +134,9 @@ __device__ __forceinline__ float act_elem(float x, float gv, const ActGrid<S>& G
 }
 
 template <int OP>
-constexpr bool act_has_g() { return OP == kBwdSoft || OP == kBwdHard; }
+constexpr bool act_has_g() {
+  return OP == kBwdSoft || OP == kBwdHard || OP == kBwdSoftD || OP == kBwdHardD;
+}
 template <int OP>
 constexpr bool act_has_out() { return OP != kInit; }
 template <int OP>
@@ -244,6 +297,99 @@ __global__ __launch_bounds__(kBlock) void act_finish(const double* __restrict__ 
   out[e] = (float)t;
 }
 
+// act_kernel's walk for the backwards with ddelta (kBwdSoftD / kBwdHardD): the same groups on
+// the same planes, so dx and the dp partials are act_kernel's.  part: planes * ND doubles laid
+// out as kBwdSoft's (ND = S soft, 0 hard), then one ddelta partial per plane.
+template <int S, bool HARD, bool VEC, int TPP>
+__global__ __launch_bounds__(kBlock) SSQ_NO_PK_F32 void act_delta_kernel(
+    const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ out,
+    const float* __restrict__ p, const float* __restrict__ delta, const float* __restrict__ zp,
+    ActShifts sh, float hi, uint32_t planes, uint32_t C, uint32_t hw, double* __restrict__ part) {
+  __shared__ double red[16];
+  constexpr int OP = HARD ? kBwdHardD : kBwdSoftD;
+  constexpr int ND = HARD ? 0 : S;
+  constexpr uint32_t GPB = kBlock / TPP;
+  const uint32_t lane = threadIdx.x % TPP;
+  const uint32_t ngroups = gridDim.x * GPB;
+  ActGrid<S> G;
+  G.z = zp[0];
+  G.hi = hi;
+  G.fast = true;
+  const float d0 = delta[0];
+#pragma unroll
+  for (int i = 0; i < S; ++i) {
+    G.d[i] = __fmul_rn(d0, sh.s[i]);
+    G.r[i] = recip_for_div(G.d[i]);
+    G.fast = G.fast && G.r[i] != 0.0f;
+  }
+  for (uint32_t pl = blockIdx.x * GPB + threadIdx.x / TPP; pl < planes; pl += ngroups) {
+    const uint32_t c = pl % C;
+#pragma unroll
+    for (int i = 0; i < S; ++i) {
+      G.p[i] = p[(size_t)c * S + i];
+      G.ps[i] = HARD ? (double)sh.s[i] : (double)G.p[i] * (double)sh.s[i];   // 48 bits: exact
+    }
+    float best = G.p[0];
+    G.k = 0;
+#pragma unroll
+    for (int i = 1; i < S; ++i) {
+      const bool gt = G.p[i] > best;
+      best = gt ? G.p[i] : best;
+      G.k = gt ? i : G.k;
+    }
+    double acc[ND + 1];
+#pragma unroll
+    for (int i = 0; i <= ND; ++i) acc[i] = 0.0;
+    const size_t off = (size_t)pl * hw;
+    act_plane<S, OP, VEC, TPP>(x + off, g + off, out + off, hw, G, lane, acc);
+#pragma unroll
+    for (int i = 0; i <= ND; ++i) {
+      double t;
+      if constexpr (TPP == kWave) t = wave_sum(acc[i]);
+      else t = block_sum(acc[i], red);
+      if (lane == 0) part[i < ND ? (size_t)pl * ND + i : (size_t)planes * ND + pl] = t;
+    }
+  }
+}
+
+// Workgroup 0: ddelta = the N*C plane partials at part + N*C*nd (nd: the dp sums per plane, S
+// soft, 0 hard) -- thread t adds planes t, t + 256, ... in ascending order, then a halving tree
+// over the 256 threads.  Workgroups 1.. (launched when dp is wanted): act_finish on dp.
+__global__ __launch_bounds__(kBlock) SSQ_NO_PK_F32 void act_finish_delta(
+    const double* __restrict__ part, uint32_t N, uint32_t C, int S, int hard,
+    float* __restrict__ dp, float* __restrict__ ddelta) {
+  __shared__ double red[kBlock];
+  if (blockIdx.x == 0) {
+    const uint32_t planes = N * C;
+    const double* pd = part + (hard ? (size_t)0 : (size_t)planes * S);
+    double t = 0.0;
+    // (eight loads in flight, added in the same ascending order)
+    uint32_t pl = threadIdx.x;
+    for (; pl + 7u * kBlock < planes; pl += 8u * kBlock) {
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = pd[pl + u * kBlock];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t += v[u];
+    }
+    for (; pl < planes; pl += kBlock) t += pd[pl];
+    red[threadIdx.x] = t;
+    __syncthreads();
+    for (uint32_t o = kBlock / 2; o > 0; o >>= 1) {
+      if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) ddelta[0] = (float)red[0];
+    return;
+  }
+  const uint32_t e = (blockIdx.x - 1) * blockDim.x + threadIdx.x;
+  if (e >= C * (uint32_t)S) return;
+  double t = 0.0;
+  if (!hard)
+    for (uint32_t n = 0; n < N; ++n) t += part[(size_t)n * C * S + e];
+  dp[e] = (float)t;
+}
+
 static bool act_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 template <int S, int OP, bool VEC>
@@ -284,6 +430,28 @@ static void act_launch(hipStream_t s, int S, bool vec, const float* x, const flo
     SSQ_ACT_CASE(4)
   }
 #undef SSQ_ACT_CASE
+}
+
+// act_launch_tpp's geometry (the dp partials must come from the same groups) for act_delta_kernel
+template <int S, bool HARD>
+static void act_delta_launch(hipStream_t s, bool vec, const float* x, const float* g, float* out,
+                             const float* p, const float* delta, const float* zp,
+                             const ActShifts& sh, float hi, uint32_t planes, uint32_t C,
+                             uint32_t hw, double* part) {
+  const uint32_t items = vec ? hw / 4 : hw;
+  constexpr uint32_t kMaxBlocks = 256 * 8;
+  constexpr uint32_t GPB = kBlock / kWave;
+  const bool wave = items <= (uint32_t)kBlock;
+  uint32_t blocks = wave ? (planes + GPB - 1) / GPB : planes;
+  blocks = blocks > kMaxBlocks ? kMaxBlocks : blocks;
+#define SSQ_ACT_DELTA(VEC, TPP)                                                                  \
+  hipLaunchKernelGGL((act_delta_kernel<S, HARD, VEC, TPP>), dim3(blocks), dim3(kBlock), 0, s, x, \
+                     g, out, p, delta, zp, sh, hi, planes, C, hw, part)
+  if (vec && wave) SSQ_ACT_DELTA(true, kWave);
+  else if (vec) SSQ_ACT_DELTA(true, kBlock);
+  else if (wave) SSQ_ACT_DELTA(false, kWave);
+  else SSQ_ACT_DELTA(false, kBlock);
+#undef SSQ_ACT_DELTA
 }
 
 // Shared argument checks; fills sh.  planes = N * C.
@@ -382,6 +550,54 @@ extern "C" int ssq_actshift_bwd(const float* x, const float* g, const float* p,
                        (uint32_t)C, (uint32_t)HW, (double*)ws);
   hipLaunchKernelGGL(act_finish, dim3(fin_grid), dim3(kBlock), 0, s, (const double*)ws,
                      (uint32_t)N, (uint32_t)C, S, 0, dp);
+  return check_launch(what);
+}
+
+// the soft form's need (dp's partials, then one double per plane); the hard form uses less
+extern "C" size_t ssq_actshift_bwd_delta_workspace_size(int64_t N, int64_t C, int64_t HW, int S) {
+  (void)HW;
+  const size_t dp_bytes = act_part_bytes(N, C, S);
+  return dp_bytes ? dp_bytes + (size_t)N * (size_t)C * sizeof(double) : 0;
+}
+
+extern "C" int ssq_actshift_bwd_delta(const float* x, const float* g, const float* p,
+                                      const float* delta, const float* zp, const float* shifts,
+                                      int S, int64_t N, int64_t C, int64_t HW, int qmax, int hard,
+                                      float* dx, float* dp, float* ddelta, void* ws,
+                                      size_t ws_bytes, ssq_stream_t stream) {
+  const char* what = "ssq_actshift_bwd_delta";
+  ActShifts sh;
+  if (int rc = act_check(what, shifts, S, N, C, HW, qmax, sh)) return rc;
+  SSQ_REQUIRE(dp != nullptr || hard, SSQ_E_ARG, "%s: null pointer (dp)", what);
+  SSQ_REQUIRE(ddelta != nullptr, SSQ_E_ARG, "%s: null pointer (ddelta)", what);
+  hipStream_t s = (hipStream_t)stream;
+  const int fin_grid = 1 + (dp ? grid_for(C * S, kBlock, 1 << 30) : 0);
+  if (N > 0) {
+    SSQ_REQUIRE(x && g && p && delta && zp && dx, SSQ_E_ARG, "%s: null pointer", what);
+    const size_t need = (size_t)N * (size_t)C * (size_t)(hard ? 1 : S + 1) * sizeof(double);
+    SSQ_REQUIRE(ws && ws_bytes >= need && ((uintptr_t)ws & 7u) == 0, SSQ_E_WS,
+                "%s: workspace of %zu bytes (8-B aligned) needed, %zu given", what, need, ws_bytes);
+    const bool vec = HW % 4 == 0 && act_aligned16(x) && act_aligned16(g) && act_aligned16(dx);
+#define SSQ_ACT_CASE(SV)                                                                        \
+  case SV:                                                                                      \
+    if (hard)                                                                                   \
+      act_delta_launch<SV, true>(s, vec, x, g, dx, p, delta, zp, sh, (float)qmax,               \
+                                 (uint32_t)(N * C), (uint32_t)C, (uint32_t)HW, (double*)ws);    \
+    else                                                                                        \
+      act_delta_launch<SV, false>(s, vec, x, g, dx, p, delta, zp, sh, (float)qmax,              \
+                                  (uint32_t)(N * C), (uint32_t)C, (uint32_t)HW, (double*)ws);   \
+    break;
+    switch (S) {
+      SSQ_ACT_CASE(1)
+      SSQ_ACT_CASE(2)
+      SSQ_ACT_CASE(3)
+      SSQ_ACT_CASE(4)
+    }
+#undef SSQ_ACT_CASE
+  }
+  // (N == 0: no plane, the finish stores ddelta = 0 and dp = 0)
+  hipLaunchKernelGGL(act_finish_delta, dim3(fin_grid), dim3(kBlock), 0, s, (const double*)ws,
+                     (uint32_t)N, (uint32_t)C, S, hard ? 1 : 0, dp, ddelta);
   return check_launch(what);
 }
 

@@ -216,10 +216,11 @@ def QuantRecursiveShiftRecon(model, layerEnabled, qnn, test_loader, prv_name="",
 
 
 def act_shift_recon(qnn, cali_data, batch_size, device, targets=(1.0, 0.5), iters=625,
-                    verbose=True):
+                    verbose=True, act_shift_learn_delta=False, act_shift_delta_lr=None):
     """--act_shift: after the act phase, per block -- cache its features in the current
     (weight + act quantized) state, learn the per-channel shifted scale of its activation
     quantizers (block_recon_fused_shiftedScale(act=True)), clear the cache.
+    act_shift_learn_delta / act_shift_delta_lr: that function's (delta learned with the shifts).
     -> {block path: [soft rec loss, hard rec loss]}."""
     out = {}
     for path in block_paths(qnn):
@@ -228,7 +229,9 @@ def act_shift_recon(qnn, cali_data, batch_size, device, targets=(1.0, 0.5), iter
         qnn.set_quant_state(True, True)
         out[path] = block_recon_fused_shiftedScale(block, iters, model=qnn, act=True,
                                                    batch_size=batch_size, verbose=verbose,
-                                                   act_shift_targets=list(targets))
+                                                   act_shift_targets=list(targets),
+                                                   act_shift_learn_delta=act_shift_learn_delta,
+                                                   act_shift_delta_lr=act_shift_delta_lr)
         block.clear_cached_features()
     return out
 

@@ -1939,6 +1939,31 @@ def actshift_bwd(x, g, p, delta, zp, shifts, n_bits, hard=False, want_dp=True):
     return dx, dpt
 
 
+def actshift_bwd_delta(x, g, p, delta, zp, shifts, n_bits, hard=False, want_dp=True):
+    """(dx, dp, ddelta) in one pass (ssq_actshift_bwd_delta): actshift_bwd's dx and dp, bit for
+    bit, and the LSQ straight-through gradient of the per-tensor delta, ddelta = sum g * sum_i
+    p[c, i] * s_i * ((c_i - zp) - in_i * x / d_i) (hard: the chosen candidate alone), summed in
+    double in a fixed order: a 0-d fp32 tensor, the same bits on every run."""
+    x, xp = fptr(x.detach(), "x")
+    g, gp = fptr(g.detach(), "g")
+    if g.shape != x.shape:
+        raise A.SSQError("actshift_bwd_delta: g must be shaped like x")
+    N, C_, hw = _actshift_geometry(x)
+    S = len(shifts)
+    p, pp = _actshift_table(p, C_, S, "p")
+    (delta, dp_), (zp, zpp) = _actshift_scalars(delta, zp)
+    dx = torch.empty_like(x)
+    if not want_dp and not hard:
+        raise A.SSQError("actshift_bwd_delta: the soft backward always computes dp")
+    dpt = torch.empty((C_, S), dtype=torch.float32, device=x.device) if want_dp else None
+    ddelta = torch.empty((), dtype=torch.float32, device=x.device)
+    wsb = query("ssq_actshift_bwd_delta_workspace_size", N, C_, hw, S)
+    ws, wsn = workspace(wsb, x.device)
+    call("ssq_actshift_bwd_delta", xp, gp, pp, dp_, zpp, A.shifts_arg(shifts), S, N, C_, hw,
+         2 ** n_bits - 1, int(bool(hard)), _vp(dx), _vp(dpt), _vp(ddelta), ws, wsn, stream_of(x))
+    return dx, dpt, ddelta
+
+
 def actshift_init(x, delta, zp, shifts, n_bits):
     """mse[c, i] = sum_{n,h,w} (x - Q_i(x))^2 in one pass over x (ssq_actshift_init): the
     errors ChannelQuantAct.init_v picks each channel's starting shift from."""
@@ -1972,9 +1997,16 @@ class ActShiftFn(torch.autograd.Function):
     def backward(ctx, g):
         x, p, delta, zp = ctx.saved_tensors
         shifts, n_bits, hard = ctx.cfg
-        dx, dp = actshift_bwd(x, g, p, delta, zp, shifts, n_bits, hard, want_dp=not hard)
+        ddelta = None
+        if ctx.needs_input_grad[2]:      # delta learns too (_act_loop(learn_delta=True))
+            dx, dp, ddelta = actshift_bwd_delta(x, g, p, delta, zp, shifts, n_bits, hard,
+                                                want_dp=not hard)
+            ddelta = ddelta.reshape(delta.shape)
+        else:
+            dx, dp = actshift_bwd(x, g, p, delta, zp, shifts, n_bits, hard, want_dp=not hard)
         return (dx if ctx.needs_input_grad[0] else None,
-                dp if ctx.needs_input_grad[1] and not hard else None, None, None, None, None, None)
+                dp if ctx.needs_input_grad[1] and not hard else None, ddelta, None, None, None,
+                None)
 
 
 def actshift(x, p, delta, zp, shifts, n_bits, hard=False):

@@ -12,8 +12,9 @@ never created, so those modes raise here too, with an explicit message.
 shifted_x_quant with the candidates Q_i = 'none'-mode q/dq at delta*s_i computed from the
 live tensor, mixed per channel by p = get_sig_soft_targets() (C, S) -> ssq_actshift_fwd /
 ssq_actshift_bwd (K33); init_v(x) starts alpha from the per-channel squared errors
-(ssq_actshift_init) by ChannelQuant.init_alpha's rule.  delta and zero_point are not
-learned in this mode.
+(ssq_actshift_init) by ChannelQuant.init_alpha's rule.  zero_point is not learned in this
+mode; delta is learned only while `learn_delta` is set (the act loop's learn_delta=True):
+its gradient is the LSQ straight-through rule per candidate, ssq_actshift_bwd_delta.
 """
 import torch
 from torch import nn
@@ -39,6 +40,7 @@ class ChannelQuantAct(nn.Module):
         self.hard_targets = False
         self.gamma, self.zeta = -0.1, 1.1
         self.alpha = None
+        self.learn_delta = False
         self.shiftedDone = False
         self.disable_act_quant = getattr(uaq, 'disable_act_quant', False)
         # code that asks an act quantizer whether its scale exists keeps working
@@ -53,7 +55,9 @@ class ChannelQuantAct(nn.Module):
         if self.opt_mode == 'shiftFeature':
             if self.alpha is None:
                 raise RuntimeError("ChannelQuantAct 'shiftFeature' needs init_v(x) first")
-            return K.actshift(K.materialize_epi(x), self.get_sig_soft_targets(), self.delta,
+            # delta takes a gradient (ssq_actshift_bwd_delta) only while a loop learns it
+            delta = self.delta if self.learn_delta else self.delta.detach()
+            return K.actshift(K.materialize_epi(x), self.get_sig_soft_targets(), delta,
                               self.zero_point, self.shiftTarget, self.n_bits, self.hard_targets)
         raise NotImplementedError(
             f"ChannelQuantAct opt_mode={self.opt_mode!r} is broken in the reference "

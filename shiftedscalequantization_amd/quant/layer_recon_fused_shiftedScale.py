@@ -19,8 +19,8 @@ from tqdm import tqdm
 
 from .. import kernels as K
 from ..parallel_dp import GradBucket, world
-from ._engine import (BatchFeeder, IterationGraph, LazyValue, SsqAdam, as_float, clear_stash,
-                      frozen_except, lazy_tail, loss_backward, probe, stash_block_weights)
+from ._engine import (BatchFeeder, CosineLR, IterationGraph, LazyValue, SsqAdam, as_float,
+                      clear_stash, frozen_except, lazy_tail, loss_backward, probe, stash_block_weights)
 from .quant_block import BaseQuantBlock
 from .quant_layer import QuantModule
 
@@ -239,13 +239,19 @@ def _act_hard_flags(quantizers):
 
 
 def _act_loop(block, iters, lmda, model, p, lr, bias_cal, batch_size, verbose, iter_hook,
-              targets):
+              targets, learn_delta=False, delta_lr=None):
     """The act half of the fused loop (evident intent of layer_recon_fused_shiftedScale.py:
     37-57): every enabled act quantizer of the block becomes a ChannelQuantAct in
     'shiftFeature' mode, its alpha (C, S) starts from the errors of one forward of the block in
     its incoming state over cached_inp[:batch_size], and Adam learns the alphas against the
     cached FP outputs (lp loss, no regulariser) over the weight loop's batch draws.  The
-    weight quantizers are not touched.  -> [soft rec loss, hard rec loss]."""
+    weight quantizers are not touched.  -> [soft rec loss, hard rec loss].
+    learn_delta: each replaced quantizer's per-tensor delta is learned through the same loss
+    (its gradient: ssq_actshift_bwd_delta), stepped by an Adam of its own at delta_lr with
+    cosine annealing to 0 over `iters` -- the rule block_reconstruction's act phase applies
+    to act deltas; delta_lr=None is that function's lr default.  zero_point stays fixed."""
+    import inspect
+    from .block_recon import block_reconstruction
     from .channelQuantAct import ChannelQuantAct
     if bias_cal:
         raise ValueError("act=True learns the activation shifts only: bias_cal=True is the "
@@ -291,24 +297,40 @@ def _act_loop(block, iters, lmda, model, p, lr, bias_cal, batch_size, verbose, i
     opt_params = [q.alpha for q in quantizers]
     on_gpu = opt_params[0].is_cuda
     optimizer = SsqAdam(opt_params, lr=lr) if on_gpu else torch.optim.Adam(opt_params, lr=lr)
+    deltas, delta_opt, delta_sched = [], None, None
+    if learn_delta:
+        if delta_lr is None:
+            delta_lr = inspect.signature(block_reconstruction).parameters['lr'].default
+        for q in quantizers:
+            q.learn_delta = True
+            if not any(q.delta is d for d in deltas):
+                deltas.append(q.delta)
+        delta_opt = (SsqAdam if on_gpu else torch.optim.Adam)(deltas, lr=delta_lr)
+        delta_sched = CosineLR(delta_lr, max(iters, 1), 0.)
     if verbose:
         print("number of elements in opt_params: {}".format(sum(t.numel() for t in opt_params)))
     loss_func = FusedScaleLossFunction(block, quantizers, round_loss='none', lmda=lmda,
                                        max_count=iters, b_range=(20, 2), decay_start=0,
                                        warmup=0.2, p=p)
     start_loss = 0.0
-    # only the alphas need a gradient: no weight gradient, no delta / zero_point gradient
-    with frozen_except(block, opt_params):
+    # only the alphas (and, learn_delta, the replaced quantizers' deltas) need a gradient: no
+    # weight gradient, no zero_point gradient
+    with frozen_except(block, opt_params + deltas):
         t = tqdm(range(iters), desc='', dynamic_ncols=True, disable=not verbose)
         for i in t:
             probe(i, opt_params)
             if iter_hook is not None:
                 iter_hook(i)
             optimizer.zero_grad()
+            if delta_opt is not None:
+                delta_opt.zero_grad()
             inp, out = feeder.next()
             loss = loss_func(block(inp), out)
             loss.backward()
             optimizer.step()
+            if delta_opt is not None:
+                delta_opt.step()
+                delta_opt.param_groups[0]['lr'] = delta_sched.step()
             if i % 500 == 0 and verbose:
                 start_loss = max(start_loss, as_float(loss_func.rec_loss))
                 t.set_description(f"{start_loss:.6f} -> {as_float(loss_func.rec_loss):.6f}")
@@ -318,6 +340,10 @@ def _act_loop(block, iters, lmda, model, p, lr, bias_cal, batch_size, verbose, i
 
     rec_loss_out = []
     optimizer.zero_grad()
+    if delta_opt is not None:
+        delta_opt.zero_grad()
+    for q in quantizers:       # the learned deltas stay; nothing after the loop steps them
+        q.learn_delta = False
     with torch.no_grad():
         loss_func(block(cur_inp), cur_out)
     if verbose:
@@ -339,19 +365,21 @@ def block_recon_fused_shiftedScale(block: BaseQuantBlock, iters: int = 20000, lm
                                    model=None, test_loader=None, act=False, adaround=False,
                                    useShiftedScale=True, bias_cal=False, batch_size=32,
                                    dp_average=False, verbose=True, iter_hook=None, graph=True,
-                                   act_shift_targets=None):
+                                   act_shift_targets=None, act_shift_learn_delta=False,
+                                   act_shift_delta_lr=None):
     """layer_recon_fused_shiftedScale.py:23-141 -> [soft rec loss, hard rec loss].
     graph=True replays the iteration body from a HIP graph after GRAPH_WARMUP eager
     iterations (at world > 1 as two graphs around the bucket all-reduce); the arithmetic
     and the batch draws are unchanged.  act=True learns the per-channel shifted scale of the
     block's activation quantizers instead (_act_loop; `graph` is ignored there,
-    act_shift_targets defaults to [1.0, 0.5])."""
+    act_shift_targets defaults to [1.0, 0.5]); act_shift_learn_delta learns their per-tensor
+    deltas with the shifts, at act_shift_delta_lr (None: block_reconstruction's lr)."""
     if act:
         # the reference's act branch crashes in ChannelQuantAct.init_v (channelQuantAct.py:
         # 126-134); its evident intent (:37-57) is implemented (DESIGN.md section 6)
         block.train()
         return _act_loop(block, iters, lmda, model, 2.0, 0.001, bias_cal, batch_size, verbose,
-                         iter_hook, act_shift_targets)
+                         iter_hook, act_shift_targets, act_shift_learn_delta, act_shift_delta_lr)
     block.train()
     return _fused_loop(block, _weight_quantizers(block), iters, lmda, model, 2.0, 0.001, bias_cal,
                        batch_size, dp_average, verbose, iter_hook, graph)
@@ -361,7 +389,8 @@ def layer_recon_fused_shiftedScale(layer: QuantModule, iters: int = 20000, lmda:
                                    model=None, test_loader=None, act=False, adaround=False,
                                    useShiftedScale=True, bias_cal=False, batch_size=32,
                                    dp_average=False, verbose=True, graph=True,
-                                   act_shift_targets=None):
+                                   act_shift_targets=None, act_shift_learn_delta=False,
+                                   act_shift_delta_lr=None):
     """layer_recon_fused_shiftedScale.py:144-221.  The reference raises UnboundLocalError
     (`opt_params += ...` before assignment, :156); this implements its evident intent: the
     block loop on one layer with p = 1.0 (:165) and Adam's default lr, finished with the
@@ -372,7 +401,7 @@ def layer_recon_fused_shiftedScale(layer: QuantModule, iters: int = 20000, lmda:
     if act:
         # the layer variant of the act path: the same loop on one QuantModule, p = 1 (:165)
         return _act_loop(layer, iters, lmda, model, 1.0, 0.001, bias_cal, batch_size, verbose,
-                         None, act_shift_targets)
+                         None, act_shift_targets, act_shift_learn_delta, act_shift_delta_lr)
 
     def set_hard(quantizers):
         if adaround:
