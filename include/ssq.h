@@ -1355,6 +1355,39 @@ int ssq_actshift_init(const float* x, const float* delta, const float* zp, const
                       int S, int64_t N, int64_t C, int64_t HW, int qmax, float* mse, void* ws,
                       size_t ws_bytes, ssq_stream_t stream);
 
+/* ---------------------------------------------------------------- K34 act quantizer in the epilogue
+ * The shifted-scale act quantizer (K33) inside the K13 epilogue pass: with
+ *   x = act(((conv + bias[c]) * gamma[c] + phi[c]) + res)     (ssq_epilogue_fwd's ops and order;
+ *                                                               bias / gamma+phi / res nullable,
+ *                                                               relu: 0 none, 1 ReLU, 2 ReLU6)
+ * ssq_epilogue_actshift_fwd writes y = ssq_actshift_fwd(x) and never stores x (8 B/elem, +4 with
+ * a residual).  ssq_epilogue_actshift_bwd recomputes x from conv (+ res) and, for the upstream
+ * g = dL/dy, writes
+ *   dconv = dx_q * mask * gamma[c],  dres = dx_q * mask        (dx_q: ssq_actshift_bwd's dx;
+ *                                                               mask: ssq_epilogue_bwd's rule)
+ *   dp (C, S) and, when ddelta is given, ddelta (one float): ssq_actshift_bwd[_delta]'s
+ * in one pass (12 B/elem, +8 with a residual and dres).  dconv, dres and ddelta may be NULL (not
+ * computed); dp may be NULL when hard; dres needs res.  bias / gamma / phi get no gradient: a
+ * caller that learns them runs ssq_epilogue_bwd after ssq_actshift_bwd.  Every output is bit for
+ * bit the two-pass sequence's (ssq_epilogue_fwd -> ssq_actshift_fwd; ssq_actshift_bwd[_delta]
+ * -> ssq_epilogue_bwd) for 16-B aligned g: the same element functions, the same plane walk, the
+ * same finish kernels.  Refused with SSQ_E_ARG before any launch: what ssq_actshift_* refuse (S
+ * outside 1..4, a null required pointer, N*C*HW >= 2^31, qmax < 1), an activation code outside
+ * 0..2, gamma without phi; SSQ_E_WS for a workspace below the query (8-B aligned).  No
+ * allocation, no sync, capturable. */
+int ssq_epilogue_actshift_fwd(const float* conv, const float* bias, const float* gamma,
+                              const float* phi, const float* res, int relu, const float* p,
+                              const float* delta, const float* zp, const float* shifts, int S,
+                              int64_t N, int64_t C, int64_t HW, int qmax, int hard, float* y,
+                              ssq_stream_t stream);
+size_t ssq_epilogue_actshift_bwd_workspace_size(int64_t N, int64_t C, int64_t HW, int S);
+int ssq_epilogue_actshift_bwd(const float* conv, const float* g, const float* bias,
+                              const float* gamma, const float* phi, const float* res, int relu,
+                              const float* p, const float* delta, const float* zp,
+                              const float* shifts, int S, int64_t N, int64_t C, int64_t HW,
+                              int qmax, int hard, float* dconv, float* dres, float* dp,
+                              float* ddelta, void* ws, size_t ws_bytes, ssq_stream_t stream);
+
 /* ---------------------------------------------------------------- bandwidth probe
  * float4 device copy, used by bench.py to report the measured stream bandwidth.      */
 int ssq_stream_copy(const float* src, float* dst, int64_t n, ssq_stream_t stream);

@@ -186,6 +186,10 @@ SIGNATURES = {
                                     _p, _p, _sz, _p]),
     "ssq_actshift_init_workspace_size": (_sz, [_i64, _i64, _i64, _i]),
     "ssq_actshift_init": (_i, [_p, _p, _p, _p, _i, _i64, _i64, _i64, _i, _p, _p, _sz, _p]),
+    "ssq_epilogue_actshift_fwd": (_i, [_p] * 5 + [_i] + [_p] * 4 + [_i, _i64, _i64, _i64, _i, _i, _p, _p]),
+    "ssq_epilogue_actshift_bwd_workspace_size": (_sz, [_i64, _i64, _i64, _i]),
+    "ssq_epilogue_actshift_bwd": (_i, [_p] * 6 + [_i] + [_p] * 4 + [_i, _i64, _i64, _i64, _i, _i]
+                                  + [_p] * 5 + [_sz, _p]),
     "ssq_stream_copy": (_i, [_p, _p, _i64, _p]),
     "ssq_stream_probe": (_i, [_p, _p, _i64, _i, _p]),
 }

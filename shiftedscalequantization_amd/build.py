@@ -20,15 +20,18 @@ ARCH = os.environ.get("SSQ_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["fq.hip", "adashift.hip", "adashift_prep.hip", "scale_init.hip", "recon.hip", "pack.hip", "conv_wgrad.hip",
            "dwconv.hip", "fc_recon.hip", "fisher.hip", "qinfer.hip", "qinfer_grouped.hip", "qinfer_grouped_chq.hip",
-           "qinfer_stem.hip", "qinfer_head.hip", "qinfer_stemconv.hip", "qinfer_stemu8.hip", "actshift.hip"]
+           "qinfer_stem.hip", "qinfer_head.hip", "qinfer_stemconv.hip", "qinfer_stemu8.hip", "actshift.hip", "actshift_epi.hip"]
 HEADERS = ["ssq_common.h", "adashift_common.h", "fin_tasks.h", "prep_ride.h", "qinfer_epi.h", "qinfer_layout.h", "qinfer_check.h",
-           "qinfer_prepare.h", "qinfer_grouped_kernels.h", os.path.join("..", "..", "include", "ssq.h")]
+           "qinfer_prepare.h", "qinfer_grouped_kernels.h", "actshift_kernels.h", "epilogue_elem.h",
+           os.path.join("..", "..", "include", "ssq.h")]
 CFLAGS = ["-O3", f"--offload-arch={ARCH}", "-fPIC", "-std=c++17", "-ffp-contract=off",
           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wall", "-Wno-unused-function"]
 # Per-source flags.  qinfer_grouped_chq.hip holds only the per-channel instantiations of K25 / K26,
 # which are built without packed fp32 instructions (csrc/qinfer_epi.h, SSQ_NO_PK_F32, says why);
-# the same IEEE arithmetic, another instruction selection.
-EXTRA_FLAGS = {"qinfer_grouped_chq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# the same IEEE arithmetic, another instruction selection.  actshift_epi.hip (K34) holds only kernels
+# written since then.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"qinfer_grouped_chq.hip": _NO_PK_F32, "actshift_epi.hip": _NO_PK_F32}
 
 
 def source_sha():

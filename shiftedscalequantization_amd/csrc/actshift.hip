@@ -33,105 +33,12 @@
 // sums are reduced like dp's and stored behind dp's partials; act_finish_delta adds the
 // N*C partials (thread t takes planes t, t + 256, ... ascending, then a halving tree over the
 // 256 threads in LDS) and stores one fp32.
-#include "ssq_common.h"
-#include "qinfer_epi.h"   // SSQ_NO_PK_F32
+//
+// The element function, the grid it reads and the host checks are in actshift_kernels.h, which
+// K34 (actshift_epi.hip) shares.
+#include "actshift_kernels.h"
 
 namespace ssq {
-
-constexpr int kActMaxS = 4;
-constexpr int kActU = 4;                 // loads in flight per thread and step
-
-enum ActOp { kFwdSoft = 0, kFwdHard = 1, kBwdSoft = 2, kBwdHard = 3, kInit = 4,
-             kBwdSoftD = 5, kBwdHardD = 6 };   // the backwards with ddelta
-
-struct ActShifts {
-  float s[kActMaxS];
-};
-
-template <int S>
-struct ActGrid {
-  float d[S], r[S], p[S];
-  float z, hi;
-  int k;
-  bool fast;
-  double ps[S];   // ddelta forms only: p[c,i] * s_i (exact in double); hard: s_i
-};
-
-// t_i of the ddelta rule, in double from the forward's fp32 c_i and in_i
-__device__ __forceinline__ double act_dterm(double xd, float c, float in, float z, float d) {
-  return ((double)c - (double)z) - (double)in * (xd / (double)d);
-}
-
-template <int S, int OP, bool FAST>
-__device__ __forceinline__ float act_elem(float x, float gv, const ActGrid<S>& G, double* acc) {
-  float Q[S], in[S], cl[S];
-#pragma unroll
-  for (int i = 0; i < S; ++i) {
-    const float t = FAST ? div_fast(x, G.d[i], G.r[i]) : x / G.d[i];
-    const float v = __fadd_rn(rintf(t), G.z);
-    in[i] = (v >= 0.0f && v <= G.hi) ? 1.0f : 0.0f;
-    cl[i] = clampf(v, 0.0f, G.hi);
-    Q[i] = __fmul_rn(__fsub_rn(cl[i], G.z), G.d[i]);
-  }
-  if (OP == kFwdSoft) {
-    float y = __fmul_rn(Q[0], G.p[0]);
-#pragma unroll
-    for (int i = 1; i < S; ++i) y = __fadd_rn(y, __fmul_rn(Q[i], G.p[i]));
-    return y;
-  } else if (OP == kFwdHard) {
-    float y = Q[0];
-#pragma unroll
-    for (int i = 1; i < S; ++i) y = i == G.k ? Q[i] : y;
-    return y;
-  } else if (OP == kBwdSoft) {
-    float m = 0.0f;
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-      m = __fadd_rn(m, __fmul_rn(G.p[i], in[i]));
-      acc[i] = fma((double)gv, (double)Q[i], acc[i]);   // the product is exact in double
-    }
-    return __fmul_rn(gv, m);
-  } else if (OP == kBwdHard) {
-    float mk = in[0];
-#pragma unroll
-    for (int i = 1; i < S; ++i) mk = i == G.k ? in[i] : mk;
-    return __fmul_rn(gv, mk);
-  } else if (OP == kBwdSoftD) {
-    // kBwdSoft's dx and dp, operation for operation; acc[S] is the ddelta sum
-    const double xd = (double)x, gd = (double)gv;
-    float m = 0.0f;
-    double e = 0.0;
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-      m = __fadd_rn(m, __fmul_rn(G.p[i], in[i]));
-      acc[i] = fma(gd, (double)Q[i], acc[i]);
-      e = fma(G.ps[i], act_dterm(xd, cl[i], in[i], G.z, G.d[i]), e);
-    }
-    acc[S] = fma(gd, e, acc[S]);
-    return __fmul_rn(gv, m);
-  } else if (OP == kBwdHardD) {
-    // kBwdHard's dx; acc[0] is the ddelta sum over the chosen candidate
-    float mk = in[0], ck = cl[0], dk = G.d[0];
-    double sk = G.ps[0];
-#pragma unroll
-    for (int i = 1; i < S; ++i) {
-      const bool sel = i == G.k;
-      mk = sel ? in[i] : mk;
-      ck = sel ? cl[i] : ck;
-      dk = sel ? G.d[i] : dk;
-      sk = sel ? G.ps[i] : sk;
-    }
-    acc[0] = fma((double)gv, sk * act_dterm((double)x, ck, mk, G.z, dk), acc[0]);
-    return __fmul_rn(gv, mk);
-  } else {
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-      const double r = (double)x - (double)Q[i];
-      acc[i] = fma(r, r, acc[i]);
-    }
-    return 0.0f;
-  }
-}
 
 template <int OP>
 constexpr bool act_has_g() {
@@ -235,6 +142,9 @@ __global__ __launch_bounds__(kBlock) void act_kernel(const float* __restrict__ x
   constexpr uint32_t GPB = kBlock / TPP;
   const uint32_t lane = threadIdx.x % TPP;
   const uint32_t ngroups = gridDim.x * GPB;
+  // (the grid is set up in place here and in act_delta_kernel, not through actshift_kernels.h's
+  // act_grid_scales / act_grid_channel, which say the same: these kernels keep the instruction
+  // schedule they were measured with)
   ActGrid<S> G;
   G.z = zp[0];
   G.hi = hi;
@@ -390,26 +300,29 @@ __global__ __launch_bounds__(kBlock) SSQ_NO_PK_F32 void act_finish_delta(
   dp[e] = (float)t;
 }
 
-static bool act_aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+void act_finish_launch(hipStream_t s, const double* part, int64_t N, int64_t C, int S, bool hard,
+                       float* dp, float* ddelta) {
+  const int dp_grid = dp ? grid_for(C * S, kBlock, 1 << 30) : 0;
+  if (ddelta)
+    hipLaunchKernelGGL(act_finish_delta, dim3(1 + dp_grid), dim3(kBlock), 0, s, part, (uint32_t)N,
+                       (uint32_t)C, S, hard ? 1 : 0, dp, ddelta);
+  else if (dp)
+    hipLaunchKernelGGL(act_finish, dim3(dp_grid), dim3(kBlock), 0, s, part, (uint32_t)N,
+                       (uint32_t)C, S, hard ? 1 : 0, dp);
+}
 
 template <int S, int OP, bool VEC>
 static void act_launch_tpp(hipStream_t s, const float* x, const float* g, float* out,
                            const float* p, const float* delta, const float* zp,
                            const ActShifts& sh, float hi, uint32_t planes, uint32_t C, uint32_t hw,
                            double* part) {
-  const uint32_t items = VEC ? hw / 4 : hw;
-  constexpr uint32_t kMaxBlocks = 256 * 8;   // 8 workgroups per CU
-  if (items <= (uint32_t)kBlock) {
-    constexpr uint32_t GPB = kBlock / kWave;
-    uint32_t blocks = (planes + GPB - 1) / GPB;
-    blocks = blocks > kMaxBlocks ? kMaxBlocks : blocks;
-    hipLaunchKernelGGL((act_kernel<S, OP, VEC, kWave>), dim3(blocks), dim3(kBlock), 0, s, x, g, out,
-                       p, delta, zp, sh, hi, planes, C, hw, part);
-  } else {
-    const uint32_t blocks = planes > kMaxBlocks ? kMaxBlocks : planes;
-    hipLaunchKernelGGL((act_kernel<S, OP, VEC, kBlock>), dim3(blocks), dim3(kBlock), 0, s, x, g,
+  const ActGeometry geo = act_geometry(VEC, planes, hw);
+  if (geo.wave)
+    hipLaunchKernelGGL((act_kernel<S, OP, VEC, kWave>), dim3(geo.blocks), dim3(kBlock), 0, s, x, g,
                        out, p, delta, zp, sh, hi, planes, C, hw, part);
-  }
+  else
+    hipLaunchKernelGGL((act_kernel<S, OP, VEC, kBlock>), dim3(geo.blocks), dim3(kBlock), 0, s, x,
+                       g, out, p, delta, zp, sh, hi, planes, C, hw, part);
 }
 
 template <int OP>
@@ -438,12 +351,9 @@ static void act_delta_launch(hipStream_t s, bool vec, const float* x, const floa
                              const float* p, const float* delta, const float* zp,
                              const ActShifts& sh, float hi, uint32_t planes, uint32_t C,
                              uint32_t hw, double* part) {
-  const uint32_t items = vec ? hw / 4 : hw;
-  constexpr uint32_t kMaxBlocks = 256 * 8;
-  constexpr uint32_t GPB = kBlock / kWave;
-  const bool wave = items <= (uint32_t)kBlock;
-  uint32_t blocks = wave ? (planes + GPB - 1) / GPB : planes;
-  blocks = blocks > kMaxBlocks ? kMaxBlocks : blocks;
+  const ActGeometry geo = act_geometry(vec, planes, hw);
+  const bool wave = geo.wave;
+  const uint32_t blocks = geo.blocks;
 #define SSQ_ACT_DELTA(VEC, TPP)                                                                  \
   hipLaunchKernelGGL((act_delta_kernel<S, HARD, VEC, TPP>), dim3(blocks), dim3(kBlock), 0, s, x, \
                      g, out, p, delta, zp, sh, hi, planes, C, hw, part)
@@ -452,28 +362,6 @@ static void act_delta_launch(hipStream_t s, bool vec, const float* x, const floa
   else if (wave) SSQ_ACT_DELTA(false, kWave);
   else SSQ_ACT_DELTA(false, kBlock);
 #undef SSQ_ACT_DELTA
-}
-
-// Shared argument checks; fills sh.  planes = N * C.
-static int act_check(const char* what, const float* shifts, int S, int64_t N, int64_t C,
-                     int64_t HW, int qmax, ActShifts& sh) {
-  SSQ_REQUIRE(S >= 1 && S <= kActMaxS, SSQ_E_ARG, "%s: S = %d shift targets (1..%d supported)",
-              what, S, kActMaxS);
-  SSQ_REQUIRE(N >= 0 && C >= 1 && C < (1ll << 28) && HW >= 1, SSQ_E_ARG, "%s: bad sizes", what);
-  SSQ_REQUIRE(N < (1ll << 31) && C < (1ll << 31) && HW < (1ll << 31) &&
-                  (N == 0 || (C * HW) < (1ll << 31) / N),
-              SSQ_E_ARG, "%s: N*C*H*W must stay below 2^31", what);
-  SSQ_REQUIRE(qmax >= 1, SSQ_E_ARG, "%s: qmax < 1", what);
-  SSQ_REQUIRE(shifts != nullptr, SSQ_E_ARG, "%s: null pointer (shifts)", what);
-  for (int i = 0; i < kActMaxS; ++i) sh.s[i] = i < S ? shifts[i] : 1.0f;
-  return SSQ_OK;
-}
-
-static size_t act_part_bytes(int64_t N, int64_t C, int S) {
-  if (N <= 0 || C <= 0 || S <= 0 || S > kActMaxS || N >= (1ll << 31) || C >= (1ll << 31) ||
-      C >= (1ll << 31) / N)
-    return 0;
-  return (size_t)N * (size_t)C * (size_t)S * sizeof(double);
 }
 
 }  // namespace ssq
@@ -526,11 +414,8 @@ extern "C" int ssq_actshift_bwd(const float* x, const float* g, const float* p,
   // the launch that writes the zeros)
   SSQ_REQUIRE(dp != nullptr || hard, SSQ_E_ARG, "%s: null pointer (dp)", what);
   hipStream_t s = (hipStream_t)stream;
-  const int fin_grid = grid_for(C * S, kBlock, 1 << 30);
   if (N == 0) {
-    if (dp)
-      hipLaunchKernelGGL(act_finish, dim3(fin_grid), dim3(kBlock), 0, s, nullptr, 0u, (uint32_t)C,
-                         S, 1, dp);
+    act_finish_launch(s, nullptr, 0, C, S, true, dp, nullptr);
     return check_launch(what);
   }
   SSQ_REQUIRE(x && g && p && delta && zp && dx, SSQ_E_ARG, "%s: null pointer", what);
@@ -538,9 +423,7 @@ extern "C" int ssq_actshift_bwd(const float* x, const float* g, const float* p,
   if (hard) {
     act_launch<kBwdHard>(s, S, vec, x, g, dx, p, delta, zp, sh, (float)qmax, (uint32_t)(N * C),
                          (uint32_t)C, (uint32_t)HW, nullptr);
-    if (dp)
-      hipLaunchKernelGGL(act_finish, dim3(fin_grid), dim3(kBlock), 0, s, nullptr, 0u, (uint32_t)C,
-                         S, 1, dp);
+    act_finish_launch(s, nullptr, 0, C, S, true, dp, nullptr);
     return check_launch(what);
   }
   const size_t need = act_part_bytes(N, C, S);
@@ -548,8 +431,7 @@ extern "C" int ssq_actshift_bwd(const float* x, const float* g, const float* p,
               "%s: workspace of %zu bytes (8-B aligned) needed, %zu given", what, need, ws_bytes);
   act_launch<kBwdSoft>(s, S, vec, x, g, dx, p, delta, zp, sh, (float)qmax, (uint32_t)(N * C),
                        (uint32_t)C, (uint32_t)HW, (double*)ws);
-  hipLaunchKernelGGL(act_finish, dim3(fin_grid), dim3(kBlock), 0, s, (const double*)ws,
-                     (uint32_t)N, (uint32_t)C, S, 0, dp);
+  act_finish_launch(s, (const double*)ws, N, C, S, false, dp, nullptr);
   return check_launch(what);
 }
 
@@ -571,7 +453,6 @@ extern "C" int ssq_actshift_bwd_delta(const float* x, const float* g, const floa
   SSQ_REQUIRE(dp != nullptr || hard, SSQ_E_ARG, "%s: null pointer (dp)", what);
   SSQ_REQUIRE(ddelta != nullptr, SSQ_E_ARG, "%s: null pointer (ddelta)", what);
   hipStream_t s = (hipStream_t)stream;
-  const int fin_grid = 1 + (dp ? grid_for(C * S, kBlock, 1 << 30) : 0);
   if (N > 0) {
     SSQ_REQUIRE(x && g && p && delta && zp && dx, SSQ_E_ARG, "%s: null pointer", what);
     const size_t need = (size_t)N * (size_t)C * (size_t)(hard ? 1 : S + 1) * sizeof(double);
@@ -596,8 +477,7 @@ extern "C" int ssq_actshift_bwd_delta(const float* x, const float* g, const floa
 #undef SSQ_ACT_CASE
   }
   // (N == 0: no plane, the finish stores ddelta = 0 and dp = 0)
-  hipLaunchKernelGGL(act_finish_delta, dim3(fin_grid), dim3(kBlock), 0, s, (const double*)ws,
-                     (uint32_t)N, (uint32_t)C, S, hard ? 1 : 0, dp, ddelta);
+  act_finish_launch(s, (const double*)ws, N, C, S, hard != 0, dp, ddelta);
   return check_launch(what);
 }
 

@@ -10,6 +10,7 @@
 
 #include <type_traits>
 
+#include "epilogue_elem.h"
 #include "fin_tasks.h"
 #include "prep_ride.h"
 #include "ssq_common.h"
@@ -121,10 +122,7 @@ __global__ __launch_bounds__(kBlock) void bias_act_kernel(const float* __restric
   }
   // channel c's operands applied to one element (the reference's op order)
   auto epi = [&](float v, float rv, float bc, float gc, float pc) {
-    float t = bias ? __fadd_rn(v, bc) : v;
-    if (AFFINE) t = __fadd_rn(__fmul_rn(t, gc), pc);  // out*alpha_out + beta_out
-    if (RES) t = __fadd_rn(t, rv);
-    return act_fwd<ACT>(t);  // torch clamp: keeps -0 and NaN
+    return k13_elem<RES, ACT, AFFINE>(bias != nullptr, v, rv, bc, gc, pc);
   };
   auto one = [&](uint32_t i, float v, float rv) {
     const uint32_t q = fdiv(i, div_hw);

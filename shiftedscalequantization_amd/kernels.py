@@ -2014,6 +2014,108 @@ def actshift(x, p, delta, zp, shifts, n_bits, hard=False):
                             bool(hard))
 
 
+# ------------------------------------------------------------------ K34 act quantizer in the epilogue
+# Where a K13 site's act quantizer is a ChannelQuantAct in 'shiftFeature' mode
+# (quant_layer.fusable_shift_act_quantizer), the site runs epilogue_actshift -- one pass forward,
+# one backward -- in place of k13 followed by the module: the same bits in every output.  "0":
+# the two passes, always (an A/B knob, as WGRAD_POLICY / FWD_1X1_GEMM).
+ACTSHIFT_EPI = os.environ.get("SSQ_ACTSHIFT_EPI", "auto")
+
+
+def _epi_actshift_operands(y, bias, gamma, phi, res, p, delta, zp, shifts):
+    """The operands of a K34 launch: (geometry (N, C, hw, S), the argument pointers in ABI order
+    conv, bias, gamma, phi, res and p, delta, zp, and what they point into)."""
+    y, yp = fptr(y.detach(), "conv output")
+    N, C_, hw = _actshift_geometry(y)
+    S = len(shifts)
+    res, rp = fptr(None if res is None else res.detach(), "residual")
+    if res is not None and res.shape != y.shape:
+        raise A.SSQError("epilogue_actshift: residual shape mismatch")
+    (bias, bp), (gamma, gmp), (phi, php) = (_chan(t, C_, w) for t, w in
+                                            ((bias, "bias"), (gamma, "gamma"), (phi, "phi")))
+    p, pp = _actshift_table(p, C_, S, "p")
+    (delta, dp_), (zp, zpp) = _actshift_scalars(delta, zp)
+    return (N, C_, hw, S), (yp, bp, gmp, php, rp), (pp, dp_, zpp), (y, bias, gamma, phi, res, p,
+                                                                    delta, zp)
+
+
+def epilogue_actshift_fwd(y, bias, gamma, phi, res, relu, p, delta, zp, shifts, n_bits,
+                          hard=False):
+    """actshift_fwd(act(((y + bias) * gamma + phi) + res)) in one pass over the conv output y
+    (ssq_epilogue_actshift_fwd); the epilogue's output is never stored."""
+    (N, C_, hw, S), epi, grid, hold = _epi_actshift_operands(y, bias, gamma, phi, res, p, delta,
+                                                             zp, shifts)
+    out = torch.empty_like(hold[0])
+    call("ssq_epilogue_actshift_fwd", *epi, int(relu), *grid, A.shifts_arg(shifts), S, N, C_, hw,
+         2 ** n_bits - 1, int(bool(hard)), _vp(out), stream_of(out))
+    return out
+
+
+def epilogue_actshift_bwd(y, g, bias, gamma, phi, res, relu, p, delta, zp, shifts, n_bits,
+                          hard=False, want=(True, True, True, False)):
+    """(dconv, dres, dp, ddelta) of epilogue_actshift_fwd for the upstream g
+    (ssq_epilogue_actshift_bwd), each None where `want` does not ask for it (dp is always
+    computed by the soft form): bit for bit actshift_bwd[_delta] followed by the K13 backward."""
+    (N, C_, hw, S), epi, grid, hold = _epi_actshift_operands(y, bias, gamma, phi, res, p, delta,
+                                                             zp, shifts)
+    y = hold[0]
+    g, gp = fptr(g.detach(), "g")
+    if g.shape != y.shape:
+        raise A.SSQError("epilogue_actshift_bwd: g must be shaped like the conv output")
+    new = (lambda on, shape: torch.empty(shape, dtype=torch.float32, device=y.device) if on
+           else None)
+    dconv = new(want[0], y.shape)
+    dres = new(want[1] and res is not None, y.shape)
+    dpt = new(want[2] or not hard, (C_, S))
+    ddelta = new(want[3], ())
+    ws, wsn = workspace(query("ssq_epilogue_actshift_bwd_workspace_size", N, C_, hw, S), y.device)
+    call("ssq_epilogue_actshift_bwd", epi[0], gp, *epi[1:], int(relu), *grid,
+         A.shifts_arg(shifts), S, N, C_, hw, 2 ** n_bits - 1, int(bool(hard)), _vp(dconv),
+         _vp(dres), _vp(dpt), _vp(ddelta), ws, wsn, stream_of(y))
+    return dconv, dres, dpt, ddelta
+
+
+class EpilogueActShiftFn(torch.autograd.Function):
+    """K34: the K13 epilogue and ChannelQuantAct 'shiftFeature' as one op.  Saves the conv
+    output and the residual, not the epilogue's output; gradients go to the conv output, the
+    residual, p and (when it asks) delta.  calls: how many forwards have run (tests read it)."""
+    calls = 0
+
+    @staticmethod
+    def forward(ctx, y, bias, gamma, phi, res, p, delta, zp, relu, shifts, n_bits, hard):
+        out = epilogue_actshift_fwd(y, bias, gamma, phi, res, relu, p, delta, zp, shifts, n_bits,
+                                    hard)
+        EpilogueActShiftFn.calls += 1
+        ctx.save_for_backward(y, bias, gamma, phi, res, p, delta, zp)
+        ctx.cfg = (relu, shifts, n_bits, hard)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y, bias, gamma, phi, res, p, delta, zp = ctx.saved_tensors
+        relu, shifts, n_bits, hard = ctx.cfg
+        need = ctx.needs_input_grad
+        dconv, dres, dp, ddelta = epilogue_actshift_bwd(
+            y, g, bias, gamma, phi, res, relu, p, delta, zp, shifts, n_bits, hard,
+            want=(need[0], need[4], need[5] and not hard, need[6]))
+        return (dconv, None, None, None, dres, dp if need[5] and not hard else None,
+                None if ddelta is None else ddelta.reshape(delta.shape), None, None, None, None,
+                None)
+
+
+def epilogue_actshift(y, bias, gamma, phi, res, relu, p, delta, zp, shifts, n_bits, hard=False):
+    """ChannelQuantAct 'shiftFeature' of the K13 epilogue of the conv output y, fused (K34).
+    bias / gamma / phi are constants here: one that needs a gradient is refused (the caller
+    takes k13 and the module, whose backward has those sums)."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                       for t in (bias, gamma, phi)):
+        raise A.SSQError("epilogue_actshift: bias / gamma / phi get no gradient from the fused "
+                         "backward; run k13 and the act quantizer as two passes")
+    return EpilogueActShiftFn.apply(y, bias, gamma, phi, materialize(res), p, delta, zp,
+                                    int(relu), tuple(float(s) for s in shifts), int(n_bits),
+                                    bool(hard))
+
+
 # ------------------------------------------------------------------ K15/K16 packed export
 def pack_encode(what, zp, d1, per_ci, d2, n_bits, qmin, qmax):
     """Hard W_hat -> (packed codes as a uint8 tensor, number of elements whose decode is not

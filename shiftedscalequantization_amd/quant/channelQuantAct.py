@@ -63,6 +63,15 @@ class ChannelQuantAct(nn.Module):
             f"ChannelQuantAct opt_mode={self.opt_mode!r} is broken in the reference "
             "(channelQuantAct.py:38-61,125-134 read attributes that are never set)")
 
+    def forward_epilogue(self, y, bias, gamma, phi, res, relu):
+        """forward(K.k13(y, bias, gamma, phi, res, relu)) of the 'shiftFeature' mode in one pass
+        over the conv output y (K34, K.epilogue_actshift): the same bits, forward and backward.
+        For the sites quant_layer.fusable_shift_act_quantizer admits."""
+        delta = self.delta if self.learn_delta else self.delta.detach()
+        return K.epilogue_actshift(y, bias, gamma, phi, res, relu, self.get_sig_soft_targets(),
+                                   delta, self.zero_point, self.shiftTarget, self.n_bits,
+                                   self.hard_targets)
+
     def get_sig_soft_targets(self):
         return torch.clamp(F.softmax(self.alpha, dim=-1) * (self.zeta - self.gamma) + self.gamma, 0, 1)
 

@@ -10,7 +10,8 @@ import torch.nn as nn
 
 from .. import kernels as K
 from .. import nets
-from .quant_layer import QuantModule, StraightThrough, UniformAffineQuantizer, fusable_act_quantizer
+from .quant_layer import (QuantModule, StraightThrough, UniformAffineQuantizer, fusable_act_quantizer,
+                          fusable_shift_act_quantizer)
 
 
 class BaseQuantBlock(nn.Module):
@@ -139,6 +140,13 @@ class BaseQuantBlock(nn.Module):
             relu = isinstance(self.activation_function, nn.ReLU)
             q = fusable_act_quantizer(self.act_quantizer, self.use_act_quant)
             gamma, phi = last.affine()
+            qs = fusable_shift_act_quantizer(
+                self.act_quantizer,
+                self.use_act_quant and q is None and getattr(self, '_int_tail', None) is None,
+                (bias, gamma, phi))
+            if qs is not None:
+                # a shifted-scale act quantizer: the tail and its q/dq in one pass (K34)
+                return qs.forward_epilogue(raw, bias, gamma, phi, residual, relu)
             # lazy only for the block the loop targets, only when no hook can see the
             # placeholder output (K.TAIL_LAZY), and only when the epilogue is the block's last
             # op (an act quantizer that is on but not fusable runs after it)

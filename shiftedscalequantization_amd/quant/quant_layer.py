@@ -249,6 +249,29 @@ def fusable_act_quantizer(q, active):
     return q
 
 
+def fusable_shift_act_quantizer(q, active, epilogue_params=()):
+    """The act quantizer `q` if its shifted-scale q/dq can run inside the K13 epilogue pass (K34,
+    K.epilogue_actshift; q.forward_epilogue): a ChannelQuantAct in 'shiftFeature' mode after
+    init_v, with scalar device delta/zp and no hooks, at a site whose epilogue parameters (bias,
+    gamma^z, phi^z) need no gradient -- the fused backward has none for them.  Else None: the
+    site runs K.k13 and then the module.  K.ACTSHIFT_EPI = "0" turns the route off."""
+    if not active or K.ACTSHIFT_EPI == "0":
+        return None
+    from .channelQuantAct import ChannelQuantAct      # (imports this module)
+    if type(q) is not ChannelQuantAct:
+        return None
+    if q.opt_mode != 'shiftFeature' or q.alpha is None:
+        return None
+    if q.delta is None or q.delta.numel() != 1 or q.zero_point.numel() != 1:
+        return None
+    if q._forward_hooks or q._forward_pre_hooks or not q.delta.is_cuda:
+        return None
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                       for t in epilogue_params):
+        return None
+    return q
+
+
 class QuantModule(nn.Module):
     """quant_layer.py:188-280: a Conv2d / Linear whose weight goes through
     `weight_quantizer` (any module: UAQ, ChannelQuant, AdaRoundQuantizer, ...), followed by
@@ -470,9 +493,18 @@ class QuantModule(nn.Module):
                 # the parent block's next conv folds this epilogue into its im2col GEMM
                 # (kernels.EPI_CONSUMER); anything else materialises it
                 return K.lazy_epilogue(out, bias, gamma, phi, relu, q)
-            out = K.k13(out, bias, gamma, phi, None, relu, q, nonaffine_q=EPI_NONAFFINE_Q,
-                        lazy=False)
-            act_q = act_q and q is None      # (on but not fusable: as a module, below)
+            qs = fusable_shift_act_quantizer(
+                self.act_quantizer,
+                act_q and q is None and getattr(self, '_int_plan', None) is None,
+                (bias, gamma, phi))
+            if qs is not None:
+                # a shifted-scale act quantizer: epilogue and q/dq in one pass (K34)
+                out = qs.forward_epilogue(out, bias, gamma, phi, None, relu)
+            else:
+                out = K.k13(out, bias, gamma, phi, None, relu, q, nonaffine_q=EPI_NONAFFINE_Q,
+                            lazy=False)
+            # (on but fusable neither way: as a module, below)
+            act_q = act_q and q is None and qs is None
         else:
             weight, bias = self._weight_bias()
             out = self._conv(input, weight, bias)
